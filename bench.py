@@ -27,14 +27,23 @@ rank processes its own B images; value = total points of all ranks / max-over-ra
 the parent touches the GPU; the counterpart of the reference's tools/run.py:59-75); under
 ``python -m torch.distributed.run`` it uses the ranks it is given.  Backend "nccl" (= RCCL).
 
-Before anything is timed the step's tensors are compared with the CPU oracle (``--no-check``
-skips it); a failing comparison prints no JSON line and exits non-zero.
+A plain run does what the headline needs and nothing else: inputs, pre-heat, W warm-up steps, K timed steps, the
+outputs (``--dump-outputs DIR``) and ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects: "roofline" (dominant kernel vs the
-8 TB/s HBM peak; step_frac = the whole step), "resident", "cpu_baseline" (the C restatement of the reference kernels on
-the bench workload -- kind "port" -- with the pure-PyTorch leg at BASELINE configs[0] inside) and
-"pytorch_fallback_cpu" (north_star's comparator: the pure-PyTorch formulation on the host cores at the shape of this
-line, 3 iterations); rank 0, N=1 only.
+``--dump-outputs DIR``: after the timed steps, what the last timed step returned to its caller (out[, mask_out], then
+the gradients) as ``DIR/<name>.npy`` in float32 (float64 for float64 tensors), on rank 0.  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.  Beyond 64 MB in all, an array larger than its
+share is replaced by a fixed, seeded sample of its elements (flattened, indices ascending; same arguments, same sample).
+
+``--full`` adds everything else:
+* before anything is timed the step's tensors are compared with the CPU oracle (``--no-check`` skips it); a failing
+  comparison prints no JSON line and exits non-zero;
+* extra objects in the line: "resident" (one input set replayed), "per_rank" (N > 1), "roofline" (dominant kernel vs
+  the 8 TB/s HBM peak; step_frac = the whole step), "cpu_baseline" (the C restatement of the reference kernels on the
+  bench workload -- kind "port" -- with the pure-PyTorch leg at BASELINE configs[0] inside) and
+  "pytorch_fallback_cpu" (north_star's comparator: the pure-PyTorch formulation on the host cores at the shape of this
+  line, 3 iterations); the last two on rank 0, N=1 only (``--no-cpu-baseline`` leaves them out).
 """
 import argparse
 import json
@@ -372,6 +381,14 @@ def kernel_profile(step, steps, variant):
 # parity gate: nothing is timed unless the step's tensors match the CPU oracle
 # --------------------------------------------------------------------------------------
 PARITY_INFO = {}       # filled by parity_report: how many points the grad_loc comparison leaves out
+# what one step returns to its caller, in order (make_step: box -> out, grads; instance -> (out, mask), grads)
+OUTPUT_NAMES = {"box": ["out", "grad_value", "grad_loc", "grad_attn"],
+                "instance": ["out", "mask_out", "grad_value", "grad_loc", "grad_spatial", "grad_level"]}
+
+
+def step_outputs(kind, out, grads):
+    """The tensors of one step's result, in the order of OUTPUT_NAMES[kind]."""
+    return ([out] if kind == "box" else list(out)) + list(grads)
 
 
 def parity_report(inp, out, grads):
@@ -398,16 +415,14 @@ def parity_report(inp, out, grads):
         args = lambda d: (d["value"], d["shapes"], d["lsi"], d["loc"], d["attn"])
         want = [oc.box_attn_forward(*args(a))] + list(oc.box_attn_backward(*args(a), a["grad_out"]))
         want[2] = oc.box_attn_backward(*args(a32), a32["grad_out"])[1].astype(np.float64)
-        got = [out] + list(grads)
-        names = ["out", "grad_value", "grad_loc", "grad_attn"]
     else:
         args = lambda d: (d["value"], d["shapes"], d["lsi"], d["loc"], d["attn"], d["level_w"])
         want = list(oc.instance_attn_forward(*args(a)))
         want += list(oc.instance_attn_backward(*args(a), a["grad_out"], a["grad_mask"]))
         want[3] = oc.instance_attn_backward(*args(a32), a32["grad_out"],
                                             a32["grad_mask"])[1].astype(np.float64)
-        got = list(out) + list(grads)
-        names = ["out", "mask_out", "grad_value", "grad_loc", "grad_spatial", "grad_level"]
+    got = step_outputs(inp["kind"], out, grads)
+    names = OUTPUT_NAMES[inp["kind"]]
     size = a["shapes"].astype(np.float64)[None, None, None, :, None, ::-1]       # (W, H)
     pix = a["loc"] * size - 0.5
     edge = (np.abs(pix - np.round(pix)) < 1e-4).any(-1, keepdims=True)
@@ -600,6 +615,89 @@ def resident_leg(args, step, np_rank, device):
             "note": "one input set replayed (cache-resident): this rank alone, no barrier"}
 
 
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(path, kind, tensors):
+    """One step's outputs -> path/<name>.npy (float32; float64 tensors stay float64).  Above DUMP_BYTES in all, the
+    budget is shared out smallest array first, and an array larger than its share is replaced by a sample of its
+    flattened elements: indices drawn without replacement by numpy's default generator seeded with the array's
+    position in OUTPUT_NAMES, ascending -- the same sample for the same shapes."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = OUTPUT_NAMES[kind]
+    wide = [t.dtype == torch.float64 for t in tensors]
+    order = sorted(range(len(tensors)), key=lambda i: tensors[i].numel() * (8 if wide[i] else 4))
+    left = DUMP_BYTES - 4096 * len(tensors)                 # (an .npy header is 128 bytes)
+    for k, i in enumerate(order):
+        a = tensors[i].detach().to(torch.float64 if wide[i] else torch.float32).cpu().numpy()
+        keep = min(a.size, left // (len(order) - k) // a.itemsize)
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(i).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, names[i] + ".npy"), a)
+        left -= a.nbytes
+
+
+def per_rank_rates(step, steps, np_rank, dist, device, world):
+    """Per-rank spread (clock / power variance between GPUs): every rank re-times ``steps`` steps alone, no barrier."""
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    mine = torch.tensor([np_rank * steps / (time.perf_counter() - t0) / 1e9],
+                        device=device, dtype=torch.float64)
+    allr = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(allr, mine)
+    vals = sorted(float(t.item()) for t in allr)
+    return {"min": round(vals[0], 3), "median": round(vals[len(vals) // 2], 3),
+            "max": round(vals[-1], 3), "unit": "Gsample-points/s per GPU (each rank re-timed alone, no barrier)"}
+
+
+def roofline_report(args, inp, dtype, ms_per_step, phases, prof):
+    """The line's ``roofline`` object: the dominant kernel's and the whole step's algorithmic bytes over their time,
+    against the HBM peak."""
+    elem = 2 if dtype == torch.bfloat16 else 4
+    b_fwd, b_bwd, b_kernel = algorithmic_bytes(inp["dims"], inp["kind"], elem)
+    # dominant kernel = the longest of the op's kernels (HIP events recorded by the library
+    # around each launch, on the launch stream)
+    kern = {k: v for k, v in (prof or {}).items() if v["ms"]}
+    if kern and any(k in b_kernel for k in kern):
+        dom = max((k for k in kern if k in b_kernel), key=lambda k: kern[k]["ms"])
+        dom_ms, dom_bytes = kern[dom]["ms"], b_kernel[dom]
+        src = ("HIP events around every launch of the kernel (boxattn_profile_*), same schedule as the "
+               "timed region; the bracketed pass runs ~10 % slower than the free-running step, so the "
+               "per-kernel averages add up to more than ms_per_step")
+    else:
+        dom, dom_ms, dom_bytes = "bwd (whole call)", phases["bwd"], b_bwd
+        src = "HIP events around the backward call"
+    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+    step_gbs = (b_fwd + b_bwd) / (ms_per_step * 1e-3) / 1e9
+    traffic, traffic_src = None, None
+    tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+    if os.path.exists(tfile):
+        with open(tfile) as fh:
+            t = json.load(fh)
+        key = "%s/%s/%s" % (args.workload, args.dtype, args.inputs)
+        traffic = t.get(key, {}).get(dom)
+        if traffic is not None:
+            traffic_src = ("profiles/hbm_traffic.json (builder's rocprofv3 --pmc run of this "
+                           "command, %s; not measured in this run)" % t.get("_round", "r02"))
+    return {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic, "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": dom_bytes,
+            "avg_launch_ms": round(dom_ms, 4), "timing": src,
+            # the whole step against the roofline: north_star's ">= 60 %" is THIS number
+            "step_frac": round(step_gbs / HBM_PEAK_GBS, 4),
+            "fwd_bwd": {"algorithmic_bytes": b_fwd + b_bwd,
+                        "achieved_GBs": round(step_gbs, 1),
+                        "frac": round(step_gbs / HBM_PEAK_GBS, 4)},
+            "fwd_ms": round(phases["fwd"], 4), "bwd_ms": round(phases["bwd"], 4),
+            "kernels": {k: {"avg_ms": round(v["ms"], 4), "launches": v["launches"],
+                            "algorithmic_bytes": b_kernel.get(k)}
+                        for k, v in kern.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -617,12 +715,18 @@ def main():
                          "(.apply + .backward)")
     ap.add_argument("--rotate", type=int, default=8, metavar="N",
                     help="the timed steps cycle N input / upstream-gradient sets generated outside the timed region "
-                         "(cache-cold: the headline); the one-set replay is reported beside it as `resident` "
+                         "(cache-cold: the headline); --full times the one-set replay beside it as `resident` "
                          "(0 / 1: the headline replays one set)")
     ap.add_argument("--graph", action="store_true",
                     help="capture the step in a HIP graph and time replays (not the headline run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the parity gate")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gate before timing, the resident leg, per-rank rates, the "
+                         "per-kernel roofline and the CPU baselines (a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (outputs, then gradients) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (larger arrays: a fixed seeded sample of their elements)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-check", action="store_true", help="--full without the parity gate")
     ap.add_argument("--preheat-s", type=float, default=PREHEAT_SECONDS,
                     help="untimed pre-heat before the protocol, seconds (profiling runs pass 0)")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant override (A/B)")
@@ -660,8 +764,8 @@ def main():
                       seed=rank)
     step0 = make_step(inp, args.entry)
 
-    # parity gate on the tensors of the step that is about to be timed (every rank its own)
-    if not args.no_check:
+    # --full: parity gate on the tensors of the step that is about to be timed (every rank its own)
+    if args.full and not args.no_check:
         failure = parity_gate(inp, step0)
         if failure is not None:
             print("bench.py: parity gate FAILED on rank %d (%s %s %s): %s" % (
@@ -669,96 +773,56 @@ def main():
             sys.exit(3)
     # The HEADLINE cycles N input / upstream-gradient sets (generated here, outside the timed region: 544 MB at C2
     # bf16): consecutive steps share nothing but the level tables, as consecutive layers / iterations of a training
-    # run do.  (One replayed set is cache-resident; it is timed too and reported as `resident`.)
+    # run do.  (One replayed set is cache-resident; --full times it too and reports it as `resident`.)
     n_sets = args.rotate if args.rotate > 1 else 1
     sets = [inp] + [make_inputs(args.workload, dtype, device, family=args.inputs, batch=args.batch,
                                 seed=1000 * (rank + 1) + i) for i in range(1, n_sets)]
     eager_fns = [step0] + [make_step(x, args.entry) for x in sets[1:]]
     fns = [graph_step(f) for f in eager_fns] if args.graph else eager_fns
-    turn = [0]
+    turn, last = [0], [None]
 
     def cycle(fs):
         def step():
             turn[0] += 1
-            return fs[turn[0] % len(fs)]()
+            f = fs[turn[0] % len(fs)]
+            last[0] = (f, f())                 # (what --dump-outputs writes of the last timed step)
+            return last[0][1]
         return step
     step, eager_step = cycle(fns), cycle(eager_fns)
 
     # Device pre-heat: the first ~100 steps after start-up run up to ~8 % slower than the steady state
     # (clock ramp, tools/gpu_ramp.py).  With a short --warmup the gap is filled here, outside
     # the W warm-up + K timed steps of the protocol, so that the number is the steady-state one.
+    # It ends on a whole cycle of the input sets: the last timed step runs the same set in every run.
     preheat, t0 = 0, time.perf_counter()
     while preheat < max(0, PREHEAT_STEPS - args.warmup) or \
-            time.perf_counter() - t0 < args.preheat_s:
+            time.perf_counter() - t0 < args.preheat_s or preheat % len(fns):
         step()
         preheat += 1
         if preheat % 64 == 0:
             torch.cuda.synchronize()
     torch.cuda.synchronize()
     elapsed = run_timed(step, args.steps, args.warmup, torch.cuda.synchronize, dist, device)
-    step = eager_step                      # the per-kernel profile needs the launches themselves
 
     np_rank = n_points(inp["dims"])
     value, ms_per_step = throughput(elapsed, np_rank, world, args.steps)
-    resident = resident_leg(args, fns[0], np_rank, device) if n_sets > 1 else None
-    per_rank = None
-    if dist is not None:                   # per-rank spread (clock / power variance between GPUs)
-        t0 = time.perf_counter()           # every rank alone, no barrier: its own rate
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        mine = torch.tensor([np_rank * args.steps / (time.perf_counter() - t0) / 1e9],
-                            device=device, dtype=torch.float64)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        vals = sorted(float(t.item()) for t in allr)
-        per_rank = {"min": round(vals[0], 3), "median": round(vals[len(vals) // 2], 3),
-                    "max": round(vals[-1], 3), "unit": "Gsample-points/s per GPU (each rank re-timed alone, no barrier)"}
+    if args.dump_outputs and rank == 0:
+        f, res = last[0]
+        out, grads = res if res is not None else f.__self__._keep     # a graph replay: the captured outputs
+        dump_outputs(args.dump_outputs, inp["kind"], step_outputs(inp["kind"], out, grads))
 
-    phases = time_phases(inp)
-    prof = kernel_profile(step, min(args.steps, 20), args.variant)
-    elem = 2 if dtype == torch.bfloat16 else 4
-    b_fwd, b_bwd, b_kernel = algorithmic_bytes(inp["dims"], inp["kind"], elem)
+    resident = per_rank = roofline = None
+    if args.full:
+        step = eager_step                  # the per-kernel profile needs the launches themselves
+        resident = resident_leg(args, fns[0], np_rank, device) if n_sets > 1 else None
+        if dist is not None:
+            per_rank = per_rank_rates(step, args.steps, np_rank, dist, device, world)
+        phases = time_phases(inp)
+        prof = kernel_profile(step, min(args.steps, 20), args.variant)
+        if rank == 0:
+            roofline = roofline_report(args, inp, dtype, ms_per_step, phases, prof)
 
     if rank == 0:
-        # dominant kernel = the longest of the op's kernels (HIP events recorded by the library
-        # around each launch, on the launch stream)
-        kern = {k: v for k, v in (prof or {}).items() if v["ms"]}
-        if kern and any(k in b_kernel for k in kern):
-            dom = max((k for k in kern if k in b_kernel), key=lambda k: kern[k]["ms"])
-            dom_ms, dom_bytes = kern[dom]["ms"], b_kernel[dom]
-            src = ("HIP events around every launch of the kernel (boxattn_profile_*), same schedule as the "
-                   "timed region; the bracketed pass runs ~10 % slower than the free-running step, so the "
-                   "per-kernel averages add up to more than ms_per_step")
-        else:
-            dom, dom_ms, dom_bytes = "bwd (whole call)", phases["bwd"], b_bwd
-            src = "HIP events around the backward call"
-        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-        step_gbs = (b_fwd + b_bwd) / (ms_per_step * 1e-3) / 1e9
-        traffic, traffic_src = None, None
-        tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tfile):
-            with open(tfile) as fh:
-                t = json.load(fh)
-            key = "%s/%s/%s" % (args.workload, args.dtype, args.inputs)
-            traffic = t.get(key, {}).get(dom)
-            if traffic is not None:
-                traffic_src = ("profiles/hbm_traffic.json (builder's rocprofv3 --pmc run of this "
-                               "command, %s; not measured in this run)" % t.get("_round", "r02"))
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                    "traffic": traffic, "traffic_source": traffic_src,
-                    "algorithmic_bytes_per_launch": dom_bytes,
-                    "avg_launch_ms": round(dom_ms, 4), "timing": src,
-                    # the whole step against the roofline: north_star's ">= 60 %" is THIS number
-                    "step_frac": round(step_gbs / HBM_PEAK_GBS, 4),
-                    "fwd_bwd": {"algorithmic_bytes": b_fwd + b_bwd,
-                                "achieved_GBs": round(step_gbs, 1),
-                                "frac": round(step_gbs / HBM_PEAK_GBS, 4)},
-                    "fwd_ms": round(phases["fwd"], 4), "bwd_ms": round(phases["bwd"], 4),
-                    "kernels": {k: {"avg_ms": round(v["ms"], 4), "launches": v["launches"],
-                                    "algorithmic_bytes": b_kernel.get(k)}
-                                for k, v in kern.items()}}
         line = {
             "metric": "box-attn fwd+bwd Gsample-points/s + achieved HBM GB/s, BoxeR-R50 COCO shapes",
             "value": round(value, 4), "unit": "Gsample-points/s", "n_gpus": world,
@@ -780,11 +844,12 @@ def main():
                                        args.inputs),
                        "points_per_step_per_gpu": np_rank, "parallelism": "dp%d" % world,
                        "preheat_steps": preheat,
-                       "parity_gate": "skipped" if args.no_check else
+                       "parity_gate": "not run (--full runs it)" if not args.full else "skipped" if args.no_check else
                        "passed (all tensors vs CPU oracle; grad_loc: %d of %d points within 1e-4 px of a bilinear "
                        "cell edge not compared)" % (PARITY_INFO.get("edge_points", -1), PARITY_INFO.get("points", -1))},
-            "roofline": roofline,
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         line["inputs"] = ("%d input / upstream-gradient sets (%.0f MB) cycled from step to step: cache-cold" % (
             n_sets, sum(t.numel() * t.element_size() for x in sets for t in x.values()
                         if isinstance(t, torch.Tensor)) / 1e6)) if n_sets > 1 else "one input set replayed (cache-resident)"
@@ -792,7 +857,7 @@ def main():
             line["resident"] = resident
         if per_rank is not None:
             line["per_rank"] = per_rank
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload)
             if inp["kind"] == "box" and not WORKLOADS[args.workload][3].startswith("box3d"):
                 # north_star's comparator at the shape of this line: the pure-PyTorch fallback on the host cores,

@@ -213,3 +213,31 @@ def test_bench_algorithmic_bytes():
         fwd, bwd, per_kernel = bench.algorithmic_bytes(dims, "box", elem)
         assert abs((fwd + bwd) / npts - per_point) < 0.01
         assert set(per_kernel) >= {"fwd", "bwd_points", "bwd_accumulate"}
+
+
+def test_bench_dump_outputs_stays_in_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one .npy per output in step order, float32; beyond the byte budget the larger arrays
+    become the same seeded sample of their elements on every call, and the files stay within the budget."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    g = torch.Generator().manual_seed(0)
+    out = torch.randn(2, 50, 256, generator=g).bfloat16()                           # 25 600 elements
+    grads = [torch.randn(2, 60, 8, 32, generator=g), torch.randn(2, 50, 8, 1, 4, 2, generator=g),
+             torch.randn(2, 50, 8, 1, 4, generator=g)]                             # 30 720, 6 400, 3 200
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "box", bench.step_outputs("box", out, grads))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(n + ".npy" for n in bench.OUTPUT_NAMES["box"])
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 200_000
+    for n, t in zip(bench.OUTPUT_NAMES["box"], [out] + grads):
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        full = t.float().numpy()
+        if a.size == full.size:
+            assert np.array_equal(a, full), n
+        else:                                   # a sample: values of the output, in ascending index order
+            idx = np.sort(np.random.default_rng(bench.OUTPUT_NAMES["box"].index(n)).choice(full.size, a.size,
+                                                                                       replace=False))
+            assert np.array_equal(a, full.reshape(-1)[idx]), n
+    assert np.load(tmp_path / "a" / "grad_attn.npy").shape == (2, 50, 8, 1, 4)   # small enough: whole, own shape

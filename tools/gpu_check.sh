@@ -8,6 +8,6 @@ echo "== pytest -m gpu" ; timeout 900 python -m pytest tests -m gpu -x -q 2>&1 |
 echo "== smoke" ; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -8 | tee gpurun_out/smoke.log
 echo "== bench"
 for dt in bf16 fp32; do for inp in model test; do
-  timeout 300 python bench.py --steps 30 --warmup 5 --dtype $dt --inputs $inp --no-cpu-baseline 2>&1 | tail -1 | tee -a gpurun_out/bench_matrix.log
+  timeout 300 python bench.py --full --steps 30 --warmup 5 --dtype $dt --inputs $inp --no-cpu-baseline 2>&1 | tail -1
 done; done
-timeout 600 python bench.py 2>&1 | tail -1 | tee gpurun_out/bench_default.json
+timeout 600 python bench.py --full 2>&1 | tail -1

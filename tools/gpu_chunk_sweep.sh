@@ -3,7 +3,7 @@
 #   gpurun --timeout 1200 -- bash tools/gpu_chunk_sweep.sh      -> gpurun_out/chunk_sweep.log
 export TMPDIR=/tmp
 run() {
-  timeout 300 python bench.py --steps 300 --warmup 20 --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
+  timeout 300 python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.readline()); k=d['roofline'].get('kernels',{})

@@ -4,7 +4,7 @@
 mkdir -p gpurun_out; export TMPDIR=/tmp
 echo "== pytest"; timeout 900 python -m pytest tests -m gpu -x -q -k "instance or inst or C3" 2>&1 | tail -8 | tee gpurun_out/inst_f32_pytest.log
 run() {
-  timeout 300 python bench.py --steps 800 --warmup 30 --dtype fp32 --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
+  timeout 300 python bench.py --full --steps 800 --warmup 30 --dtype fp32 --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.readline()); k=d['roofline'].get('kernels',{})

@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 run() { # workload dtype opt
-timeout 300 python bench.py --workload $1 --dtype $2 --steps 1500 --warmup 100 --rotate 0 --no-cpu-baseline --no-check --opt 20=$3 2>/dev/null | python -c "
+timeout 300 python bench.py --full --workload $1 --dtype $2 --steps 1500 --warmup 100 --rotate 0 --no-cpu-baseline --no-check --opt 20=$3 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

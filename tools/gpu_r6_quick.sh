@@ -10,7 +10,7 @@ if [ "$sel" != "skip" ]; then
 fi
 run() {  # dtype, extra args...
   local dt=$1; shift
-  timeout 300 python bench.py --steps 2000 --warmup 50 --dtype $dt --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
+  timeout 300 python bench.py --full --steps 2000 --warmup 50 --dtype $dt --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.readline()); k=d['roofline'].get('kernels',{})

@@ -6,11 +6,11 @@
 R=gpurun_out/r04; mkdir -p $R; export TMPDIR=/tmp
 rocm-smi --showproductname 2>/dev/null | head -8 > $R/gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 > $R/smoke.log
-timeout 600 python bench.py > $R/bench_default.json 2> $R/bench_default.err
-timeout 300 python bench.py --steps 20 --warmup 5 > $R/bench_driver_flags.json 2>> $R/bench_default.err
-timeout 300 python bench.py --entry function --no-cpu-baseline > $R/bench_function_entry.json 2>> $R/bench_default.err
+timeout 600 python bench.py --full > $R/bench_default.json 2> $R/bench_default.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $R/bench_driver_flags.json 2>> $R/bench_default.err
+timeout 300 python bench.py --full --entry function --no-cpu-baseline > $R/bench_function_entry.json 2>> $R/bench_default.err
 for dt in bf16 fp32; do for inp in model test; do
-  timeout 300 python bench.py --steps 200 --warmup 20 --dtype $dt --inputs $inp --no-cpu-baseline 2>/dev/null | tail -1 >> $R/bench_matrix.log
+  timeout 300 python bench.py --full --steps 200 --warmup 20 --dtype $dt --inputs $inp --no-cpu-baseline 2>/dev/null | tail -1 >> $R/bench_matrix.log
 done; done
 for cfg in "C2_bf16_model" "C2_fp32_model --dtype fp32" "C2_bf16_test --inputs test"; do
   set -- $cfg; tag=$1; shift
@@ -35,7 +35,7 @@ rm -rf gpurun_out/pmc_r04sq_1 gpurun_out/pmc_r04sq_2 gpurun_out/pmc_r04sq_3
 for o in "" "15=1" "15=2" "15=3" "20=2065" "20=1058" "10=1536" "17=1" "11=1" "17=1 --opt 11=1 --opt 15=1"; do
   for inp in model test; do
     echo -n "opt ${o:-default} inputs $inp : " >> $R/ab_switches.log
-    timeout 300 python bench.py --steps 300 --warmup 20 --no-cpu-baseline --inputs $inp ${o:+--opt $o} 2>/dev/null | tail -1 | python -c "
+    timeout 300 python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --inputs $inp ${o:+--opt $o} 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); r = d['roofline']
 print('Gpts/s', d['value'], 'us/step', round(1000 * d['ms_per_step'], 1), {k: round(1000 * v['avg_ms'], 1) for k, v in r['kernels'].items()})" >> $R/ab_switches.log

@@ -6,12 +6,12 @@
 R=gpurun_out/r05; mkdir -p $R; export TMPDIR=/tmp
 rocm-smi --showproductname 2>/dev/null | head -8 > $R/gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 > $R/smoke.log
-timeout 600 python bench.py > $R/bench_default.json 2> $R/bench_default.err
-timeout 300 python bench.py --steps 20 --warmup 5 > $R/bench_driver_flags.json 2>> $R/bench_default.err
-timeout 300 python bench.py --entry function --no-cpu-baseline > $R/bench_function_entry.json 2>> $R/bench_default.err
-timeout 300 python bench.py --entry reference --no-cpu-baseline > $R/bench_reference_entry.json 2>> $R/bench_default.err
+timeout 600 python bench.py --full > $R/bench_default.json 2> $R/bench_default.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $R/bench_driver_flags.json 2>> $R/bench_default.err
+timeout 300 python bench.py --full --entry function --no-cpu-baseline > $R/bench_function_entry.json 2>> $R/bench_default.err
+timeout 300 python bench.py --full --entry reference --no-cpu-baseline > $R/bench_reference_entry.json 2>> $R/bench_default.err
 for dt in bf16 fp32; do for inp in model test; do
-  timeout 300 python bench.py --steps 200 --warmup 20 --dtype $dt --inputs $inp --no-cpu-baseline --rotate 0 2>/dev/null | tail -1 >> $R/bench_matrix.log
+  timeout 300 python bench.py --full --steps 200 --warmup 20 --dtype $dt --inputs $inp --no-cpu-baseline --rotate 0 2>/dev/null | tail -1 >> $R/bench_matrix.log
 done; done
 for cfg in "C2_bf16_model" "C2_fp32_model --dtype fp32" "C2_bf16_test --inputs test"; do
   set -- $cfg; tag=$1; shift
@@ -41,7 +41,7 @@ rm -rf gpurun_out/pmc_r05sqf_1 gpurun_out/pmc_r05sqf_2 gpurun_out/pmc_r05sqf_3
 for o in "" "15=1" "15=2" "17=1" "11=1"; do
   for inp in model test; do
     echo -n "opt ${o:-default} inputs $inp : " >> $R/ab_switches.log
-    timeout 300 python bench.py --steps 300 --warmup 20 --no-cpu-baseline --rotate 0 --inputs $inp ${o:+--opt $o} 2>/dev/null | tail -1 | python -c "
+    timeout 300 python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --rotate 0 --inputs $inp ${o:+--opt $o} 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); r = d['roofline']
 print('Gpts/s', d['value'], 'us/step', round(1000 * d['ms_per_step'], 1), {k: round(1000 * v['avg_ms'], 1) for k, v in r['kernels'].items()})" >> $R/ab_switches.log
@@ -50,7 +50,7 @@ done
 # float32 switches: accumulate flavour (19), window-staged kernels (21)
 for o in "" "19=1" "19=2" "21=1" "15=1"; do
   echo -n "fp32 opt ${o:-default} : " >> $R/ab_switches.log
-  timeout 300 python bench.py --steps 300 --warmup 20 --no-cpu-baseline --rotate 0 --dtype fp32 ${o:+--opt $o} 2>/dev/null | tail -1 | python -c "
+  timeout 300 python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --rotate 0 --dtype fp32 ${o:+--opt $o} 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); r = d['roofline']
 print('Gpts/s', d['value'], 'us/step', round(1000 * d['ms_per_step'], 1), {k: round(1000 * v['avg_ms'], 1) for k, v in r['kernels'].items()})" >> $R/ab_switches.log

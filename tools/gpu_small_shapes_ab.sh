@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 run() {
-  timeout 300 python bench.py --steps 1500 --warmup 50 --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
+  timeout 300 python bench.py --full --steps 1500 --warmup 50 --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.readline()); k=d['roofline'].get('kernels',{})

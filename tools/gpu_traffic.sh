@@ -3,11 +3,12 @@
 # (FETCH_SIZE and WRITE_SIZE do not fit one pass).  Writes gpurun_out/traffic_<tag>.json
 # usage: gpurun -- bash tools/gpu_traffic.sh <tag> [bench args]
 tag=$1; shift
+repo=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   out=$GRAFT_REPO_ROOT/gpurun_out/pmc_${tag}_$c
   mkdir -p $out
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out -o pmc -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-check --preheat-s 0 "$@" > $out/bench.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out -o pmc -- python3 "$repo/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-check --preheat-s 0 "$@" > $out/bench.log 2>&1
 done
 python3 - $GRAFT_REPO_ROOT/gpurun_out $tag <<'PY'
 import csv, sys, collections, json, glob, os

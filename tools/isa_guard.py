@@ -23,7 +23,10 @@ MFMA = re.compile(r"\bv_mfma_")
 def code_objects(lib_path, tmp):
     """-> paths of the gfx950 code objects of every offload bundle in the library."""
     fat = os.path.join(tmp, "fat.bin")
-    subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, lib_path], check=True)
+    # (output "-" = stdout, discarded: without an output file llvm-objcopy rewrites its input in place, and a process
+    # that has the library loaded would then map a second copy of it on its next dlopen)
+    subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, lib_path, "-"], check=True,
+                   stdout=subprocess.DEVNULL)
     blob = open(fat, "rb").read()
     starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
     out = []

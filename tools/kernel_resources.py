@@ -19,7 +19,10 @@ def code_objects(path, tmp):
     the concatenation of its objects' offload bundles (each starts with the bundler's magic string; the unbundler
     itself only reads the first one)."""
     fat = os.path.join(tmp, "fat.bin")
-    subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, path], check=True)
+    # (output "-" = stdout, discarded: without an output file llvm-objcopy rewrites its input in place, and a process
+    # that has the library loaded would then map a second copy of it on its next dlopen)
+    subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, path, "-"], check=True,
+                   stdout=subprocess.DEVNULL)
     blob = open(fat, "rb").read()
     magic = b"__CLANG_OFFLOAD_BUNDLE__"
     starts = [m.start() for m in re.finditer(re.escape(magic), blob)] or [0]
