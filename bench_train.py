@@ -13,7 +13,7 @@ features (N(0,1)), positional embeddings, matcher / criterion (a dummy regressio
 class and box heads).  One process per GPU; gradients are all-reduced by DistributedDataParallel
 (RCCL with backend "nccl", gloo in the CPU test) -- the operator itself never communicates.
 
-  python bench_train.py [--steps 30 --warmup 10 --dtype bf16|fp32 --fused-grid --fused-pointwise
+  python bench_train.py [--steps 30 --warmup 10 --dtype bf16|fp16|fp32 --fused-grid --fused-pointwise
                          --model 2d|3d --mask-decoder --split-k-wgrad --graph]
   python bench_train.py --gpus N          (starts its own N ranks; or under torch.distributed.run)
 prints ONE JSON line on rank 0: ms per step (MAX over ranks), images/s, operator share.
@@ -154,8 +154,8 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=2)
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"],
-                    help="bf16: autocast for the dense layers + the operator's native bf16 mode")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"],
+                    help="bf16 / fp16: autocast for the dense layers + the operator's native bf16 / fp16 mode")
     ap.add_argument("--fused-grid", nargs="?", const=1, default=0, type=int,
                     help="1: grid construction in one kernel each way; 2: inside the sampling kernels")
     ap.add_argument("--graph", action="store_true",
@@ -199,6 +199,7 @@ def main():
                            use_mask=args.mask_decoder and args.model == "2d").to(device)
     for m in model.attention_modules():
         m.native_bf16 = args.dtype == "bf16"
+        m.native_f16 = args.dtype == "fp16"
         m.fused_grid = args.fused_grid
         m.fused_pointwise = args.fused_pointwise
         with torch.no_grad():                                # trained-like box offsets
@@ -212,7 +213,7 @@ def main():
         raise SystemExit("--graph captures a single-GPU step (the DDP all-reduce is not captured)")
     opt = torch.optim.AdamW(model.parameters(), lr=1e-4, capturable=args.graph)
     batch = make_batch(levels, args.batch, 256, device, seed=100 + rank)
-    amp = torch.bfloat16 if args.dtype == "bf16" else None
+    amp = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.dtype)
 
     for _ in range(args.warmup):
         train_step(model, opt, batch, amp)

@@ -64,10 +64,14 @@ _ll = ctypes.c_longlong
 _POINTWISE_SIGNATURES = {
     "boxattn_softmax_fwd_f32": [_vp, _ll, _i, _vp, _vp],
     "boxattn_softmax_fwd_bf16": [_vp, _ll, _i, _vp, _vp],
+    "boxattn_softmax_fwd_f16": [_vp, _ll, _i, _vp, _vp],
     "boxattn_softmax_bwd_f32": [_vp, _vp, _ll, _i, _vp, _vp],
     "boxattn_softmax_bwd_bf16": [_vp, _vp, _ll, _i, _vp, _vp],
+    "boxattn_softmax_bwd_f16": [_vp, _vp, _ll, _i, _vp, _vp],
     "boxattn_value_prep_f32": [_vp, _vp, _ll, _i, _vp, _vp],
     "boxattn_value_prep_bf16": [_vp, _vp, _ll, _i, _vp, _vp],
+    "boxattn_value_prep_f32_f16": [_vp, _vp, _ll, _i, _vp, _vp],     # float32 -> f16
+    "boxattn_value_prep_f16": [_vp, _vp, _ll, _i, _vp, _vp],
 }
 _GRID_SIGNATURES = {
     # ref, ref_dim, ref_per_head, offsets, V, angle_mode, kernel_idx, valid_ratios, [grad_grid,]
@@ -78,12 +82,14 @@ _GRID_SIGNATURES = {
 EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "boxattn_set_option",
            "boxattn_options_epoch",
            "boxattn_set_debug_buffer",
-           "boxattn_fwd_hl_f32", "boxattn_fwd_hl_bf16", *sorted(_POINTWISE_SIGNATURES),
+           "boxattn_fwd_hl_f32", "boxattn_fwd_hl_bf16", "boxattn_fwd_hl_f16", *sorted(_POINTWISE_SIGNATURES),
            "boxattn_profile_begin", "boxattn_profile_end", "boxattn_bwd_workspace_bytes",
            "boxattn_plan_bytes", "boxattn_state_bytes",
            "boxattn_grid_fwd_f32", "boxattn_grid_bwd_f32"] + [
-    "%s_%s" % (stem, suf) for stem in _SIGNATURES for suf in ("f32", "f64", "bf16")] + [
-    "%s_%s" % (stem, suf) for stem in _WS_SIGNATURES for suf in ("f32", "bf16")]
+    "%s_%s" % (stem, suf) for stem in _SIGNATURES for suf in ("f32", "f64", "bf16", "f16")] + [
+    "%s_%s" % (stem, suf) for stem in _WS_SIGNATURES for suf in ("f32", "bf16", "f16")]
+# 16-bit storage types: the suffix of their entry points, which share signatures (uint16_t storage)
+H16_SUFFIXES = ("bf16", "f16")
 ABI_VERSION = 8
 
 
@@ -186,18 +192,18 @@ def load():
     lib.boxattn_set_variant.argtypes = [_i]
     lib.boxattn_set_variant.restype = _i
     for stem, args in _SIGNATURES.items():
-        for suf in ("f32", "f64", "bf16"):
+        for suf in ("f32", "f64") + H16_SUFFIXES:
             fn = getattr(lib, "%s_%s" % (stem, suf))
-            extra = [_vp] if (suf == "bf16" and stem.endswith("bwd")) else []
+            extra = [_vp] if (suf in H16_SUFFIXES and stem.endswith("bwd")) else []
             fn.argtypes = args[:-1] + extra + args[-1:]        # ..., [grad_value_ws], stream
             fn.restype = _i
     for stem, args in _WS_SIGNATURES.items():
-        for suf in ("f32", "bf16"):
+        for suf in ("f32",) + H16_SUFFIXES:
             fn = getattr(lib, "%s_%s" % (stem, suf))
             fn.argtypes = args
             fn.restype = _i
     for stem, args in _HL_SIGNATURES.items():
-        for suf in ("f32", "bf16"):
+        for suf in ("f32",) + H16_SUFFIXES:
             fn = getattr(lib, "%s_%s" % (stem, suf))
             fn.argtypes = args
             fn.restype = _i

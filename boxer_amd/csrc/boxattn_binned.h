@@ -410,7 +410,7 @@ void binned_accumulate_kernel(
             r.y = __uint_as_float(rw[(2 * i + 1) / 4][(2 * i + 1) % 4]);
         } else {
             const unsigned wd = rw[i / 4][i % 4];
-            r.x = __uint_as_float(wd << 16); r.y = __uint_as_float(wd & 0xffff0000u);
+            r.x = Half16<ST>::lo(wd); r.y = Half16<ST>::hi(wd);
         }
         return r;
     };
@@ -522,8 +522,7 @@ void binned_accumulate_kernel(
         };
         auto fetched_elem = [](const u32x4 &v, int e) -> float {   // element e of a 16-byte piece
             if constexpr (sizeof(ST) == 4) return __uint_as_float(v[e]);
-            else return (e & 1) ? __uint_as_float(v[e / 2] & 0xffff0000u)
-                                : __uint_as_float(v[e / 2] << 16);
+            else return (e & 1) ? Half16<ST>::hi(v[e / 2]) : Half16<ST>::lo(v[e / 2]);
         };
 #define BOXATTN_FETCH_ROWS()                                                                    \
     _Pragma("unroll") for (int ps = 0; ps < NPASS; ++ps) {                                      \

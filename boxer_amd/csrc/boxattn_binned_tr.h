@@ -1,6 +1,7 @@
-// The matrix-core accumulate of the destination-binned backward for bf16 storage: one round of 64 records
+// The matrix-core accumulate of the destination-binned backward for 16-bit storage: one round of 64 records
 // against the 32 pixels of a block is the product grad_value^T[c][pixel] += G^T[c][k] A^T[k][pixel] on
-// v_mfma_f32_32x32x16_bf16 (A split into two bf16 terms), built around the instruction count.  The SQ
+// v_mfma_f32_32x32x16_bf16 (A split into two bf16 terms), or for f16 storage on v_mfma_f32_32x32x16_f16 with
+// two f16 terms (Half16<ST>, boxattn_device.h), built around the instruction count.  The SQ
 // counters of round 3 show every kernel of the step retiring one instruction per SIMD every
 // ~4 cycles whatever its type -- scalar instructions included -- so the 420 instructions the first version
 // of this kernel (rounds 1-2) issued per round WERE its 50 us.  Where they went, and what replaces them:
@@ -56,7 +57,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
     const int *__restrict__ records, ST *__restrict__ grad_value, float *__restrict__ partials, ChunkCombine cc,
     ZeroRole zr)
 {
-    static_assert(sizeof(ST) == 2, "bf16 storage");
+    static_assert(IsHalf16<ST>::value, "16-bit storage");
+    typedef Half16<ST> H16;
+    typedef typename H16::x8 tr_h16x8;
     static_assert(C == 16 || C == 32 || C == 64, "channels per head");
     constexpr int BW = 8, PB = 32, R = 64;
     constexpr int CP = C < 32 ? 32 : C;            // operand rows: channels padded to the MFMA's 32
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
                 fetch_rows(rec_n2, ahead);
                 rec_n3 = fetch_rec(rr + 3 * R);
             }
-            // ---- lane = record: its <= 4 weights go to A^T[pixel][lane] as hi + lo bf16
+            // ---- lane = record: its <= 4 weights go to A^T[pixel][lane] as hi + lo 16-bit terms
             const float x = __int_as_float(rec_c.y), y = __int_as_float(rec_c.z), a = __int_as_float(rec_c.w);
             float h_im, w_im;
             {
@@ -187,9 +190,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
             const float hh = 1.f - lh, hw = 1.f - lw;
             const float ha = hh * a, la = lh * a;
             const float w0 = ha * hw, w1 = ha * lw, w2 = la * hw, w3 = la * lw;
-            const unsigned hi01 = pack_bf16x2(w0, w1), hi23 = pack_bf16x2(w2, w3);
-            const unsigned lo01 = pack_bf16x2(w0 - __uint_as_float(hi01 << 16), w1 - __uint_as_float(hi01 & 0xffff0000u));
-            const unsigned lo23 = pack_bf16x2(w2 - __uint_as_float(hi23 << 16), w3 - __uint_as_float(hi23 & 0xffff0000u));
+            const unsigned hi01 = H16::pack(w0, w1), hi23 = H16::pack(w2, w3);
+            const unsigned lo01 = H16::pack(w0 - H16::lo(hi01), w1 - H16::hi(hi01));
+            const unsigned lo23 = H16::pack(w2 - H16::lo(hi23), w3 - H16::hi(hi23));
             // byte offsets of the corners' rows / columns inside A^T, kBig when outside the block (idle lanes: all)
             const int r0 = (unsigned)py < (unsigned)bh ? __mul24(py, BW * ASB) : kBig;
             const int r1 = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * ASB) + BW * ASB : kBig;
@@ -204,17 +207,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
             put(2, (unsigned short)(hi23 & 0xffffu)); put(3, (unsigned short)(hi23 >> 16));
             wave_lds_sync();
             // ---- the product: 4 K-steps of 16 records per 32-channel block, hi term then lo term
-            tr_bf16x8 g[R / 16][NCB];
+            tr_h16x8 g[R / 16][NCB];
 #pragma unroll
             for (int t = 0; t < R / 16; ++t) {
-                const tr_bf16x8 p_hi = __builtin_bit_cast(
-                    tr_bf16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + a_off + 32 * t));
+                const tr_h16x8 p_hi = __builtin_bit_cast(
+                    tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + a_off + 32 * t));
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb) {
                     const uint2 g0 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024);
                     const uint2 g1 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024 + 256);
-                    g[t][cb] = __builtin_bit_cast(tr_bf16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
-                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g[t][cb], p_hi, acc[cb], 0, 0, 0);
+                    g[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
+                    acc[cb] = H16::mfma32x32x16(g[t][cb], p_hi, acc[cb]);
                 }
             }
             wave_lds_sync();                         // a wave's LDS operations execute in order
@@ -223,11 +226,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
             wave_lds_sync();
 #pragma unroll
             for (int t = 0; t < R / 16; ++t) {
-                const tr_bf16x8 p_lo = __builtin_bit_cast(
-                    tr_bf16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + a_off + 32 * t));
+                const tr_h16x8 p_lo = __builtin_bit_cast(
+                    tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + a_off + 32 * t));
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb)
-                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g[t][cb], p_lo, acc[cb], 0, 0, 0);
+                    acc[cb] = H16::mfma32x32x16(g[t][cb], p_lo, acc[cb]);
             }
             wave_lds_sync();
             // ---- clear this round's weights, stage the next round's rows (they have arrived)
@@ -258,7 +261,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
             for (int cb = 0; cb < NCB; ++cb) {
                 unsigned pk[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) pk[i] = pack_bf16x2(acc[cb][2 * i], acc[cb][2 * i + 1]);
+                for (int i = 0; i < 8; ++i) pk[i] = H16::pack(acc[cb][2 * i], acc[cb][2 * i + 1]);
                 // pk[2 g], pk[2 g + 1]: channels 8 g + 4 kb + 0..3.  After swap(g = 0, g = 1) the lanes of
                 // kb = 0 hold channels 0-7 and those of kb = 1 channels 8-15; g = 2, 3 alike (+ 16).
                 u32x4 piece_lo, piece_hi;

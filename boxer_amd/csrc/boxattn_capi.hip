@@ -319,12 +319,12 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
     if constexpr (!std::is_same<ST, double>::value) {
         if (fast_ok<ST>(d, value, loc, out, INST ? (const void *)mask : (const void *)out,
                         out)) {
-            if constexpr (!INST && std::is_same<ST, bf16_t>::value) {     // encoder case: window-staged matrix-core forward
+            if constexpr (!INST && IsHalf16<ST>::value) {     // encoder case: window-staged matrix-core forward
                 DensePlan dp;
                 if (allow_dense && shapes_host && lsi_host && aligned(value, 16) && aligned(out, 16) &&
                     aligned(loc, 8) && make_dense_plan(d, shapes_host, lsi_host, dp, 2)) {
                     ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
-                    launch_fwd_dense(value, loc, w_sp, out, dp, (unsigned)(d.n_value() * sizeof(bf16_t)),
+                    launch_fwd_dense<ST>(value, loc, w_sp, out, dp, (unsigned)(d.n_value() * sizeof(ST)),
                                      count_ride ? *count_ride : BinRide{}, stats, st);
                     if (count_ride && ride_taken) *ride_taken = true;
                     return finish();
@@ -413,7 +413,7 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
 }
 
 // ----------------------------------------------------------------------------- backward
-// GV = accumulation buffer for grad_value (the output itself for f32/f64, scratch for bf16)
+// GV = accumulation buffer for grad_value (the output itself for f32/f64, scratch for bf16 / f16)
 template <typename ST, bool INST>
 int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                const typename Storage<ST>::compute *loc,
@@ -484,11 +484,15 @@ int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
         int rc = finish();
         if (rc) return rc;
     }
-    if constexpr (std::is_same<ST, bf16_t>::value) {
+    if constexpr (IsHalf16<ST>::value) {
         if (nv) {
             const int blocks = (int)std::min<size_t>((nv / 4 + 255) / 256 + 1, 256 * 16);
-            hipLaunchKernelGGL(cvt_f32_to_bf16_kernel, dim3(blocks), dim3(256), 0, st,
-                               grad_value_acc, grad_value, nv);
+            if constexpr (std::is_same<ST, bf16_t>::value)
+                hipLaunchKernelGGL(cvt_f32_to_bf16_kernel, dim3(blocks), dim3(256), 0, st,
+                                   grad_value_acc, grad_value, nv);
+            else
+                hipLaunchKernelGGL(cvt_f32_to_f16_kernel, dim3(blocks), dim3(256), 0, st,
+                                   grad_value_acc, grad_value, nv);
             return finish();
         }
     }
@@ -605,10 +609,10 @@ void launch_pointgrad(const ST *value, const int64_t *shapes, const int64_t *lsi
 {
     if (ride_taken) *ride_taken = false;
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], st);
-    if constexpr (std::is_same<ST, bf16_t>::value && !INST) {
+    if constexpr (IsHalf16<ST>::value && !INST) {
         if (dense_pointgrad_ok(dp, value, loc, w_sp, grad_out, grad_loc, grad_sp)) {
-            launch_pointgrad_dense(value, loc, w_sp, grad_out, *dp, grad_loc, grad_sp,
-                                   (unsigned)(d.n_value() * sizeof(bf16_t)), st, fill_ride ? *fill_ride : BinRide{});
+            launch_pointgrad_dense<ST>(value, loc, w_sp, grad_out, *dp, grad_loc, grad_sp,
+                                   (unsigned)(d.n_value() * sizeof(ST)), st, fill_ride ? *fill_ride : BinRide{});
             if (fill_ride && ride_taken) *ride_taken = true;
             return;
         }
@@ -685,9 +689,9 @@ int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, cons
     const int ns = d.B * d.H, ns8 = (ns + 7) / 8 * 8;
     const int wg_per_slice = std::min(kAccWgCap, std::max(1, plan.item_cap));
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdAccum], st);
-    if constexpr (std::is_same<ST, bf16_t>::value && !INST) {
+    if constexpr (IsHalf16<ST>::value && !INST) {
         if (acc == kAccTr) {
-            launch_accumulate_tr(C, grad_out, (size_t)d.B * d.Lq * d.H * C * sizeof(ST), plan, d.S, d.H, d.Lq, items,
+            launch_accumulate_tr<ST>(C, grad_out, (size_t)d.B * d.Lq * d.H * C * sizeof(ST), plan, d.S, d.H, d.Lq, items,
                                  n_items, records, grad_value, partials, wg_per_slice, ns8, cc, zr, st);
             return finish();
         }
@@ -804,7 +808,7 @@ int launch_bwd_ws(const ST *value, const int64_t *shapes, const int64_t *lsi, co
                   size_t workspace_bytes, const void *plan_buf, size_t plan_bytes, int hints, hipStream_t st,
                   void *state = nullptr, size_t state_bytes = 0)
 {
-    constexpr bool kBf16 = std::is_same<ST, bf16_t>::value;
+    constexpr bool kH16 = IsHalf16<ST>::value;           // 16-bit storage (bf16 / f16): float32 scratch for the atomics
     if (!d.valid()) return (int)hipErrorInvalidValue;
     BinPlan plan;
     const size_t nv = d.n_value();
@@ -818,7 +822,7 @@ int launch_bwd_ws(const ST *value, const int64_t *shapes, const int64_t *lsi, co
     bool plan_ready = false;
     if (binned) {
         pl = plan_layout(d, plan);
-        sl = scratch_layout(d, plan, wide_workspace(kBf16, d));
+        sl = scratch_layout(d, plan, wide_workspace(kH16, d));
         plan_ready = plan_buf && plan_bytes >= pl.total && aligned(plan_buf, 256);
         binned = workspace_bytes >= (plan_ready ? sl.total : pl.total + sl.total);
     }
@@ -827,7 +831,7 @@ int launch_bwd_ws(const ST *value, const int64_t *shapes, const int64_t *lsi, co
         // unaligned grad_out view -- rule the binned path out: the atomic path needs no plan)
         if (g_variant == 3) return (int)hipErrorInvalidValue;
         float *acc = nullptr;
-        if constexpr (kBf16) {
+        if constexpr (kH16) {
             if (!workspace || workspace_bytes < nv * sizeof(float)) return (int)hipErrorInvalidValue;
             acc = (float *)workspace;
         } else {
@@ -956,6 +960,12 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
 }  // namespace
 
 
+namespace {
+// the C ABI passes 16-bit storage as uint16_t; f16 storage is f16_t inside
+inline const f16_t *as_f16(const uint16_t *p) { return reinterpret_cast<const f16_t *>(p); }
+inline f16_t *as_f16(uint16_t *p) { return reinterpret_cast<f16_t *>(p); }
+}  // namespace
+
 extern "C" {
 
 #define DIMS Dims{B, S, H, C, L, Lq, P}
@@ -979,6 +989,15 @@ int boxattn_fwd_train_bf16(const uint16_t *value, const int64_t *shapes, const i
     return launch_fwd_train<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
                                            shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
 }
+int boxattn_fwd_train_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *loc, const float *attn, int B, int S, int H, int C, int L,
+                          int Lq, int P, uint16_t *out, const int64_t *shapes_host,
+                          const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
+                          size_t state_bytes, int hints, int *plan_built, void *stream)
+{
+    return launch_fwd_train<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, DIMS, as_f16(out), nullptr,
+                                           shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
+}
 int instattn_fwd_train_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                            const float *loc, const float *spatial_w, const float *level_w, int B,
                            int S, int H, int C, int L, int Lq, int P, float *out, float *mask_out,
@@ -998,11 +1017,21 @@ int instattn_fwd_train_bf16(const uint16_t *value, const int64_t *shapes, const 
     return launch_fwd_train<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out, mask_out,
                                           shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
 }
+int instattn_fwd_train_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *loc, const float *spatial_w, const float *level_w, int B,
+                           int S, int H, int C, int L, int Lq, int P, uint16_t *out,
+                           uint16_t *mask_out, const int64_t *shapes_host,
+                           const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
+                           size_t state_bytes, int hints, int *plan_built, void *stream)
+{
+    return launch_fwd_train<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, DIMS, as_f16(out), as_f16(mask_out),
+                                          shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
+}
 
-size_t boxattn_plan_bytes(int is_bf16, int B, int S, int H, int C, int L, int Lq, int P,
+size_t boxattn_plan_bytes(int is_16bit, int B, int S, int H, int C, int L, int Lq, int P,
                           const int64_t *shapes_host, const int64_t *lsi_host)
 {
-    (void)is_bf16;
+    (void)is_16bit;
     const Dims d = DIMS;
     BinPlan plan;
     if (!d.valid() || !make_plan(d, shapes_host, lsi_host, plan)) return 0;
@@ -1018,16 +1047,16 @@ size_t boxattn_state_bytes(int B, int S, int H, int C, int L, int Lq, int P, con
     return state_layout(d, planned ? &plan : nullptr).total;
 }
 
-size_t boxattn_bwd_workspace_bytes(int is_bf16, int B, int S, int H, int C, int L, int Lq, int P,
+size_t boxattn_bwd_workspace_bytes(int is_16bit, int B, int S, int H, int C, int L, int Lq, int P,
                                    const int64_t *shapes_host, const int64_t *lsi_host)
 {
     const Dims d = DIMS;
     if (!d.valid()) return 0;
-    const size_t fallback = is_bf16 ? align_up(d.n_value() * sizeof(float)) : 0;
+    const size_t fallback = is_16bit ? align_up(d.n_value() * sizeof(float)) : 0;
     BinPlan plan;
     if (!make_plan(d, shapes_host, lsi_host, plan)) return fallback;
     return std::max(fallback, plan_layout(d, plan).total +
-                                  scratch_layout(d, plan, wide_workspace(is_bf16 != 0, d)).total);
+                                  scratch_layout(d, plan, wide_workspace(is_16bit != 0, d)).total);
 }
 
 int boxattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -1051,6 +1080,18 @@ int boxattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int6
 {
     return launch_bwd_ws<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
                                         grad_value, grad_loc, grad_attn, nullptr, shapes_host, lsi_host,
+                                        workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
+}
+int boxattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                       const float *loc, const float *attn, const uint16_t *grad_out, int B,
+                       int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
+                       float *grad_loc, float *grad_attn, const int64_t *shapes_host,
+                       const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                       const void *plan, size_t plan_bytes, void *state,
+       size_t state_bytes, int hints, void *stream)
+{
+    return launch_bwd_ws<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr, DIMS,
+                                        as_f16(grad_value), grad_loc, grad_attn, nullptr, shapes_host, lsi_host,
                                         workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
 }
 int instattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -1079,6 +1120,19 @@ int instattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int
                                        grad_value, grad_loc, grad_spatial_w, grad_level_w, shapes_host,
                                        lsi_host, workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
 }
+int instattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                        const float *loc, const float *spatial_w, const float *level_w,
+                        const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
+                        int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
+                        float *grad_spatial_w, float *grad_level_w, const int64_t *shapes_host,
+                        const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                        const void *plan, size_t plan_bytes, void *state,
+       size_t state_bytes, int hints, void *stream)
+{
+    return launch_bwd_ws<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out), as_f16(grad_mask), DIMS,
+                                       as_f16(grad_value), grad_loc, grad_spatial_w, grad_level_w, shapes_host,
+                                       lsi_host, workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
+}
 
 
 int boxattn_abi_version(void) { return BOXATTN_ABI_VERSION; }
@@ -1086,9 +1140,9 @@ int boxattn_abi_version(void) { return BOXATTN_ABI_VERSION; }
 const char *boxattn_build_info(void)
 {
     return "boxattn gfx950 (CDNA4, wave64) | hipcc " __VERSION__
-           " | kernels: generic{f32,f64,bf16}, gather{f32 4ch/lane, bf16 8ch/lane} C={16,32,64}, "
-           "window-staged encoder forward + point gradients{bf16 on MFMA 4x4x4, f32 on VALU}, "
-           "binned-bwd{bf16 on MFMA 32x32x16, f32 on the same MFMA over exact three-term bf16 splits} "
+           " | kernels: generic{f32,f64,bf16,f16}, gather{f32 4ch/lane, bf16/f16 8ch/lane} C={16,32,64}, "
+           "window-staged encoder forward + point gradients{bf16/f16 on MFMA 4x4x4, f32 on VALU}, "
+           "binned-bwd{bf16/f16 on MFMA 32x32x16, f32 on the bf16 MFMA over exact three-term bf16 splits} "
            "with fill / combine riding in the point-gradient and accumulate launches, "
            "one-pass fill into guessed bin ranges (caller-owned state), box-grid{f32} | abi 8";
 }
@@ -1152,6 +1206,13 @@ int boxattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t
     return launch_fwd<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out,
                                      nullptr, ST_);
 }
+int boxattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                    const float *loc, const float *attn, int B, int S, int H, int C, int L,
+                    int Lq, int P, uint16_t *out, void *stream)
+{
+    return launch_fwd<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, DIMS, as_f16(out),
+                                     nullptr, ST_);
+}
 
 int boxattn_fwd_hl_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                        const float *loc, const float *attn, int B, int S, int H, int C, int L,
@@ -1167,6 +1228,14 @@ int boxattn_fwd_hl_bf16(const uint16_t *value, const int64_t *shapes, const int6
                         const int64_t *lsi_host, void *stream)
 {
     return launch_fwd<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
+                                     ST_, shapes_host, lsi_host);
+}
+int boxattn_fwd_hl_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                       const float *loc, const float *attn, int B, int S, int H, int C, int L,
+                       int Lq, int P, uint16_t *out, const int64_t *shapes_host,
+                       const int64_t *lsi_host, void *stream)
+{
+    return launch_fwd<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, DIMS, as_f16(out), nullptr,
                                      ST_, shapes_host, lsi_host);
 }
 
@@ -1197,6 +1266,15 @@ int boxattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t
                                      DIMS, grad_value, grad_loc, grad_attn, nullptr,
                                      grad_value_ws, ST_);
 }
+int boxattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                    const float *loc, const float *attn, const uint16_t *grad_out, int B,
+                    int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
+                    float *grad_loc, float *grad_attn, float *grad_value_ws, void *stream)
+{
+    return launch_bwd<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr,
+                                     DIMS, as_f16(grad_value), grad_loc, grad_attn, nullptr,
+                                     grad_value_ws, ST_);
+}
 
 int instattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                      const float *loc, const float *spatial_w, const float *level_w, int B,
@@ -1221,6 +1299,14 @@ int instattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_
 {
     return launch_fwd<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out,
                                     mask_out, ST_);
+}
+int instattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                     const float *loc, const float *spatial_w, const float *level_w, int B,
+                     int S, int H, int C, int L, int Lq, int P, uint16_t *out,
+                     uint16_t *mask_out, void *stream)
+{
+    return launch_fwd<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, DIMS, as_f16(out),
+                                    as_f16(mask_out), ST_);
 }
 
 int instattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -1252,6 +1338,17 @@ int instattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_
 {
     return launch_bwd<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out,
                                     grad_mask, DIMS, grad_value, grad_loc, grad_spatial_w,
+                                    grad_level_w, grad_value_ws, ST_);
+}
+int instattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                     const float *loc, const float *spatial_w, const float *level_w,
+                     const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
+                     int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
+                     float *grad_spatial_w, float *grad_level_w, float *grad_value_ws,
+                     void *stream)
+{
+    return launch_bwd<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out),
+                                    as_f16(grad_mask), DIMS, as_f16(grad_value), grad_loc, grad_spatial_w,
                                     grad_level_w, grad_value_ws, ST_);
 }
 

@@ -45,7 +45,7 @@ namespace boxattn {
 #endif
 typedef unsigned int dense_u32x4 __attribute__((ext_vector_type(4)));
 
-// one 64-byte row (32 bf16 channels) as 16 words.  (The words go through a plain array: a bit_cast
+// one 64-byte row (32 bf16 / f16 channels) as 16 words.  (The words go through a plain array: a bit_cast
 // of element i of an ext_vector selects element 0 for every i with this compiler)
 template <typename PTR> __device__ __forceinline__ void dense_load_row(PTR p, unsigned (&w)[16])
 {
@@ -55,16 +55,15 @@ template <typename PTR> __device__ __forceinline__ void dense_load_row(PTR p, un
         w[4 * i] = t.x; w[4 * i + 1] = t.y; w[4 * i + 2] = t.z; w[4 * i + 3] = t.w;
     }
 }
+template <typename ST>
 __device__ __forceinline__ float dense_dot_row(const unsigned (&g)[16], const unsigned (&v)[16])
 {
-    // bf16 x bf16 products are exact in fp32; two chains: a v_dot2c waits for its own accumulator
+    // 16-bit x 16-bit products are exact in fp32; two chains: a v_dot2c waits for its own accumulator
     float d0 = 0.f, d1 = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; i += 2) {
-        d0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, g[i]),
-                                             __builtin_bit_cast(bf16x2_t, v[i]), d0, false);
-        d1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, g[i + 1]),
-                                             __builtin_bit_cast(bf16x2_t, v[i + 1]), d1, false);
+        d0 = Half16<ST>::dot2(g[i], v[i], d0);
+        d1 = Half16<ST>::dot2(g[i + 1], v[i + 1], d1);
     }
     return d0 + d1;
 }
@@ -251,9 +250,10 @@ __device__ __forceinline__ DensePoint dense_locate(float x, float y, int H, int 
 // The four corner sums S_k = sum_c g_c v_k,c of one sample point: from the staged window if the part of
 // its footprint that lies inside the map lies inside the window, else from global memory (`slow`,
 // decided per lane, entered per wave).  Corners outside the map give exactly 0.
+template <typename ST>
 __device__ __forceinline__ void dense_corner_sums(const DensePoint &s, const DenseMap &T, const DenseWinPos &o,
                                                   const unsigned char *lds, const unsigned (&gw)[16],
-                                                  const bf16_t *value, unsigned row0, int H, int h, bool vq,
+                                                  const ST *value, unsigned row0, int H, int h, bool vq,
                                                   int lane_p, float (&sk)[4])
 {
     constexpr int C = 32;
@@ -289,7 +289,7 @@ __device__ __forceinline__ void dense_corner_sums(const DensePoint &s, const Den
             unsigned va[16], vb[16];
             dense_load_row(lds + slot[k0], va);
             dense_load_row(lds + slot[k0 + 1], vb);
-            const float da = dense_dot_row(gw, va), db = dense_dot_row(gw, vb);
+            const float da = dense_dot_row<ST>(gw, va), db = dense_dot_row<ST>(gw, vb);
             sk[k0] = __uint_as_float(__float_as_uint(da) & m[k0]);
             sk[k0 + 1] = __uint_as_float(__float_as_uint(db) & m[k0 + 1]);
         }
@@ -298,7 +298,7 @@ __device__ __forceinline__ void dense_corner_sums(const DensePoint &s, const Den
         for (int k = 0; k < 4; ++k) {
             unsigned va[16];
             dense_load_row(lds + slot[k], va);
-            sk[k] = __uint_as_float(__float_as_uint(dense_dot_row(gw, va)) & m[k]);
+            sk[k] = __uint_as_float(__float_as_uint(dense_dot_row<ST>(gw, va)) & m[k]);
         }
 #endif
     } else {
@@ -344,8 +344,7 @@ __device__ __forceinline__ void dense_corner_sums(const DensePoint &s, const Den
                     float dd = 0.f;
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        dd = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, gch[i]),
-                                                            __builtin_bit_cast(bf16x2_t, vw[i]), dd, false);
+                        dd = Half16<ST>::dot2(gch[i], vw[i], dd);
                     part[k] = group_sum<4>(dd);
                 }
                 if (p == t0 + u && slow) {
@@ -359,10 +358,10 @@ __device__ __forceinline__ void dense_corner_sums(const DensePoint &s, const Den
 
 constexpr int kDenseResFloats = 16 * 16 * 3;       // per wave: the results of 16 queries x 16 points
 
-template <int L>
+template <typename ST, int L>
 __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel(
-    const bf16_t *__restrict__ value, const float *__restrict__ loc, const float *__restrict__ attn,
-    const bf16_t *__restrict__ grad_out, float *__restrict__ grad_loc, float *__restrict__ grad_attn,
+    const ST *__restrict__ value, const float *__restrict__ loc, const float *__restrict__ attn,
+    const ST *__restrict__ grad_out, float *__restrict__ grad_loc, float *__restrict__ grad_attn,
     DensePlan pl, unsigned value_bytes, BinRide ride)
 {
     constexpr int C = 32, P = 4, LP = L * P;
@@ -413,7 +412,7 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
     const unsigned pt0 = qh * (unsigned)LP;
     const float2 *loc2 = reinterpret_cast<const float2 *>(loc);
     const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t *>(value), 0, value_bytes, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<ST *>(value), 0, value_bytes, 0x00020000);
     // the window rows first: they are what the workgroup's barrier waits for; the lane's own inputs
     // (locations, weights, grad_out row) are requested behind them and land while the rows are staged
     DenseWinPos win[L];
@@ -462,7 +461,7 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
         const DenseMap T = hot.lv[l];
         const DensePoint s = dense_locate(xy[l].x, xy[l].y, T.H, T.W);
         float sk[4];
-        dense_corner_sums(s, T, win[l], win_lds, gw, value, t.b * (unsigned)hot.S + (unsigned)T.start, H, h, vq, p, sk);
+        dense_corner_sums<ST>(s, T, win[l], win_lds, gw, value, t.b * (unsigned)hot.S + (unsigned)T.start, H, h, vq, p, sk);
         const float w1 = s.hh * s.hw, w2 = s.hh * s.lw, w3 = s.lh * s.hw, w4 = s.lh * s.lw;
         const float gs_ = w1 * sk[0] + w2 * sk[1] + w3 * sk[2] + w4 * sk[3];
         const float al = BOXATTN_TUNE_PG_STASH ? a_stash[l] : a[l];

@@ -1,5 +1,5 @@
 // Translation unit of the kernels that run float32 VALU arithmetic next to MFMAs: the window-staged
-// encoder kernels (boxattn_dense.h) and the matrix-core accumulate (boxattn_binned_tr.h).  Built with
+// encoder kernels (boxattn_dense.h) and the matrix-core accumulate (boxattn_binned_tr.h), bf16 and f16.  Built with
 // -fno-slp-vectorize (boxer_amd/_lib.py SOURCES): a packed float32 instruction
 // (v_pk_mul_f32 / v_pk_fma_f32, which the SLP vectoriser makes of neighbouring scalar operations) issued
 // while an MFMA of the same wave is completing was seen to return wrong values on MI355X.
@@ -17,15 +17,16 @@ static BinRide place_riders(BinRide ride, unsigned own_blocks, unsigned *total)
     return ride;
 }
 
-void launch_pointgrad_dense(const uint16_t *value, const float *loc, const float *attn,
-                            const uint16_t *grad_out, const DensePlan &dp, float *grad_loc,
+template <typename ST>
+void launch_pointgrad_dense(const ST *value, const float *loc, const float *attn,
+                            const ST *grad_out, const DensePlan &dp, float *grad_loc,
                             float *grad_attn, unsigned value_bytes, hipStream_t st, const BinRide &ride_in)
 {
     unsigned total = 0;
     const BinRide ride = place_riders(ride_in, dense_blocks(dp), &total);
 #define BOXATTN_DENSE_PG(LV_)                                                                           \
     case LV_:                                                                                           \
-        hipLaunchKernelGGL((pointgrad_dense_kernel<LV_>), dim3(total), dim3(256), 0, st, value, loc, attn, \
+        hipLaunchKernelGGL((pointgrad_dense_kernel<ST, LV_>), dim3(total), dim3(256), 0, st, value, loc, attn, \
                            grad_out, grad_loc, grad_attn, dp, value_bytes, ride);                      \
         break;
     switch (dp.L) {
@@ -34,7 +35,8 @@ void launch_pointgrad_dense(const uint16_t *value, const float *loc, const float
 #undef BOXATTN_DENSE_PG
 }
 
-void launch_fwd_dense(const uint16_t *value, const float *loc, const float *attn, uint16_t *out,
+template <typename ST>
+void launch_fwd_dense(const ST *value, const float *loc, const float *attn, ST *out,
                       const DensePlan &dp, unsigned value_bytes, const BinRide &ride_in,
                       unsigned long long *stats, hipStream_t st)
 {
@@ -42,7 +44,7 @@ void launch_fwd_dense(const uint16_t *value, const float *loc, const float *attn
     const BinRide ride = place_riders(ride_in, dense_blocks(dp), &total);
 #define BOXATTN_DENSE_FWD(LV_)                                                                       \
     case LV_:                                                                                        \
-        hipLaunchKernelGGL((fwd_dense_kernel<LV_>), dim3(total), dim3(256), 0, st, value, loc, attn, out, \
+        hipLaunchKernelGGL((fwd_dense_kernel<ST, LV_>), dim3(total), dim3(256), 0, st, value, loc, attn, out, \
                            dp, value_bytes, ride, stats);                                            \
         break;
     switch (dp.L) {
@@ -84,13 +86,14 @@ void launch_fwd_dense_f32(const float *value, const float *loc, const float *att
 #undef BOXATTN_DENSE_FWD32
 }
 
-void launch_accumulate_tr(int C, const uint16_t *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
+template <typename ST>
+void launch_accumulate_tr(int C, const ST *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
                           int H, int Lq, const int4 *items, const int *n_items, const int *records,
-                          uint16_t *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
+                          ST *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
                           const ZeroRole &zr, hipStream_t st)
 {
 #define BOXATTN_ACC_TR(C_)                                                                              \
-    hipLaunchKernelGGL((binned_accumulate_tr_kernel<uint16_t, C_>), dim3(wg_per_slice + plan.zero_workers, ns8), dim3(64), 0, st, \
+    hipLaunchKernelGGL((binned_accumulate_tr_kernel<ST, C_>), dim3(wg_per_slice + plan.zero_workers, ns8), dim3(64), 0, st, \
                        grad_out, (unsigned)grad_out_bytes, plan, S, H, Lq, items, n_items, records,     \
                        grad_value, partials, cc, zr)
     switch (C) {
@@ -100,6 +103,20 @@ void launch_accumulate_tr(int C, const uint16_t *grad_out, size_t grad_out_bytes
     }
 #undef BOXATTN_ACC_TR
 }
+
+// one source per kernel family, instantiated for both 16-bit storage types
+#define BOXATTN_DENSE_H16(ST_)                                                                              \
+    template void launch_pointgrad_dense<ST_>(const ST_ *, const float *, const float *, const ST_ *,       \
+                                              const DensePlan &, float *, float *, unsigned, hipStream_t,   \
+                                              const BinRide &);                                             \
+    template void launch_fwd_dense<ST_>(const ST_ *, const float *, const float *, ST_ *, const DensePlan &, \
+                                        unsigned, const BinRide &, unsigned long long *, hipStream_t);      \
+    template void launch_accumulate_tr<ST_>(int, const ST_ *, size_t, const BinPlan &, int, int, int,       \
+                                            const int4 *, const int *, const int *, ST_ *, float *, int, int, \
+                                            const ChunkCombine &, const ZeroRole &, hipStream_t);
+BOXATTN_DENSE_H16(bf16_t)
+BOXATTN_DENSE_H16(f16_t)
+#undef BOXATTN_DENSE_H16
 
 void launch_accumulate_split(const float *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S, int H, int Lq,
                              const int4 *items, const int *n_items, const int *records, float *grad_value,

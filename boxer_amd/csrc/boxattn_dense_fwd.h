@@ -1,5 +1,5 @@
-// Window-staged FORWARD for the encoder case of bf16 box attention (one query per pixel, C = 32, 2x2 points,
-// <= 4 levels): the staging of boxattn_dense.h (the value windows of an 8x8 query tile and head in LDS) with the
+// Window-staged FORWARD for the encoder case of 16-bit (bf16 or f16) box attention (one query per pixel, C = 32,
+// 2x2 points, <= 4 levels): the staging of boxattn_dense.h (the value windows of an 8x8 query tile and head in LDS) with the
 // arithmetic on the matrix cores.
 //
 // out[q][c] = sum over the query's 16 points and their 4 corners of w * v[corner][c], w a float32 weight.  On the
@@ -10,7 +10,8 @@
 //     D[i][j] += sum_k A[i][k] B[k][j]      k = corner, j = channel (4 per instruction), i = term of the weight
 //
 //   A (lane i of the quad holds row i): the point's four corner weights split into two bf16 terms, w = hi + lo
-//     (|w - hi - lo| <= 2^-17 |w|): row 0 = hi, row 1 = lo (rows 2, 3 repeat them; their results are not used);
+//     (|w - hi - lo| <= 2^-17 |w|; f16 terms on v_mfma_f32_4x4x4_16b_f16: <= 2^-22 |w| + 2^-25):
+//     row 0 = hi, row 1 = lo (rows 2, 3 repeat them; their results are not used);
 //     broadcast inside the quad from the lane that located the point (DPP quad_perm), hi or lo by the lane's parity;
 //   B (lane j holds column j = 4 corners of one channel): exactly what ds_read_b64_tr_b16 delivers -- in a 16-lane
 //     group lane 4 k + q supplies the address of corner k's row for the query of quad q, and lane 4 q + r receives
@@ -51,10 +52,10 @@ __device__ __forceinline__ unsigned quad_evenodd_u32(unsigned v, int u)
 typedef short fwd_i16x4 __attribute__((ext_vector_type(4)));
 typedef float fwd_f32x4 __attribute__((ext_vector_type(4)));
 
-template <int L>
+template <typename ST, int L>
 __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
-    const bf16_t *__restrict__ value, const float *__restrict__ loc, const float *__restrict__ attn,
-    bf16_t *__restrict__ out, DensePlan pl, unsigned value_bytes, BinRide ride,
+    const ST *__restrict__ value, const float *__restrict__ loc, const float *__restrict__ attn,
+    ST *__restrict__ out, DensePlan pl, unsigned value_bytes, BinRide ride,
     unsigned long long *__restrict__ stats)
 {
     constexpr int C = 32, P = 4, LP = L * P;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
     const unsigned pt0 = qh * (unsigned)LP;
     const float2 *loc2 = reinterpret_cast<const float2 *>(loc);
     const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t *>(value), 0, value_bytes, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<ST *>(value), 0, value_bytes, 0x00020000);
     DenseWinPos win[L];
     dense_stage_issue<L>(hot, wrow, t, lane, wv, rs, win_lds, win);
     float2 xy[L];
@@ -137,9 +138,10 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
         const float aa = s.inside ? a[l] : 0.f;
         const float ha = s.hh * aa, la = s.lh * aa;
         const float wk[4] = {ha * s.hw, ha * s.lw, la * s.hw, la * s.lw};
-        const unsigned hi01 = pack_bf16x2(wk[0], wk[1]), hi23 = pack_bf16x2(wk[2], wk[3]);
-        const unsigned lo01 = pack_bf16x2(wk[0] - __uint_as_float(hi01 << 16), wk[1] - __uint_as_float(hi01 & 0xffff0000u));
-        const unsigned lo23 = pack_bf16x2(wk[2] - __uint_as_float(hi23 << 16), wk[3] - __uint_as_float(hi23 & 0xffff0000u));
+        typedef Half16<ST> H16;
+        const unsigned hi01 = H16::pack(wk[0], wk[1]), hi23 = H16::pack(wk[2], wk[3]);
+        const unsigned lo01 = H16::pack(wk[0] - H16::lo(hi01), wk[1] - H16::hi(hi01));
+        const unsigned lo23 = H16::pack(wk[2] - H16::lo(hi23), wk[3] - H16::hi(hi23));
         const int dj = (jc & 1) * kDenseSlotBytes + (jc >> 1) * pitchb - kBias;       // my corner relative to the packed slot
         // A operand: lane i of a quad holds row i -- rows 0, 2: the hi terms, rows 1, 3: the lo terms of the point
         // the quad is working on.  Arranged once per level so that ONE quad permute per register and point
@@ -159,12 +161,12 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
                 const bool counts = ((pk >> (20 + jc)) & 1u) != 0u;
                 const int addr = counts ? (int)(pk & 0xfffffu) + dj : kZeroOff;
                 const unsigned a0 = quad_evenodd_u32(z01[tp >> 1], tp & 1), a1 = quad_evenodd_u32(z23[tp >> 1], tp & 1);
-                const fwd_i16x4 av = __builtin_bit_cast(fwd_i16x4, uint2{a0, a1});
+                const uint2 av = uint2{a0, a1};
                 typedef __attribute__((address_space(3))) fwd_i16x4 lds_vec;
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
                     const fwd_i16x4 bv = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_vec *)(win_lds + addr + 8 * m));
-                    acc[m] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(av, bv, acc[m], 0, 0, 0);
+                    acc[m] = H16::mfma4x4x4(av, __builtin_bit_cast(uint2, bv), acc[m]);
                 }
             }
         }
@@ -195,8 +197,8 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
                     const unsigned w4[4] = {rw[k].x, rw[k].y, rw[k].z, rw[k].w};
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        accv[2 * i] = fmaf(wv_[k], __uint_as_float(w4[i] << 16), accv[2 * i]);
-                        accv[2 * i + 1] = fmaf(wv_[k], __uint_as_float(w4[i] & 0xffff0000u), accv[2 * i + 1]);
+                        accv[2 * i] = fmaf(wv_[k], H16::lo(w4[i]), accv[2 * i]);
+                        accv[2 * i + 1] = fmaf(wv_[k], H16::hi(w4[i]), accv[2 * i + 1]);
                     }
                 }
             }
@@ -224,10 +226,10 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
     const float4 x0 = *reinterpret_cast<const float4 *>(res + 8 * r), x1 = *reinterpret_cast<const float4 *>(res + 8 * r + 4);
     if (vq) {
         dense_u32x4 o4;
-        o4.x = pack_bf16x2(x0.x + accv[0], x0.y + accv[1]);
-        o4.y = pack_bf16x2(x0.z + accv[2], x0.w + accv[3]);
-        o4.z = pack_bf16x2(x1.x + accv[4], x1.y + accv[5]);
-        o4.w = pack_bf16x2(x1.z + accv[6], x1.w + accv[7]);
+        o4.x = Half16<ST>::pack(x0.x + accv[0], x0.y + accv[1]);
+        o4.y = Half16<ST>::pack(x0.z + accv[2], x0.w + accv[3]);
+        o4.z = Half16<ST>::pack(x1.x + accv[4], x1.y + accv[5]);
+        o4.w = Half16<ST>::pack(x1.z + accv[6], x1.w + accv[7]);
         *reinterpret_cast<dense_u32x4 *>(out + (size_t)qh * C + 8 * r) = o4;
     }
 }

@@ -72,15 +72,18 @@ inline unsigned dense_blocks(const DensePlan &p)
     return 8u * (unsigned)p.H * longest;
 }
 
-// grad_loc / grad_attn of bf16 box attention on a query grid (+ the backward's fill riders, if any:
-// ride.grid.n_riders > 0; the caller sets ride.grid.n_riders / .shift, the launcher places them: boxattn_ride.h)
-void launch_pointgrad_dense(const uint16_t *value, const float *loc, const float *attn,
-                            const uint16_t *grad_out, const DensePlan &dp, float *grad_loc,
+// grad_loc / grad_attn of 16-bit (ST = bf16_t or f16_t) box attention on a query grid (+ the backward's fill
+// riders, if any: ride.grid.n_riders > 0; the caller sets ride.grid.n_riders / .shift, the launcher places them:
+// boxattn_ride.h)
+template <typename ST>
+void launch_pointgrad_dense(const ST *value, const float *loc, const float *attn,
+                            const ST *grad_out, const DensePlan &dp, float *grad_loc,
                             float *grad_attn, unsigned value_bytes, hipStream_t st, const BinRide &ride);
 
-// out of bf16 box attention on a query grid (boxattn_dense_fwd.h) (+ the training forward's count riders
+// out of 16-bit box attention on a query grid (boxattn_dense_fwd.h) (+ the training forward's count riders
 // and the scans chained behind them, if any; stats: kDenseStatSlots pairs of locality counters or null)
-void launch_fwd_dense(const uint16_t *value, const float *loc, const float *attn, uint16_t *out,
+template <typename ST>
+void launch_fwd_dense(const ST *value, const float *loc, const float *attn, ST *out,
                       const DensePlan &dp, unsigned value_bytes, const BinRide &ride,
                       unsigned long long *stats, hipStream_t st);
 
@@ -94,13 +97,14 @@ void launch_fwd_dense_f32(const float *value, const float *loc, const float *att
 #define BOXATTN_DENSE_F32_LDS 53248
 #endif
 
-// The matrix-core accumulate of bf16 box attention (boxattn_binned_tr.h; lives in this translation unit
+// The matrix-core accumulate of 16-bit box attention (boxattn_binned_tr.h; lives in this translation unit
 // because it mixes float32 VALU work with MFMAs, see boxattn_dense.hip).  C = 16, 32 or 64 channels per
 // head, grad_out below 2 GB (32-bit row offsets, and an out-of-range offset for idle lanes).
 constexpr size_t kAccTrMaxBytes = (size_t)1 << 31;
-void launch_accumulate_tr(int C, const uint16_t *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
+template <typename ST>
+void launch_accumulate_tr(int C, const ST *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
                           int H, int Lq, const int4 *items, const int *n_items, const int *records,
-                          uint16_t *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
+                          ST *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
                           const ZeroRole &zr, hipStream_t st);
 
 // float32 storage, C = 32: the accumulate on the bf16 matrix cores with exact three-term splits (boxattn_binned_tr.h:

@@ -11,6 +11,7 @@
 namespace boxattn {
 
 typedef uint16_t bf16_t;          // raw bfloat16 storage
+typedef _Float16 f16_t;           // IEEE binary16 storage (a type of its own: dispatch never mistakes it for bf16_t)
 constexpr int kWave = 64;         // CDNA wavefront
 constexpr int kMaxLevels = 16;    // level table kept in LDS by the fast kernels
 
@@ -43,14 +44,78 @@ template <> struct Storage<bf16_t> {
     static __device__ __forceinline__ float ld(const bf16_t *p) { return bf16_bits_to_f32(*p); }
     static __device__ __forceinline__ void st(bf16_t *p, float v) { *p = f32_to_bf16(v); }
 };
+template <> struct Storage<f16_t> {
+    typedef float compute;
+    static __device__ __forceinline__ float ld(const f16_t *p) { return (float)*p; }         // v_cvt_f32_f16
+    static __device__ __forceinline__ void st(f16_t *p, float v) { *p = (f16_t)v; }          // RNE
+};
 
 // Two fp32 -> packed bf16 pair, round-to-nearest-even, one v_cvt_pk_bf16_f32.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     const f32x2 v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
+
+// "16-bit storage": bf16 and f16 take the same kernels, which reach the number format only through
+// Half16<ST> below (packed pairs as raw 32-bit words, low channel in the low half).
+template <typename ST> struct IsHalf16 { static constexpr bool value = false; };
+template <> struct IsHalf16<bf16_t> { static constexpr bool value = true; };
+template <> struct IsHalf16<f16_t> { static constexpr bool value = true; };
+
+typedef float h16_f32x4 __attribute__((ext_vector_type(4)));
+typedef float h16_f32x16 __attribute__((ext_vector_type(16)));
+template <typename ST> struct Half16;
+template <> struct Half16<bf16_t> {
+    typedef __bf16 x8 __attribute__((ext_vector_type(8)));
+    typedef short x4 __attribute__((ext_vector_type(4)));
+    // unpack: a shift or a mask
+    static __device__ __forceinline__ float lo(uint32_t w) { return __uint_as_float(w << 16); }
+    static __device__ __forceinline__ float hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+    static __device__ __forceinline__ uint32_t pack(float l, float h) { return pack_bf16x2(l, h); }
+    // sum + a.lo * b.lo + a.hi * b.hi (products exact in fp32): v_dot2c_f32_bf16
+    static __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float sum) {
+        return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b),
+                                               sum, false);
+    }
+    // v_mfma_f32_4x4x4_16b_bf16 / v_mfma_f32_32x32x16_bf16 on raw words
+    static __device__ __forceinline__ h16_f32x4 mfma4x4x4(uint2 a, uint2 b, h16_f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(x4, a), __builtin_bit_cast(x4, b), c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ x8 op8(uint4 a) { return __builtin_bit_cast(x8, a); }
+    static __device__ __forceinline__ h16_f32x16 mfma32x32x16(x8 a, x8 b, h16_f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Half16<f16_t> {
+    typedef _Float16 x8 __attribute__((ext_vector_type(8)));
+    typedef _Float16 x4 __attribute__((ext_vector_type(4)));
+    // unpack: one v_cvt_f32_f16 per element (the high half through SDWA WORD_1)
+    static __device__ __forceinline__ float lo(uint32_t w) {
+        return (float)__builtin_bit_cast(f16_t, (uint16_t)w);
+    }
+    static __device__ __forceinline__ float hi(uint32_t w) {
+        return (float)__builtin_bit_cast(f16_t, (uint16_t)(w >> 16));
+    }
+    // two fp32 -> packed f16 pair, round-to-nearest-even
+    static __device__ __forceinline__ uint32_t pack(float l, float h) {
+        const f32x2 v = {l, h};
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
+    }
+    // v_dot2c_f32_f16 (f16 x f16 products are exact in fp32 as well)
+    static __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float sum) {
+        return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2_t, a), __builtin_bit_cast(f16x2_t, b), sum, false);
+    }
+    static __device__ __forceinline__ h16_f32x4 mfma4x4x4(uint2 a, uint2 b, h16_f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(x4, a), __builtin_bit_cast(x4, b), c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ x8 op8(uint4 a) { return __builtin_bit_cast(x8, a); }
+    static __device__ __forceinline__ h16_f32x16 mfma32x32x16(x8 a, x8 b, h16_f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+};
 
 // Vector access of VEC consecutive channels (VEC*sizeof(ST) is 8 or 16 bytes, aligned).
 template <typename ST, int VEC> struct VecIO;
@@ -63,36 +128,42 @@ template <> struct VecIO<float, 4> {
         *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
     }
 };
-template <> struct VecIO<bf16_t, 4> {
-    static __device__ __forceinline__ void ld(const bf16_t *p, float (&v)[4]) {
+template <typename ST> struct VecIO16_4 {
+    typedef Half16<ST> H;
+    static __device__ __forceinline__ void ld(const ST *p, float (&v)[4]) {
         const uint2 t = *reinterpret_cast<const uint2 *>(p);
-        v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-        v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
+        v[0] = H::lo(t.x); v[1] = H::hi(t.x);
+        v[2] = H::lo(t.y); v[3] = H::hi(t.y);
     }
-    static __device__ __forceinline__ void st(bf16_t *p, const float (&v)[4]) {
+    static __device__ __forceinline__ void st(ST *p, const float (&v)[4]) {
         uint2 t;
-        t.x = pack_bf16x2(v[0], v[1]);
-        t.y = pack_bf16x2(v[2], v[3]);
+        t.x = H::pack(v[0], v[1]);
+        t.y = H::pack(v[2], v[3]);
         *reinterpret_cast<uint2 *>(p) = t;
     }
 };
-template <> struct VecIO<bf16_t, 8> {
-    static __device__ __forceinline__ void ld(const bf16_t *p, float (&v)[8]) {
+template <typename ST> struct VecIO16_8 {
+    typedef Half16<ST> H;
+    static __device__ __forceinline__ void ld(const ST *p, float (&v)[8]) {
         const uint4 t = *reinterpret_cast<const uint4 *>(p);
-        v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-        v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-        v[4] = __uint_as_float(t.z << 16); v[5] = __uint_as_float(t.z & 0xffff0000u);
-        v[6] = __uint_as_float(t.w << 16); v[7] = __uint_as_float(t.w & 0xffff0000u);
+        v[0] = H::lo(t.x); v[1] = H::hi(t.x);
+        v[2] = H::lo(t.y); v[3] = H::hi(t.y);
+        v[4] = H::lo(t.z); v[5] = H::hi(t.z);
+        v[6] = H::lo(t.w); v[7] = H::hi(t.w);
     }
-    static __device__ __forceinline__ void st(bf16_t *p, const float (&v)[8]) {
+    static __device__ __forceinline__ void st(ST *p, const float (&v)[8]) {
         uint4 t;
-        t.x = pack_bf16x2(v[0], v[1]);
-        t.y = pack_bf16x2(v[2], v[3]);
-        t.z = pack_bf16x2(v[4], v[5]);
-        t.w = pack_bf16x2(v[6], v[7]);
+        t.x = H::pack(v[0], v[1]);
+        t.y = H::pack(v[2], v[3]);
+        t.z = H::pack(v[4], v[5]);
+        t.w = H::pack(v[6], v[7]);
         *reinterpret_cast<uint4 *>(p) = t;
     }
 };
+template <> struct VecIO<bf16_t, 4> : VecIO16_4<bf16_t> {};
+template <> struct VecIO<bf16_t, 8> : VecIO16_8<bf16_t> {};
+template <> struct VecIO<f16_t, 4> : VecIO16_4<f16_t> {};
+template <> struct VecIO<f16_t, 8> : VecIO16_8<f16_t> {};
 
 // ---------------------------------------------------------------------------------------
 // atomics: hardware global_atomic_add_f32 / _f64 (no CAS loop).  Memory from hipMalloc /

@@ -130,15 +130,15 @@ static int softmax_bwd(const float *attn, const float *grad_attn, long long rows
     return finish();
 }
 
-template <typename T>
+template <typename T, typename OT = bf16_t>
 static int value_prep(const T *value, const unsigned char *mask, long long rows, int d,
-                      uint16_t *out, hipStream_t st)
+                      OT *out, hipStream_t st)
 {
     if (rows < 0 || d <= 0 || d % 8 != 0) return (int)hipErrorInvalidValue;
     if (rows == 0) return 0;
     if (!value || !out || !aligned(value, 16) || !aligned(out, 16)) return (int)hipErrorInvalidValue;
     const size_t n8 = (size_t)rows * d / 8;
-    hipLaunchKernelGGL((value_mask_cast_kernel<T>), dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL((value_mask_cast_kernel<T, OT>), dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0,
                        st, value, mask, (size_t)rows, d, out);
     return finish();
 }
@@ -153,6 +153,10 @@ int boxattn_softmax_fwd_bf16(const uint16_t *logits, long long rows, int n, floa
 {
     return softmax_fwd<bf16_t>(logits, rows, n, attn, (hipStream_t)stream);
 }
+int boxattn_softmax_fwd_f16(const uint16_t *logits, long long rows, int n, float *attn, void *stream)
+{
+    return softmax_fwd<f16_t>(reinterpret_cast<const f16_t *>(logits), rows, n, attn, (hipStream_t)stream);
+}
 int boxattn_softmax_bwd_f32(const float *attn, const float *grad_attn, long long rows, int n,
                             float *grad_logits, void *stream)
 {
@@ -164,6 +168,12 @@ int boxattn_softmax_bwd_bf16(const float *attn, const float *grad_attn, long lon
     return softmax_bwd<bf16_t>(attn, grad_attn, rows, n, grad_logits, (hipStream_t)stream);
 }
 
+int boxattn_softmax_bwd_f16(const float *attn, const float *grad_attn, long long rows, int n,
+                            uint16_t *grad_logits, void *stream)
+{
+    return softmax_bwd<f16_t>(attn, grad_attn, rows, n, reinterpret_cast<f16_t *>(grad_logits), (hipStream_t)stream);
+}
+
 int boxattn_value_prep_f32(const float *value, const unsigned char *mask, long long rows, int d,
                            uint16_t *out, void *stream)
 {
@@ -173,6 +183,17 @@ int boxattn_value_prep_bf16(const uint16_t *value, const unsigned char *mask, lo
                             uint16_t *out, void *stream)
 {
     return value_prep<bf16_t>(value, mask, rows, d, out, (hipStream_t)stream);
+}
+int boxattn_value_prep_f32_f16(const float *value, const unsigned char *mask, long long rows, int d,
+                               uint16_t *out, void *stream)
+{
+    return value_prep<float, f16_t>(value, mask, rows, d, reinterpret_cast<f16_t *>(out), (hipStream_t)stream);
+}
+int boxattn_value_prep_f16(const uint16_t *value, const unsigned char *mask, long long rows, int d,
+                           uint16_t *out, void *stream)
+{
+    return value_prep<f16_t, f16_t>(reinterpret_cast<const f16_t *>(value), mask, rows, d,
+                                    reinterpret_cast<f16_t *>(out), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -63,8 +63,8 @@ __device__ __forceinline__ void loads_issued()
     if constexpr (kGatherSched) __builtin_amdgcn_sched_barrier(0);
 }
 
-// The VEC channels a lane owns, as raw 32-bit words (fp32: VEC words, bf16: VEC / 2 words).
-// They are fetched in 16-byte pieces (8 bytes for bf16 x 4).  A lane with two pieces (fp32,
+// The VEC channels a lane owns, as raw 32-bit words (fp32: VEC words, bf16 / f16: VEC / 2 words).
+// They are fetched in 16-byte pieces (8 bytes for 16-bit x 4).  A lane with two pieces (fp32,
 // VEC = 8) owns channels [4 slot, 4 slot + 4) and [4 G + 4 slot, ...): piece i of the G lanes
 // of a pair is then one contiguous 16 G-byte run, i.e. every load instruction touches whole
 // 64-byte segments (two pieces side by side per lane would leave 16-byte holes in each
@@ -122,7 +122,7 @@ __device__ __forceinline__ f32x2 row_pair(const Row<ST, VEC> &v, int i)
     if constexpr (sizeof(ST) == 4) {
         r.x = __uint_as_float(v.w[2 * i]); r.y = __uint_as_float(v.w[2 * i + 1]);
     } else {
-        r.x = __uint_as_float(v.w[i] << 16); r.y = __uint_as_float(v.w[i] & 0xffff0000u);
+        r.x = Half16<ST>::lo(v.w[i]); r.y = Half16<ST>::hi(v.w[i]);
     }
     return r;
 }
@@ -160,11 +160,9 @@ __device__ __forceinline__ float row_dot(const Row<ST, VEC> &g, const Row<ST, VE
             a = __builtin_elementwise_fma(row_pair<ST, VEC>(g, i), row_pair<ST, VEC>(v, i), a);
         return a.x + a.y;
     } else {
-        float a = 0.f;                               // bf16 x bf16 products are exact in fp32
+        float a = 0.f;                               // 16-bit x 16-bit products are exact in fp32
 #pragma unroll
-        for (int i = 0; i < VEC / 2; ++i)
-            a = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, g.w[i]),
-                                                __builtin_bit_cast(bf16x2_t, v.w[i]), a, false);
+        for (int i = 0; i < VEC / 2; ++i) a = Half16<ST>::dot2(g.w[i], v.w[i], a);
         return a;
     }
 }
@@ -179,12 +177,12 @@ __device__ __forceinline__ void row_store(ST *p, const f32x2 (&acc)[VEC / 2])
                 make_float4(acc[2 * i].x, acc[2 * i].y, acc[2 * i + 1].x, acc[2 * i + 1].y);
     } else if constexpr (VEC == 4) {
         u32x2_t t;
-        t.x = pack_bf16x2(acc[0].x, acc[0].y); t.y = pack_bf16x2(acc[1].x, acc[1].y);
+        t.x = Half16<ST>::pack(acc[0].x, acc[0].y); t.y = Half16<ST>::pack(acc[1].x, acc[1].y);
         *reinterpret_cast<u32x2_t *>(p) = t;
     } else {
         u32x4_t t;
-        t.x = pack_bf16x2(acc[0].x, acc[0].y); t.y = pack_bf16x2(acc[1].x, acc[1].y);
-        t.z = pack_bf16x2(acc[2].x, acc[2].y); t.w = pack_bf16x2(acc[3].x, acc[3].y);
+        t.x = Half16<ST>::pack(acc[0].x, acc[0].y); t.y = Half16<ST>::pack(acc[1].x, acc[1].y);
+        t.z = Half16<ST>::pack(acc[2].x, acc[2].y); t.w = Half16<ST>::pack(acc[3].x, acc[3].y);
         *reinterpret_cast<u32x4_t *>(p) = t;
     }
 }

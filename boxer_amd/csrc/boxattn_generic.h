@@ -1,4 +1,4 @@
-// Generic kernels: any channel count C, any L / P / H, float / double / bf16 storage.
+// Generic kernels: any channel count C, any L / P / H, float / double / bf16 / f16 storage.
 // They are the correctness backstop (and the fp64 gradcheck path); the hot BoxeR shapes
 // (C a multiple of 4, H*C/4 lanes per query) take the kernels in boxattn_fast.h.
 //
@@ -206,6 +206,20 @@ __global__ __launch_bounds__(256) void cvt_f32_to_bf16_kernel(const float *__res
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
         dst[i] = f32_to_bf16(src[i]);
+}
+
+// float32 accumulation buffer -> f16 grad_value (v_cvt_pk_f16_f32, round-to-nearest-even; beyond +-65504: inf)
+__global__ __launch_bounds__(256) void cvt_f32_to_f16_kernel(const float *__restrict__ src,
+                                                             f16_t *__restrict__ dst, size_t n)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t n4 = n / 4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const float4 v = reinterpret_cast<const float4 *>(src)[i];
+        reinterpret_cast<uint2 *>(dst)[i] = make_uint2(Half16<f16_t>::pack(v.x, v.y), Half16<f16_t>::pack(v.z, v.w));
+    }
+    for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        dst[i] = (f16_t)src[i];
 }
 
 }  // namespace boxattn

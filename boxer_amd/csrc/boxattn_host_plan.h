@@ -23,7 +23,8 @@ inline int bin_chunk(const Dims &d)
 }
 
 // Which accumulate kernel a call runs, and with it the record format of the bin passes:
-//   kAccTr   bf16 box attention, C = 16 / 32 / 64: binned_accumulate_tr_kernel (v_mfma_f32_32x32x16_bf16) from
+//   kAccTr   bf16 / f16 box attention, C = 16 / 32 / 64: binned_accumulate_tr_kernel (v_mfma_f32_32x32x16_bf16 /
+//            _f16) from
 //            16-byte records {id, x, y, weight}, contiguous query ranges per bin workgroup;
 //   kAccF32  float32 box attention, C = 32, opt-in (boxattn_set_option(19, 2)): binned_accumulate_f32_kernel
 //            (v_mfma_f32_32x32x2_f32: float32-exact), 16-byte records -- measured at C2 97 us against the VALU
@@ -48,7 +49,7 @@ constexpr size_t kInstSplitMinPoints = 65536;
 inline bool f32_split_ok(const Dims &d) { return opt(kOptAccF32) == 0 && f32_matrix_shape_ok(d); }
 template <typename ST, bool INST> inline AccKind acc_kind(const Dims &d)
 {
-    if constexpr (!INST && std::is_same<ST, bf16_t>::value) {
+    if constexpr (!INST && IsHalf16<ST>::value) {
         if (accumulate_tr_ok(d)) return kAccTr;
     }
     if constexpr (!INST && std::is_same<ST, float>::value) {
@@ -67,10 +68,10 @@ template <typename ST, bool INST> inline AccKind acc_kind(const Dims &d)
     return kAccValu;
 }
 // the workspace query only knows the storage type and the dimensions: room for 16-byte records
-// whenever a flavour of that type may write them
-inline bool wide_workspace(bool is_bf16, const Dims &d)
+// whenever a flavour of that type may write them (is_h16: bf16 or f16 storage, which plan alike)
+inline bool wide_workspace(bool is_h16, const Dims &d)
 {
-    return is_bf16 ? accumulate_tr_ok(d) : f32_mfma_ok(d) || f32_split_ok(d);
+    return is_h16 ? accumulate_tr_ok(d) : f32_mfma_ok(d) || f32_split_ok(d);
 }
 constexpr int kMaxBlocks = 8192;      // per (image, head) slice: one LDS int each in bin_kernel
 
@@ -316,8 +317,8 @@ inline void state_learned(const void *state)
 }
 
 // ------------------------------------------------- window-staged encoder kernels (boxattn_dense.h)
-// Encoder case: one query per pixel of packed levels, bf16 storage, C = 32, 2x2 points, <= 4 levels.
-// elem: bytes per stored element -- 2: bf16 storage (64-byte pixels, geometry in 16-byte units, boxattn_dense.h),
+// Encoder case: one query per pixel of packed levels, 16-bit or float32 storage, C = 32, 2x2 points, <= 4 levels.
+// elem: bytes per stored element -- 2: bf16 / f16 storage (64-byte pixels, geometry in 16-byte units, boxattn_dense.h),
 // 4: float32 storage (128-byte pixels, 32-byte units, boxattn_dense_f32.h)
 inline bool make_dense_plan(const Dims &d, const int64_t *sh, const int64_t *ls, DensePlan &p, int elem)
 {

@@ -55,11 +55,11 @@ __global__ __launch_bounds__(256) void grid_bwd_kernel(const float *__restrict__
 // Pointwise work around the operator (reference e2edet/module/box_attention.py:222-231),
 // SURVEY.md 8(f) N3:
 //   * attention weights = softmax over the L*P logits of a (query, head), computed in float32
-//     whatever the logits' type (float32 or the bfloat16 of an autocast projection) -- one pass
+//     whatever the logits' type (float32, or the bfloat16 / float16 of an autocast projection) -- one pass
 //     instead of cast + softmax (+ cast); its backward grad_logits = a (g - sum_j a_j g_j),
 //     written in the logits' type;
-//   * value rows of padded pixels (v_mask) zeroed and cast to bfloat16 in the same pass
-//     (`value.masked_fill(v_mask[..., None], 0)` followed by the op's bf16 conversion).
+//   * value rows of padded pixels (v_mask) zeroed and cast to bfloat16 / float16 in the same pass
+//     (`value.masked_fill(v_mask[..., None], 0)` followed by the op's 16-bit conversion).
 // Rows whose length is 4 * 2^k (k <= 4; BoxeR: 16 = 4 levels x 2x2 points): 2^k lanes per row,
 // four consecutive values per lane, so a wave reads and writes whole contiguous runs
 // (element index = 4 * thread) and the row max / sum are cross-lane butterflies.  Any other
@@ -68,9 +68,11 @@ __global__ __launch_bounds__(256) void grid_bwd_kernel(const float *__restrict__
 template <typename T> __device__ __forceinline__ float pw_ld(const T *p);
 template <> __device__ __forceinline__ float pw_ld<float>(const float *p) { return *p; }
 template <> __device__ __forceinline__ float pw_ld<bf16_t>(const bf16_t *p) { return bf16_bits_to_f32(*p); }
+template <> __device__ __forceinline__ float pw_ld<f16_t>(const f16_t *p) { return (float)*p; }
 template <typename T> __device__ __forceinline__ void pw_st(T *p, float v);
 template <> __device__ __forceinline__ void pw_st<float>(float *p, float v) { *p = v; }
 template <> __device__ __forceinline__ void pw_st<bf16_t>(bf16_t *p, float v) { *p = f32_to_bf16(v); }
+template <> __device__ __forceinline__ void pw_st<f16_t>(f16_t *p, float v) { *p = (f16_t)v; }
 
 template <typename T, int NMAX>      // n <= NMAX: the row stays in registers
 __global__ __launch_bounds__(256) void softmax_rows_fwd_kernel(const T *__restrict__ logits,
@@ -169,20 +171,21 @@ __global__ __launch_bounds__(256) void softmax_vec_bwd_kernel(const float *__res
     if (live) VecIO<T, 4>::st(grad_logits + i, a);
 }
 
-// value (rows, d) of type T -> bfloat16, rows with mask != 0 zeroed; 8 channels per thread
-template <typename T>
+// value (rows, d) of type T -> 16-bit OT (bfloat16 or float16), rows with mask != 0 zeroed; 8 channels
+// per thread
+template <typename T, typename OT>
 __global__ __launch_bounds__(256) void value_mask_cast_kernel(const T *__restrict__ value,
                                                               const unsigned char *__restrict__ mask,
                                                               size_t rows, int d,
-                                                              bf16_t *__restrict__ out)
+                                                              OT *__restrict__ out)
 {
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
     if (i >= rows * (size_t)d) return;
     const size_t r = i / (unsigned)d;
     const bool dead = mask && mask[r];
     float v[8];
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        VecIO<bf16_t, 8>::ld(value + i, v);
+    if constexpr (IsHalf16<T>::value) {
+        VecIO<T, 8>::ld(value + i, v);
     } else {
         float lo[4], hi[4];
         VecIO<float, 4>::ld(value + i, lo);
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(256) void value_mask_cast_kernel(const T *__restric
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = 0.f;
     }
-    VecIO<bf16_t, 8>::st(out + i, v);
+    VecIO<OT, 8>::st(out + i, v);
 }
 
 }  // namespace boxattn

@@ -61,8 +61,9 @@ Dims prepare(const at::Tensor &value, const at::Tensor &shapes, const at::Tensor
     check_input(loc, "sampling_loc");
     for (const at::Tensor *w : weights) check_input(*w, "attn_weight");
     const auto vt = value.scalar_type();
-    TORCH_CHECK(vt == at::kFloat || vt == at::kDouble || vt == at::kBFloat16,
-                "box_attn: unsupported dtype (float32, float64, bfloat16)");
+    const bool h16 = vt == at::kBFloat16 || vt == at::kHalf;     // 16-bit storage
+    TORCH_CHECK(vt == at::kFloat || vt == at::kDouble || h16,
+                "box_attn: unsupported dtype (float32, float64, bfloat16, float16)");
     TORCH_CHECK(shapes.scalar_type() == at::kLong && lsi.scalar_type() == at::kLong,
                 "spatial_shapes / level_start_index must be int64");
     TORCH_CHECK(value.dim() == 4 && loc.dim() == 6 && loc.size(5) == 2,
@@ -74,9 +75,9 @@ Dims prepare(const at::Tensor &value, const at::Tensor &shapes, const at::Tensor
     TORCH_CHECK(loc.size(0) == d.B && loc.size(2) == d.H && loc.size(3) == d.L &&
                     lsi.numel() == d.L,
                 "sampling_loc / spatial_shapes do not match value");
-    const auto wt = vt == at::kBFloat16 ? at::kFloat : vt;     // bf16 storage: fp32 geometry
+    const auto wt = h16 ? at::kFloat : vt;     // 16-bit storage: fp32 geometry
     TORCH_CHECK(loc.scalar_type() == wt, "sampling_loc must be ",
-                vt == at::kBFloat16 ? "float32 for bfloat16 value" : "of value's dtype");
+                h16 ? "float32 for bfloat16 / float16 value" : "of value's dtype");
     const int64_t n_w = (int64_t)d.B * d.Lq * d.H * d.L * d.P;
     for (const at::Tensor *w : weights) {
         TORCH_CHECK(w->numel() == n_w, "attention weights must have B*Lq*H*L*P elements");
@@ -84,6 +85,11 @@ Dims prepare(const at::Tensor &value, const at::Tensor &shapes, const at::Tensor
     }
     check_chunks(d.B, im2col_step);
     return d;
+}
+
+int is_h16(const at::Tensor &value)
+{
+    return value.scalar_type() == at::kBFloat16 || value.scalar_type() == at::kHalf;
 }
 
 void check_rc(int rc, const char *what)
@@ -168,7 +174,7 @@ bool capturing()
 at::Tensor workspace(const at::Tensor &value, const Dims &d, const HostTables &h, void *stream)
 {
     const size_t bytes = std::max<size_t>(
-        boxattn_bwd_workspace_bytes(value.scalar_type() == at::kBFloat16, d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
+        boxattn_bwd_workspace_bytes(is_h16(value), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
                                     h.sh(), h.ls()), 256);
     const StreamKey key(value.get_device(), stream);
     const bool keep = !capturing();
@@ -252,13 +258,18 @@ bool wants_plan(std::initializer_list<const at::Tensor *> ts)
 }
 at::Tensor plan_buffer(const at::Tensor &value, const Dims &d, const HostTables &h)
 {
-    const size_t bytes = boxattn_plan_bytes(value.scalar_type() == at::kBFloat16, d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
+    const size_t bytes = boxattn_plan_bytes(is_h16(value), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
                                             h.sh(), h.ls());
     return bytes ? at::empty({(int64_t)bytes}, value.options().dtype(at::kByte)) : at::Tensor();
 }
 
 const uint16_t *bf(const at::Tensor &t) { return (const uint16_t *)t.data_ptr(); }
 uint16_t *bf(at::Tensor &t) { return (uint16_t *)t.data_ptr(); }
+// the entry point of the 16-bit storage type of `value` (the bf16 and f16 twins share a signature)
+template <class F> F h16_entry(const at::Tensor &value, F bf16, F f16)
+{
+    return value.scalar_type() == at::kHalf ? f16 : bf16;
+}
 
 }  // namespace
 
@@ -292,7 +303,7 @@ at::Tensor box_attn_forward(const at::Tensor &value, const at::Tensor &spatial_s
                                            out.data_ptr<float>(), h.sh(), h.ls(), plan.data_ptr(), (size_t)plan.numel(),
                                            state_buf.data_ptr(), (size_t)state_buf.numel(), hints, &built, st);
             else
-                rc = boxattn_fwd_train_bf16(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
+                rc = h16_entry(value, boxattn_fwd_train_bf16, boxattn_fwd_train_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
                                             attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, bf(out),
                                             h.sh(), h.ls(), plan.data_ptr(), (size_t)plan.numel(), state_buf.data_ptr(),
                                             (size_t)state_buf.numel(), hints, &built, st);
@@ -303,7 +314,7 @@ at::Tensor box_attn_forward(const at::Tensor &value, const at::Tensor &spatial_s
                                     attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq,
                                     d.P, out.data_ptr<float>(), h.sh(), h.ls(), st);
         else
-            rc = boxattn_fwd_hl_bf16(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
+            rc = h16_entry(value, boxattn_fwd_hl_bf16, boxattn_fwd_hl_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
                                      attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq,
                                      d.P, bf(out), h.sh(), h.ls(), st);
     }
@@ -354,7 +365,7 @@ std::vector<at::Tensor> box_attn_backward(const at::Tensor &value, const at::Ten
                                     h.ls(), ws.data_ptr(), (size_t)ws.numel(), pp, pn, state_buf.data_ptr(),
                                     (size_t)state_buf.numel(), hints, st);
         else
-            rc = boxattn_bwd_ws_bf16(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
+            rc = h16_entry(value, boxattn_bwd_ws_bf16, boxattn_bwd_ws_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
                                      attn_weight.data_ptr<float>(), bf(grad_output), d.B, d.S, d.H,
                                      d.C, d.L, d.Lq, d.P, bf(grad_value), grad_loc.data_ptr<float>(),
                                      grad_attn.data_ptr<float>(), h.sh(), h.ls(), ws.data_ptr(),
@@ -397,7 +408,7 @@ std::vector<at::Tensor> instance_attn_forward(const at::Tensor &value,
                                             mask.data_ptr<float>(), h.sh(), h.ls(), plan.data_ptr(), (size_t)plan.numel(),
                                             state_buf.data_ptr(), (size_t)state_buf.numel(), hints, &built, st);
             else
-                rc = instattn_fwd_train_bf16(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
+                rc = h16_entry(value, instattn_fwd_train_bf16, instattn_fwd_train_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
                                              spatial_attn_weight.data_ptr<float>(), level_attn_weight.data_ptr<float>(),
                                              d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, bf(out), bf(mask), h.sh(), h.ls(),
                                              plan.data_ptr(), (size_t)plan.numel(), state_buf.data_ptr(),
@@ -420,7 +431,7 @@ std::vector<at::Tensor> instance_attn_forward(const at::Tensor &value,
                               level_attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
                               out.data_ptr<float>(), mask.data_ptr<float>(), st);
     else
-        rc = instattn_fwd_bf16(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
+        rc = h16_entry(value, instattn_fwd_bf16, instattn_fwd_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
                                spatial_attn_weight.data_ptr<float>(),
                                level_attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq,
                                d.P, bf(out), bf(mask), st);
@@ -479,7 +490,7 @@ std::vector<at::Tensor> instance_attn_backward(
                 grad_sw.data_ptr<float>(), grad_lw.data_ptr<float>(), h.sh(), h.ls(), ws.data_ptr(),
                 (size_t)ws.numel(), pp, pn, state_buf.data_ptr(), (size_t)state_buf.numel(), hints, st);
         else
-            rc = instattn_bwd_ws_bf16(
+            rc = h16_entry(value, instattn_bwd_ws_bf16, instattn_bwd_ws_f16)(
                 bf(value), sh, ls, sampling_loc.data_ptr<float>(),
                 spatial_attn_weight.data_ptr<float>(), level_attn_weight.data_ptr<float>(),
                 bf(grad_output), bf(grad_mask_output), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,

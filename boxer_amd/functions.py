@@ -10,6 +10,8 @@ is cast to float32 and the op runs with autocast disabled).
 ``BoxAttnBF16Function`` / ``InstanceAttnBF16Function`` are the new native-bf16 mode
 (BASELINE.json configs[1]): ``value`` and the upstream gradients are bfloat16, locations and
 weights stay float32, accumulation is float32.  Same signatures otherwise.
+``BoxAttnF16Function`` / ``InstanceAttnF16Function`` are the same mode with IEEE float16 storage
+(the ``use_fp16: float16`` trainer setting, ``model.half()`` inference).
 """
 import torch
 from torch.amp import custom_bwd, custom_fwd
@@ -117,54 +119,94 @@ class InstanceAttnFunction(Function):
         return _inst_backward(ctx, grad_output, grad_mask_output)
 
 
-def _to_bf16_args(value, loc, *weights):
-    return (value.to(torch.bfloat16).contiguous(), loc.float().contiguous(),
+def _to_storage_args(storage, value, loc, *weights):
+    return (value.to(storage).contiguous(), loc.float().contiguous(),
             *[w.float().contiguous() for w in weights])
 
 
-class BoxAttnBF16Function(Function):
+# The 16-bit storage modes share one implementation; the concrete Functions below only name their
+# storage dtype (bfloat16 or float16), which forward keeps on ctx for the backward.
+def _box16_forward(ctx, storage, value, value_spatial_shapes, value_level_start_index,
+                   sampling_locations, attention_weights, im2col_step):
+    ctx.im2col_step = im2col_step
+    ctx.storage = storage
+    ctx.loc_dtype, ctx.attn_dtype = sampling_locations.dtype, attention_weights.dtype
+    ctx.value_dtype = value.dtype
+    value, loc, attn = _to_storage_args(storage, value, sampling_locations, attention_weights)
+    output, ctx.plan = _box_forward(ctx, value, value_spatial_shapes,
+                                    value_level_start_index, loc, attn, im2col_step)
+    ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, loc, attn)
+    return output
+
+
+def _inst16_forward(ctx, storage, value, value_spatial_shapes, value_level_start_index,
+                    sampling_locations, spatial_attention_weights, level_attention_weights,
+                    mask_size, im2col_step):
+    ctx.im2col_step = im2col_step
+    ctx.storage = storage
+    ctx.loc_dtype, ctx.w_dtype = sampling_locations.dtype, spatial_attention_weights.dtype
+    ctx.value_dtype = value.dtype
+    value, loc, sw, lw = _to_storage_args(storage, value, sampling_locations,
+                                          spatial_attention_weights, level_attention_weights)
+    (output, mask_output), ctx.plan = _inst_forward(
+        ctx, value, value_spatial_shapes, value_level_start_index, loc, sw, lw, im2col_step)
+    ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, loc, sw, lw)
+    b, l, _, c = mask_output.shape
+    return output, mask_output.view(b, l, mask_size, mask_size, c)
+
+
+class _BoxAttn16Function(Function):
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        grads = _box_backward(ctx, grad_output.to(ctx.storage))
+        return (grads[0].to(ctx.value_dtype),) + grads[1:]
+
+
+class _InstanceAttn16Function(Function):
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output, grad_mask_output):
+        grads = _inst_backward(ctx, grad_output.to(ctx.storage), grad_mask_output.to(ctx.storage))
+        return (grads[0].to(ctx.value_dtype),) + grads[1:]
+
+
+class BoxAttnBF16Function(_BoxAttn16Function):
     """Native-bf16 flavour: output and grad_value are bfloat16, accumulation is float32."""
 
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
                 attention_weights, im2col_step):
-        ctx.im2col_step = im2col_step
-        ctx.loc_dtype, ctx.attn_dtype = sampling_locations.dtype, attention_weights.dtype
-        ctx.value_dtype = value.dtype
-        value, loc, attn = _to_bf16_args(value, sampling_locations, attention_weights)
-        output, ctx.plan = _box_forward(ctx, value, value_spatial_shapes,
-                                        value_level_start_index, loc, attn, im2col_step)
-        ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, loc, attn)
-        return output
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        grads = _box_backward(ctx, grad_output.to(torch.bfloat16))
-        return (grads[0].to(ctx.value_dtype),) + grads[1:]
+        return _box16_forward(ctx, torch.bfloat16, value, value_spatial_shapes, value_level_start_index,
+                              sampling_locations, attention_weights, im2col_step)
 
 
-class InstanceAttnBF16Function(Function):
+class InstanceAttnBF16Function(_InstanceAttn16Function):
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
                 spatial_attention_weights, level_attention_weights, mask_size, im2col_step):
-        ctx.im2col_step = im2col_step
-        ctx.loc_dtype, ctx.w_dtype = sampling_locations.dtype, spatial_attention_weights.dtype
-        ctx.value_dtype = value.dtype
-        value, loc, sw, lw = _to_bf16_args(value, sampling_locations, spatial_attention_weights,
-                                           level_attention_weights)
-        (output, mask_output), ctx.plan = _inst_forward(
-            ctx, value, value_spatial_shapes, value_level_start_index, loc, sw, lw, im2col_step)
-        ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, loc, sw, lw)
-        b, l, _, c = mask_output.shape
-        return output, mask_output.view(b, l, mask_size, mask_size, c)
+        return _inst16_forward(ctx, torch.bfloat16, value, value_spatial_shapes, value_level_start_index,
+                               sampling_locations, spatial_attention_weights, level_attention_weights,
+                               mask_size, im2col_step)
+
+
+class BoxAttnF16Function(_BoxAttn16Function):
+    """Native-fp16 flavour: output and grad_value are IEEE float16, accumulation is float32."""
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output, grad_mask_output):
-        grads = _inst_backward(ctx, grad_output.to(torch.bfloat16),
-                               grad_mask_output.to(torch.bfloat16))
-        return (grads[0].to(ctx.value_dtype),) + grads[1:]
+    def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
+                attention_weights, im2col_step):
+        return _box16_forward(ctx, torch.float16, value, value_spatial_shapes, value_level_start_index,
+                              sampling_locations, attention_weights, im2col_step)
+
+
+class InstanceAttnF16Function(_InstanceAttn16Function):
+    @staticmethod
+    def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
+                spatial_attention_weights, level_attention_weights, mask_size, im2col_step):
+        return _inst16_forward(ctx, torch.float16, value, value_spatial_shapes, value_level_start_index,
+                               sampling_locations, spatial_attention_weights, level_attention_weights,
+                               mask_size, im2col_step)
 
 
 class BoxGridFunction(Function):
@@ -176,11 +218,12 @@ class BoxGridFunction(Function):
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, ref_windows, offsets, kernel_indices, valid_ratios, angle_mode):
-        ref_windows = ref_windows.contiguous()
-        offsets = offsets.contiguous()
-        kernel_indices = kernel_indices.contiguous()
+        # (float32 whatever the module's type: a .half() module hands float16 here without autocast)
+        ref_windows = ref_windows.float().contiguous()
+        offsets = offsets.float().contiguous()
+        kernel_indices = kernel_indices.float().contiguous()
         if valid_ratios is not None:
-            valid_ratios = valid_ratios.contiguous()
+            valid_ratios = valid_ratios.float().contiguous()
         ctx.save_for_backward(ref_windows, offsets, kernel_indices, valid_ratios)
         ctx.angle_mode = angle_mode
         return ops.box_grid_forward(ref_windows, offsets, kernel_indices, valid_ratios, angle_mode)
@@ -225,14 +268,14 @@ class LogitSoftmaxFunction(Function):
 
 
 class ValueMaskCastFunction(Function):
-    """value -> bfloat16 with padded rows zeroed (``ops.value_mask_cast``); the gradient is the
-    upstream one with the same rows zeroed, in the input's type."""
+    """value -> bfloat16 (or ``dtype``: float16) with padded rows zeroed (``ops.value_mask_cast``);
+    the gradient is the upstream one with the same rows zeroed, in the input's type."""
 
     @staticmethod
-    def forward(ctx, value, v_mask):
+    def forward(ctx, value, v_mask, dtype=torch.bfloat16):
         ctx.save_for_backward(v_mask)
         ctx.value_dtype = value.dtype
-        return ops.value_mask_cast(value.contiguous(), v_mask)
+        return ops.value_mask_cast(value.contiguous(), v_mask, dtype)
 
     @staticmethod
     @once_differentiable
@@ -241,7 +284,7 @@ class ValueMaskCastFunction(Function):
         grad = grad.to(ctx.value_dtype)
         if v_mask is not None:
             grad = grad.masked_fill(v_mask[..., None], 0)
-        return grad, None
+        return grad, None, None
 
 
 def _ref_grad(ref_windows, rows):

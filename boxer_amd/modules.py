@@ -10,9 +10,10 @@ signature and return tuples.  The sampling itself runs in the HIP operator behin
 The three reference classes repeat their code; here the shared parts (parameters, kernel
 grid, box decoding, value projection) live in one base class.
 
-Extra, not in the reference: ``native_bf16`` (default False).  When set, the op runs in the
-bf16 storage mode (value / output bfloat16, fp32 locations, weights and accumulation)
-instead of the reference's "always float32" contract.
+Extra, not in the reference: ``native_bf16`` / ``native_f16`` (default False).  When one is set,
+the op runs in the 16-bit storage mode (value / output bfloat16 or IEEE float16, fp32 locations,
+weights and accumulation) instead of the reference's "always float32" contract.  Setting both is
+an error.
 """
 import math
 
@@ -21,9 +22,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import dense
-from .functions import (BoxAttnBF16Function, BoxAttnFunction, BoxGridFunction,
-                        InstanceAttnBF16Function, InstanceAttnFunction, LogitSoftmaxFunction,
-                        ValueMaskCastFunction)
+from .functions import (BoxAttnBF16Function, BoxAttnF16Function, BoxAttnFunction, BoxGridFunction,
+                        InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
+                        LogitSoftmaxFunction, ValueMaskCastFunction)
 
 
 def _kernel_offsets(kernel_size, divisor):
@@ -49,13 +50,14 @@ class _BoxAttentionBase(nn.Module):
         self.head_dim = d_model // num_head
         self.kernel_size = kernel_size
         self.native_bf16 = False
+        self.native_f16 = False
         # opt-in: box -> grid expansion in one HIP kernel each way (BoxGridFunction).  (Until round
         # 5 the value 2 built the grid inside the sampling kernels; it never removed the grid tensor -- both bin passes
         # and the point gradients read it -- and was no faster than the one-kernel grid build: removed in round 6, any
         # true value means the grid kernels.)
         self.fused_grid = False
-        # opt-in: the softmax over the L*P logits and, in the bf16 storage mode, the value
-        # mask-fill + bf16 cast as single HIP passes (LogitSoftmaxFunction, ValueMaskCastFunction)
+        # opt-in: the softmax over the L*P logits and, in the 16-bit storage modes, the value
+        # mask-fill + 16-bit cast as single HIP passes (LogitSoftmaxFunction, ValueMaskCastFunction)
         self.fused_pointwise = False
 
         self.linear_box_weight = nn.Parameter(torch.zeros(num_level * num_head * box_vars, d_model))
@@ -81,10 +83,11 @@ class _BoxAttentionBase(nn.Module):
     def _project_value(self, value, v_mask):
         b, s = value.shape[:2]
         value = dense.linear(value, self.value_proj.weight, self.value_proj.bias)
-        if (self.fused_pointwise and self.native_bf16 and value.is_cuda and
-                value.dtype in (torch.float32, torch.bfloat16) and self.d_model % 8 == 0 and
-                (v_mask is not None or value.dtype != torch.bfloat16)):   # else: nothing to do
-            value = ValueMaskCastFunction.apply(value, v_mask)
+        storage = self._storage_dtype()
+        if (self.fused_pointwise and storage is not None and value.is_cuda and
+                value.dtype in (torch.float32, storage) and self.d_model % 8 == 0 and
+                (v_mask is not None or value.dtype != storage)):   # else: nothing to do
+            value = ValueMaskCastFunction.apply(value, v_mask, storage)
         elif v_mask is not None:
             value = value.masked_fill(v_mask[..., None], float(0))
         return value.view(b, s, self.num_head, self.head_dim)
@@ -92,7 +95,8 @@ class _BoxAttentionBase(nn.Module):
     def _softmax(self, logits):
         """softmax over the last axis (the L * P logits of a (query, head))."""
         if (self.fused_pointwise and logits.is_cuda and logits.size(-1) <= 64 and
-                logits.dtype in (torch.float32, torch.bfloat16)):
+                (logits.dtype in (torch.float32, torch.bfloat16) or
+                 (logits.dtype == torch.float16 and self._storage_dtype() == torch.float16))):
             return LogitSoftmaxFunction.apply(logits)
         return F.softmax(logits, dim=-1)
 
@@ -117,8 +121,15 @@ class _BoxAttentionBase(nn.Module):
         boxes = boxes.unsqueeze(-2)
         return boxes[..., :2], boxes[..., 2:]
 
+    def _storage_dtype(self):
+        """The 16-bit storage mode the op runs in: torch.bfloat16, torch.float16 or None (float32)."""
+        if self.native_bf16 and self.native_f16:
+            raise ValueError("native_bf16 and native_f16 are exclusive: set one of them")
+        return torch.bfloat16 if self.native_bf16 else torch.float16 if self.native_f16 else None
+
     def _box_function(self):
-        return BoxAttnBF16Function if self.native_bf16 else BoxAttnFunction
+        return {torch.bfloat16: BoxAttnBF16Function, torch.float16: BoxAttnF16Function}.get(
+            self._storage_dtype(), BoxAttnFunction)
 
     def _use_fused_grid(self, query, v_valid_ratios):
         """The fused kernel covers the reference's call shapes: CUDA tensors and
@@ -231,7 +242,8 @@ class InstanceAttention(_BoxAttentionBase):
         if not self.inferencing:
             level_attn_weights = F.softmax(
                 logits.view(b, l1, self.num_head, self.num_level, k, k), dim=3)
-            fn = InstanceAttnBF16Function if self.native_bf16 else InstanceAttnFunction
+            fn = {torch.bfloat16: InstanceAttnBF16Function, torch.float16: InstanceAttnF16Function}.get(
+                self._storage_dtype(), InstanceAttnFunction)
             output, mask_output = fn.apply(value, v_shape, v_start_index, sampled_grid,
                                            spatial_attn_weights, level_attn_weights, k,
                                            self.im2col_step)

@@ -8,9 +8,9 @@ instance_attn.cu:15-157), implemented as thin calls into the C-ABI HIP library
 ``batch % min(batch, im2col_step)`` is asserted (box_attn.cu:40-42).  Kernel launch errors
 raise instead of being printed (box_attn_kernel.cuh:1118-1122).
 
-Beyond the reference: ``value`` (and the upstream gradients) may be bfloat16; sampling
-locations and attention weights are then taken in float32 (bf16 ones are upcast) and all
-accumulation is float32.  float32 / float64 calls behave exactly like the reference.
+Beyond the reference: ``value`` (and the upstream gradients) may be bfloat16 or float16; sampling
+locations and attention weights are then taken in float32 (16-bit ones are upcast), their gradients
+come back in float32, and all accumulation is float32.  float32 / float64 calls behave exactly like the reference.
 """
 import os
 
@@ -18,7 +18,8 @@ import torch
 
 from . import _lib
 
-_SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
+_SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
+_H16 = (torch.bfloat16, torch.float16)      # 16-bit storage: float32 geometry, same kernels and workspace sizes
 
 
 def _check(t, name):
@@ -41,7 +42,7 @@ def _prepare(value, shapes, lsi, loc, weights, extra=()):
     for name, t in extra:
         _check(t, name)
     if value.dtype not in _SUFFIX:
-        raise RuntimeError("box_attn: unsupported dtype %s (float32, float64, bfloat16)" % value.dtype)
+        raise RuntimeError("box_attn: unsupported dtype %s (float32, float64, bfloat16, float16)" % value.dtype)
     if shapes.dtype != torch.int64 or lsi.dtype != torch.int64:
         raise RuntimeError("spatial_shapes / level_start_index must be int64")
     if value.dim() != 4 or loc.dim() != 6 or loc.size(-1) != 2:
@@ -55,8 +56,8 @@ def _prepare(value, shapes, lsi, loc, weights, extra=()):
     for w in weights:
         if w.numel() != n_w:
             raise RuntimeError("attention weights must have B*Lq*H*L*P elements")
-    cdt = torch.float32 if value.dtype == torch.bfloat16 else value.dtype
-    if value.dtype == torch.bfloat16:
+    cdt = torch.float32 if value.dtype in _H16 else value.dtype
+    if value.dtype in _H16:
         loc = loc.float() if loc.dtype != torch.float32 else loc
         weights = [w.float() if w.dtype != torch.float32 else w for w in weights]
     elif loc.dtype != cdt or any(w.dtype != cdt for w in weights):
@@ -126,7 +127,7 @@ def _device_guard(device):
     return _NO_GUARD if device.index == torch.cuda.current_device() else torch.cuda.device(device)
 
 
-_SIZES = {}          # (query name, is_bf16, dims, level tables) -> bytes: the size queries are pure functions
+_SIZES = {}          # (query name, is_h16, dims, level tables) -> bytes: the size queries are pure functions
 _CACHE_CAP = 1024    # entries per shape-keyed cache: a detector trained on variably padded batches sees thousands of
                      # shapes; everything cached per shape is cheap to rebuild
 
@@ -143,11 +144,11 @@ def _sized_buffer(query, value, shapes, lsi, dims, minimum=256):
     """A scratch tensor of the size the library asks for (query: boxattn_plan_bytes /
     boxattn_bwd_workspace_bytes; None for 0 bytes when minimum is 0) + the host level tables."""
     sh, ls = _host_table(shapes), _host_table(lsi)
-    is_bf16 = int(value.dtype == torch.bfloat16)
-    key = (query.__name__, is_bf16, dims, sh.tobytes(), ls.tobytes(), _lib.options_epoch())
+    is_h16 = int(value.dtype in _H16)
+    key = (query.__name__, is_h16, dims, sh.tobytes(), ls.tobytes(), _lib.options_epoch())
     nbytes = _SIZES.get(key)
     if nbytes is None:
-        nbytes = _bounded(_SIZES)[key] = int(query(is_bf16, *dims, sh.ctypes.data, ls.ctypes.data))
+        nbytes = _bounded(_SIZES)[key] = int(query(is_h16, *dims, sh.ctypes.data, ls.ctypes.data))
     nbytes = max(nbytes, minimum)
     buf = torch.empty(nbytes, dtype=torch.uint8, device=value.device) if nbytes else None
     return buf, sh, ls
@@ -268,7 +269,7 @@ def _state_for(lib, value, dims, sh, ls, stream):
 
 
 def _locality(key):
-    # (only the window-staged kernels of bf16 box attention with one query per pixel collect the counters;
+    # (only the window-staged kernels of box attention with one query per pixel collect the counters;
     # everything else simply never sees a non-zero miss count)
     loc = _LOCALITY.get(key)
     if loc is None:
@@ -311,9 +312,9 @@ def workspace_bytes(value, shapes, lsi, dims):
     """(plan bytes, backward workspace bytes) the library asks for at these dimensions."""
     lib = _lib.load()
     sh, ls = _host_table(shapes), _host_table(lsi)
-    is_bf16 = int(value.dtype == torch.bfloat16)
-    return (int(lib.boxattn_plan_bytes(is_bf16, *dims, sh.ctypes.data, ls.ctypes.data)),
-            int(lib.boxattn_bwd_workspace_bytes(is_bf16, *dims, sh.ctypes.data, ls.ctypes.data)))
+    is_h16 = int(value.dtype in _H16)
+    return (int(lib.boxattn_plan_bytes(is_h16, *dims, sh.ctypes.data, ls.ctypes.data)),
+            int(lib.boxattn_bwd_workspace_bytes(is_h16, *dims, sh.ctypes.data, ls.ctypes.data)))
 
 
 _WORKSPACE = {}      # (device index, stream handle) -> the backward's scratch tensor (grown as needed)
@@ -324,11 +325,11 @@ def _workspace(query, value, shapes, lsi, dims, stream):
     (device, stream), reused: calls on a stream never overlap, and a 0.3 GB torch.empty per backward was a tenth
     of the host time of a training step."""
     sh, ls = _host_table(shapes), _host_table(lsi)
-    is_bf16 = int(value.dtype == torch.bfloat16)
-    key = (query.__name__, is_bf16, dims, sh.tobytes(), ls.tobytes(), _lib.options_epoch())
+    is_h16 = int(value.dtype in _H16)
+    key = (query.__name__, is_h16, dims, sh.tobytes(), ls.tobytes(), _lib.options_epoch())
     nbytes = _SIZES.get(key)
     if nbytes is None:
-        nbytes = _bounded(_SIZES)[key] = int(query(is_bf16, *dims, sh.ctypes.data, ls.ctypes.data))
+        nbytes = _bounded(_SIZES)[key] = int(query(is_h16, *dims, sh.ctypes.data, ls.ctypes.data))
     nbytes = max(nbytes, 256)
     wkey = (value.device.index, stream)
     ws = _WORKSPACE.get(wkey)
@@ -420,7 +421,7 @@ def _parked(value, dims, loc, weights):
 
 
 def _backward_with_workspace(name, value, shapes, lsi, loc, weights, dims, args, plan=None):
-    """Run the *_bwd_ws_* entry point (float32 / bfloat16): host level tables + scratch (+ plan)."""
+    """Run the *_bwd_ws_* entry point (float32 / bfloat16 / float16): host level tables + scratch (+ plan)."""
     lib = _lib.load()
     ready = plan is not None and plan.buf is not None and plan.key == _plan_key(dims, loc, weights, value.dtype)
     fn = getattr(lib, "%s_%s" % (name, _SUFFIX[value.dtype]))
@@ -492,7 +493,7 @@ def box_attn_forward_train(value, spatial_shapes, level_start_index, sampling_lo
 def box_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                       grad_output, im2col_step, plan=None):
     """-> [grad_value, grad_sampling_loc, grad_attn_weight] (box_attn.cu:74-135).
-    For bfloat16 ``value`` the location / weight gradients are float32."""
+    For bfloat16 / float16 ``value`` the location / weight gradients are float32."""
     dims, loc, (attn,), cdt = _prepare(value, spatial_shapes, level_start_index, sampling_loc,
                                        [attn_weight], [("grad_output", grad_output)])
     B, S, H, C, L, Lq, P = dims
@@ -661,12 +662,14 @@ def _pw_suffix(t, what):
         return "f32"
     if t.dtype == torch.bfloat16:
         return "bf16"
-    raise RuntimeError("%s: float32 or bfloat16 expected, got %s" % (what, t.dtype))
+    if t.dtype == torch.float16:
+        return "f16"
+    raise RuntimeError("%s: float32, bfloat16 or float16 expected, got %s" % (what, t.dtype))
 
 
 def softmax_forward(logits):
     """softmax over the last axis (the L*P logits of a (query, head); at most 64) of float32 /
-    bfloat16 ``logits`` -> float32 weights, one pass (box_attention.py:227-229)."""
+    bfloat16 / float16 ``logits`` -> float32 weights, one pass (box_attention.py:227-229)."""
     _check(logits, "logits")
     n = logits.size(-1)
     rows = logits.numel() // max(n, 1)
@@ -688,9 +691,10 @@ def softmax_backward(attn, grad_attn, dtype):
     return out
 
 
-def value_mask_cast(value, v_mask):
-    """(B, S, d) float32 / bfloat16 -> bfloat16 with the rows of padded pixels (``v_mask`` (B, S)
-    bool, or None) zeroed, one pass (box_attention.py:223-225 + the op's bf16 conversion)."""
+def value_mask_cast(value, v_mask, dtype=torch.bfloat16):
+    """(B, S, d) float32 / ``dtype`` -> ``dtype`` (bfloat16 or float16) with the rows of padded pixels
+    (``v_mask`` (B, S) bool, or None) zeroed, one pass (box_attention.py:223-225 + the op's 16-bit
+    conversion)."""
     _check(value, "value")
     d = value.size(-1)
     rows = value.numel() // max(d, 1)
@@ -700,6 +704,12 @@ def value_mask_cast(value, v_mask):
         if v_mask.dtype != torch.bool or v_mask.numel() != rows:
             raise RuntimeError("v_mask must be a bool tensor with one entry per value row")
         mask = v_mask
-    out = torch.empty(value.shape, dtype=torch.bfloat16, device=value.device)
-    _grid_call("boxattn_value_prep_" + _pw_suffix(value, "value"), value, value, mask, rows, d, out)
+    if dtype not in _H16:
+        raise RuntimeError("value_mask_cast: bfloat16 or float16 output expected, got %s" % dtype)
+    if value.dtype != torch.float32 and value.dtype != dtype:
+        raise RuntimeError("value_mask_cast: float32 or %s value expected, got %s" % (dtype, value.dtype))
+    out = torch.empty(value.shape, dtype=dtype, device=value.device)
+    # entry points: value_prep_{f32, bf16} write bf16; value_prep_{f32_f16, f16} write f16
+    suffix = _pw_suffix(value, "value") + ("_f16" if dtype == torch.float16 and value.dtype == torch.float32 else "")
+    _grid_call("boxattn_value_prep_" + suffix, value, value, mask, rows, d, out)
     return out

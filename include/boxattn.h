@@ -35,6 +35,11 @@
  *          loc, weights and their gradients stay float32; accumulation is float32.
  *          (New: the reference raises on BFloat16, box_attn.cu:54.)  The backward needs a
  *          float32 scratch of B*S*H*C elements for the grad_value accumulation.
+ *   _f16   the same with IEEE binary16 storage (uint16_t bit patterns): every _bf16 entry point
+ *          has an _f16 twin of the same signature and contract, running the same kernels.
+ *          Results are rounded to nearest even; magnitudes beyond 65504 become +-inf (no
+ *          overflow guarding: under loss scaling that is the scaler's business).
+ *   "16-bit storage" below means _bf16 or _f16.
  */
 #ifndef BOXATTN_H_
 #define BOXATTN_H_
@@ -63,6 +68,9 @@ int boxattn_fwd_f64(const double *value, const int64_t *shapes, const int64_t *l
 int boxattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                      const float *loc, const float *attn, int B, int S, int H, int C, int L,
                      int Lq, int P, uint16_t *out, void *stream);
+int boxattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                    const float *loc, const float *attn, int B, int S, int H, int C, int L,
+                    int Lq, int P, uint16_t *out, void *stream);
 
 /* Forward with HOST copies of the two level tables next to the device ones (either may be
  * NULL): lets the library recognise the encoder case -- one query per pixel of the packed
@@ -77,6 +85,10 @@ int boxattn_fwd_hl_bf16(const uint16_t *value, const int64_t *shapes, const int6
                         const float *loc, const float *attn, int B, int S, int H, int C, int L,
                         int Lq, int P, uint16_t *out, const int64_t *shapes_host,
                         const int64_t *lsi_host, void *stream);
+int boxattn_fwd_hl_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                       const float *loc, const float *attn, int B, int S, int H, int C, int L,
+                       int Lq, int P, uint16_t *out, const int64_t *shapes_host,
+                       const int64_t *lsi_host, void *stream);
 
 /* ---- replaces box_attn_backward (box_attn.h:56-83, box_attn.cu:74-135) ---------------- */
 int boxattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -92,6 +104,10 @@ int boxattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t
                      const float *loc, const float *attn, const uint16_t *grad_out, int B,
                      int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
                      float *grad_loc, float *grad_attn, float *grad_value_ws, void *stream);
+int boxattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                    const float *loc, const float *attn, const uint16_t *grad_out, int B,
+                    int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
+                    float *grad_loc, float *grad_attn, float *grad_value_ws, void *stream);
 
 /* ---- replaces instance_attn_forward (instance_attn.h:32-59, instance_attn.cu:15-82) --- */
 int instattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -106,6 +122,10 @@ int instattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_
                       const float *loc, const float *spatial_w, const float *level_w, int B,
                       int S, int H, int C, int L, int Lq, int P, uint16_t *out,
                       uint16_t *mask_out, void *stream);
+int instattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                     const float *loc, const float *spatial_w, const float *level_w, int B,
+                     int S, int H, int C, int L, int Lq, int P, uint16_t *out,
+                     uint16_t *mask_out, void *stream);
 
 /* ---- replaces instance_attn_backward (instance_attn.h:61-92, instance_attn.cu:85-157) - */
 int instattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -124,6 +144,12 @@ int instattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_
                       int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
                       float *grad_spatial_w, float *grad_level_w, float *grad_value_ws,
                       void *stream);
+int instattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                     const float *loc, const float *spatial_w, const float *level_w,
+                     const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
+                     int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
+                     float *grad_spatial_w, float *grad_level_w, float *grad_value_ws,
+                     void *stream);
 
 /*
  * ---- backward with a caller-provided workspace (the fast path) ---------------------------
@@ -133,14 +159,14 @@ int instattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_
  *       library plan the destination-binned algorithm without a
  *       device->host sync.  May be NULL: the call then behaves like the plain backward.
  *   workspace / workspace_bytes : device scratch, 256-byte aligned, contents ignored and
- *       clobbered; size from boxattn_bwd_workspace_bytes() (covers the bf16 fp32 scratch too).
+ *       clobbered; size from boxattn_bwd_workspace_bytes() (covers the 16-bit fp32 scratch too).
  *       It only lives inside the call (bin records, partial tiles).
  *   plan / plan_bytes : NULL / 0 -- the call plans for itself (count + scan passes first) -- or the
  *       buffer a *_fwd_train_* call filled (*plan_built == 1) for the SAME sampling locations,
  *       dimensions and option settings; it is only read.
  *   hints : 0, or BOXATTN_HINT_* bits (see *_fwd_train_*); speed only, never results.
  *   state / state_bytes : NULL / 0, or the caller's state buffer of this (stream, dimensions, level shapes) -- see
- *       *_fwd_train_* below.  With it, box attention whose accumulate runs on the matrix cores (bf16 storage at 16 /
+ *       *_fwd_train_* below.  With it, box attention whose accumulate runs on the matrix cores (16-bit storage at 16 /
  *       32 / 64 channels per head, float32 at 32) on maps of up to 1 535 blocks of 8x4 pixels per (image, head) fills
  *       its bins in ONE pass: the state keeps, per block, the record range the previous call planned
  *       from its own counts; the fill riders claim slots in those ranges with one returned atomic per block and step;
@@ -148,14 +174,16 @@ int instattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_
  *       launch; every call re-plans the ranges for the next one.  Results never depend on what the state holds; the
  *       first call on a zeroed (or foreign-shaped) state runs the two-pass passes.  Such a call takes no plan.
  * If the shape is not eligible or the workspace is too small, the call falls back to the
- * atomic kernels of the plain entry points (for _bf16 the workspace must then still hold
+ * atomic kernels of the plain entry points (for _bf16 / _f16 the workspace must then still hold
  * B*S*H*C floats); a plan the backward cannot use (operands the fast paths reject) is ignored.
- * Only float32 and bfloat16 exist here; float64 uses the plain backward.
+ * Only float32, bfloat16 and float16 exist here; float64 uses the plain backward.
+ * is_16bit (here and in boxattn_plan_bytes): non-zero for 16-bit storage, bf16 or f16 alike -- both
+ * types plan the same way and ask for the same sizes.
  * The binned path uses no float atomics and no zero-fill.  Everything runs on `stream`:
  *   [count + scans, unless a plan is given] -> point-gradient kernel with the fill pass riding in its
  *   launch -> accumulate kernel (the partial tiles of chunked blocks summed by their last chunk).
  */
-size_t boxattn_bwd_workspace_bytes(int is_bf16, int B, int S, int H, int C, int L, int Lq, int P,
+size_t boxattn_bwd_workspace_bytes(int is_16bit, int B, int S, int H, int C, int L, int Lq, int P,
                                    const int64_t *shapes_host, const int64_t *lsi_host);
 int boxattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                        const float *loc, const float *attn, const float *grad_out, int B, int S,
@@ -170,6 +198,13 @@ int boxattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int6
                         const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
                         const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
                         void *stream);
+int boxattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                       const float *loc, const float *attn, const uint16_t *grad_out, int B,
+                       int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
+                       float *grad_loc, float *grad_attn, const int64_t *shapes_host,
+                       const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                       const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+                       void *stream);
 int instattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                         const float *loc, const float *spatial_w, const float *level_w,
                         const float *grad_out, const float *grad_mask, int B, int S, int H, int C,
@@ -186,6 +221,14 @@ int instattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int
                          const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
                          const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
                         void *stream);
+int instattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                        const float *loc, const float *spatial_w, const float *level_w,
+                        const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
+                        int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
+                        float *grad_spatial_w, float *grad_level_w, const int64_t *shapes_host,
+                        const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                        const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+                       void *stream);
 
 /*
  * ---- reference windows + box offsets -> sampling grid (opt-in) ---------------
@@ -251,7 +294,7 @@ int boxattn_grid_bwd_f32(const float *ref, int ref_dim, int ref_per_head, const 
 #define BOXATTN_HINT_FRESH_STATE 2
 size_t boxattn_state_bytes(int B, int S, int H, int C, int L, int Lq, int P, const int64_t *shapes_host,
                            const int64_t *lsi_host);
-size_t boxattn_plan_bytes(int is_bf16, int B, int S, int H, int C, int L, int Lq, int P,
+size_t boxattn_plan_bytes(int is_16bit, int B, int S, int H, int C, int L, int Lq, int P,
                           const int64_t *shapes_host, const int64_t *lsi_host);
 int boxattn_fwd_train_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                           const float *loc, const float *attn, int B, int S, int H, int C, int L,
@@ -263,6 +306,11 @@ int boxattn_fwd_train_bf16(const uint16_t *value, const int64_t *shapes, const i
                            int Lq, int P, uint16_t *out, const int64_t *shapes_host,
                            const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
                            size_t state_bytes, int hints, int *plan_built, void *stream);
+int boxattn_fwd_train_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *loc, const float *attn, int B, int S, int H, int C, int L,
+                          int Lq, int P, uint16_t *out, const int64_t *shapes_host,
+                          const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
+                          size_t state_bytes, int hints, int *plan_built, void *stream);
 int instattn_fwd_train_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                            const float *loc, const float *spatial_w, const float *level_w, int B,
                            int S, int H, int C, int L, int Lq, int P, float *out, float *mask_out,
@@ -275,6 +323,12 @@ int instattn_fwd_train_bf16(const uint16_t *value, const int64_t *shapes, const 
                             uint16_t *mask_out, const int64_t *shapes_host,
                             const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
                             size_t state_bytes, int hints, int *plan_built, void *stream);
+int instattn_fwd_train_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *loc, const float *spatial_w, const float *level_w, int B,
+                           int S, int H, int C, int L, int Lq, int P, uint16_t *out,
+                           uint16_t *mask_out, const int64_t *shapes_host,
+                           const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
+                           size_t state_bytes, int hints, int *plan_built, void *stream);
 
 /*
  * Kernel-variant override for tests and A/B benchmarks (process-global, not thread-safe):
@@ -290,23 +344,32 @@ int boxattn_set_variant(int variant);
  * ---- pointwise work around the operator (opt-in, beyond the reference's native module) ------
  * The modules' softmax over the L*P attention logits of every (query, head) and the zeroing of
  * padded value rows (reference e2edet/module/box_attention.py:222-231), as single passes:
- *   boxattn_softmax_fwd_*: logits (rows, n) float32 / bfloat16 -> attn (rows, n) float32, n <= 64
+ *   boxattn_softmax_fwd_*: logits (rows, n) float32 / bfloat16 / float16 -> attn (rows, n) float32, n <= 64
  *   boxattn_softmax_bwd_*: grad_logits = attn * (grad_attn - sum_j attn_j grad_attn_j), written
  *                          in the logits' type
  *   boxattn_value_prep_*:  value (rows, d) float32 / bfloat16 -> bfloat16 with the rows whose mask
- *                          byte is non-zero set to 0 (mask may be NULL); d % 8 == 0
+ *                          byte is non-zero set to 0 (mask may be NULL); d % 8 == 0;
+ *                          _f32_f16 / _f16: float32 / float16 -> float16 likewise
  */
 int boxattn_softmax_fwd_f32(const float *logits, long long rows, int n, float *attn, void *stream);
 int boxattn_softmax_fwd_bf16(const uint16_t *logits, long long rows, int n, float *attn,
                              void *stream);
+int boxattn_softmax_fwd_f16(const uint16_t *logits, long long rows, int n, float *attn,
+                            void *stream);
 int boxattn_softmax_bwd_f32(const float *attn, const float *grad_attn, long long rows, int n,
                             float *grad_logits, void *stream);
 int boxattn_softmax_bwd_bf16(const float *attn, const float *grad_attn, long long rows, int n,
                              uint16_t *grad_logits, void *stream);
+int boxattn_softmax_bwd_f16(const float *attn, const float *grad_attn, long long rows, int n,
+                            uint16_t *grad_logits, void *stream);
 int boxattn_value_prep_f32(const float *value, const unsigned char *mask, long long rows, int d,
                            uint16_t *out, void *stream);
 int boxattn_value_prep_bf16(const uint16_t *value, const unsigned char *mask, long long rows, int d,
                             uint16_t *out, void *stream);
+int boxattn_value_prep_f32_f16(const float *value, const unsigned char *mask, long long rows, int d,
+                               uint16_t *out, void *stream);
+int boxattn_value_prep_f16(const uint16_t *value, const unsigned char *mask, long long rows, int d,
+                           uint16_t *out, void *stream);
 
 /*
  * Tuning options for A/B runs (process-wide, relaxed atomics; 0 = default).  Returns the
@@ -315,7 +378,7 @@ int boxattn_value_prep_bf16(const uint16_t *value, const unsigned char *mask, lo
  *  10  binned backward: records per work item (multiple of 64; default: from the number of sample
  *      points, 128 ... 1024).  Set it before boxattn_plan_bytes / boxattn_bwd_workspace_bytes: the
  *      layouts depend on it.
- *  11  window-staged kernels of the encoder case (box attention, bf16 or float32 storage, Lq == S, C = 32,
+ *  11  window-staged kernels of the encoder case (box attention, 16-bit or float32 storage, Lq == S, C = 32,
  *      2x2 points, <= 4 levels; forward and point gradients): 0 library default (on), 1 off
  *      (row-gather kernels -- the parity cross-check of the two kernel families; faster for uniformly random
  *      sampling locations, which the BOXATTN_HINT_NOT_LOCAL hint selects per call), 2 on
