@@ -72,6 +72,10 @@ _POINTWISE_SIGNATURES = {
     "boxattn_value_prep_bf16": [_vp, _vp, _ll, _i, _vp, _vp],
     "boxattn_value_prep_f32_f16": [_vp, _vp, _ll, _i, _vp, _vp],     # float32 -> f16
     "boxattn_value_prep_f16": [_vp, _vp, _ll, _i, _vp, _vp],
+    # logits, rows, L, k, spatial_w, level_w | NULL, stream
+    **{"instattn_weights_fwd_" + suf: [_vp, _ll, _i, _i, _vp, _vp, _vp] for suf in ("f32", "bf16", "f16")},
+    # logits, grad_spatial_w | NULL, grad_level_w | NULL, rows, L, k, grad_logits, stream
+    **{"instattn_weights_bwd_" + suf: [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp] for suf in ("f32", "bf16", "f16")},
 }
 _GRID_SIGNATURES = {
     # ref, ref_dim, ref_per_head, offsets, V, angle_mode, kernel_idx, valid_ratios, [grad_grid,]

@@ -1,7 +1,8 @@
 // C ABI, part two (declared in include/boxattn.h): the opt-in extras around the operator that are
 // plain elementwise kernels -- reference windows + box offsets -> sampling grid (first step;
 // the modules' `_where_to_attend`, e2edet/module/box_attention.py:63-81, 196-214, 304-338) and the softmax /
-// mask-fill + cast passes (N3; box_attention.py:222-231).  The operator itself is boxattn_capi.hip.
+// mask-fill + cast passes (N3; box_attention.py:222-231), instance attention's weights from its 2x2 logits
+// (box_attention.py:100-121).  The operator itself is boxattn_capi.hip.
 #include "../../include/boxattn.h"
 
 #include <hip/hip_runtime.h>
@@ -143,6 +144,73 @@ static int value_prep(const T *value, const unsigned char *mask, long long rows,
     return finish();
 }
 
+// ---- instance attention: spatial / level weights from the 2x2 logits and back --------------------------
+// k even, 2 <= k <= 32; 1 <= L <= 16 (4 L <= 64 cells: a row fits the lanes of a wave)
+static bool inst_dims(int L, int k, InstDims &d)
+{
+    if (L < 1 || L > 16 || k < 2 || k > 32 || k % 2 != 0) return false;
+    const unsigned n4_level = (unsigned)(k * k / 4);
+    const float m = (float)(k / 2);
+    d = InstDims{L, k, n4_level, n4_level * (unsigned)L, 1.f / (float)k, 1.f / (float)n4_level,
+                 1.f / (float)(n4_level * (unsigned)L), 1.f / (m * m)};
+    return true;
+}
+// lanes per row: 4 * (L rounded up to a power of two); blocks of 4 waves with 64 / G rows each, 0: too many
+static int inst_group(int L, long long rows, unsigned &blocks)
+{
+    int g = 4;
+    while (g < 4 * L) g *= 2;
+    const long long per_block = 4 * (64 / g);
+    const long long n = (rows + per_block - 1) / per_block;
+    blocks = (unsigned)n;
+    return n > 0x7fffffffLL ? 0 : g;
+}
+#define BOXATTN_INST_GROUPS(LAUNCH) \
+    if (g == 4) LAUNCH(4); \
+    else if (g == 8) LAUNCH(8); \
+    else if (g == 16) LAUNCH(16); \
+    else if (g == 32) LAUNCH(32); \
+    else LAUNCH(64)
+
+template <typename T>
+static int inst_weights_fwd(const T *logits, long long rows, int L, int k, float *spatial_w, float *level_w,
+                            hipStream_t st)
+{
+    InstDims d{};
+    unsigned blocks = 0;
+    if (rows < 0 || !inst_dims(L, k, d)) return (int)hipErrorInvalidValue;
+    if (rows == 0) return 0;
+    const int g = inst_group(L, rows, blocks);
+    if (!g || !logits || !spatial_w || !aligned(spatial_w, 16) || !aligned(level_w, 16))
+        return (int)hipErrorInvalidValue;
+#define BOXATTN_INST_FWD(G) \
+    hipLaunchKernelGGL((inst_weights_fwd_kernel<T, G>), dim3(blocks), dim3(256), 0, st, logits, (size_t)rows, d, \
+                       spatial_w, level_w)
+    BOXATTN_INST_GROUPS(BOXATTN_INST_FWD);
+#undef BOXATTN_INST_FWD
+    return finish();
+}
+
+template <typename T>
+static int inst_weights_bwd(const T *logits, const float *grad_spatial_w, const float *grad_level_w, long long rows,
+                            int L, int k, T *grad_logits, hipStream_t st)
+{
+    InstDims d{};
+    unsigned blocks = 0;
+    if (rows < 0 || !inst_dims(L, k, d)) return (int)hipErrorInvalidValue;
+    if (rows == 0) return 0;
+    const int g = inst_group(L, rows, blocks);
+    if (!g || !logits || !grad_logits || !aligned(grad_spatial_w, 16) || !aligned(grad_level_w, 16))
+        return (int)hipErrorInvalidValue;
+#define BOXATTN_INST_BWD(G) \
+    hipLaunchKernelGGL((inst_weights_bwd_kernel<T, G>), dim3(blocks), dim3(256), 0, st, logits, grad_spatial_w, \
+                       grad_level_w, (size_t)rows, d, grad_logits)
+    BOXATTN_INST_GROUPS(BOXATTN_INST_BWD);
+#undef BOXATTN_INST_BWD
+    return finish();
+}
+#undef BOXATTN_INST_GROUPS
+
 extern "C" {
 
 int boxattn_softmax_fwd_f32(const float *logits, long long rows, int n, float *attn, void *stream)
@@ -194,6 +262,41 @@ int boxattn_value_prep_f16(const uint16_t *value, const unsigned char *mask, lon
 {
     return value_prep<f16_t, f16_t>(reinterpret_cast<const f16_t *>(value), mask, rows, d,
                                     reinterpret_cast<f16_t *>(out), (hipStream_t)stream);
+}
+
+int instattn_weights_fwd_f32(const float *logits, long long rows, int L, int k, float *spatial_w, float *level_w,
+                             void *stream)
+{
+    return inst_weights_fwd<float>(logits, rows, L, k, spatial_w, level_w, (hipStream_t)stream);
+}
+int instattn_weights_fwd_bf16(const uint16_t *logits, long long rows, int L, int k, float *spatial_w,
+                              float *level_w, void *stream)
+{
+    return inst_weights_fwd<bf16_t>(logits, rows, L, k, spatial_w, level_w, (hipStream_t)stream);
+}
+int instattn_weights_fwd_f16(const uint16_t *logits, long long rows, int L, int k, float *spatial_w,
+                             float *level_w, void *stream)
+{
+    return inst_weights_fwd<f16_t>(reinterpret_cast<const f16_t *>(logits), rows, L, k, spatial_w, level_w,
+                                   (hipStream_t)stream);
+}
+int instattn_weights_bwd_f32(const float *logits, const float *grad_spatial_w, const float *grad_level_w,
+                             long long rows, int L, int k, float *grad_logits, void *stream)
+{
+    return inst_weights_bwd<float>(logits, grad_spatial_w, grad_level_w, rows, L, k, grad_logits,
+                                   (hipStream_t)stream);
+}
+int instattn_weights_bwd_bf16(const uint16_t *logits, const float *grad_spatial_w, const float *grad_level_w,
+                              long long rows, int L, int k, uint16_t *grad_logits, void *stream)
+{
+    return inst_weights_bwd<bf16_t>(logits, grad_spatial_w, grad_level_w, rows, L, k, grad_logits,
+                                    (hipStream_t)stream);
+}
+int instattn_weights_bwd_f16(const uint16_t *logits, const float *grad_spatial_w, const float *grad_level_w,
+                             long long rows, int L, int k, uint16_t *grad_logits, void *stream)
+{
+    return inst_weights_bwd<f16_t>(reinterpret_cast<const f16_t *>(logits), grad_spatial_w, grad_level_w, rows, L,
+                                   k, reinterpret_cast<f16_t *>(grad_logits), (hipStream_t)stream);
 }
 
 }  // extern "C"

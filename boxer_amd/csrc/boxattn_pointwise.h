@@ -1,7 +1,8 @@
 // The elementwise kernels around the operator (one translation unit: boxattn_extras.hip): reference windows +
 // box offsets -> sampling grid and back (first step), softmax over the L*P logits of a
-// (query, head) each way, value mask-fill + bf16 cast (N3).  The device helpers they share with the sampling
-// kernels (grid_box, grid_point, grid_grad_*) live in boxattn_grid.h.
+// (query, head) each way, instance attention's spatial / level weights from its 2x2 logits each way, value
+// mask-fill + bf16 cast (N3).  The device helpers they share with the sampling kernels (grid_box, grid_point,
+// grid_grad_*) live in boxattn_grid.h.
 #pragma once
 #include "boxattn_grid.h"
 
@@ -169,6 +170,185 @@ __global__ __launch_bounds__(256) void softmax_vec_bwd_kernel(const float *__res
 #pragma unroll
     for (int k = 0; k < 4; ++k) a[k] *= g[k] - dot;
     if (live) VecIO<T, 4>::st(grad_logits + i, a);
+}
+
+// ---------------------------------------------------------------------------------------
+// Instance attention: both weight tensors from the 2x2 logits of every level, and the gradients back
+// (modules.py InstanceAttention; reference box_attention.py:100-121 expands the logits with two
+// repeat_interleave and runs two softmaxes over the expanded tensor).  Per row r = (b, q, h): logits
+// z[l][i][j] (l < L; i, j in {0, 1}), m = k / 2, point (l, y, x) lies in cell c = (l, y >= m, x >= m):
+//   a = softmax of z over the 4 L cells of the row,   t[l][i][j] = softmax of z[.][i][j] over l
+//   spatial_w[l][y][x] = a[c] / m^2      (every exponential appears m^2 times in the expanded denominator)
+//   level_w[l][y][x]   = t[c]
+//   grad_z[c] = a[c] / m^2 (Gs[c] - sum_c' a[c'] Gs[c']) + t[c] (Gt[c] - sum_l' t[l'][i][j] Gt[l'][i][j])
+// with Gs / Gt the sums of the upstream gradients over the m^2 points of a cell.  The backward reads the logits
+// and the upstream gradients only: a and t are recomputed.
+// Lane layout of both kernels: a row takes G = 4 * (L rounded up to a power of two) adjacent lanes, lane c of the
+// group holds cell c (l = c / 4, i = c / 2 % 2, j = c % 2), a wave holds 64 / G consecutive rows.  The softmax over
+// the row is a butterfly over the group, the one over the levels a butterfly over the lanes 4 apart: fixed order,
+// no atomics, so both kernels are bitwise reproducible.
+// The (rows, L, k, k) tensors are accessed as float4 (k even: k^2 is a multiple of 4, a float4 never crosses a
+// level) and must be 16-byte aligned -- the entry points reject other pointers; the logits and their gradient are
+// accessed element by element (consecutive lanes, consecutive elements) and need no alignment.
+// ---------------------------------------------------------------------------------------
+template <int FROM, int G> __device__ __forceinline__ float lanes_max(float v)   // over lanes FROM, 2 FROM, .. G/2 apart
+{
+#pragma unroll
+    for (int o = FROM; o < G; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+template <int FROM, int G> __device__ __forceinline__ float lanes_add(float v)
+{
+#pragma unroll
+    for (int o = FROM; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// q / d for q < 2^20 from rcp = 1.f / d: (q + 0.5) / d is at least 0.5 / d away from an integer, the two
+// roundings (rcp, the product) move it by less than (q + 0.5) / d * 2^-22
+__device__ __forceinline__ unsigned small_div(unsigned q, float rcp)
+{
+    return (unsigned)(((float)q + 0.5f) * rcp);
+}
+
+struct InstDims {
+    int L, k;
+    unsigned n4_level, n4_row;             // float4s per level (k^2 / 4) and per row
+    float rcp_k, rcp_n4_level, rcp_n4_row;
+    float inv_m2;                          // 1 / m^2
+};
+
+// this lane's cell: a (softmax over the row, not yet divided by m^2) and t (softmax over the levels)
+template <typename T, int G>
+__device__ __forceinline__ void inst_cell_softmax(const T *__restrict__ logits, size_t row, int c, int L,
+                                                  float &a, float &t)
+{
+    const float z = c < 4 * L ? pw_ld<T>(logits + row * (size_t)(4 * L) + c) : -INFINITY;
+    const float ea = __expf(z - lanes_max<1, G>(z));
+    a = ea * (1.f / lanes_add<1, G>(ea));
+    const float et = __expf(z - lanes_max<4, G>(z));          // (level 0 is always there: the maxima are finite)
+    t = et * (1.f / lanes_add<4, G>(et));
+}
+
+__device__ __forceinline__ float inst_pick(bool hi_y, bool hi_x, float c0, float c1, float c2, float c3)
+{
+    return hi_y ? (hi_x ? c3 : c2) : (hi_x ? c1 : c0);
+}
+
+// Store-bound: the 64 / G rows of a wave are one contiguous run of float4s in each output, written 64 float4s
+// (1 KB) at a time; a float4's four cell values come from the lanes of its (row, level) by ds_bpermute and each
+// element picks its cell with two compares.
+template <typename T, int G>
+__global__ __launch_bounds__(256) void inst_weights_fwd_kernel(const T *__restrict__ logits, size_t rows,
+                                                               InstDims d, float *__restrict__ spatial_w,
+                                                               float *__restrict__ level_w)
+{
+    constexpr int R = 64 / G;
+    const int lane = threadIdx.x & 63;
+    const size_t row0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
+    if (row0 >= rows) return;                                  // (wave-uniform)
+    const size_t my_row = row0 + lane / G;
+    float a, t;
+    inst_cell_softmax<T, G>(logits, my_row < rows ? my_row : rows - 1, lane % G, d.L, a, t);
+    a *= d.inv_m2;
+
+    const unsigned live_rows = rows - row0 < (size_t)R ? (unsigned)(rows - row0) : (unsigned)R;
+    const unsigned n4 = live_rows * d.n4_row;
+    const int m = d.k / 2;
+    float4 *sw = reinterpret_cast<float4 *>(spatial_w) + row0 * d.n4_row;
+    float4 *lw = level_w ? reinterpret_cast<float4 *>(level_w) + row0 * d.n4_row : nullptr;
+    for (unsigned base = 0; base < n4; base += 64) {          // uniform trip count: every lane takes part in the permutes
+        const bool live = base + lane < n4;
+        const unsigned q = live ? base + lane : 0;
+        const unsigned rw = small_div(q, d.rcp_n4_row), q_row = q - rw * d.n4_row;
+        const unsigned l = small_div(q_row, d.rcp_n4_level), e0 = 4 * (q_row - l * d.n4_level);
+        const int y0 = (int)small_div(e0, d.rcp_k), x0 = (int)e0 - y0 * d.k;
+        bool hi_y[4], hi_x[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                          // x0 + 3 < 2 k: at most one wrap
+            const bool wrap = x0 + j >= d.k;
+            hi_x[j] = (wrap ? x0 + j - d.k : x0 + j) >= m;
+            hi_y[j] = y0 + (wrap ? 1 : 0) >= m;
+        }
+        const int src = (int)(rw * G + l * 4);
+        {
+            const float c0 = __shfl(a, src, 64), c1 = __shfl(a, src + 1, 64), c2 = __shfl(a, src + 2, 64),
+                        c3 = __shfl(a, src + 3, 64);
+            if (live)
+                sw[q] = make_float4(inst_pick(hi_y[0], hi_x[0], c0, c1, c2, c3), inst_pick(hi_y[1], hi_x[1], c0, c1, c2, c3),
+                                    inst_pick(hi_y[2], hi_x[2], c0, c1, c2, c3), inst_pick(hi_y[3], hi_x[3], c0, c1, c2, c3));
+        }
+        if (lw) {                                              // (uniform)
+            const float c0 = __shfl(t, src, 64), c1 = __shfl(t, src + 1, 64), c2 = __shfl(t, src + 2, 64),
+                        c3 = __shfl(t, src + 3, 64);
+            if (live)
+                lw[q] = make_float4(inst_pick(hi_y[0], hi_x[0], c0, c1, c2, c3), inst_pick(hi_y[1], hi_x[1], c0, c1, c2, c3),
+                                    inst_pick(hi_y[2], hi_x[2], c0, c1, c2, c3), inst_pick(hi_y[3], hi_x[3], c0, c1, c2, c3));
+        }
+    }
+}
+
+struct InstCellSums { float c0, c1, c2, c3; };
+__device__ __forceinline__ void inst_cell_add(InstCellSums &s, bool hi_y, bool hi_x, float g)
+{
+    s.c0 += !hi_y && !hi_x ? g : 0.f;
+    s.c1 += !hi_y && hi_x ? g : 0.f;
+    s.c2 += hi_y && !hi_x ? g : 0.f;
+    s.c3 += hi_y && hi_x ? g : 0.f;
+}
+// the four lanes of a level: sum the partial cell sums over them (DPP quad), lane s keeps cell s
+__device__ __forceinline__ float inst_cell_total(const InstCellSums &s, int sub)
+{
+    const float c0 = lanes_add<1, 4>(s.c0), c1 = lanes_add<1, 4>(s.c1), c2 = lanes_add<1, 4>(s.c2),
+                c3 = lanes_add<1, 4>(s.c3);
+    return sub == 0 ? c0 : sub == 1 ? c1 : sub == 2 ? c2 : c3;
+}
+
+// Load-bound: the four lanes of a (row, level) walk that level's k^2 / 4 float4s of each upstream gradient (a
+// quad reads 64 consecutive bytes), every lane keeps four per-cell sums per gradient, chosen by predicate; quad
+// sums, then lane c holds Gs[c] and Gt[c] next to its a[c] and t[c].  Either gradient may be NULL (= zeros).
+template <typename T, int G>
+__global__ __launch_bounds__(256) void inst_weights_bwd_kernel(const T *__restrict__ logits,
+                                                               const float *__restrict__ grad_spatial,
+                                                               const float *__restrict__ grad_level,
+                                                               size_t rows, InstDims d,
+                                                               T *__restrict__ grad_logits)
+{
+    constexpr int R = 64 / G;
+    const int lane = threadIdx.x & 63;
+    const size_t row0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
+    if (row0 >= rows) return;                                  // (wave-uniform)
+    const size_t my_row = row0 + lane / G;
+    const int c = lane % G, l = c / 4, sub = c % 4;
+    const bool live = my_row < rows && l < d.L;
+    const size_t row = my_row < rows ? my_row : rows - 1;
+    float a, t;
+    inst_cell_softmax<T, G>(logits, row, c, d.L, a, t);
+
+    const int m = d.k / 2;
+    InstCellSums gs{0.f, 0.f, 0.f, 0.f}, gt{0.f, 0.f, 0.f, 0.f};
+    if (live) {
+        const size_t at = (row * (unsigned)d.L + (unsigned)l) * d.n4_level;
+        const float4 *ps = grad_spatial ? reinterpret_cast<const float4 *>(grad_spatial) + at : nullptr;
+        const float4 *pt = grad_level ? reinterpret_cast<const float4 *>(grad_level) + at : nullptr;
+#pragma unroll 4
+        for (unsigned q = sub; q < d.n4_level; q += 4) {
+            const float4 s = ps ? ps[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 u = pt ? pt[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const int y0 = (int)small_div(4 * q, d.rcp_k), x0 = (int)(4 * q) - y0 * d.k;
+            const float sv[4] = {s.x, s.y, s.z, s.w}, uv[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool wrap = x0 + j >= d.k;
+                const bool hi_x = (wrap ? x0 + j - d.k : x0 + j) >= m, hi_y = y0 + (wrap ? 1 : 0) >= m;
+                inst_cell_add(gs, hi_y, hi_x, sv[j]);
+                inst_cell_add(gt, hi_y, hi_x, uv[j]);
+            }
+        }
+    }
+    const float Gs = inst_cell_total(gs, sub), Gt = inst_cell_total(gt, sub);
+    const float dot_s = lanes_add<1, G>(a * Gs), dot_t = lanes_add<4, G>(t * Gt);
+    if (live) pw_st<T>(grad_logits + row * (size_t)(4 * d.L) + c, a * d.inv_m2 * (Gs - dot_s) + t * (Gt - dot_t));
 }
 
 // value (rows, d) of type T -> 16-bit OT (bfloat16 or float16), rows with mask != 0 zeroed; 8 channels

@@ -267,6 +267,30 @@ class LogitSoftmaxFunction(Function):
         return ops.softmax_backward(attn, grad_attn.contiguous().float(), ctx.logits_dtype)
 
 
+class InstanceWeightsFunction(Function):
+    """(logits (B,Lq,H,L,2,2), kernel_size, need_level) -> (spatial_w, level_w or None), each (B,Lq,H,L,k,k)
+    float32: ``InstanceAttention``'s repeat_interleave + two softmaxes as one HIP pass each way
+    (``module.fused_pointwise``; see ``ops.instance_weights_forward``).  Only the logits are kept for the
+    backward, which recomputes both softmaxes from them; the gradient of an output nothing used arrives as None
+    and reaches the kernel as a NULL pointer."""
+
+    @staticmethod
+    def forward(ctx, logits, kernel_size, need_level=True):
+        ctx.set_materialize_grads(False)
+        logits = logits.contiguous()
+        ctx.save_for_backward(logits)
+        return ops.instance_weights_forward(logits, kernel_size, need_level)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_spatial, grad_level):
+        if grad_spatial is None and grad_level is None:
+            return None, None, None
+        (logits,) = ctx.saved_tensors
+        grads = [g if g is None else g.contiguous().float() for g in (grad_spatial, grad_level)]
+        return ops.instance_weights_backward(logits, *grads), None, None
+
+
 class ValueMaskCastFunction(Function):
     """value -> bfloat16 (or ``dtype``: float16) with padded rows zeroed (``ops.value_mask_cast``);
     the gradient is the upstream one with the same rows zeroed, in the input's type."""

@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from . import dense
 from .functions import (BoxAttnBF16Function, BoxAttnF16Function, BoxAttnFunction, BoxGridFunction,
                         InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
-                        LogitSoftmaxFunction, ValueMaskCastFunction)
+                        InstanceWeightsFunction, LogitSoftmaxFunction, ValueMaskCastFunction)
 
 
 def _kernel_offsets(kernel_size, divisor):
@@ -56,8 +56,10 @@ class _BoxAttentionBase(nn.Module):
         # and the point gradients read it -- and was no faster than the one-kernel grid build: removed in round 6, any
         # true value means the grid kernels.)
         self.fused_grid = False
-        # opt-in: the softmax over the L*P logits and, in the 16-bit storage modes, the value
-        # mask-fill + 16-bit cast as single HIP passes (LogitSoftmaxFunction, ValueMaskCastFunction)
+        # opt-in: the attention weights -- BoxAttention / Box3dAttention: the softmax over the L*P logits
+        # (LogitSoftmaxFunction); InstanceAttention: spatial and level weights from the 2x2 logits per level
+        # (InstanceWeightsFunction) -- and, in the 16-bit storage modes, the value mask-fill + 16-bit cast
+        # (ValueMaskCastFunction) as single HIP passes
         self.fused_pointwise = False
 
         self.linear_box_weight = nn.Parameter(torch.zeros(num_level * num_head * box_vars, d_model))
@@ -92,11 +94,16 @@ class _BoxAttentionBase(nn.Module):
             value = value.masked_fill(v_mask[..., None], float(0))
         return value.view(b, s, self.num_head, self.head_dim)
 
+    def _fused_logits(self, logits):
+        """Whether the single-pass weight kernels take these logits: float32 / bfloat16, or float16 in the
+        float16 storage mode."""
+        return (self.fused_pointwise and logits.is_cuda and
+                (logits.dtype in (torch.float32, torch.bfloat16) or
+                 (logits.dtype == torch.float16 and self._storage_dtype() == torch.float16)))
+
     def _softmax(self, logits):
         """softmax over the last axis (the L * P logits of a (query, head))."""
-        if (self.fused_pointwise and logits.is_cuda and logits.size(-1) <= 64 and
-                (logits.dtype in (torch.float32, torch.bfloat16) or
-                 (logits.dtype == torch.float16 and self._storage_dtype() == torch.float16))):
+        if logits.size(-1) <= 64 and self._fused_logits(logits):
             return LogitSoftmaxFunction.apply(logits)
         return F.softmax(logits, dim=-1)
 
@@ -231,17 +238,24 @@ class InstanceAttention(_BoxAttentionBase):
 
         logits = dense.linear(query, self.linear_attn_weight, self.linear_attn_bias)
         logits = logits.view(b, l1, self.num_head, self.num_level, 2, 2)
-        logits = logits.repeat_interleave(k // 2, dim=-1).repeat_interleave(k // 2, dim=-2)
-        spatial_attn_weights = F.softmax(logits.reshape(b, l1, self.num_head, -1), dim=-1).view(
-            b, l1, self.num_head, self.num_level, k, k)
+        # (the kernels' shapes: k even, 2 ... 32, at most 16 levels)
+        fused = (k % 2 == 0 and 2 <= k <= 32 and self.num_level <= 16 and self._fused_logits(logits))
+        if fused:
+            spatial_attn_weights, level_attn_weights = InstanceWeightsFunction.apply(
+                logits, k, not self.inferencing)
+        else:
+            logits = logits.repeat_interleave(k // 2, dim=-1).repeat_interleave(k // 2, dim=-2)
+            spatial_attn_weights = F.softmax(logits.reshape(b, l1, self.num_head, -1), dim=-1).view(
+                b, l1, self.num_head, self.num_level, k, k)
 
         sampled_grid = self._where_to_attend(query, v_valid_ratios, ref_windows)
 
         # `inferencing` is injected by the model (base_model.py:49-67); like the reference,
         # a bare module without it raises AttributeError here.
         if not self.inferencing:
-            level_attn_weights = F.softmax(
-                logits.view(b, l1, self.num_head, self.num_level, k, k), dim=3)
+            if not fused:
+                level_attn_weights = F.softmax(
+                    logits.view(b, l1, self.num_head, self.num_level, k, k), dim=3)
             fn = {torch.bfloat16: InstanceAttnBF16Function, torch.float16: InstanceAttnF16Function}.get(
                 self._storage_dtype(), InstanceAttnFunction)
             output, mask_output = fn.apply(value, v_shape, v_start_index, sampled_grid,

@@ -713,3 +713,53 @@ def value_mask_cast(value, v_mask, dtype=torch.bfloat16):
     suffix = _pw_suffix(value, "value") + ("_f16" if dtype == torch.float16 and value.dtype == torch.float32 else "")
     _grid_call("boxattn_value_prep_" + suffix, value, value, mask, rows, d, out)
     return out
+
+
+def _inst_logits(logits):
+    """-> (rows, L) of (..., L, 2, 2) logits."""
+    _check(logits, "logits")
+    if logits.dim() < 3 or tuple(logits.shape[-2:]) != (2, 2):
+        raise RuntimeError("expected logits (..., L, 2, 2), got %s" % (tuple(logits.shape),))
+    L = logits.size(-3)
+    return logits.numel() // max(4 * L, 1), L
+
+
+def _aligned16(t):
+    """The (..., L, k, k) tensors are accessed 16 bytes at a time: a view into the middle of a storage is copied."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def instance_weights_forward(logits, kernel_size, need_level=True):
+    """InstanceAttention's weights from its 2x2 logits per level, one pass (box_attention.py:100-121):
+    ``logits`` (..., L, 2, 2) float32 / bfloat16 / float16 -> ``spatial_w`` = softmax over the L*k*k logits
+    replicated to k x k, and ``level_w`` = their softmax over L (None unless ``need_level``), each
+    (..., L, k, k) float32.  ``kernel_size`` even, 2 ... 32; L <= 16."""
+    rows, L = _inst_logits(logits)
+    k = int(kernel_size)
+    shape = tuple(logits.shape[:-2]) + (max(k, 0), max(k, 0))
+    spatial = torch.empty(shape, dtype=torch.float32, device=logits.device)
+    level = torch.empty(shape, dtype=torch.float32, device=logits.device) if need_level else None
+    _grid_call("instattn_weights_fwd_" + _pw_suffix(logits, "logits"), logits, logits, rows, L, k, spatial,
+               level if need_level else 0)
+    return spatial, level
+
+
+def instance_weights_backward(logits, grad_spatial, grad_level=None):
+    """-> grad_logits in the logits' type from the logits and the float32 gradients of the two outputs of
+    ``instance_weights_forward`` (either may be None: zeros): the closed form of include/boxattn.h, nothing of the
+    forward is needed."""
+    rows, L = _inst_logits(logits)
+    given = [g for g in (grad_spatial, grad_level) if g is not None]
+    if not given:
+        raise RuntimeError("instance_weights_backward: at least one gradient expected")
+    k = given[0].size(-1)
+    for g in given:
+        _check(g, "grad")
+        if g.dtype != torch.float32 or tuple(g.shape) != tuple(logits.shape[:-2]) + (k, k):
+            raise RuntimeError("instance_weights_backward: float32 gradients (..., L, k, k) matching the logits "
+                               "expected")
+    out = torch.empty_like(logits)
+    _grid_call("instattn_weights_bwd_" + _pw_suffix(logits, "logits"), logits, logits,
+               _aligned16(grad_spatial) if grad_spatial is not None else 0,
+               _aligned16(grad_level) if grad_level is not None else 0, rows, L, k, out)
+    return out

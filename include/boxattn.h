@@ -372,6 +372,38 @@ int boxattn_value_prep_f16(const uint16_t *value, const unsigned char *mask, lon
                            uint16_t *out, void *stream);
 
 /*
+ * Instance attention: the two weight tensors the instattn_* entry points take, from the 2x2 logits per level the
+ * module predicts (reference e2edet/module/box_attention.py:100-121: two repeat_interleave and two softmaxes
+ * over the expanded tensor), one pass each way.  Per row (batch, query, head): logits z[l][i][j], l < L, i, j in
+ * {0, 1}; m = k / 2; point (l, y, x) lies in cell c = (l, y >= m, x >= m).  With a = softmax of z over the 4 L
+ * cells of the row and t[l][i][j] = softmax of z[.][i][j] over the levels:
+ *   instattn_weights_fwd_*: logits (rows, L, 2, 2) float32 / bfloat16 / float16 ->
+ *                           spatial_w[l][y][x] = a[c] / m^2 and, unless level_w is NULL, level_w[l][y][x] = t[c],
+ *                           each (rows, L, k, k) float32; arithmetic in float32.
+ *   instattn_weights_bwd_*: grad_logits[c] = a[c] / m^2 (Gs[c] - sum_c' a[c'] Gs[c'])
+ *                                          + t[c] (Gt[c] - sum_l' t[l'][i][j] Gt[l'][i][j]),
+ *                           Gs / Gt = the sums of grad_spatial_w / grad_level_w over the m^2 points of a cell;
+ *                           written in the logits' type.  Reads the logits and the two gradients only (a and t are
+ *                           recomputed); a NULL gradient counts as zeros.  No atomics: bitwise reproducible.
+ * k even, 2 <= k <= 32; 1 <= L <= 16; rows >= 0 (0: nothing is launched); anything else is hipErrorInvalidValue,
+ * and so is a (rows, L, k, k) pointer that is not 16-byte aligned.  The logits need no alignment.
+ */
+int instattn_weights_fwd_f32(const float *logits, long long rows, int L, int k, float *spatial_w,
+                             float *level_w, void *stream);
+int instattn_weights_fwd_bf16(const uint16_t *logits, long long rows, int L, int k, float *spatial_w,
+                              float *level_w, void *stream);
+int instattn_weights_fwd_f16(const uint16_t *logits, long long rows, int L, int k, float *spatial_w,
+                             float *level_w, void *stream);
+int instattn_weights_bwd_f32(const float *logits, const float *grad_spatial_w, const float *grad_level_w,
+                             long long rows, int L, int k, float *grad_logits, void *stream);
+int instattn_weights_bwd_bf16(const uint16_t *logits, const float *grad_spatial_w,
+                              const float *grad_level_w, long long rows, int L, int k,
+                              uint16_t *grad_logits, void *stream);
+int instattn_weights_bwd_f16(const uint16_t *logits, const float *grad_spatial_w,
+                             const float *grad_level_w, long long rows, int L, int k,
+                             uint16_t *grad_logits, void *stream);
+
+/*
  * Tuning options for A/B runs (process-wide, relaxed atomics; 0 = default).  Returns the
  * previous value, -1 for an unknown key.  (The key numbers of earlier ABI versions are kept; the keys
  * of kernels that were removed are gone.)
