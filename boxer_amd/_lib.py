@@ -54,6 +54,11 @@ _WS_SIGNATURES = {
     "instattn_fwd_train": [_vp] * 6 + _DIMS + [_vp] * 2 + [_vp, _vp, _vp, ctypes.c_size_t, _vp,
                                                           ctypes.c_size_t, _i, _vp, _vp],
 }
+WANT_VALUE, WANT_POINTS, WANT_ALL = 1, 2, 3      # BOXATTN_WANT_*: the gradient groups of a partial backward
+# *_bwd_part_*: the arguments of *_bwd_ws_* (float64: of the plain backward) + int want
+_PART_SIGNATURES = {stem.replace("_bwd_ws", "_bwd_part"): args + [_i] for stem, args in _WS_SIGNATURES.items()
+                    if "_bwd_ws" in stem}
+_PART_F64_SIGNATURES = {stem + "_part_f64": _SIGNATURES[stem] + [_i] for stem in ("boxattn_bwd", "instattn_bwd")}
 _HL_SIGNATURES = {
     # forward args + shapes_host, lsi_host, stream
     "boxattn_fwd_hl": [_vp] * 5 + _DIMS + [_vp] + [_vp, _vp, _vp],
@@ -91,7 +96,8 @@ EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "
            "boxattn_plan_bytes", "boxattn_state_bytes",
            "boxattn_grid_fwd_f32", "boxattn_grid_bwd_f32"] + [
     "%s_%s" % (stem, suf) for stem in _SIGNATURES for suf in ("f32", "f64", "bf16", "f16")] + [
-    "%s_%s" % (stem, suf) for stem in _WS_SIGNATURES for suf in ("f32", "bf16", "f16")]
+    "%s_%s" % (stem, suf) for stem in _WS_SIGNATURES for suf in ("f32", "bf16", "f16")] + [
+    "%s_%s" % (stem, suf) for stem in _PART_SIGNATURES for suf in ("f32", "bf16", "f16")] + sorted(_PART_F64_SIGNATURES)
 # 16-bit storage types: the suffix of their entry points, which share signatures (uint16_t storage)
 H16_SUFFIXES = ("bf16", "f16")
 ABI_VERSION = 8
@@ -206,6 +212,14 @@ def load():
             fn = getattr(lib, "%s_%s" % (stem, suf))
             fn.argtypes = args
             fn.restype = _i
+    for stem, args in _PART_SIGNATURES.items():
+        for suf in ("f32",) + H16_SUFFIXES:
+            fn = getattr(lib, "%s_%s" % (stem, suf))
+            fn.argtypes = args
+            fn.restype = _i
+    for name, args in _PART_F64_SIGNATURES.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = _i
     for stem, args in _HL_SIGNATURES.items():
         for suf in ("f32",) + H16_SUFFIXES:
             fn = getattr(lib, "%s_%s" % (stem, suf))

@@ -413,7 +413,12 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
 }
 
 // ----------------------------------------------------------------------------- backward
-// GV = accumulation buffer for grad_value (the output itself for f32/f64, scratch for bf16 / f16)
+// The two gradient groups of a backward (BOXATTN_WANT_*): VALUE = grad_value, POINTS = grad_loc + the weight gradients.
+enum { kWantValue = BOXATTN_WANT_VALUE, kWantPoints = BOXATTN_WANT_POINTS, kWantAll = kWantValue | kWantPoints };
+
+// The atomic kernels.  GV = accumulation buffer for grad_value (the output itself for f32/f64, scratch for bf16 / f16)
+// want: the groups to compute (a partial backward, *_bwd_part_*) -- the pointers of the other group are neither checked
+// nor used, and the kernel is the flavour that leaves its work out (bwd_fast_kernel / bwd_generic_kernel: SCATTER, POINTS)
 template <typename ST, bool INST>
 int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                const typename Storage<ST>::compute *loc,
@@ -422,46 +427,56 @@ int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                const ST *grad_mask, const Dims &d, ST *grad_value,
                typename Storage<ST>::compute *grad_loc, typename Storage<ST>::compute *grad_sp,
                typename Storage<ST>::compute *grad_lv,
-               typename Storage<ST>::compute *grad_value_acc, hipStream_t st)
+               typename Storage<ST>::compute *grad_value_acc, hipStream_t st, int want = kWantAll)
 {
     typedef typename Storage<ST>::compute T;
     if (!d.valid()) return (int)hipErrorInvalidValue;
+    const bool wv = (want & kWantValue) != 0, wp = (want & kWantPoints) != 0;
     const size_t nv = d.n_value();
     const size_t n_qh = d.n_qh();
-    if (nv) {
+    if (nv && wv) {
         if (!grad_value || !grad_value_acc) return (int)hipErrorInvalidValue;
+    }
+    if (n_qh) {
+        if (!shapes || !lsi || !loc || !w_sp || !grad_out || (wp && (!grad_loc || !grad_sp)) ||
+            (INST && (!w_lv || !grad_mask || (wp && !grad_lv))))
+            return (int)hipErrorInvalidValue;
+        if (nv && !value) return (int)hipErrorInvalidValue;
+    }
+    if (nv && wv) {
         hipError_t e = zero_async(grad_value_acc, nv * sizeof(T), st);
         if (e != hipSuccess) return (int)e;
     }
-    if (n_qh) {
-        if (!shapes || !lsi || !loc || !w_sp || !grad_out || !grad_loc || !grad_sp ||
-            (INST && (!w_lv || !grad_mask || !grad_lv)))
-            return (int)hipErrorInvalidValue;
-        if (!nv) {                                             // no pixels: all gradients 0
-            const size_t np = n_qh * d.L * d.P;
-            hipError_t e = zero_async(grad_loc, 2 * np * sizeof(T), st);
-            if (e == hipSuccess) e = zero_async(grad_sp, np * sizeof(T), st);
-            if (e == hipSuccess && INST) e = zero_async(grad_lv, np * sizeof(T), st);
-            return (int)e;
-        }
-        if (!value) return (int)hipErrorInvalidValue;
+    if (n_qh && !nv) {                                         // no pixels: all gradients 0
+        if (!wp) return 0;
+        const size_t np = n_qh * d.L * d.P;
+        hipError_t e = zero_async(grad_loc, 2 * np * sizeof(T), st);
+        if (e == hipSuccess) e = zero_async(grad_sp, np * sizeof(T), st);
+        if (e == hipSuccess && INST) e = zero_async(grad_lv, np * sizeof(T), st);
+        return (int)e;
     }
     if (n_qh && nv) {
-        ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], st);
+        // (the value-only kernel is the accumulate step of its call: it is timed as one)
+        ScopedKernelTimer timer(g_prof.ev[wp ? kSlotBwdPoints : kSlotBwdAccum], st);
         bool done = false;
         if constexpr (!std::is_same<ST, double>::value) {
+            // (grad_loc takes part in the choice only where it is an output of the call)
             if (fast_ok<ST>(d, value, loc, grad_out,
                             INST ? (const void *)grad_mask : (const void *)grad_out,
-                            grad_loc)) {
+                            wp ? (const void *)grad_loc : (const void *)grad_out)) {
                 const int G = fast_group(d);
                 const int pairs = kWave / G;
                 const int blocks = ceil_div_sz(n_qh, (size_t)pairs * 4);
-#define BOXATTN_BWD_CASE(GG)                                                                  \
-    case GG:                                                                                  \
-        hipLaunchKernelGGL((bwd_fast_kernel<ST, 4, GG, INST>), dim3(blocks), dim3(256), 0, st, \
+#define BOXATTN_BWD_LAUNCH(GG, ...)                                                           \
+        hipLaunchKernelGGL((bwd_fast_kernel<ST, 4, GG, INST, ##__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, \
                            value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d.S,    \
                            d.H, d.L, d.Lq, d.P, grad_value_acc, grad_loc, grad_sp, grad_lv,  \
-                           n_qh);                                                             \
+                           n_qh)
+#define BOXATTN_BWD_CASE(GG)                                                                  \
+    case GG:                                                                                  \
+        if (want == kWantAll) BOXATTN_BWD_LAUNCH(GG);                                         \
+        else if (wp) BOXATTN_BWD_LAUNCH(GG, false);                                           \
+        else BOXATTN_BWD_LAUNCH(GG, true, false);                                             \
         break;
                 switch (G) {
                     BOXATTN_BWD_CASE(4)
@@ -469,6 +484,7 @@ int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                     BOXATTN_BWD_CASE(16)
                 }
 #undef BOXATTN_BWD_CASE
+#undef BOXATTN_BWD_LAUNCH
                 done = true;
             } else if (g_variant == 2) {
                 return (int)hipErrorInvalidValue;
@@ -476,16 +492,21 @@ int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
         }
         if (!done) {
             const int blocks = (int)std::min<size_t>((n_qh + 3) / 4, (size_t)1 << 20);
-            hipLaunchKernelGGL((bwd_generic_kernel<ST, INST>), dim3(blocks), dim3(256), 0, st,
-                               value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d.S,
-                               d.H, d.C, d.L, d.Lq, d.P, grad_value_acc, grad_loc, grad_sp,
-                               grad_lv, n_qh);
+#define BOXATTN_BWD_GENERIC(...)                                                              \
+            hipLaunchKernelGGL((bwd_generic_kernel<ST, INST, ##__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, \
+                               value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d.S, \
+                               d.H, d.C, d.L, d.Lq, d.P, grad_value_acc, grad_loc, grad_sp,  \
+                               grad_lv, n_qh)
+            if (want == kWantAll) BOXATTN_BWD_GENERIC();
+            else if (wp) BOXATTN_BWD_GENERIC(false);
+            else BOXATTN_BWD_GENERIC(true, false);
+#undef BOXATTN_BWD_GENERIC
         }
         int rc = finish();
         if (rc) return rc;
     }
     if constexpr (IsHalf16<ST>::value) {
-        if (nv) {
+        if (nv && wv) {
             const int blocks = (int)std::min<size_t>((nv / 4 + 255) / 256 + 1, 256 * 16);
             if constexpr (std::is_same<ST, bf16_t>::value)
                 hipLaunchKernelGGL(cvt_f32_to_bf16_kernel, dim3(blocks), dim3(256), 0, st,
@@ -725,6 +746,7 @@ int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, cons
 
 // A binned backward: [count -> scans, unless the training forward left a plan] -> point gradients with the
 // fill pass riding in their launch -> accumulate (chunked blocks summed by their last chunk).
+// points = false: the grad_value half alone (grad_loc / grad_sp / grad_lv are not used).
 // spec: the caller's state of the one-pass fill (boxattn_spec.h) -- nullptr: two-pass binning; spec_warm: its ranges were
 // planned by an earlier call (else this call runs the two-pass passes and spec_layout_kernel plans them from its scan)
 template <typename ST, int G, bool INST>
@@ -733,7 +755,7 @@ int run_binned(const ST *value, const int64_t *shapes, const int64_t *lsi, const
                const Dims &d, const BinPlan &plan, const PlanLayout &pl, char *pbuf, const ScratchLayout &sl,
                char *sbuf, ST *grad_value, float *grad_loc, float *grad_sp, float *grad_lv, bool plan_ready,
                hipStream_t st, const DensePlan *dp, const SpecRide *spec = nullptr,
-               bool spec_warm = false, int *spec_tickets = nullptr)
+               bool spec_warm = false, int *spec_tickets = nullptr, bool points = true)
 {
     const int ns = d.B * d.H;
     const AccKind acc = acc_kind<ST, INST>(d);
@@ -745,7 +767,10 @@ int run_binned(const ST *value, const int64_t *shapes, const int64_t *lsi, const
     const bool one_pass = spec && spec_warm;
     if (!plan_ready && !one_pass) launch_binning(flavour, loc, w_sp, d, plan, pl, pbuf, records, st, kBinCount | kBinScan);
     bool filled = false;
-    if (one_pass) {
+    if (!points) {
+        // grad_value only (*_bwd_part_*, BOXATTN_WANT_VALUE; spec is null): no point-gradient launch, so nothing the fill
+        // pass could ride in -- it runs as a launch of its own, below
+    } else if (one_pass) {
         // point gradients + the fill riders' ONE pass over the locations into the ranges the state holds; the slice's
         // last rider writes the work items (and the next call's ranges)
         BinRide ride = make_ride(loc, w_sp, d, plan, pl, pbuf, &sl, sbuf, flavour | kRideSpec, true);
@@ -880,6 +905,104 @@ int launch_bwd_ws(const ST *value, const int64_t *shapes, const int64_t *lsi, co
         BOXATTN_BINNED_CASE(8)
         BOXATTN_BINNED_CASE(16)
 #undef BOXATTN_BINNED_CASE
+    }
+    return rc;
+}
+
+// A partial backward (*_bwd_part_*): one of the two gradient groups, with launch_bwd_ws' arguments.  The pointers of the
+// group that is not wanted are never looked at.
+//   POINTS: launch_pointgrad without a fill ride where the full call would run the binned backward (given a workspace:
+//           this call takes none), else the atomic kernels' points-only flavour.  No workspace, plan or state.
+//   VALUE:  the binned backward without its point-gradient launch -- [count, scans, unless a plan is passed,] fill as a
+//           launch of its own, accumulate, combine -- else zero-fill + the atomic kernels' value-only flavour [+ the
+//           16-bit conversion].  The two-pass binning only: the one-pass fill lives in the riders of the point-gradient
+//           launch, so the state is neither read nor written (nor noted as learned).
+template <typename ST, bool INST>
+int launch_bwd_part(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
+                    const float *w_sp, const float *w_lv, const ST *grad_out, const ST *grad_mask,
+                    const Dims &d, ST *grad_value, float *grad_loc, float *grad_sp, float *grad_lv,
+                    const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
+                    size_t workspace_bytes, const void *plan_buf, size_t plan_bytes, void *state,
+                    size_t state_bytes, int hints, hipStream_t st, int want)
+{
+    if (want == kWantAll)
+        return launch_bwd_ws<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_value,
+                                       grad_loc, grad_sp, grad_lv, shapes_host, lsi_host, workspace, workspace_bytes,
+                                       plan_buf, plan_bytes, hints, st, state, state_bytes);
+    if (want != kWantValue && want != kWantPoints) return (int)hipErrorInvalidValue;
+    constexpr bool kH16 = IsHalf16<ST>::value;
+    if (!d.valid()) return (int)hipErrorInvalidValue;
+    const bool wp = want == kWantPoints;
+    BinPlan plan;
+    const size_t nv = d.n_value();
+    // launch_bwd_ws' test, less what belongs to the other group (POINTS: workspace and grad_value; VALUE: grad_loc)
+    bool binned = (g_variant == 0 || g_variant == 3) && nv && d.n_qh() &&
+                  make_plan(d, shapes_host, lsi_host, plan) &&
+                  fast_ok<ST>(d, value, loc, grad_out,
+                              INST ? (const void *)grad_mask : (const void *)grad_out,
+                              wp ? (const void *)grad_loc : (const void *)grad_out);
+    const bool inputs_ok = shapes && lsi && loc && w_sp && grad_out && value && (!INST || (w_lv && grad_mask));
+    DensePlan dense;
+    if (wp) {
+        if (!binned) {
+            if (g_variant == 3) return (int)hipErrorInvalidValue;
+            return launch_bwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, nullptr,
+                                        grad_loc, grad_sp, grad_lv, nullptr, st, kWantPoints);
+        }
+        if (!inputs_ok || !grad_loc || !grad_sp || (INST && !grad_lv)) return (int)hipErrorInvalidValue;
+        const DensePlan *dp = !INST && !(hints & BOXATTN_HINT_NOT_LOCAL) &&
+                                      make_dense_plan(d, shapes_host, lsi_host, dense, (int)sizeof(ST)) ? &dense : nullptr;
+        switch (fast_group(d)) {
+#define BOXATTN_PART_CASE(GG)                                                                   \
+    case GG:                                                                                    \
+        launch_pointgrad<ST, GG, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_loc, \
+                                       grad_sp, grad_lv, st, nullptr, nullptr, dp);             \
+        break;
+            BOXATTN_PART_CASE(4)
+            BOXATTN_PART_CASE(8)
+            BOXATTN_PART_CASE(16)
+#undef BOXATTN_PART_CASE
+        }
+        return finish();
+    }
+    binned = binned && workspace && aligned(workspace, 256) && aligned(grad_value, 16);
+    PlanLayout pl{};
+    ScratchLayout sl{};
+    bool plan_ready = false;
+    if (binned) {
+        pl = plan_layout(d, plan);
+        sl = scratch_layout(d, plan, wide_workspace(kH16, d));
+        plan_ready = plan_buf && plan_bytes >= pl.total && aligned(plan_buf, 256);
+        binned = workspace_bytes >= (plan_ready ? sl.total : pl.total + sl.total);
+    }
+    if (!binned) {
+        if (g_variant == 3) return (int)hipErrorInvalidValue;
+        float *acc = nullptr;
+        if constexpr (kH16) {
+            if (!workspace || workspace_bytes < nv * sizeof(float)) return (int)hipErrorInvalidValue;
+            acc = (float *)workspace;
+        } else {
+            acc = grad_value;
+        }
+        return launch_bwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_value,
+                                    nullptr, nullptr, nullptr, acc, st, kWantValue);
+    }
+    if (!inputs_ok || !grad_value) return (int)hipErrorInvalidValue;
+    char *ws = (char *)workspace;
+    char *pbuf = plan_ready ? const_cast<char *>((const char *)plan_buf) : ws;
+    char *sbuf = plan_ready ? ws : ws + pl.total;
+    int rc = 0;
+    switch (fast_group(d)) {
+#define BOXATTN_PART_CASE(GG)                                                                   \
+    case GG:                                                                                    \
+        rc = run_binned<ST, GG, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, \
+                                      d, plan, pl, pbuf, sl, sbuf, grad_value, nullptr, nullptr, nullptr, \
+                                      plan_ready, st, nullptr, nullptr, false, nullptr, false);  \
+        break;
+        BOXATTN_PART_CASE(4)
+        BOXATTN_PART_CASE(8)
+        BOXATTN_PART_CASE(16)
+#undef BOXATTN_PART_CASE
     }
     return rc;
 }
@@ -1134,6 +1257,88 @@ int instattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int6
                                        lsi_host, workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
 }
 
+
+// Partial backward (BOXATTN_WANT_*): the arguments of *_bwd_ws_* (f64: of *_bwd_f64) + want
+int boxattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+        const float *loc, const float *attn, const float *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
+        float *grad_value, float *grad_loc, float *grad_attn, const int64_t *shapes_host, const int64_t *lsi_host,
+        void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
+        int hints, void *stream, int want)
+{
+    return launch_bwd_part<float, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
+                                      grad_value, grad_loc, grad_attn, nullptr, shapes_host, lsi_host, workspace,
+                                      workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+}
+int boxattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+        const float *loc, const float *attn, const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
+        uint16_t *grad_value, float *grad_loc, float *grad_attn, const int64_t *shapes_host, const int64_t *lsi_host,
+        void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
+        int hints, void *stream, int want)
+{
+    return launch_bwd_part<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
+                                      grad_value, grad_loc, grad_attn, nullptr, shapes_host, lsi_host, workspace,
+                                      workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+}
+int boxattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+        const float *loc, const float *attn, const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
+        uint16_t *grad_value, float *grad_loc, float *grad_attn, const int64_t *shapes_host, const int64_t *lsi_host,
+        void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
+        int hints, void *stream, int want)
+{
+    return launch_bwd_part<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr, DIMS,
+                                      as_f16(grad_value), grad_loc, grad_attn, nullptr, shapes_host, lsi_host, workspace,
+                                      workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+}
+int instattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+        const float *loc, const float *spatial_w, const float *level_w, const float *grad_out, const float *grad_mask,
+        int B, int S, int H, int C, int L, int Lq, int P, float *grad_value, float *grad_loc, float *grad_spatial_w,
+        float *grad_level_w, const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
+        size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+        void *stream, int want)
+{
+    return launch_bwd_part<float, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
+                                     grad_value, grad_loc, grad_spatial_w, grad_level_w, shapes_host, lsi_host, workspace,
+                                     workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+}
+int instattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+        const float *loc, const float *spatial_w, const float *level_w, const uint16_t *grad_out, const uint16_t *grad_mask,
+        int B, int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc, float *grad_spatial_w,
+        float *grad_level_w, const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
+        size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+        void *stream, int want)
+{
+    return launch_bwd_part<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
+                                     grad_value, grad_loc, grad_spatial_w, grad_level_w, shapes_host, lsi_host, workspace,
+                                     workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+}
+int instattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+        const float *loc, const float *spatial_w, const float *level_w, const uint16_t *grad_out, const uint16_t *grad_mask,
+        int B, int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc, float *grad_spatial_w,
+        float *grad_level_w, const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
+        size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+        void *stream, int want)
+{
+    return launch_bwd_part<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out), as_f16(grad_mask), DIMS,
+                                     as_f16(grad_value), grad_loc, grad_spatial_w, grad_level_w, shapes_host, lsi_host, workspace,
+                                     workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+}
+int boxattn_bwd_part_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
+        const double *loc, const double *attn, const double *grad_out, int B, int S, int H, int C, int L, int Lq,
+        int P, double *grad_value, double *grad_loc, double *grad_attn, void *stream, int want)
+{
+    if (want != kWantValue && want != kWantPoints && want != kWantAll) return (int)hipErrorInvalidValue;
+    return launch_bwd<double, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, grad_value,
+                                     grad_loc, grad_attn, nullptr, grad_value, ST_, want);
+}
+int instattn_bwd_part_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
+        const double *loc, const double *spatial_w, const double *level_w, const double *grad_out,
+        const double *grad_mask, int B, int S, int H, int C, int L, int Lq, int P, double *grad_value,
+        double *grad_loc, double *grad_spatial_w, double *grad_level_w, void *stream, int want)
+{
+    if (want != kWantValue && want != kWantPoints && want != kWantAll) return (int)hipErrorInvalidValue;
+    return launch_bwd<double, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
+                                    grad_value, grad_loc, grad_spatial_w, grad_level_w, grad_value, ST_, want);
+}
 
 int boxattn_abi_version(void) { return BOXATTN_ABI_VERSION; }
 

@@ -183,8 +183,14 @@ __global__ __launch_bounds__(256) void fwd_fast_kernel(
 // backward
 // ---------------------------------------------------------------------------------------
 // SCATTER = false turns the kernel into the "point gradients" half of the binned backward
-// (grad_loc / grad_weight only; grad_value comes from boxattn_binned.h without atomics).
-template <typename ST, int VEC, int G, bool INST, bool SCATTER = true>
+// (grad_loc / grad_weight only; grad_value comes from boxattn_binned.h without atomics: grad_value
+// is not touched and may be null).  POINTS = false is the mirror image, the grad_value atomics alone
+// (a partial backward, *_bwd_part_*): no corner loads, no channel sums, no lane-group reductions, no
+// stores -- grad_loc / grad_sp / grad_lv are not touched and may be null.  Both are compile-time
+// flags of ONE body: every branch on them is `if constexpr`, and the lane-group reductions sit
+// outside all run-time branches, so a flavour can neither add a divergent barrier nor change the
+// instructions of another.
+template <typename ST, int VEC, int G, bool INST, bool SCATTER = true, bool POINTS = true>
 __global__ __launch_bounds__(256) void bwd_fast_kernel(
     const ST *__restrict__ value, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ lsi, const float *__restrict__ loc,
@@ -193,6 +199,7 @@ __global__ __launch_bounds__(256) void bwd_fast_kernel(
     int Lq, int P, float *__restrict__ grad_value, float *__restrict__ grad_loc,
     float *__restrict__ grad_sp, float *__restrict__ grad_lv, size_t n_qh)
 {
+    static_assert(SCATTER || POINTS, "a backward kernel that computes nothing");
     constexpr int C = VEC * G;
     constexpr int PAIRS = kWave / G;
     __shared__ LevelTable lv;
@@ -228,10 +235,13 @@ __global__ __launch_bounds__(256) void bwd_fast_kernel(
             const float al = INST ? w_lv[i] : 0.f;
             const Sample<float> s = locate<float>(xy.x, xy.y, Hl, Wl);
             float v1[VEC], v2[VEC], v3[VEC], v4[VEC], gm[VEC];
-            gather_corner<ST, VEC>(vl, s.pix[0], HC, s.ok[0], v1);
-            gather_corner<ST, VEC>(vl, s.pix[1], HC, s.ok[1], v2);
-            gather_corner<ST, VEC>(vl, s.pix[2], HC, s.ok[2], v3);
-            gather_corner<ST, VEC>(vl, s.pix[3], HC, s.ok[3], v4);
+            (void)vl; (void)writer;
+            if constexpr (POINTS) {
+                gather_corner<ST, VEC>(vl, s.pix[0], HC, s.ok[0], v1);
+                gather_corner<ST, VEC>(vl, s.pix[1], HC, s.ok[1], v2);
+                gather_corner<ST, VEC>(vl, s.pix[2], HC, s.ok[2], v3);
+                gather_corner<ST, VEC>(vl, s.pix[3], HC, s.ok[3], v4);
+            }
             if constexpr (INST)
                 VecIO<ST, VEC>::ld(grad_mask + (bq * P + p) * HC + (size_t)m * C + cl, gm);
             const float w1 = s.hh * s.hw, w2 = s.hh * s.lw, w3 = s.lh * s.hw, w4 = s.lh * s.lw;
@@ -240,13 +250,15 @@ __global__ __launch_bounds__(256) void bwd_fast_kernel(
 #pragma unroll
             for (int c = 0; c < VEC; ++c) {
                 t[c] = INST ? g[c] * as + gm[c] * al : g[c] * as;
-                const float val = w1 * v1[c] + w2 * v2[c] + w3 * v3[c] + w4 * v4[c];
-                ps += g[c] * val;
-                if constexpr (INST) pl += gm[c] * val;
-                const float dw = s.hh * (v2[c] - v1[c]) + s.lh * (v4[c] - v3[c]);
-                const float dh = s.hw * (v3[c] - v1[c]) + s.lw * (v4[c] - v2[c]);
-                px += dw * t[c];
-                py += dh * t[c];
+                if constexpr (POINTS) {
+                    const float val = w1 * v1[c] + w2 * v2[c] + w3 * v3[c] + w4 * v4[c];
+                    ps += g[c] * val;
+                    if constexpr (INST) pl += gm[c] * val;
+                    const float dw = s.hh * (v2[c] - v1[c]) + s.lh * (v4[c] - v3[c]);
+                    const float dh = s.hw * (v3[c] - v1[c]) + s.lw * (v4[c] - v2[c]);
+                    px += dw * t[c];
+                    py += dh * t[c];
+                }
             }
             if (SCATTER && active) {
                 if (s.ok[0]) {
@@ -270,15 +282,17 @@ __global__ __launch_bounds__(256) void bwd_fast_kernel(
                     for (int c = 0; c < VEC; ++c) atomic_add(d + c, w4 * t[c]);
                 }
             }
-            ps = group_sum<G>(ps);
-            px = group_sum<G>(px);
-            py = group_sum<G>(py);
-            if constexpr (INST) pl = group_sum<G>(pl);
-            if (writer) {
-                grad_sp[i] = s.inside ? ps : 0.f;
-                if constexpr (INST) grad_lv[i] = s.inside ? pl : 0.f;
-                reinterpret_cast<float2 *>(grad_loc)[i] =
-                    s.inside ? make_float2((float)Wl * px, (float)Hl * py) : make_float2(0.f, 0.f);
+            if constexpr (POINTS) {
+                ps = group_sum<G>(ps);
+                px = group_sum<G>(px);
+                py = group_sum<G>(py);
+                if constexpr (INST) pl = group_sum<G>(pl);
+                if (writer) {
+                    grad_sp[i] = s.inside ? ps : 0.f;
+                    if constexpr (INST) grad_lv[i] = s.inside ? pl : 0.f;
+                    reinterpret_cast<float2 *>(grad_loc)[i] =
+                        s.inside ? make_float2((float)Wl * px, (float)Hl * py) : make_float2(0.f, 0.f);
+                }
             }
         }
     }

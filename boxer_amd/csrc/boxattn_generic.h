@@ -81,8 +81,13 @@ __global__ __launch_bounds__(256) void fwd_generic_kernel(
     }
 }
 
-// GT = type grad_value is accumulated in (float for bf16 storage, else the compute type).
-template <typename ST, bool INST>
+// grad_value is accumulated in the compute type (float for 16-bit storage).
+// SCATTER / POINTS: which of the two gradient groups the kernel computes, as in bwd_fast_kernel
+// (boxattn_fast.h) -- SCATTER = false: grad_loc / grad_weight only, grad_value is not touched and may be
+// null; POINTS = false: the grad_value atomics only, no value loads, no sums, no wave reductions, no stores
+// (grad_loc / grad_sp / grad_lv may be null).  Compile-time flags of one body; the wave reductions stay
+// under the wave-uniform `s.inside` test only.
+template <typename ST, bool INST, bool SCATTER = true, bool POINTS = true>
 __global__ __launch_bounds__(256) void bwd_generic_kernel(
     const ST *__restrict__ value, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ lsi, const typename Storage<ST>::compute *__restrict__ loc,
@@ -94,6 +99,7 @@ __global__ __launch_bounds__(256) void bwd_generic_kernel(
     typename Storage<ST>::compute *__restrict__ grad_sp,
     typename Storage<ST>::compute *__restrict__ grad_lv, size_t n_qh)
 {
+    static_assert(SCATTER || POINTS, "a backward kernel that computes nothing");
     typedef typename Storage<ST>::compute T;
     const int lane = threadIdx.x & (kWave - 1);
     const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
@@ -126,44 +132,58 @@ __global__ __launch_bounds__(256) void bwd_generic_kernel(
                         T gh = 0, gw = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0;
                         if (s.ok[0]) {
                             const size_t o = lo + (size_t)s.pix[0] * HC + c;
-                            v1 = Storage<ST>::ld(value + o);
-                            gh -= s.hw * v1; gw -= s.hh * v1;
-                            atomic_add(grad_value + o, w1 * t);
+                            if constexpr (POINTS) {
+                                v1 = Storage<ST>::ld(value + o);
+                                gh -= s.hw * v1; gw -= s.hh * v1;
+                            }
+                            if constexpr (SCATTER) atomic_add(grad_value + o, w1 * t);
                         }
                         if (s.ok[1]) {
                             const size_t o = lo + (size_t)s.pix[1] * HC + c;
-                            v2 = Storage<ST>::ld(value + o);
-                            gh -= s.lw * v2; gw += s.hh * v2;
-                            atomic_add(grad_value + o, w2 * t);
+                            if constexpr (POINTS) {
+                                v2 = Storage<ST>::ld(value + o);
+                                gh -= s.lw * v2; gw += s.hh * v2;
+                            }
+                            if constexpr (SCATTER) atomic_add(grad_value + o, w2 * t);
                         }
                         if (s.ok[2]) {
                             const size_t o = lo + (size_t)s.pix[2] * HC + c;
-                            v3 = Storage<ST>::ld(value + o);
-                            gh += s.hw * v3; gw -= s.lh * v3;
-                            atomic_add(grad_value + o, w3 * t);
+                            if constexpr (POINTS) {
+                                v3 = Storage<ST>::ld(value + o);
+                                gh += s.hw * v3; gw -= s.lh * v3;
+                            }
+                            if constexpr (SCATTER) atomic_add(grad_value + o, w3 * t);
                         }
                         if (s.ok[3]) {
                             const size_t o = lo + (size_t)s.pix[3] * HC + c;
-                            v4 = Storage<ST>::ld(value + o);
-                            gh += s.lw * v4; gw += s.lh * v4;
-                            atomic_add(grad_value + o, w4 * t);
+                            if constexpr (POINTS) {
+                                v4 = Storage<ST>::ld(value + o);
+                                gh += s.lw * v4; gw += s.lh * v4;
+                            }
+                            if constexpr (SCATTER) atomic_add(grad_value + o, w4 * t);
                         }
-                        const T val = w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
-                        g_sp += tg * val;
-                        if (INST) g_lv += tm * val;
-                        g_x += (T)Wl * gw * t;
-                        g_y += (T)Hl * gh * t;
+                        if constexpr (POINTS) {
+                            const T val = w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
+                            g_sp += tg * val;
+                            if (INST) g_lv += tm * val;
+                            g_x += (T)Wl * gw * t;
+                            g_y += (T)Hl * gh * t;
+                        }
                     }
-                    g_sp = wave_sum(g_sp);
-                    g_x = wave_sum(g_x);
-                    g_y = wave_sum(g_y);
-                    if (INST) g_lv = wave_sum(g_lv);
+                    if constexpr (POINTS) {
+                        g_sp = wave_sum(g_sp);
+                        g_x = wave_sum(g_x);
+                        g_y = wave_sum(g_y);
+                        if (INST) g_lv = wave_sum(g_lv);
+                    }
                 }
-                if (lane == 0) {                 // also defines the outputs of skipped points
-                    grad_sp[i] = g_sp;
-                    grad_loc[2 * i] = g_x;
-                    grad_loc[2 * i + 1] = g_y;
-                    if (INST) grad_lv[i] = g_lv;
+                if constexpr (POINTS) {
+                    if (lane == 0) {             // also defines the outputs of skipped points
+                        grad_sp[i] = g_sp;
+                        grad_loc[2 * i] = g_x;
+                        grad_loc[2 * i + 1] = g_y;
+                        if (INST) grad_lv[i] = g_lv;
+                    }
                 }
             }
         }

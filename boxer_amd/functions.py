@@ -38,27 +38,36 @@ def set_plan_in_forward(flag):
 
 
 def _box_forward(ctx, value, shapes, lsi, loc, attn, im2col_step):
-    """Training forward (also prepares the backward's plan) when asked to (PLAN_IN_FORWARD) and a
-    gradient will be needed."""
-    if PLAN_IN_FORWARD and any(ctx.needs_input_grad):
+    """Training forward (also prepares the backward's plan) when asked to (PLAN_IN_FORWARD) and the backward will
+    compute grad_value -- the plan only serves that half.  Otherwise the plain forward; it parks a plan (as ever, with
+    PLAN_IN_FORWARD off) unless value needs no gradient: then no riders, no plan, nothing parked."""
+    need_value = ctx.needs_input_grad[0]
+    if PLAN_IN_FORWARD and need_value:
         return ops.box_attn_forward_train(value, shapes, lsi, loc, attn, im2col_step)
-    return ops.box_attn_forward(value, shapes, lsi, loc, attn, im2col_step), None
+    return ops.box_attn_forward(value, shapes, lsi, loc, attn, im2col_step, park=need_value), None
 
 
 def _inst_forward(ctx, value, shapes, lsi, loc, sw, lw, im2col_step):
-    if PLAN_IN_FORWARD and any(ctx.needs_input_grad):
+    need_value = ctx.needs_input_grad[0]
+    if PLAN_IN_FORWARD and need_value:
         return ops.instance_attn_forward_train(value, shapes, lsi, loc, sw, lw, im2col_step)
-    return ops.instance_attn_forward(value, shapes, lsi, loc, sw, lw, im2col_step), None
+    return ops.instance_attn_forward(value, shapes, lsi, loc, sw, lw, im2col_step, park=need_value), None
 
 
+# The backward computes the gradient groups autograd asks for (ops.*_backward `want`: 1 grad_value | 2 the location and
+# weight gradients, which share every load and nearly all arithmetic and stay together) and returns None for every
+# input that needs no gradient.  (Written out, without helpers: the decoder shapes' steps are host-bound.)
 def _box_backward(ctx, grad_output):
     if not grad_output.is_contiguous():
         grad_output = grad_output.contiguous()
     value, shapes, lsi, loc, attn = ctx.saved_tensors
+    need_v, _, _, need_l, need_a, _ = ctx.needs_input_grad
     grad_value, grad_loc, grad_attn = ops.box_attn_backward(
-        value, shapes, lsi, loc, attn, grad_output, ctx.im2col_step, plan=ctx.plan)
+        value, shapes, lsi, loc, attn, grad_output, ctx.im2col_step, plan=ctx.plan,
+        want=(1 if need_v else 0) | (2 if need_l or need_a else 0))
     ctx.plan = None
-    return grad_value, None, None, grad_loc.to(ctx.loc_dtype), grad_attn.to(ctx.attn_dtype), None
+    return (grad_value if need_v else None, None, None, grad_loc.to(ctx.loc_dtype) if need_l else None,
+            grad_attn.to(ctx.attn_dtype) if need_a else None, None)
 
 
 def _inst_backward(ctx, grad_output, grad_mask_output):
@@ -67,12 +76,13 @@ def _inst_backward(ctx, grad_output, grad_mask_output):
     if not grad_mask_output.is_contiguous():
         grad_mask_output = grad_mask_output.contiguous()
     value, shapes, lsi, loc, sw, lw = ctx.saved_tensors
+    need_v, _, _, need_l, need_s, need_w = ctx.needs_input_grad[:6]
     grad_value, grad_loc, grad_sw, grad_lw = ops.instance_attn_backward(
         value, shapes, lsi, loc, sw, lw, grad_output, grad_mask_output, ctx.im2col_step,
-        plan=ctx.plan)
+        plan=ctx.plan, want=(1 if need_v else 0) | (2 if need_l or need_s or need_w else 0))
     ctx.plan = None
-    return (grad_value, None, None, grad_loc.to(ctx.loc_dtype), grad_sw.to(ctx.w_dtype),
-            grad_lw.to(ctx.w_dtype), None, None)
+    return (grad_value if need_v else None, None, None, grad_loc.to(ctx.loc_dtype) if need_l else None,
+            grad_sw.to(ctx.w_dtype) if need_s else None, grad_lw.to(ctx.w_dtype) if need_w else None, None, None)
 
 
 class BoxAttnFunction(Function):
@@ -160,7 +170,7 @@ class _BoxAttn16Function(Function):
     @once_differentiable
     def backward(ctx, grad_output):
         grads = _box_backward(ctx, grad_output.to(ctx.storage))
-        return (grads[0].to(ctx.value_dtype),) + grads[1:]
+        return (None if grads[0] is None else grads[0].to(ctx.value_dtype),) + grads[1:]
 
 
 class _InstanceAttn16Function(Function):
@@ -168,7 +178,7 @@ class _InstanceAttn16Function(Function):
     @once_differentiable
     def backward(ctx, grad_output, grad_mask_output):
         grads = _inst_backward(ctx, grad_output.to(ctx.storage), grad_mask_output.to(ctx.storage))
-        return (grads[0].to(ctx.value_dtype),) + grads[1:]
+        return (None if grads[0] is None else grads[0].to(ctx.value_dtype),) + grads[1:]
 
 
 class BoxAttnBF16Function(_BoxAttn16Function):

@@ -441,18 +441,58 @@ def _backward_with_workspace(name, value, shapes, lsi, loc, weights, dims, args,
     state._boxattn_fresh = False
 
 
-def _call(name, value, *args):
+def _want_groups(want):
+    """-> (grad_value wanted, location / weight gradients wanted) of a backward's ``want`` (BOXATTN_WANT_* bits)."""
+    if want not in (_lib.WANT_VALUE, _lib.WANT_POINTS, _lib.WANT_ALL):
+        raise ValueError("want must be 1 (grad_value), 2 (location and weight gradients) or 3 (all), not %r" % (want,))
+    return bool(want & _lib.WANT_VALUE), bool(want & _lib.WANT_POINTS)
+
+
+def _ptr(a):
+    """What goes over the C ABI: tensors as device pointers, a gradient nobody wants (None) as NULL."""
+    return a.data_ptr() if isinstance(a, torch.Tensor) else 0 if a is None else a
+
+
+def _backward_part(name, value, shapes, lsi, loc, weights, dims, args, plan, want):
+    """Run the *_bwd_part_* entry point (float32 / bfloat16 / float16) for ONE gradient group.  POINTS: one launch,
+    no scratch, no state.  VALUE: scratch (+ the plan of a training forward); the state buffer is not the partial
+    call's business (include/boxattn.h), so none is looked up."""
+    lib = _lib.load()
+    fn = getattr(lib, "%s_%s" % (name, _SUFFIX[value.dtype]))
+    with _device_guard(value.device):
+        stream = torch.cuda.current_stream(value.device).cuda_stream
+        ws, ready = None, False
+        if want == _lib.WANT_VALUE:
+            ws, sh, ls = _workspace(lib.boxattn_bwd_workspace_bytes, value, shapes, lsi, dims, stream)
+            ready = plan is not None and plan.buf is not None and plan.key == _plan_key(dims, loc, weights, value.dtype)
+        else:
+            sh, ls = _host_table(shapes), _host_table(lsi)
+        if plan is not None:
+            hints = plan.hints
+        else:
+            adapt = _LOCALITY.get(_shape_key(value, stream, dims, sh, ls)) if _LOCALITY else None
+            hints = adapt.last_hints if adapt is not None else 0
+        rc = fn(*[_ptr(a) for a in args], sh.ctypes.data, ls.ctypes.data,
+                ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
+                plan.buf.data_ptr() if ready else 0, plan.buf.numel() if ready else 0, 0, 0, hints, stream, want)
+    if rc != 0:
+        raise RuntimeError("%s_%s (want=%d) failed with hipError %d" % (name, _SUFFIX[value.dtype], want, rc))
+
+
+def _call(name, value, *args, want=None):
     fn = getattr(_lib.load(), "%s_%s" % (name, _SUFFIX[value.dtype]))
     with torch.cuda.device(value.device):
         stream = torch.cuda.current_stream(value.device).cuda_stream
-        rc = fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], stream)
+        rc = fn(*[_ptr(a) for a in args], stream, *(() if want is None else (want,)))
     if rc != 0:
         raise RuntimeError("%s_%s failed with hipError %d" % (name, _SUFFIX[value.dtype], rc))
 
 
 def box_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                     im2col_step):
-    """-> output (B, Lq, H*C).  Reference: box_attn_cuda_forward (box_attn.cu:15-71)."""
+                     im2col_step, park=True):
+    """-> output (B, Lq, H*C).  Reference: box_attn_cuda_forward (box_attn.cu:15-71).
+    ``park=False``: never the training forward, whatever requires a gradient (a caller that knows the backward
+    will not need grad_value: the plan only serves that half)."""
     dims, loc, (attn,), _ = _prepare(value, spatial_shapes, level_start_index, sampling_loc,
                                      [attn_weight])
     B, S, H, C, L, Lq, P = dims
@@ -460,7 +500,7 @@ def box_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, att
     out = torch.empty((B, Lq, H * C), dtype=value.dtype, device=value.device)
     if value.dtype == torch.float64:
         _call("boxattn_fwd", value, value, spatial_shapes, level_start_index, loc, attn, *dims, out)
-    elif _wants_plan(value, sampling_loc, attn_weight):      # a backward will follow: build and park its plan
+    elif park and _wants_plan(value, sampling_loc, attn_weight):      # a backward will follow: build and park its plan
         _park(value, _forward_train("boxattn_fwd_train", value, spatial_shapes, level_start_index, loc,
                                     (attn,), dims,
                                     [value, spatial_shapes, level_start_index, loc, attn, *dims, out]), (loc, attn))
@@ -491,40 +531,54 @@ def box_attn_forward_train(value, spatial_shapes, level_start_index, sampling_lo
 
 
 def box_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                      grad_output, im2col_step, plan=None):
+                      grad_output, im2col_step, plan=None, want=3):
     """-> [grad_value, grad_sampling_loc, grad_attn_weight] (box_attn.cu:74-135).
-    For bfloat16 / float16 ``value`` the location / weight gradients are float32."""
+    For bfloat16 / float16 ``value`` the location / weight gradients are float32.
+    ``want``: the gradient groups to compute -- 1 grad_value, 2 the location and weight gradients, 3 (default) all.
+    The entries of a group that is not wanted are None: never allocated, never computed (include/boxattn.h,
+    *_bwd_part_*)."""
+    want_value, want_points = (True, True) if want == 3 else _want_groups(want)
     dims, loc, (attn,), cdt = _prepare(value, spatial_shapes, level_start_index, sampling_loc,
                                        [attn_weight], [("grad_output", grad_output)])
     B, S, H, C, L, Lq, P = dims
     _chunk_assert(B, im2col_step)
     if grad_output.numel() != B * Lq * H * C:
         raise RuntimeError("grad_output must have B*Lq*H*C elements")
-    grad_value = torch.empty_like(value)
-    grad_loc = torch.empty(sampling_loc.shape, dtype=cdt, device=value.device)
-    grad_attn = torch.empty(attn_weight.shape, dtype=cdt, device=value.device)
+    grad_value = torch.empty_like(value) if want_value else None
+    grad_loc = torch.empty(sampling_loc.shape, dtype=cdt, device=value.device) if want_points else None
+    grad_attn = torch.empty(attn_weight.shape, dtype=cdt, device=value.device) if want_points else None
     args = [value, spatial_shapes, level_start_index, loc, attn, grad_output, *dims, grad_value,
             grad_loc, grad_attn]
     if value.dtype == torch.float64:
-        _call("boxattn_bwd", value, *args)
+        if want == 3:
+            _call("boxattn_bwd", value, *args)
+        else:
+            _call("boxattn_bwd_part", value, *args, want=want)
     else:
+        # (a plan parked for this call leaves the table whether or not the call has a use for it -- only the
+        # grad_value half has: the table must not keep its tensors alive)
         if plan is None:
             plan = _parked(value, dims, loc, (attn,))
-        _backward_with_workspace("boxattn_bwd_ws", value, spatial_shapes, level_start_index, loc,
-                                 (attn,), dims, args, plan)
+        if want == 3:
+            _backward_with_workspace("boxattn_bwd_ws", value, spatial_shapes, level_start_index, loc,
+                                     (attn,), dims, args, plan)
+        else:
+            _backward_part("boxattn_bwd_part", value, spatial_shapes, level_start_index, loc, (attn,), dims, args,
+                           plan, want)
     return [grad_value, grad_loc, grad_attn]
 
 
 def instance_attn_forward(value, spatial_shapes, level_start_index, sampling_loc,
-                          spatial_attn_weight, level_attn_weight, im2col_step):
-    """-> [output (B,Lq,H*C), mask_output (B,Lq,P,H*C)] (instance_attn.cu:15-82)."""
+                          spatial_attn_weight, level_attn_weight, im2col_step, park=True):
+    """-> [output (B,Lq,H*C), mask_output (B,Lq,P,H*C)] (instance_attn.cu:15-82).  ``park``: see box_attn_forward."""
     dims, loc, (sw, lw), _ = _prepare(value, spatial_shapes, level_start_index, sampling_loc,
                                       [spatial_attn_weight, level_attn_weight])
     B, S, H, C, L, Lq, P = dims
     _chunk_assert(B, im2col_step)
     out = torch.empty((B, Lq, H * C), dtype=value.dtype, device=value.device)
     mask = torch.empty((B, Lq, P, H * C), dtype=value.dtype, device=value.device)
-    if value.dtype != torch.float64 and _wants_plan(value, sampling_loc, spatial_attn_weight, level_attn_weight):
+    if value.dtype != torch.float64 and park and _wants_plan(value, sampling_loc, spatial_attn_weight,
+                                                             level_attn_weight):
         _park(value, _forward_train("instattn_fwd_train", value, spatial_shapes, level_start_index, loc,
                                     (sw, lw), dims,
                                     [value, spatial_shapes, level_start_index, loc, sw, lw, *dims, out, mask]),
@@ -555,9 +609,10 @@ def instance_attn_forward_train(value, spatial_shapes, level_start_index, sampli
 
 def instance_attn_backward(value, spatial_shapes, level_start_index, sampling_loc,
                            spatial_attn_weight, level_attn_weight, grad_output,
-                           grad_mask_output, im2col_step, plan=None):
+                           grad_mask_output, im2col_step, plan=None, want=3):
     """-> [grad_value, grad_sampling_loc, grad_spatial_attn_weight, grad_level_attn_weight]
-    (instance_attn.cu:85-157)."""
+    (instance_attn.cu:85-157).  ``want``: see box_attn_backward."""
+    want_value, want_points = (True, True) if want == 3 else _want_groups(want)
     dims, loc, (sw, lw), cdt = _prepare(
         value, spatial_shapes, level_start_index, sampling_loc,
         [spatial_attn_weight, level_attn_weight],
@@ -566,19 +621,25 @@ def instance_attn_backward(value, spatial_shapes, level_start_index, sampling_lo
     _chunk_assert(B, im2col_step)
     if grad_output.numel() != B * Lq * H * C or grad_mask_output.numel() != B * Lq * P * H * C:
         raise RuntimeError("grad_output / grad_mask_output have the wrong number of elements")
-    grad_value = torch.empty_like(value)
-    grad_loc = torch.empty(sampling_loc.shape, dtype=cdt, device=value.device)
-    grad_sw = torch.empty(spatial_attn_weight.shape, dtype=cdt, device=value.device)
-    grad_lw = torch.empty(level_attn_weight.shape, dtype=cdt, device=value.device)
+    new = lambda like: torch.empty(like.shape, dtype=cdt, device=value.device) if want_points else None
+    grad_value = torch.empty_like(value) if want_value else None
+    grad_loc, grad_sw, grad_lw = new(sampling_loc), new(spatial_attn_weight), new(level_attn_weight)
     args = [value, spatial_shapes, level_start_index, loc, sw, lw, grad_output, grad_mask_output,
             *dims, grad_value, grad_loc, grad_sw, grad_lw]
     if value.dtype == torch.float64:
-        _call("instattn_bwd", value, *args)
+        if want == 3:
+            _call("instattn_bwd", value, *args)
+        else:
+            _call("instattn_bwd_part", value, *args, want=want)
     else:
         if plan is None:
             plan = _parked(value, dims, loc, (sw, lw))
-        _backward_with_workspace("instattn_bwd_ws", value, spatial_shapes, level_start_index, loc,
-                                 (sw, lw), dims, args, plan)
+        if want == 3:
+            _backward_with_workspace("instattn_bwd_ws", value, spatial_shapes, level_start_index, loc,
+                                     (sw, lw), dims, args, plan)
+        else:
+            _backward_part("instattn_bwd_part", value, spatial_shapes, level_start_index, loc, (sw, lw), dims,
+                           args, plan, want)
     return [grad_value, grad_loc, grad_sw, grad_lw]
 
 

@@ -231,6 +231,91 @@ int instattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int6
                        void *stream);
 
 /*
+ * ---- partial backward: only the gradients the caller asks for -----------------------------------
+ * A backward has two gradient groups, computed by independent launches wherever the fast paths run:
+ *     VALUE  : grad_value
+ *     POINTS : grad_loc + grad_attn (instance attention: grad_loc + grad_spatial_w + grad_level_w)
+ * *_bwd_part_* take the arguments of *_bwd_ws_* (float64: of *_bwd_f64) and `want`, the groups to compute:
+ *   - want is BOXATTN_WANT_VALUE (1), BOXATTN_WANT_POINTS (2) or both (3); anything else is hipErrorInvalidValue.
+ *   - want == 3 IS the *_bwd_ws_* call (float64: the plain call) -- same checks, same launches, same results.
+ *   - The output pointers of a group that is not wanted are ignored and may be NULL; nothing is written through
+ *     them.  A wanted group with a NULL member is hipErrorInvalidValue (nothing is launched).
+ *   - The wanted outputs are fully defined by the call, as everywhere in this ABI.
+ *   - The degenerate cases keep their meaning for the wanted group: no pixels (B*S == 0) -> the wanted POINTS
+ *     gradients are zero-filled; no queries -> a wanted grad_value is zero-filled.
+ * want == POINTS:
+ *   `workspace`, `plan` and `state` are ignored (NULL / 0 are fine).  ONE launch: the point-gradient kernel the full
+ *   call would pick -- window-staged in the encoder case (16-bit and float32; BOXATTN_HINT_NOT_LOCAL and option 11
+ *   are honoured), else the row-gather kernel, else the atomic kernels' points-only form (float64, channel counts
+ *   the fast kernels do not take, variants 1 / 2) -- with no fill pass riding in it.  No zero-fill of grad_value, no
+ *   binning, no accumulate, no 16-bit conversion pass.  shapes_host / lsi_host may be NULL: the call then takes the
+ *   non-staged (atomic-family) kernels, as a full call without them would.
+ * want == VALUE:
+ *   Where the binned path is eligible (the test of *_bwd_ws_*, less the alignment of grad_loc):
+ *   [count + scans, unless a valid plan is passed] -> the fill pass as a launch of its own -> accumulate -> the
+ *   combine wherever the full call would run it.  The one-pass fill is NOT used (its riders live in the
+ *   point-gradient launch): `state` is neither read nor written and the library notes nothing about it -- a later
+ *   full call on that state behaves as if the partial call had not happened.
+ *   Otherwise: zero-fill, the atomic kernels' value-only form (no loads of `value`, no reductions), and for 16-bit
+ *   storage the conversion pass; the workspace must then hold B*S*H*C floats, as for *_bwd_ws_*.
+ */
+#define BOXATTN_WANT_VALUE  1
+#define BOXATTN_WANT_POINTS 2
+int boxattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                         const float *loc, const float *attn, const float *grad_out, int B, int S,
+                         int H, int C, int L, int Lq, int P, float *grad_value, float *grad_loc,
+                         float *grad_attn, const int64_t *shapes_host, const int64_t *lsi_host,
+                         void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes,
+                         void *state, size_t state_bytes, int hints, void *stream, int want);
+int boxattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *loc, const float *attn, const uint16_t *grad_out, int B,
+                          int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
+                          float *grad_loc, float *grad_attn, const int64_t *shapes_host,
+                          const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                          const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+                          void *stream, int want);
+int boxattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                         const float *loc, const float *attn, const uint16_t *grad_out, int B,
+                         int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
+                         float *grad_loc, float *grad_attn, const int64_t *shapes_host,
+                         const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                         const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+                         void *stream, int want);
+int boxattn_bwd_part_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
+                         const double *loc, const double *attn, const double *grad_out, int B,
+                         int S, int H, int C, int L, int Lq, int P, double *grad_value,
+                         double *grad_loc, double *grad_attn, void *stream, int want);
+int instattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *loc, const float *spatial_w, const float *level_w,
+                          const float *grad_out, const float *grad_mask, int B, int S, int H, int C,
+                          int L, int Lq, int P, float *grad_value, float *grad_loc,
+                          float *grad_spatial_w, float *grad_level_w, const int64_t *shapes_host,
+                          const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                          const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+                          void *stream, int want);
+int instattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *loc, const float *spatial_w, const float *level_w,
+                           const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
+                           int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
+                           float *grad_spatial_w, float *grad_level_w, const int64_t *shapes_host,
+                           const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                           const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+                           void *stream, int want);
+int instattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *loc, const float *spatial_w, const float *level_w,
+                          const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
+                          int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
+                          float *grad_spatial_w, float *grad_level_w, const int64_t *shapes_host,
+                          const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
+                          const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
+                          void *stream, int want);
+int instattn_bwd_part_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
+                          const double *loc, const double *spatial_w, const double *level_w,
+                          const double *grad_out, const double *grad_mask, int B, int S, int H,
+                          int C, int L, int Lq, int P, double *grad_value, double *grad_loc,
+                          double *grad_spatial_w, double *grad_level_w, void *stream, int want);
+
+/*
  * ---- reference windows + box offsets -> sampling grid (opt-in) ---------------
  * Everything of the modules' `_where_to_attend` after the box-offset projection
  * (e2edet/module/box_attention.py:63-81 BoxAttention / InstanceAttention, :304-338
