@@ -124,6 +124,17 @@ inline int fast_group(const Dims &d)
     return (g == 4 || g == 8 || g == 16) ? g : 0;
 }
 
+// Calls f(std::integral_constant<int, G>{}) for the group size g the fast kernels are instantiated for (4, 8 or
+// 16: what fast_group returns when it does not return 0); any other g: nothing is called.
+template <typename F> inline void for_group(int g, F &&f)
+{
+    switch (g) {
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+
 template <typename ST>
 bool fast_ok(const Dims &d, const void *value, const void *loc, const void *a, const void *b,
              const void *c)
@@ -292,17 +303,24 @@ inline BinRide place_riders(const BinRide *ride_in, unsigned own_blocks, unsigne
 // ------------------------------------------------------------------------------ forward
 inline bool make_dense_plan(const Dims &d, const int64_t *sh, const int64_t *ls, DensePlan &p, int elem);
 
-// count_ride: the backward's count pass + scans to run as rider workgroups of the forward kernel (training
-// forward); *ride_taken says whether the kernel that was launched carried them
+// What only some forward entry points pass.  count_ride: the backward's count pass + scans to run as rider workgroups
+// of the forward kernel (training forward); *ride_taken says whether the kernel that was launched carried them
+struct FwdExtras {
+    const int64_t *shapes_host = nullptr, *lsi_host = nullptr;
+    const BinRide *count_ride = nullptr;
+    bool *ride_taken = nullptr;
+    bool allow_dense = true;
+    unsigned long long *stats = nullptr;
+};
 template <typename ST, bool INST>
 int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                const typename Storage<ST>::compute *loc,
                const typename Storage<ST>::compute *w_sp,
                const typename Storage<ST>::compute *w_lv, const Dims &d, ST *out, ST *mask,
-               hipStream_t st, const int64_t *shapes_host = nullptr,
-               const int64_t *lsi_host = nullptr, const BinRide *count_ride = nullptr,
-               bool *ride_taken = nullptr, bool allow_dense = true, unsigned long long *stats = nullptr)
+               const FwdExtras &x, hipStream_t st)
 {
+    const BinRide *const count_ride = x.count_ride;
+    bool *const ride_taken = x.ride_taken;
     if (ride_taken) *ride_taken = false;
     if (!d.valid()) return (int)hipErrorInvalidValue;
     if (d.empty()) return 0;                                   // no queries: nothing to write
@@ -319,24 +337,15 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
     if constexpr (!std::is_same<ST, double>::value) {
         if (fast_ok<ST>(d, value, loc, out, INST ? (const void *)mask : (const void *)out,
                         out)) {
-            if constexpr (!INST && IsHalf16<ST>::value) {     // encoder case: window-staged matrix-core forward
+            if constexpr (!INST) {     // encoder case: window-staged forward (16-bit: matrix cores; float32: VALU)
                 DensePlan dp;
-                if (allow_dense && shapes_host && lsi_host && aligned(value, 16) && aligned(out, 16) &&
-                    aligned(loc, 8) && make_dense_plan(d, shapes_host, lsi_host, dp, 2)) {
+                if (x.allow_dense && x.shapes_host && x.lsi_host && aligned(value, 16) && aligned(out, 16) &&
+                    aligned(loc, 8) && make_dense_plan(d, x.shapes_host, x.lsi_host, dp, (int)sizeof(ST))) {
                     ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
-                    launch_fwd_dense<ST>(value, loc, w_sp, out, dp, (unsigned)(d.n_value() * sizeof(ST)),
-                                     count_ride ? *count_ride : BinRide{}, stats, st);
-                    if (count_ride && ride_taken) *ride_taken = true;
-                    return finish();
-                }
-            }
-            if constexpr (!INST && std::is_same<ST, float>::value) {      // encoder case, float32: window-staged VALU forward
-                DensePlan dp;
-                if (allow_dense && shapes_host && lsi_host && aligned(value, 16) && aligned(out, 16) &&
-                    aligned(loc, 8) && make_dense_plan(d, shapes_host, lsi_host, dp, 4)) {
-                    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
-                    launch_fwd_dense_f32(value, loc, w_sp, out, dp, (unsigned)(d.n_value() * sizeof(float)),
-                                         count_ride ? *count_ride : BinRide{}, stats, st);
+                    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST));
+                    const BinRide ride = count_ride ? *count_ride : BinRide{};
+                    if constexpr (IsHalf16<ST>::value) launch_fwd_dense<ST>(value, loc, w_sp, out, dp, vbytes, ride, x.stats, st);
+                    else launch_fwd_dense_f32(value, loc, w_sp, out, dp, vbytes, ride, x.stats, st);
                     if (count_ride && ride_taken) *ride_taken = true;
                     return finish();
                 }
@@ -386,18 +395,10 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
 #undef BOXATTN_FWD2
                 if (count_ride && ride_taken) *ride_taken = true;
             } else {
-#define BOXATTN_FWD_CASE(GG)                                                                  \
-    case GG:                                                                                  \
-        hipLaunchKernelGGL((fwd_fast_kernel<ST, 4, GG, INST>), dim3(blocks), dim3(256), 0, st, \
-                           value, shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.L, d.Lq, d.P, out, \
-                           mask, n_qh);                                                       \
-        break;
-                switch (G) {
-                    BOXATTN_FWD_CASE(4)
-                    BOXATTN_FWD_CASE(8)
-                    BOXATTN_FWD_CASE(16)
-                }
-#undef BOXATTN_FWD_CASE
+                for_group(G, [&](auto g) {
+                    hipLaunchKernelGGL((fwd_fast_kernel<ST, 4, decltype(g)::value, INST>), dim3(blocks), dim3(256), 0, st,
+                                       value, shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.L, d.Lq, d.P, out, mask, n_qh);
+                });
             }
             return finish();
         }
@@ -416,32 +417,45 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
 // The two gradient groups of a backward (BOXATTN_WANT_*): VALUE = grad_value, POINTS = grad_loc + the weight gradients.
 enum { kWantValue = BOXATTN_WANT_VALUE, kWantPoints = BOXATTN_WANT_POINTS, kWantAll = kWantValue | kWantPoints };
 
-// The atomic kernels.  GV = accumulation buffer for grad_value (the output itself for f32/f64, scratch for bf16 / f16)
-// want: the groups to compute (a partial backward, *_bwd_part_*) -- the pointers of the other group are neither checked
-// nor used, and the kernel is the flavour that leaves its work out (bwd_fast_kernel / bwd_generic_kernel: SCATTER, POINTS)
+// A backward call's operands and its outputs, filled by the extern "C" wrappers (T: float; double for float64 storage).
+// shapes_host / lsi_host: the host copies of the level tables (NULL in the entry points that take none).
+template <typename ST> struct BwdIn {
+    typedef typename Storage<ST>::compute T;
+    const ST *value;
+    const int64_t *shapes, *lsi;
+    const T *loc, *w_sp, *w_lv;
+    const ST *grad_out, *grad_mask;
+    Dims d;
+    const int64_t *shapes_host, *lsi_host;
+    hipStream_t st;
+};
+template <typename ST> struct BwdOut {
+    typedef typename Storage<ST>::compute T;
+    ST *grad_value;
+    T *grad_loc, *grad_sp, *grad_lv;
+};
+
+// The atomic kernels.  grad_value_acc = accumulation buffer for grad_value (the output itself for f32/f64, scratch for
+// bf16 / f16).  want: the groups to compute -- the pointers of the other group are neither checked nor used, and the
+// kernel is the flavour that leaves its work out (bwd_fast_kernel / bwd_generic_kernel: SCATTER, POINTS)
 template <typename ST, bool INST>
-int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
-               const typename Storage<ST>::compute *loc,
-               const typename Storage<ST>::compute *w_sp,
-               const typename Storage<ST>::compute *w_lv, const ST *grad_out,
-               const ST *grad_mask, const Dims &d, ST *grad_value,
-               typename Storage<ST>::compute *grad_loc, typename Storage<ST>::compute *grad_sp,
-               typename Storage<ST>::compute *grad_lv,
-               typename Storage<ST>::compute *grad_value_acc, hipStream_t st, int want = kWantAll)
+int launch_bwd(const BwdIn<ST> &in, const BwdOut<ST> &out, typename Storage<ST>::compute *grad_value_acc, int want)
 {
     typedef typename Storage<ST>::compute T;
+    const Dims &d = in.d;
+    const hipStream_t st = in.st;
     if (!d.valid()) return (int)hipErrorInvalidValue;
     const bool wv = (want & kWantValue) != 0, wp = (want & kWantPoints) != 0;
     const size_t nv = d.n_value();
     const size_t n_qh = d.n_qh();
     if (nv && wv) {
-        if (!grad_value || !grad_value_acc) return (int)hipErrorInvalidValue;
+        if (!out.grad_value || !grad_value_acc) return (int)hipErrorInvalidValue;
     }
     if (n_qh) {
-        if (!shapes || !lsi || !loc || !w_sp || !grad_out || (wp && (!grad_loc || !grad_sp)) ||
-            (INST && (!w_lv || !grad_mask || (wp && !grad_lv))))
+        if (!in.shapes || !in.lsi || !in.loc || !in.w_sp || !in.grad_out || (wp && (!out.grad_loc || !out.grad_sp)) ||
+            (INST && (!in.w_lv || !in.grad_mask || (wp && !out.grad_lv))))
             return (int)hipErrorInvalidValue;
-        if (nv && !value) return (int)hipErrorInvalidValue;
+        if (nv && !in.value) return (int)hipErrorInvalidValue;
     }
     if (nv && wv) {
         hipError_t e = zero_async(grad_value_acc, nv * sizeof(T), st);
@@ -450,9 +464,9 @@ int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
     if (n_qh && !nv) {                                         // no pixels: all gradients 0
         if (!wp) return 0;
         const size_t np = n_qh * d.L * d.P;
-        hipError_t e = zero_async(grad_loc, 2 * np * sizeof(T), st);
-        if (e == hipSuccess) e = zero_async(grad_sp, np * sizeof(T), st);
-        if (e == hipSuccess && INST) e = zero_async(grad_lv, np * sizeof(T), st);
+        hipError_t e = zero_async(out.grad_loc, 2 * np * sizeof(T), st);
+        if (e == hipSuccess) e = zero_async(out.grad_sp, np * sizeof(T), st);
+        if (e == hipSuccess && INST) e = zero_async(out.grad_lv, np * sizeof(T), st);
         return (int)e;
     }
     if (n_qh && nv) {
@@ -461,30 +475,22 @@ int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
         bool done = false;
         if constexpr (!std::is_same<ST, double>::value) {
             // (grad_loc takes part in the choice only where it is an output of the call)
-            if (fast_ok<ST>(d, value, loc, grad_out,
-                            INST ? (const void *)grad_mask : (const void *)grad_out,
-                            wp ? (const void *)grad_loc : (const void *)grad_out)) {
+            if (fast_ok<ST>(d, in.value, in.loc, in.grad_out,
+                            INST ? (const void *)in.grad_mask : (const void *)in.grad_out,
+                            wp ? (const void *)out.grad_loc : (const void *)in.grad_out)) {
                 const int G = fast_group(d);
-                const int pairs = kWave / G;
-                const int blocks = ceil_div_sz(n_qh, (size_t)pairs * 4);
-#define BOXATTN_BWD_LAUNCH(GG, ...)                                                           \
-        hipLaunchKernelGGL((bwd_fast_kernel<ST, 4, GG, INST, ##__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, \
-                           value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d.S,    \
-                           d.H, d.L, d.Lq, d.P, grad_value_acc, grad_loc, grad_sp, grad_lv,  \
-                           n_qh)
-#define BOXATTN_BWD_CASE(GG)                                                                  \
-    case GG:                                                                                  \
-        if (want == kWantAll) BOXATTN_BWD_LAUNCH(GG);                                         \
-        else if (wp) BOXATTN_BWD_LAUNCH(GG, false);                                           \
-        else BOXATTN_BWD_LAUNCH(GG, true, false);                                             \
-        break;
-                switch (G) {
-                    BOXATTN_BWD_CASE(4)
-                    BOXATTN_BWD_CASE(8)
-                    BOXATTN_BWD_CASE(16)
-                }
-#undef BOXATTN_BWD_CASE
-#undef BOXATTN_BWD_LAUNCH
+                const int blocks = ceil_div_sz(n_qh, (size_t)(kWave / G) * 4);
+                const auto launch = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, in.value, in.shapes, in.lsi, in.loc,
+                                       in.w_sp, in.w_lv, in.grad_out, in.grad_mask, d.S, d.H, d.L, d.Lq, d.P,
+                                       grad_value_acc, out.grad_loc, out.grad_sp, out.grad_lv, n_qh);
+                };
+                for_group(G, [&](auto g) {
+                    constexpr int GG = decltype(g)::value;
+                    if (want == kWantAll) launch(bwd_fast_kernel<ST, 4, GG, INST>);
+                    else if (wp) launch(bwd_fast_kernel<ST, 4, GG, INST, false>);
+                    else launch(bwd_fast_kernel<ST, 4, GG, INST, true, false>);
+                });
                 done = true;
             } else if (g_variant == 2) {
                 return (int)hipErrorInvalidValue;
@@ -492,15 +498,14 @@ int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
         }
         if (!done) {
             const int blocks = (int)std::min<size_t>((n_qh + 3) / 4, (size_t)1 << 20);
-#define BOXATTN_BWD_GENERIC(...)                                                              \
-            hipLaunchKernelGGL((bwd_generic_kernel<ST, INST, ##__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, \
-                               value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d.S, \
-                               d.H, d.C, d.L, d.Lq, d.P, grad_value_acc, grad_loc, grad_sp,  \
-                               grad_lv, n_qh)
-            if (want == kWantAll) BOXATTN_BWD_GENERIC();
-            else if (wp) BOXATTN_BWD_GENERIC(false);
-            else BOXATTN_BWD_GENERIC(true, false);
-#undef BOXATTN_BWD_GENERIC
+            const auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, in.value, in.shapes, in.lsi, in.loc, in.w_sp,
+                                   in.w_lv, in.grad_out, in.grad_mask, d.S, d.H, d.C, d.L, d.Lq, d.P, grad_value_acc,
+                                   out.grad_loc, out.grad_sp, out.grad_lv, n_qh);
+            };
+            if (want == kWantAll) launch(bwd_generic_kernel<ST, INST>);
+            else if (wp) launch(bwd_generic_kernel<ST, INST, false>);
+            else launch(bwd_generic_kernel<ST, INST, true, false>);
         }
         int rc = finish();
         if (rc) return rc;
@@ -510,16 +515,15 @@ int launch_bwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
             const int blocks = (int)std::min<size_t>((nv / 4 + 255) / 256 + 1, 256 * 16);
             if constexpr (std::is_same<ST, bf16_t>::value)
                 hipLaunchKernelGGL(cvt_f32_to_bf16_kernel, dim3(blocks), dim3(256), 0, st,
-                                   grad_value_acc, grad_value, nv);
+                                   grad_value_acc, out.grad_value, nv);
             else
                 hipLaunchKernelGGL(cvt_f32_to_f16_kernel, dim3(blocks), dim3(256), 0, st,
-                                   grad_value_acc, grad_value, nv);
+                                   grad_value_acc, out.grad_value, nv);
             return finish();
         }
     }
     return 0;
 }
-
 
 
 #include "boxattn_host_plan.h"       // make_plan / make_dense_plan, plan_layout / scratch_layout, acc_kind, riders_ok
@@ -559,7 +563,7 @@ inline BinRide make_ride(const float *loc, const float *w_sp, const Dims &d, con
 enum { kBinCount = 1, kBinScan = 2, kBinFill = 4 };
 inline void launch_binning(int flavour, const float *loc, const float *w_sp, const Dims &d, const BinPlan &plan,
                            const PlanLayout &w, char *pbuf, int *records, hipStream_t st, int stages,
-                           int *ctickets = nullptr)
+                           int *ctickets)
 {
     constexpr int BW = 8, BH = 4;
     const int ns = d.B * d.H;
@@ -623,25 +627,21 @@ inline bool dense_pointgrad_ok(const DensePlan *dp, const void *value, const voi
 // Point gradients (grad_loc / grad_weight): query-major, independent of how grad_value is accumulated;
 // `fill_ride`: the backward's fill pass as rider workgroups of this launch (*ride_taken: carried).
 template <typename ST, int G, bool INST>
-void launch_pointgrad(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
-                      const float *w_sp, const float *w_lv, const ST *grad_out, const ST *grad_mask,
-                      const Dims &d, float *grad_loc, float *grad_sp, float *grad_lv, hipStream_t st,
-                      const BinRide *fill_ride, bool *ride_taken, const DensePlan *dp)
+void launch_pointgrad(const BwdIn<ST> &in, const BwdOut<ST> &out, const BinRide *fill_ride, bool *ride_taken,
+                      const DensePlan *dp)
 {
+    const Dims &d = in.d;
+    const hipStream_t st = in.st;
     if (ride_taken) *ride_taken = false;
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], st);
-    if constexpr (IsHalf16<ST>::value && !INST) {
-        if (dense_pointgrad_ok(dp, value, loc, w_sp, grad_out, grad_loc, grad_sp)) {
-            launch_pointgrad_dense<ST>(value, loc, w_sp, grad_out, *dp, grad_loc, grad_sp,
-                                   (unsigned)(d.n_value() * sizeof(ST)), st, fill_ride ? *fill_ride : BinRide{});
-            if (fill_ride && ride_taken) *ride_taken = true;
-            return;
-        }
-    }
-    if constexpr (std::is_same<ST, float>::value && !INST) {
-        if (dense_pointgrad_ok(dp, value, loc, w_sp, grad_out, grad_loc, grad_sp)) {
-            launch_pointgrad_dense_f32(value, loc, w_sp, grad_out, *dp, grad_loc, grad_sp,
-                                       (unsigned)(d.n_value() * sizeof(float)), st, fill_ride ? *fill_ride : BinRide{});
+    if constexpr (!INST) {      // encoder case: the window-staged kernels (16-bit: matrix cores; float32: VALU)
+        if (dense_pointgrad_ok(dp, in.value, in.loc, in.w_sp, in.grad_out, out.grad_loc, out.grad_sp)) {
+            const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST));
+            const BinRide ride = fill_ride ? *fill_ride : BinRide{};
+            if constexpr (IsHalf16<ST>::value)
+                launch_pointgrad_dense<ST>(in.value, in.loc, in.w_sp, in.grad_out, *dp, out.grad_loc, out.grad_sp, vbytes, st, ride);
+            else
+                launch_pointgrad_dense_f32(in.value, in.loc, in.w_sp, in.grad_out, *dp, out.grad_loc, out.grad_sp, vbytes, st, ride);
             if (fill_ride && ride_taken) *ride_taken = true;
             return;
         }
@@ -650,8 +650,8 @@ void launch_pointgrad(const ST *value, const int64_t *shapes, const int64_t *lsi
     const size_t vbytes = d.n_value() * sizeof(ST);
     GatherIdx ix{};
     if (vbytes < kOobOffset && gather_idx(d, ix, sizeof(ST))) {
-        const GatherCfg cfg = gather_cfg<ST>(d, aligned(value, 16) && aligned(grad_out, 16) &&
-                                                (!INST || aligned(grad_mask, 16)));
+        const GatherCfg cfg = gather_cfg<ST>(d, aligned(in.value, 16) && aligned(in.grad_out, 16) &&
+                                                (!INST || aligned(in.grad_mask, 16)));
         const int blocks = gather_blocks(d, ix, kWave / cfg.G);
         // few pairs x many points (instance attention on the mask-decoder grid): one wave
         // per pair, its lane groups over the point tiles; else one lane group per pair
@@ -665,30 +665,28 @@ void launch_pointgrad(const ST *value, const int64_t *shapes, const int64_t *lsi
             const BinRide ride = place_riders(fill_ride, (unsigned)wblocks, &total);
 #define BOXATTN_PG2W(GG, VV)                                                                         \
 hipLaunchKernelGGL((pointgrad2_kernel<ST, GG, INST, GatherUnroll<ST, GG, VV>::value, VV, true>), \
-                   dim3(total, split), dim3(256), 0, st, value, shapes, lsi, loc, w_sp, w_lv,    \
-                   grad_out, grad_mask, d.S, d.H, d.L, d.Lq, d.P, grad_loc, grad_sp, grad_lv,    \
+                   dim3(total, split), dim3(256), 0, st, in.value, in.shapes, in.lsi, in.loc, in.w_sp, in.w_lv, \
+                   in.grad_out, in.grad_mask, d.S, d.H, d.L, d.Lq, d.P, out.grad_loc, out.grad_sp, out.grad_lv, \
                    with_grid(ix, wblocks, split, tiles), (unsigned)vbytes, ride);
             BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_PG2W);
 #undef BOXATTN_PG2W
         } else {
             const int split = point_split(blocks, tiles);
             const BinRide ride = place_riders(fill_ride, (unsigned)blocks, &total);
-            {
 #define BOXATTN_PG2(GG, VV)                                                                   \
 hipLaunchKernelGGL((pointgrad2_kernel<ST, GG, INST, GatherUnroll<ST, GG, VV>::value, VV>), \
-                   dim3(total, split), dim3(256), 0, st, value, shapes, lsi, loc, w_sp,    \
-                   w_lv, grad_out, grad_mask, d.S, d.H, d.L, d.Lq, d.P, grad_loc, grad_sp, \
-                   grad_lv, with_grid(ix, blocks, split, tiles), (unsigned)vbytes, ride);
-                BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_PG2);
+                   dim3(total, split), dim3(256), 0, st, in.value, in.shapes, in.lsi, in.loc, in.w_sp, \
+                   in.w_lv, in.grad_out, in.grad_mask, d.S, d.H, d.L, d.Lq, d.P, out.grad_loc, out.grad_sp, \
+                   out.grad_lv, with_grid(ix, blocks, split, tiles), (unsigned)vbytes, ride);
+            BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_PG2);
 #undef BOXATTN_PG2
-            }
         }
         if (fill_ride && ride_taken) *ride_taken = true;
     } else {
         const int blocks = ceil_div_sz(n_qh, (size_t)(kWave / G) * 4);
         hipLaunchKernelGGL((bwd_fast_kernel<ST, 4, G, INST, false>), dim3(blocks), dim3(256),
-                           0, st, value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask,
-                           d.S, d.H, d.L, d.Lq, d.P, (float *)nullptr, grad_loc, grad_sp, grad_lv,
+                           0, st, in.value, in.shapes, in.lsi, in.loc, in.w_sp, in.w_lv, in.grad_out, in.grad_mask,
+                           d.S, d.H, d.L, d.Lq, d.P, (float *)nullptr, out.grad_loc, out.grad_sp, out.grad_lv,
                            n_qh);
     }
 }
@@ -746,17 +744,17 @@ int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, cons
 
 // A binned backward: [count -> scans, unless the training forward left a plan] -> point gradients with the
 // fill pass riding in their launch -> accumulate (chunked blocks summed by their last chunk).
-// points = false: the grad_value half alone (grad_loc / grad_sp / grad_lv are not used).
+// points = false: the grad_value half alone (out.grad_loc / grad_sp / grad_lv and dp are not used; spec is null).
 // spec: the caller's state of the one-pass fill (boxattn_spec.h) -- nullptr: two-pass binning; spec_warm: its ranges were
 // planned by an earlier call (else this call runs the two-pass passes and spec_layout_kernel plans them from its scan)
 template <typename ST, int G, bool INST>
-int run_binned(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
-               const float *w_sp, const float *w_lv, const ST *grad_out, const ST *grad_mask,
-               const Dims &d, const BinPlan &plan, const PlanLayout &pl, char *pbuf, const ScratchLayout &sl,
-               char *sbuf, ST *grad_value, float *grad_loc, float *grad_sp, float *grad_lv, bool plan_ready,
-               hipStream_t st, const DensePlan *dp, const SpecRide *spec = nullptr,
-               bool spec_warm = false, int *spec_tickets = nullptr, bool points = true)
+int run_binned(const BwdIn<ST> &in, const BwdOut<ST> &out, const BinPlan &plan, const PlanLayout &pl, char *pbuf,
+               const ScratchLayout &sl, char *sbuf, bool plan_ready, const DensePlan *dp, const SpecRide *spec,
+               bool spec_warm, int *spec_tickets, bool points)
 {
+    const Dims &d = in.d;
+    const hipStream_t st = in.st;
+    const float *loc = in.loc, *w_sp = in.w_sp;
     const int ns = d.B * d.H;
     const AccKind acc = acc_kind<ST, INST>(d);
     const int flavour = bin_flavour<ST, INST>(d, loc, w_sp);
@@ -765,28 +763,26 @@ int run_binned(const ST *value, const int64_t *shapes, const int64_t *lsi, const
     const int *n_items = (const int *)(pbuf + pl.n_items), *offsets = (const int *)(pbuf + pl.offsets);
     const int4 *items = (const int4 *)(pbuf + pl.items), *combos = (const int4 *)(pbuf + pl.combos);
     const bool one_pass = spec && spec_warm;
-    if (!plan_ready && !one_pass) launch_binning(flavour, loc, w_sp, d, plan, pl, pbuf, records, st, kBinCount | kBinScan);
+    if (!plan_ready && !one_pass)
+        launch_binning(flavour, loc, w_sp, d, plan, pl, pbuf, records, st, kBinCount | kBinScan, nullptr);
     bool filled = false;
     if (!points) {
-        // grad_value only (*_bwd_part_*, BOXATTN_WANT_VALUE; spec is null): no point-gradient launch, so nothing the fill
-        // pass could ride in -- it runs as a launch of its own, below
+        // grad_value only (*_bwd_part_*, BOXATTN_WANT_VALUE): no point-gradient launch, so nothing the fill pass could
+        // ride in -- it runs as a launch of its own, below
     } else if (one_pass) {
         // point gradients + the fill riders' ONE pass over the locations into the ranges the state holds; the slice's
         // last rider writes the work items (and the next call's ranges)
         BinRide ride = make_ride(loc, w_sp, d, plan, pl, pbuf, &sl, sbuf, flavour | kRideSpec, true);
         ride.spec = *spec;
         ride.tickets = spec_tickets;
-        launch_pointgrad<ST, G, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_loc,
-                                      grad_sp, grad_lv, st, &ride, &filled, dp);
+        launch_pointgrad<ST, G, INST>(in, out, &ride, &filled, dp);
         if (!filled)        // (the launched kernel carries no riders: the two-pass passes as launches, below)
-            launch_binning(flavour, loc, w_sp, d, plan, pl, pbuf, records, st, kBinCount | kBinScan);
+            launch_binning(flavour, loc, w_sp, d, plan, pl, pbuf, records, st, kBinCount | kBinScan, nullptr);
     } else if (riders_ok(plan, pl)) {
         const BinRide ride = make_ride(loc, w_sp, d, plan, pl, pbuf, &sl, sbuf, flavour, true);
-        launch_pointgrad<ST, G, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_loc,
-                                      grad_sp, grad_lv, st, &ride, &filled, dp);
+        launch_pointgrad<ST, G, INST>(in, out, &ride, &filled, dp);
     } else {
-        launch_pointgrad<ST, G, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_loc,
-                                      grad_sp, grad_lv, st, nullptr, nullptr, dp);
+        launch_pointgrad<ST, G, INST>(in, out, nullptr, nullptr, dp);
     }
     // Chunked blocks: summed by their last chunk inside the accumulate launch (chunk_finish; the fill pass -- riding
     // or not -- clears the blocks' tickets) wherever the riders run: one launch less, C2 bf16 125.7 -> 122.9 us, C2 fp32
@@ -809,8 +805,8 @@ int run_binned(const ST *value, const int64_t *shapes, const int64_t *lsi, const
         zr = ZeroRole{nullptr, nullptr, spec->redo, loc, w_sp, d.P};
         plan_acc.zero_workers = kSpecRedoWorkers;
     }
-    int rc = launch_accumulate<ST, G, INST>(acc, grad_out, grad_mask, loc, w_sp, w_lv, d, plan_acc, offsets, items,
-                                            n_items, records, grad_value, partials, cc, zr, st);
+    int rc = launch_accumulate<ST, G, INST>(acc, in.grad_out, in.grad_mask, loc, w_sp, in.w_lv, d, plan_acc, offsets, items,
+                                            n_items, records, out.grad_value, partials, cc, zr, st);
     if (rc) return rc;
     if (spec && !(one_pass && filled))      // a cold state: the next call's ranges from this call's exact scan
         hipLaunchKernelGGL(spec_layout_kernel<256>, dim3(ns), dim3(256), 0, st, plan, offsets, spec->cursor, spec->cbase,
@@ -818,71 +814,90 @@ int run_binned(const ST *value, const int64_t *shapes, const int64_t *lsi, const
     if (own_combine) {
         ScopedKernelTimer timer(g_prof.ev[kSlotBwdCombine], st);
         hipLaunchKernelGGL((combine_partials_kernel<ST, 4 * G>), dim3(64, ns), dim3(64), 0, st, combos,
-                           n_items, partials, combine_plan(plan), d.S, d.H, grad_value);
+                           n_items, partials, combine_plan(plan), d.S, d.H, out.grad_value);
     }
     return finish();
 }
 
-// Backward with a caller-provided workspace (and, optionally, the plan a training forward built); falls back
-// to the atomic kernels when the binned algorithm does not apply.
+// The backward behind *_bwd_ws_* (want = kWantAll) and *_bwd_part_*: the one place where a call's route is decided.
+// wv / wp: grad_value (VALUE) / the point gradients (POINTS) are wanted; the pointers of a group that is not wanted
+// are dropped on entry and never looked at.
+//
+//   binned   variant 0 or 3, pixels and queries, make_plan, fast_ok (grad_loc takes part only with wp)
+//            + with wv: a 256-aligned workspace that holds the scratch (and the plan, unless the caller's
+//              plan_buf is usable: plan_ready) and a 16-aligned grad_value
+//   not binned: variant 3 refuses; else the atomic kernels (launch_bwd) -- with wv and 16-bit storage the workspace is
+//            their float32 accumulation buffer and must hold B S H C floats
+//   binned, POINTS only: launch_pointgrad without a fill ride.  No workspace, plan or state
+//   binned, VALUE only:  run_binned without its point-gradient launch: two-pass binning (count and scans unless
+//            plan_ready, the fill as a launch of its own); the state is neither read nor written
+//   binned, all: run_binned; the fill rides in the point-gradient launch, and where the shape allows (spec_ok) and no
+//            plan came with the call it is the one-pass fill on the ranges the caller's state holds
 template <typename ST, bool INST>
-int launch_bwd_ws(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
-                  const float *w_sp, const float *w_lv, const ST *grad_out, const ST *grad_mask,
-                  const Dims &d, ST *grad_value, float *grad_loc, float *grad_sp, float *grad_lv,
-                  const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
-                  size_t workspace_bytes, const void *plan_buf, size_t plan_bytes, int hints, hipStream_t st,
-                  void *state = nullptr, size_t state_bytes = 0)
+int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size_t workspace_bytes,
+                      const void *plan_buf, size_t plan_bytes, void *state, size_t state_bytes, int hints, int want)
 {
     constexpr bool kH16 = IsHalf16<ST>::value;           // 16-bit storage (bf16 / f16): float32 scratch for the atomics
-    if (!d.valid()) return (int)hipErrorInvalidValue;
+    const Dims &d = in.d;
+    if ((want != kWantValue && want != kWantPoints && want != kWantAll) || !d.valid()) return (int)hipErrorInvalidValue;
+    const bool wv = (want & kWantValue) != 0, wp = (want & kWantPoints) != 0;
+    if (!wv) out.grad_value = nullptr;
+    if (!wp) out.grad_loc = out.grad_sp = out.grad_lv = nullptr;
     BinPlan plan;
     const size_t nv = d.n_value();
-    bool binned = (g_variant == 0 || g_variant == 3) && workspace && nv && d.n_qh() &&
-                  make_plan(d, shapes_host, lsi_host, plan) &&
-                  fast_ok<ST>(d, value, loc, grad_out,
-                              INST ? (const void *)grad_mask : (const void *)grad_out, grad_loc) &&
-                  aligned(workspace, 256) && aligned(grad_value, 16);
+    bool binned = (g_variant == 0 || g_variant == 3) && nv && d.n_qh() &&
+                  make_plan(d, in.shapes_host, in.lsi_host, plan) &&
+                  fast_ok<ST>(d, in.value, in.loc, in.grad_out,
+                              INST ? (const void *)in.grad_mask : (const void *)in.grad_out,
+                              wp ? (const void *)out.grad_loc : (const void *)in.grad_out);
     PlanLayout pl{};
     ScratchLayout sl{};
     bool plan_ready = false;
-    if (binned) {
+    if (binned && wv) {
         pl = plan_layout(d, plan);
         sl = scratch_layout(d, plan, wide_workspace(kH16, d));
         plan_ready = plan_buf && plan_bytes >= pl.total && aligned(plan_buf, 256);
-        binned = workspace_bytes >= (plan_ready ? sl.total : pl.total + sl.total);
+        binned = workspace && aligned(workspace, 256) && aligned(out.grad_value, 16) &&
+                 workspace_bytes >= (plan_ready ? sl.total : pl.total + sl.total);
     }
     if (!binned) {
         // (a plan the forward built is simply not used when the backward's own checks -- e.g. an
         // unaligned grad_out view -- rule the binned path out: the atomic path needs no plan)
         if (g_variant == 3) return (int)hipErrorInvalidValue;
         float *acc = nullptr;
-        if constexpr (kH16) {
-            if (!workspace || workspace_bytes < nv * sizeof(float)) return (int)hipErrorInvalidValue;
-            acc = (float *)workspace;
-        } else {
-            acc = grad_value;
+        if (wv) {
+            if constexpr (kH16) {
+                if (!workspace || workspace_bytes < nv * sizeof(float)) return (int)hipErrorInvalidValue;
+                acc = (float *)workspace;
+            } else {
+                acc = out.grad_value;
+            }
         }
-        return launch_bwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d,
-                                    grad_value, grad_loc, grad_sp, grad_lv, acc, st);
+        return launch_bwd<ST, INST>(in, out, acc, want);
     }
-    if (!shapes || !lsi || !loc || !w_sp || !grad_out || !grad_loc || !grad_sp || !grad_value ||
-        !value || (INST && (!w_lv || !grad_mask || !grad_lv)))
+    if (!in.shapes || !in.lsi || !in.loc || !in.w_sp || !in.grad_out || !in.value || (INST && (!in.w_lv || !in.grad_mask)) ||
+        (wv && !out.grad_value) || (wp && (!out.grad_loc || !out.grad_sp || (INST && !out.grad_lv))))
         return (int)hipErrorInvalidValue;
+    DensePlan dense;
+    const DensePlan *dp = wp && !INST && !(hints & BOXATTN_HINT_NOT_LOCAL) &&
+                                  make_dense_plan(d, in.shapes_host, in.lsi_host, dense, (int)sizeof(ST)) ? &dense : nullptr;
+    if (!wv) {
+        for_group(fast_group(d), [&](auto g) {
+            launch_pointgrad<ST, decltype(g)::value, INST>(in, out, nullptr, nullptr, dp);
+        });
+        return finish();
+    }
     char *ws = (char *)workspace;
     char *pbuf = plan_ready ? const_cast<char *>((const char *)plan_buf) : ws;
     char *sbuf = plan_ready ? ws : ws + pl.total;
-    int rc = 0;
-    DensePlan dense;
-    const DensePlan *dp = !std::is_same<ST, double>::value && !INST && !(hints & BOXATTN_HINT_NOT_LOCAL) &&
-                                  make_dense_plan(d, shapes_host, lsi_host, dense, (int)sizeof(ST)) ? &dense : nullptr;
     // the one-pass fill (boxattn_spec.h): the caller's state holds the bins' ranges
     SpecRide spec{};
     const SpecRide *sp = nullptr;
     bool spec_warm = false;
     int *spec_tickets = nullptr;
-    if (!plan_ready && spec_ok<ST, INST>(d, plan, pl)) {
+    if (wp && !plan_ready && spec_ok<ST, INST>(d, plan, pl)) {
         const StateLayout sy = state_layout(d, &plan);
-        const int chk = state_check(state, state_bytes, sy, d, shapes_host, st, (hints & BOXATTN_HINT_FRESH_STATE) != 0);
+        const int chk = state_check(state, state_bytes, sy, d, in.shapes_host, in.st, (hints & BOXATTN_HINT_FRESH_STATE) != 0);
         if (chk < 0) return (int)hipErrorInvalidValue;
         if (chk > 0) {
             char *sb = (char *)state;
@@ -894,116 +909,11 @@ int launch_bwd_ws(const ST *value, const int64_t *shapes, const int64_t *lsi, co
             state_learned(state);        // (whichever way this call goes, it leaves the next call's ranges behind)
         }
     }
-    switch (fast_group(d)) {
-#define BOXATTN_BINNED_CASE(GG)                                                                 \
-    case GG:                                                                                    \
-        rc = run_binned<ST, GG, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, \
-                                      d, plan, pl, pbuf, sl, sbuf, grad_value, grad_loc, grad_sp, grad_lv, \
-                                      plan_ready, st, dp, sp, spec_warm, spec_tickets);     \
-        break;
-        BOXATTN_BINNED_CASE(4)
-        BOXATTN_BINNED_CASE(8)
-        BOXATTN_BINNED_CASE(16)
-#undef BOXATTN_BINNED_CASE
-    }
-    return rc;
-}
-
-// A partial backward (*_bwd_part_*): one of the two gradient groups, with launch_bwd_ws' arguments.  The pointers of the
-// group that is not wanted are never looked at.
-//   POINTS: launch_pointgrad without a fill ride where the full call would run the binned backward (given a workspace:
-//           this call takes none), else the atomic kernels' points-only flavour.  No workspace, plan or state.
-//   VALUE:  the binned backward without its point-gradient launch -- [count, scans, unless a plan is passed,] fill as a
-//           launch of its own, accumulate, combine -- else zero-fill + the atomic kernels' value-only flavour [+ the
-//           16-bit conversion].  The two-pass binning only: the one-pass fill lives in the riders of the point-gradient
-//           launch, so the state is neither read nor written (nor noted as learned).
-template <typename ST, bool INST>
-int launch_bwd_part(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
-                    const float *w_sp, const float *w_lv, const ST *grad_out, const ST *grad_mask,
-                    const Dims &d, ST *grad_value, float *grad_loc, float *grad_sp, float *grad_lv,
-                    const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
-                    size_t workspace_bytes, const void *plan_buf, size_t plan_bytes, void *state,
-                    size_t state_bytes, int hints, hipStream_t st, int want)
-{
-    if (want == kWantAll)
-        return launch_bwd_ws<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_value,
-                                       grad_loc, grad_sp, grad_lv, shapes_host, lsi_host, workspace, workspace_bytes,
-                                       plan_buf, plan_bytes, hints, st, state, state_bytes);
-    if (want != kWantValue && want != kWantPoints) return (int)hipErrorInvalidValue;
-    constexpr bool kH16 = IsHalf16<ST>::value;
-    if (!d.valid()) return (int)hipErrorInvalidValue;
-    const bool wp = want == kWantPoints;
-    BinPlan plan;
-    const size_t nv = d.n_value();
-    // launch_bwd_ws' test, less what belongs to the other group (POINTS: workspace and grad_value; VALUE: grad_loc)
-    bool binned = (g_variant == 0 || g_variant == 3) && nv && d.n_qh() &&
-                  make_plan(d, shapes_host, lsi_host, plan) &&
-                  fast_ok<ST>(d, value, loc, grad_out,
-                              INST ? (const void *)grad_mask : (const void *)grad_out,
-                              wp ? (const void *)grad_loc : (const void *)grad_out);
-    const bool inputs_ok = shapes && lsi && loc && w_sp && grad_out && value && (!INST || (w_lv && grad_mask));
-    DensePlan dense;
-    if (wp) {
-        if (!binned) {
-            if (g_variant == 3) return (int)hipErrorInvalidValue;
-            return launch_bwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, nullptr,
-                                        grad_loc, grad_sp, grad_lv, nullptr, st, kWantPoints);
-        }
-        if (!inputs_ok || !grad_loc || !grad_sp || (INST && !grad_lv)) return (int)hipErrorInvalidValue;
-        const DensePlan *dp = !INST && !(hints & BOXATTN_HINT_NOT_LOCAL) &&
-                                      make_dense_plan(d, shapes_host, lsi_host, dense, (int)sizeof(ST)) ? &dense : nullptr;
-        switch (fast_group(d)) {
-#define BOXATTN_PART_CASE(GG)                                                                   \
-    case GG:                                                                                    \
-        launch_pointgrad<ST, GG, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_loc, \
-                                       grad_sp, grad_lv, st, nullptr, nullptr, dp);             \
-        break;
-            BOXATTN_PART_CASE(4)
-            BOXATTN_PART_CASE(8)
-            BOXATTN_PART_CASE(16)
-#undef BOXATTN_PART_CASE
-        }
-        return finish();
-    }
-    binned = binned && workspace && aligned(workspace, 256) && aligned(grad_value, 16);
-    PlanLayout pl{};
-    ScratchLayout sl{};
-    bool plan_ready = false;
-    if (binned) {
-        pl = plan_layout(d, plan);
-        sl = scratch_layout(d, plan, wide_workspace(kH16, d));
-        plan_ready = plan_buf && plan_bytes >= pl.total && aligned(plan_buf, 256);
-        binned = workspace_bytes >= (plan_ready ? sl.total : pl.total + sl.total);
-    }
-    if (!binned) {
-        if (g_variant == 3) return (int)hipErrorInvalidValue;
-        float *acc = nullptr;
-        if constexpr (kH16) {
-            if (!workspace || workspace_bytes < nv * sizeof(float)) return (int)hipErrorInvalidValue;
-            acc = (float *)workspace;
-        } else {
-            acc = grad_value;
-        }
-        return launch_bwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, d, grad_value,
-                                    nullptr, nullptr, nullptr, acc, st, kWantValue);
-    }
-    if (!inputs_ok || !grad_value) return (int)hipErrorInvalidValue;
-    char *ws = (char *)workspace;
-    char *pbuf = plan_ready ? const_cast<char *>((const char *)plan_buf) : ws;
-    char *sbuf = plan_ready ? ws : ws + pl.total;
     int rc = 0;
-    switch (fast_group(d)) {
-#define BOXATTN_PART_CASE(GG)                                                                   \
-    case GG:                                                                                    \
-        rc = run_binned<ST, GG, INST>(value, shapes, lsi, loc, w_sp, w_lv, grad_out, grad_mask, \
-                                      d, plan, pl, pbuf, sl, sbuf, grad_value, nullptr, nullptr, nullptr, \
-                                      plan_ready, st, nullptr, nullptr, false, nullptr, false);  \
-        break;
-        BOXATTN_PART_CASE(4)
-        BOXATTN_PART_CASE(8)
-        BOXATTN_PART_CASE(16)
-#undef BOXATTN_PART_CASE
-    }
+    for_group(fast_group(d), [&](auto g) {
+        rc = run_binned<ST, decltype(g)::value, INST>(in, out, plan, pl, pbuf, sl, sbuf, plan_ready, dp, sp, spec_warm,
+                                                      spec_tickets, wp);
+    });
     return rc;
 }
 
@@ -1017,7 +927,6 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
                      hipStream_t st)
 {
     if (plan_built) *plan_built = 0;
-    const bool allow_dense = !(hints & BOXATTN_HINT_NOT_LOCAL);
     // the locality counters of the window-staged forward, then the riders' tickets, then the one-pass fill's ranges
     const size_t tbytes = (size_t)std::max(0, d.B) * (size_t)std::max(0, d.H) * kRideTickets * sizeof(int);
     BinPlan plan;
@@ -1028,14 +937,17 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
     if (state_check(state, state_bytes, sy, d, shapes_host, st, (hints & BOXATTN_HINT_FRESH_STATE) != 0) < 0)
         return (int)hipErrorInvalidValue;
     const bool have_state = state != nullptr;
-    unsigned long long *stats = have_state ? (unsigned long long *)state : nullptr;
+    FwdExtras x;                  // of every launch_fwd below; the one that carries the count riders adds them
+    x.shapes_host = shapes_host;
+    x.lsi_host = lsi_host;
+    x.allow_dense = !(hints & BOXATTN_HINT_NOT_LOCAL);
+    x.stats = have_state ? (unsigned long long *)state : nullptr;
     // The backward of this shape fills its bins in one pass, from ranges it keeps in the state buffer: nothing of the
     // backward rides in the forward, and there is no plan to hand over (*plan_built stays 0)
     if (have_state && planned && d.n_value() && d.n_qh() && (g_variant == 0 || g_variant == 3) &&
         fast_ok<ST>(d, value, loc, out, INST ? (const void *)mask : (const void *)out, out) &&
         spec_ok<ST, INST>(d, plan, plan_layout(d, plan)))
-        return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, st,
-                                    shapes_host, lsi_host, nullptr, nullptr, allow_dense, stats);
+        return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
     bool ok = (g_variant == 0 || g_variant == 3) && plan_buf && planned &&
               d.n_value() && d.n_qh() &&
               aligned(plan_buf, 256) &&
@@ -1048,8 +960,7 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
         ok = plan_bytes >= pl.total;
     }
     if (!ok)
-        return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, st,
-                                    shapes_host, lsi_host, nullptr, nullptr, allow_dense, stats);
+        return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
     char *pbuf = (char *)plan_buf;
     const int flavour = bin_flavour<ST, INST>(d, loc, w_sp);
     bool taken = false;
@@ -1066,15 +977,15 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
             hipError_t e = zero_async(pbuf + pl.tickets, tbytes, st);
             if (e != hipSuccess) return (int)e;
         }
-        rc = launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, st, shapes_host, lsi_host,
-                                  &ride, &taken, allow_dense, stats);
+        x.count_ride = &ride;
+        x.ride_taken = &taken;
+        rc = launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
     } else {
-        rc = launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, st, shapes_host, lsi_host,
-                                  nullptr, nullptr, allow_dense, stats);
+        rc = launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
     }
     if (rc) return rc;
     if (!taken)
-        launch_binning(flavour, loc, w_sp, d, plan, pl, pbuf, nullptr, st, kBinCount | kBinScan);
+        launch_binning(flavour, loc, w_sp, d, plan, pl, pbuf, nullptr, st, kBinCount | kBinScan, nullptr);
     rc = finish();
     if (rc == 0 && plan_built) *plan_built = 1;
     return rc;
@@ -1189,9 +1100,9 @@ int boxattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t 
                        void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state,
         size_t state_bytes, int hints, void *stream)
 {
-    return launch_bwd_ws<float, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
-                                       grad_value, grad_loc, grad_attn, nullptr, shapes_host, lsi_host,
-                                       workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
+    return launch_bwd_routed<float, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
+        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, workspace, workspace_bytes, plan,
+        plan_bytes, state, state_bytes, hints, kWantAll);
 }
 int boxattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                         const float *loc, const float *attn, const uint16_t *grad_out, int B,
@@ -1201,9 +1112,9 @@ int boxattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int6
                         const void *plan, size_t plan_bytes, void *state,
         size_t state_bytes, int hints, void *stream)
 {
-    return launch_bwd_ws<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
-                                        grad_value, grad_loc, grad_attn, nullptr, shapes_host, lsi_host,
-                                        workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
+    return launch_bwd_routed<bf16_t, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
+        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, workspace, workspace_bytes, plan,
+        plan_bytes, state, state_bytes, hints, kWantAll);
 }
 int boxattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                        const float *loc, const float *attn, const uint16_t *grad_out, int B,
@@ -1213,9 +1124,9 @@ int boxattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64
                        const void *plan, size_t plan_bytes, void *state,
        size_t state_bytes, int hints, void *stream)
 {
-    return launch_bwd_ws<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr, DIMS,
-                                        as_f16(grad_value), grad_loc, grad_attn, nullptr, shapes_host, lsi_host,
-                                        workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
+    return launch_bwd_routed<f16_t, false>({as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr,
+        DIMS, shapes_host, lsi_host, ST_}, {as_f16(grad_value), grad_loc, grad_attn, nullptr}, workspace,
+        workspace_bytes, plan, plan_bytes, state, state_bytes, hints, kWantAll);
 }
 int instattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                         const float *loc, const float *spatial_w, const float *level_w,
@@ -1226,9 +1137,9 @@ int instattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t
                         const void *plan, size_t plan_bytes, void *state,
         size_t state_bytes, int hints, void *stream)
 {
-    return launch_bwd_ws<float, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-                                      grad_value, grad_loc, grad_spatial_w, grad_level_w, shapes_host,
-                                      lsi_host, workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
+    return launch_bwd_routed<float, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
+        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, workspace, workspace_bytes,
+        plan, plan_bytes, state, state_bytes, hints, kWantAll);
 }
 int instattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                          const float *loc, const float *spatial_w, const float *level_w,
@@ -1239,9 +1150,9 @@ int instattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int
                          const void *plan, size_t plan_bytes, void *state,
         size_t state_bytes, int hints, void *stream)
 {
-    return launch_bwd_ws<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-                                       grad_value, grad_loc, grad_spatial_w, grad_level_w, shapes_host,
-                                       lsi_host, workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
+    return launch_bwd_routed<bf16_t, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
+        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, workspace, workspace_bytes,
+        plan, plan_bytes, state, state_bytes, hints, kWantAll);
 }
 int instattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                         const float *loc, const float *spatial_w, const float *level_w,
@@ -1252,9 +1163,9 @@ int instattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int6
                         const void *plan, size_t plan_bytes, void *state,
        size_t state_bytes, int hints, void *stream)
 {
-    return launch_bwd_ws<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out), as_f16(grad_mask), DIMS,
-                                       as_f16(grad_value), grad_loc, grad_spatial_w, grad_level_w, shapes_host,
-                                       lsi_host, workspace, workspace_bytes, plan, plan_bytes, hints, ST_, state, state_bytes);
+    return launch_bwd_routed<f16_t, true>({as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out),
+        as_f16(grad_mask), DIMS, shapes_host, lsi_host, ST_}, {as_f16(grad_value), grad_loc, grad_spatial_w,
+        grad_level_w}, workspace, workspace_bytes, plan, plan_bytes, state, state_bytes, hints, kWantAll);
 }
 
 
@@ -1265,9 +1176,9 @@ int boxattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64_
         void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
         int hints, void *stream, int want)
 {
-    return launch_bwd_part<float, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
-                                      grad_value, grad_loc, grad_attn, nullptr, shapes_host, lsi_host, workspace,
-                                      workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+    return launch_bwd_routed<float, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
+        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, workspace, workspace_bytes, plan,
+        plan_bytes, state, state_bytes, hints, want);
 }
 int boxattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
         const float *loc, const float *attn, const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
@@ -1275,9 +1186,9 @@ int boxattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const in
         void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
         int hints, void *stream, int want)
 {
-    return launch_bwd_part<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
-                                      grad_value, grad_loc, grad_attn, nullptr, shapes_host, lsi_host, workspace,
-                                      workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+    return launch_bwd_routed<bf16_t, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
+        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, workspace, workspace_bytes, plan,
+        plan_bytes, state, state_bytes, hints, want);
 }
 int boxattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
         const float *loc, const float *attn, const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
@@ -1285,9 +1196,9 @@ int boxattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int
         void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
         int hints, void *stream, int want)
 {
-    return launch_bwd_part<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr, DIMS,
-                                      as_f16(grad_value), grad_loc, grad_attn, nullptr, shapes_host, lsi_host, workspace,
-                                      workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+    return launch_bwd_routed<f16_t, false>({as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr,
+        DIMS, shapes_host, lsi_host, ST_}, {as_f16(grad_value), grad_loc, grad_attn, nullptr}, workspace,
+        workspace_bytes, plan, plan_bytes, state, state_bytes, hints, want);
 }
 int instattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
         const float *loc, const float *spatial_w, const float *level_w, const float *grad_out, const float *grad_mask,
@@ -1296,9 +1207,9 @@ int instattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64
         size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
         void *stream, int want)
 {
-    return launch_bwd_part<float, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-                                     grad_value, grad_loc, grad_spatial_w, grad_level_w, shapes_host, lsi_host, workspace,
-                                     workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+    return launch_bwd_routed<float, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
+        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, workspace, workspace_bytes,
+        plan, plan_bytes, state, state_bytes, hints, want);
 }
 int instattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
         const float *loc, const float *spatial_w, const float *level_w, const uint16_t *grad_out, const uint16_t *grad_mask,
@@ -1307,9 +1218,9 @@ int instattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const i
         size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
         void *stream, int want)
 {
-    return launch_bwd_part<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-                                     grad_value, grad_loc, grad_spatial_w, grad_level_w, shapes_host, lsi_host, workspace,
-                                     workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+    return launch_bwd_routed<bf16_t, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
+        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, workspace, workspace_bytes,
+        plan, plan_bytes, state, state_bytes, hints, want);
 }
 int instattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
         const float *loc, const float *spatial_w, const float *level_w, const uint16_t *grad_out, const uint16_t *grad_mask,
@@ -1318,17 +1229,17 @@ int instattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const in
         size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
         void *stream, int want)
 {
-    return launch_bwd_part<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out), as_f16(grad_mask), DIMS,
-                                     as_f16(grad_value), grad_loc, grad_spatial_w, grad_level_w, shapes_host, lsi_host, workspace,
-                                     workspace_bytes, plan, plan_bytes, state, state_bytes, hints, ST_, want);
+    return launch_bwd_routed<f16_t, true>({as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out),
+        as_f16(grad_mask), DIMS, shapes_host, lsi_host, ST_}, {as_f16(grad_value), grad_loc, grad_spatial_w,
+        grad_level_w}, workspace, workspace_bytes, plan, plan_bytes, state, state_bytes, hints, want);
 }
 int boxattn_bwd_part_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
         const double *loc, const double *attn, const double *grad_out, int B, int S, int H, int C, int L, int Lq,
         int P, double *grad_value, double *grad_loc, double *grad_attn, void *stream, int want)
 {
     if (want != kWantValue && want != kWantPoints && want != kWantAll) return (int)hipErrorInvalidValue;
-    return launch_bwd<double, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, grad_value,
-                                     grad_loc, grad_attn, nullptr, grad_value, ST_, want);
+    return launch_bwd<double, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, nullptr,
+        nullptr, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, grad_value, want);
 }
 int instattn_bwd_part_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
         const double *loc, const double *spatial_w, const double *level_w, const double *grad_out,
@@ -1336,8 +1247,8 @@ int instattn_bwd_part_f64(const double *value, const int64_t *shapes, const int6
         double *grad_loc, double *grad_spatial_w, double *grad_level_w, void *stream, int want)
 {
     if (want != kWantValue && want != kWantPoints && want != kWantAll) return (int)hipErrorInvalidValue;
-    return launch_bwd<double, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-                                    grad_value, grad_loc, grad_spatial_w, grad_level_w, grad_value, ST_, want);
+    return launch_bwd<double, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS, nullptr,
+        nullptr, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, grad_value, want);
 }
 
 int boxattn_abi_version(void) { return BOXATTN_ABI_VERSION; }
@@ -1395,28 +1306,28 @@ int boxattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *ls
                     int Lq, int P, float *out, void *stream)
 {
     return launch_fwd<float, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
-                                    ST_);
+                                    {}, ST_);
 }
 int boxattn_fwd_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
                     const double *loc, const double *attn, int B, int S, int H, int C, int L,
                     int Lq, int P, double *out, void *stream)
 {
     return launch_fwd<double, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out,
-                                     nullptr, ST_);
+                                     nullptr, {}, ST_);
 }
 int boxattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                      const float *loc, const float *attn, int B, int S, int H, int C, int L,
                      int Lq, int P, uint16_t *out, void *stream)
 {
     return launch_fwd<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out,
-                                     nullptr, ST_);
+                                     nullptr, {}, ST_);
 }
 int boxattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                     const float *loc, const float *attn, int B, int S, int H, int C, int L,
                     int Lq, int P, uint16_t *out, void *stream)
 {
     return launch_fwd<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, DIMS, as_f16(out),
-                                     nullptr, ST_);
+                                     nullptr, {}, ST_);
 }
 
 int boxattn_fwd_hl_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -1425,7 +1336,7 @@ int boxattn_fwd_hl_f32(const float *value, const int64_t *shapes, const int64_t 
                        const int64_t *lsi_host, void *stream)
 {
     return launch_fwd<float, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
-                                    ST_, shapes_host, lsi_host);
+                                    {shapes_host, lsi_host}, ST_);
 }
 int boxattn_fwd_hl_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                         const float *loc, const float *attn, int B, int S, int H, int C, int L,
@@ -1433,7 +1344,7 @@ int boxattn_fwd_hl_bf16(const uint16_t *value, const int64_t *shapes, const int6
                         const int64_t *lsi_host, void *stream)
 {
     return launch_fwd<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
-                                     ST_, shapes_host, lsi_host);
+                                     {shapes_host, lsi_host}, ST_);
 }
 int boxattn_fwd_hl_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                        const float *loc, const float *attn, int B, int S, int H, int C, int L,
@@ -1441,7 +1352,7 @@ int boxattn_fwd_hl_f16(const uint16_t *value, const int64_t *shapes, const int64
                        const int64_t *lsi_host, void *stream)
 {
     return launch_fwd<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, DIMS, as_f16(out), nullptr,
-                                     ST_, shapes_host, lsi_host);
+                                     {shapes_host, lsi_host}, ST_);
 }
 
 int boxattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -1449,36 +1360,32 @@ int boxattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *ls
                     int H, int C, int L, int Lq, int P, float *grad_value, float *grad_loc,
                     float *grad_attn, void *stream)
 {
-    return launch_bwd<float, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr,
-                                    DIMS, grad_value, grad_loc, grad_attn, nullptr, grad_value,
-                                    ST_);
+    return launch_bwd<float, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, nullptr,
+        nullptr, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, grad_value, kWantAll);
 }
 int boxattn_bwd_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
                     const double *loc, const double *attn, const double *grad_out, int B,
                     int S, int H, int C, int L, int Lq, int P, double *grad_value,
                     double *grad_loc, double *grad_attn, void *stream)
 {
-    return launch_bwd<double, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr,
-                                     DIMS, grad_value, grad_loc, grad_attn, nullptr,
-                                     grad_value, ST_);
+    return launch_bwd<double, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, nullptr,
+        nullptr, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, grad_value, kWantAll);
 }
 int boxattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                      const float *loc, const float *attn, const uint16_t *grad_out, int B,
                      int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
                      float *grad_loc, float *grad_attn, float *grad_value_ws, void *stream)
 {
-    return launch_bwd<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr,
-                                     DIMS, grad_value, grad_loc, grad_attn, nullptr,
-                                     grad_value_ws, ST_);
+    return launch_bwd<bf16_t, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, nullptr,
+        nullptr, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, grad_value_ws, kWantAll);
 }
 int boxattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                     const float *loc, const float *attn, const uint16_t *grad_out, int B,
                     int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
                     float *grad_loc, float *grad_attn, float *grad_value_ws, void *stream)
 {
-    return launch_bwd<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr,
-                                     DIMS, as_f16(grad_value), grad_loc, grad_attn, nullptr,
-                                     grad_value_ws, ST_);
+    return launch_bwd<f16_t, false>({as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr, DIMS,
+        nullptr, nullptr, ST_}, {as_f16(grad_value), grad_loc, grad_attn, nullptr}, grad_value_ws, kWantAll);
 }
 
 int instattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -1487,7 +1394,7 @@ int instattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *l
                      void *stream)
 {
     return launch_fwd<float, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out,
-                                   mask_out, ST_);
+                                   mask_out, {}, ST_);
 }
 int instattn_fwd_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
                      const double *loc, const double *spatial_w, const double *level_w, int B,
@@ -1495,7 +1402,7 @@ int instattn_fwd_f64(const double *value, const int64_t *shapes, const int64_t *
                      void *stream)
 {
     return launch_fwd<double, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out,
-                                    mask_out, ST_);
+                                    mask_out, {}, ST_);
 }
 int instattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                       const float *loc, const float *spatial_w, const float *level_w, int B,
@@ -1503,7 +1410,7 @@ int instattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_
                       uint16_t *mask_out, void *stream)
 {
     return launch_fwd<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out,
-                                    mask_out, ST_);
+                                    mask_out, {}, ST_);
 }
 int instattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                      const float *loc, const float *spatial_w, const float *level_w, int B,
@@ -1511,7 +1418,7 @@ int instattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t
                      uint16_t *mask_out, void *stream)
 {
     return launch_fwd<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, DIMS, as_f16(out),
-                                    as_f16(mask_out), ST_);
+                                    as_f16(mask_out), {}, ST_);
 }
 
 int instattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -1520,9 +1427,8 @@ int instattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *l
                      int L, int Lq, int P, float *grad_value, float *grad_loc,
                      float *grad_spatial_w, float *grad_level_w, void *stream)
 {
-    return launch_bwd<float, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out,
-                                   grad_mask, DIMS, grad_value, grad_loc, grad_spatial_w,
-                                   grad_level_w, grad_value, ST_);
+    return launch_bwd<float, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS, nullptr,
+        nullptr, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, grad_value, kWantAll);
 }
 int instattn_bwd_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
                      const double *loc, const double *spatial_w, const double *level_w,
@@ -1530,9 +1436,8 @@ int instattn_bwd_f64(const double *value, const int64_t *shapes, const int64_t *
                      int C, int L, int Lq, int P, double *grad_value, double *grad_loc,
                      double *grad_spatial_w, double *grad_level_w, void *stream)
 {
-    return launch_bwd<double, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out,
-                                    grad_mask, DIMS, grad_value, grad_loc, grad_spatial_w,
-                                    grad_level_w, grad_value, ST_);
+    return launch_bwd<double, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS, nullptr,
+        nullptr, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, grad_value, kWantAll);
 }
 int instattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                       const float *loc, const float *spatial_w, const float *level_w,
@@ -1541,9 +1446,8 @@ int instattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_
                       float *grad_spatial_w, float *grad_level_w, float *grad_value_ws,
                       void *stream)
 {
-    return launch_bwd<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, grad_out,
-                                    grad_mask, DIMS, grad_value, grad_loc, grad_spatial_w,
-                                    grad_level_w, grad_value_ws, ST_);
+    return launch_bwd<bf16_t, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS, nullptr,
+        nullptr, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, grad_value_ws, kWantAll);
 }
 int instattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                      const float *loc, const float *spatial_w, const float *level_w,
@@ -1552,9 +1456,9 @@ int instattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t
                      float *grad_spatial_w, float *grad_level_w, float *grad_value_ws,
                      void *stream)
 {
-    return launch_bwd<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out),
-                                    as_f16(grad_mask), DIMS, as_f16(grad_value), grad_loc, grad_spatial_w,
-                                    grad_level_w, grad_value_ws, ST_);
+    return launch_bwd<f16_t, true>({as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out),
+        as_f16(grad_mask), DIMS, nullptr, nullptr, ST_}, {as_f16(grad_value), grad_loc, grad_spatial_w, grad_level_w},
+        grad_value_ws, kWantAll);
 }
 
 

@@ -290,7 +290,7 @@ inline bool same_dims(const Dims &a, const Dims &b)
 // fresh (BOXATTN_HINT_FRESH_STATE): the caller has zeroed the buffer since its last call -- a new buffer, possibly at an
 // address another one had: whatever is remembered of the address is dropped
 inline int state_check(void *state, size_t bytes, const StateLayout &sy, const Dims &d, const int64_t *sh, hipStream_t st,
-                       bool fresh = false)
+                       bool fresh)
 {
     if (!state) return 0;
     if (!aligned(state, 8) || bytes < sy.total) return -1;

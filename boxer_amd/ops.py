@@ -127,7 +127,8 @@ def _device_guard(device):
     return _NO_GUARD if device.index == torch.cuda.current_device() else torch.cuda.device(device)
 
 
-_SIZES = {}          # (query name, is_h16, dims, level tables) -> bytes: the size queries are pure functions
+_SIZES = {}          # (query name, is_h16, dims, level tables, options epoch) | ("state", dims, dtype, level tables)
+                     # -> bytes: the size queries are pure functions (_query_bytes)
 _CACHE_CAP = 1024    # entries per shape-keyed cache: a detector trained on variably padded batches sees thousands of
                      # shapes; everything cached per shape is cheap to rebuild
 
@@ -140,16 +141,23 @@ def _bounded(cache):
     return cache
 
 
-def _sized_buffer(query, value, shapes, lsi, dims, minimum=256):
-    """A scratch tensor of the size the library asks for (query: boxattn_plan_bytes /
-    boxattn_bwd_workspace_bytes; None for 0 bytes when minimum is 0) + the host level tables."""
-    sh, ls = _host_table(shapes), _host_table(lsi)
-    is_h16 = int(value.dtype in _H16)
-    key = (query.__name__, is_h16, dims, sh.tobytes(), ls.tobytes(), _lib.options_epoch())
+def _query_bytes(query, is_h16, dims, sh, ls, key=None):
+    """What a size query of the library answers (boxattn_plan_bytes, boxattn_bwd_workspace_bytes; boxattn_state_bytes,
+    which takes no storage flag: is_h16 None), asked once per shape and options epoch.  key: the cache key, from a
+    caller that has the tables' bytes at hand already (the state's size depends on no option: no epoch in its key)."""
+    if key is None:
+        key = (query.__name__, is_h16, dims, sh.tobytes(), ls.tobytes(), _lib.options_epoch())
     nbytes = _SIZES.get(key)
     if nbytes is None:
-        nbytes = _bounded(_SIZES)[key] = int(query(is_h16, *dims, sh.ctypes.data, ls.ctypes.data))
-    nbytes = max(nbytes, minimum)
+        flag = () if is_h16 is None else (is_h16,)
+        nbytes = _bounded(_SIZES)[key] = int(query(*flag, *dims, sh.ctypes.data, ls.ctypes.data))
+    return nbytes
+
+
+def _sized_buffer(query, value, shapes, lsi, dims):
+    """A scratch tensor of the size the library asks for (None for 0 bytes) + the host level tables."""
+    sh, ls = _host_table(shapes), _host_table(lsi)
+    nbytes = _query_bytes(query, int(value.dtype in _H16), dims, sh, ls)
     buf = torch.empty(nbytes, dtype=torch.uint8, device=value.device) if nbytes else None
     return buf, sh, ls
 
@@ -261,10 +269,7 @@ def _fresh_hint(state):
 
 def _state_for(lib, value, dims, sh, ls, stream):
     key = _shape_key(value, stream, dims, sh, ls)
-    skey = ("state",) + key[2:]
-    nbytes = _SIZES.get(skey)
-    if nbytes is None:
-        nbytes = _bounded(_SIZES)[skey] = int(lib.boxattn_state_bytes(*dims, sh.ctypes.data, ls.ctypes.data))
+    nbytes = _query_bytes(lib.boxattn_state_bytes, None, dims, sh, ls, ("state",) + key[2:])
     return key, _state_buffer(key, value.device, nbytes)
 
 
@@ -281,7 +286,7 @@ def _forward_train(name, value, shapes, lsi, loc, weights, dims, args):
     """*_fwd_train_*: forward + (when the binned backward applies) the backward's plan."""
     import ctypes
     lib = _lib.load()
-    buf, sh, ls = _sized_buffer(lib.boxattn_plan_bytes, value, shapes, lsi, dims, minimum=0)
+    buf, sh, ls = _sized_buffer(lib.boxattn_plan_bytes, value, shapes, lsi, dims)
     built = ctypes.c_int(0)
     fn = getattr(lib, "%s_%s" % (name, _SUFFIX[value.dtype]))
     with _device_guard(value.device):
@@ -313,24 +318,18 @@ def workspace_bytes(value, shapes, lsi, dims):
     lib = _lib.load()
     sh, ls = _host_table(shapes), _host_table(lsi)
     is_h16 = int(value.dtype in _H16)
-    return (int(lib.boxattn_plan_bytes(is_h16, *dims, sh.ctypes.data, ls.ctypes.data)),
-            int(lib.boxattn_bwd_workspace_bytes(is_h16, *dims, sh.ctypes.data, ls.ctypes.data)))
+    return (_query_bytes(lib.boxattn_plan_bytes, is_h16, tuple(dims), sh, ls),
+            _query_bytes(lib.boxattn_bwd_workspace_bytes, is_h16, tuple(dims), sh, ls))
 
 
 _WORKSPACE = {}      # (device index, stream handle) -> the backward's scratch tensor (grown as needed)
 
 
-def _workspace(query, value, shapes, lsi, dims, stream):
+def _workspace(lib, value, dims, sh, ls, stream):
     """The backward's scratch (bin records, partial tiles: contents only live inside one call).  One tensor per
     (device, stream), reused: calls on a stream never overlap, and a 0.3 GB torch.empty per backward was a tenth
     of the host time of a training step."""
-    sh, ls = _host_table(shapes), _host_table(lsi)
-    is_h16 = int(value.dtype in _H16)
-    key = (query.__name__, is_h16, dims, sh.tobytes(), ls.tobytes(), _lib.options_epoch())
-    nbytes = _SIZES.get(key)
-    if nbytes is None:
-        nbytes = _bounded(_SIZES)[key] = int(query(is_h16, *dims, sh.ctypes.data, ls.ctypes.data))
-    nbytes = max(nbytes, 256)
+    nbytes = max(_query_bytes(lib.boxattn_bwd_workspace_bytes, int(value.dtype in _H16), dims, sh, ls), 256)
     wkey = (value.device.index, stream)
     ws = _WORKSPACE.get(wkey)
     if ws is None or ws.numel() < nbytes:
@@ -341,7 +340,7 @@ def _workspace(query, value, shapes, lsi, dims, stream):
             if len(_WORKSPACE) >= _WORKSPACE_CAP:          # streams come and go: start over rather than grow
                 _WORKSPACE.clear()
             _WORKSPACE[wkey] = ws
-    return ws, sh, ls
+    return ws
 
 
 _CACHE_WORKSPACE = os.environ.get("BOXATTN_CACHE_WORKSPACE", "1") != "0"
@@ -420,27 +419,6 @@ def _parked(value, dims, loc, weights):
     return plan
 
 
-def _backward_with_workspace(name, value, shapes, lsi, loc, weights, dims, args, plan=None):
-    """Run the *_bwd_ws_* entry point (float32 / bfloat16 / float16): host level tables + scratch (+ plan)."""
-    lib = _lib.load()
-    ready = plan is not None and plan.buf is not None and plan.key == _plan_key(dims, loc, weights, value.dtype)
-    fn = getattr(lib, "%s_%s" % (name, _SUFFIX[value.dtype]))
-    with _device_guard(value.device):
-        stream = torch.cuda.current_stream(value.device).cuda_stream
-        ws, sh, ls = _workspace(lib.boxattn_bwd_workspace_bytes, value, shapes, lsi, dims, stream)
-        # the state buffer of this (stream, shape): the record ranges of the one-pass fill live in it from call to call
-        key, state = _state_for(lib, value, dims, sh, ls, stream)
-        hints = plan.hints if plan is not None else (_LOCALITY[key].last_hints if key in _LOCALITY else 0)
-        rc = fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
-                sh.ctypes.data, ls.ctypes.data, ws.data_ptr(), ws.numel(),
-                plan.buf.data_ptr() if ready else 0, plan.buf.numel() if ready else 0,
-                state.data_ptr(), state.numel(), hints | _fresh_hint(state), stream)
-    if rc != 0:
-        _STATE.pop(key, None)
-        raise RuntimeError("%s_%s failed with hipError %d" % (name, _SUFFIX[value.dtype], rc))
-    state._boxattn_fresh = False
-
-
 def _want_groups(want):
     """-> (grad_value wanted, location / weight gradients wanted) of a backward's ``want`` (BOXATTN_WANT_* bits)."""
     if want not in (_lib.WANT_VALUE, _lib.WANT_POINTS, _lib.WANT_ALL):
@@ -453,30 +431,44 @@ def _ptr(a):
     return a.data_ptr() if isinstance(a, torch.Tensor) else 0 if a is None else a
 
 
-def _backward_part(name, value, shapes, lsi, loc, weights, dims, args, plan, want):
-    """Run the *_bwd_part_* entry point (float32 / bfloat16 / float16) for ONE gradient group.  POINTS: one launch,
-    no scratch, no state.  VALUE: scratch (+ the plan of a training forward); the state buffer is not the partial
-    call's business (include/boxattn.h), so none is looked up."""
+def _backward(name, value, shapes, lsi, loc, weights, dims, args, plan, want):
+    """Run the *_bwd_part_* entry point (float32 / bfloat16 / float16) for the gradient groups ``want``; with all
+    groups wanted it is the *_bwd_ws_* call.  The host work follows the route (include/boxattn.h):
+    POINTS alone: one launch, no scratch, no state.  VALUE: scratch (+ the plan of a training forward).  Only the
+    full call looks the state buffer up -- the record ranges of the one-pass fill live in it from call to call -- and
+    answers for it: the fresh-state hint, and no reuse of a buffer whose call failed."""
     lib = _lib.load()
+    full = want == _lib.WANT_ALL
     fn = getattr(lib, "%s_%s" % (name, _SUFFIX[value.dtype]))
     with _device_guard(value.device):
         stream = torch.cuda.current_stream(value.device).cuda_stream
-        ws, ready = None, False
-        if want == _lib.WANT_VALUE:
-            ws, sh, ls = _workspace(lib.boxattn_bwd_workspace_bytes, value, shapes, lsi, dims, stream)
-            ready = plan is not None and plan.buf is not None and plan.key == _plan_key(dims, loc, weights, value.dtype)
-        else:
-            sh, ls = _host_table(shapes), _host_table(lsi)
+        sh, ls = _host_table(shapes), _host_table(lsi)
+        ws_ptr = ws_len = plan_ptr = plan_len = state_ptr = state_len = fresh = 0
+        if want & _lib.WANT_VALUE:
+            ws = _workspace(lib, value, dims, sh, ls, stream)
+            ws_ptr, ws_len = ws.data_ptr(), ws.numel()
+            if plan is not None and plan.buf is not None and plan.key == _plan_key(dims, loc, weights, value.dtype):
+                plan_ptr, plan_len = plan.buf.data_ptr(), plan.buf.numel()
+        if full:
+            key, state = _state_for(lib, value, dims, sh, ls, stream)
+            state_ptr, state_len, fresh = state.data_ptr(), state.numel(), _fresh_hint(state)
         if plan is not None:
             hints = plan.hints
-        else:
-            adapt = _LOCALITY.get(_shape_key(value, stream, dims, sh, ls)) if _LOCALITY else None
+        elif _LOCALITY:      # no plan: as the shape's last training forward ran
+            adapt = _LOCALITY.get(key if full else _shape_key(value, stream, dims, sh, ls))
             hints = adapt.last_hints if adapt is not None else 0
-        rc = fn(*[_ptr(a) for a in args], sh.ctypes.data, ls.ctypes.data,
-                ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
-                plan.buf.data_ptr() if ready else 0, plan.buf.numel() if ready else 0, 0, 0, hints, stream, want)
+        else:
+            hints = 0
+        # (the pointers inline, not through _ptr: sixteen calls are a microsecond of a host-bound decoder step)
+        rc = fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else 0 if a is None else a for a in args],
+                sh.ctypes.data, ls.ctypes.data, ws_ptr, ws_len, plan_ptr, plan_len,
+                state_ptr, state_len, hints | fresh, stream, want)
     if rc != 0:
+        if full:
+            _STATE.pop(key, None)                                # (its ranges may be half written)
         raise RuntimeError("%s_%s (want=%d) failed with hipError %d" % (name, _SUFFIX[value.dtype], want, rc))
+    if full:
+        state._boxattn_fresh = False
 
 
 def _call(name, value, *args, want=None):
@@ -550,21 +542,13 @@ def box_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, at
     args = [value, spatial_shapes, level_start_index, loc, attn, grad_output, *dims, grad_value,
             grad_loc, grad_attn]
     if value.dtype == torch.float64:
-        if want == 3:
-            _call("boxattn_bwd", value, *args)
-        else:
-            _call("boxattn_bwd_part", value, *args, want=want)
+        _call("boxattn_bwd_part", value, *args, want=want)
     else:
         # (a plan parked for this call leaves the table whether or not the call has a use for it -- only the
         # grad_value half has: the table must not keep its tensors alive)
         if plan is None:
             plan = _parked(value, dims, loc, (attn,))
-        if want == 3:
-            _backward_with_workspace("boxattn_bwd_ws", value, spatial_shapes, level_start_index, loc,
-                                     (attn,), dims, args, plan)
-        else:
-            _backward_part("boxattn_bwd_part", value, spatial_shapes, level_start_index, loc, (attn,), dims, args,
-                           plan, want)
+        _backward("boxattn_bwd_part", value, spatial_shapes, level_start_index, loc, (attn,), dims, args, plan, want)
     return [grad_value, grad_loc, grad_attn]
 
 
@@ -627,19 +611,11 @@ def instance_attn_backward(value, spatial_shapes, level_start_index, sampling_lo
     args = [value, spatial_shapes, level_start_index, loc, sw, lw, grad_output, grad_mask_output,
             *dims, grad_value, grad_loc, grad_sw, grad_lw]
     if value.dtype == torch.float64:
-        if want == 3:
-            _call("instattn_bwd", value, *args)
-        else:
-            _call("instattn_bwd_part", value, *args, want=want)
+        _call("instattn_bwd_part", value, *args, want=want)
     else:
         if plan is None:
             plan = _parked(value, dims, loc, (sw, lw))
-        if want == 3:
-            _backward_with_workspace("instattn_bwd_ws", value, spatial_shapes, level_start_index, loc,
-                                     (sw, lw), dims, args, plan)
-        else:
-            _backward_part("instattn_bwd_part", value, spatial_shapes, level_start_index, loc, (sw, lw), dims,
-                           args, plan, want)
+        _backward("instattn_bwd_part", value, spatial_shapes, level_start_index, loc, (sw, lw), dims, args, plan, want)
     return [grad_value, grad_loc, grad_sw, grad_lw]
 
 

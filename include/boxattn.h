@@ -237,7 +237,8 @@ int instattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int6
  *     POINTS : grad_loc + grad_attn (instance attention: grad_loc + grad_spatial_w + grad_level_w)
  * *_bwd_part_* take the arguments of *_bwd_ws_* (float64: of *_bwd_f64) and `want`, the groups to compute:
  *   - want is BOXATTN_WANT_VALUE (1), BOXATTN_WANT_POINTS (2) or both (3); anything else is hipErrorInvalidValue.
- *   - want == 3 IS the *_bwd_ws_* call (float64: the plain call) -- same checks, same launches, same results.
+ *   - want == 3 IS the *_bwd_ws_* call (float64: the plain call): both entry points are wrappers of one routine that
+ *     takes `want` -- same checks, same launches, same results.
  *   - The output pointers of a group that is not wanted are ignored and may be NULL; nothing is written through
  *     them.  A wanted group with a NULL member is hipErrorInvalidValue (nothing is launched).
  *   - The wanted outputs are fully defined by the call, as everywhere in this ABI.

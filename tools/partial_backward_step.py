@@ -4,7 +4,7 @@ for three ``requires_grad`` patterns -- every input ("all"), everything but ``va
 memory), ``value`` only ("value": frozen attention heads).
 
     python tools/partial_backward_step.py [--steps K] [--warmup W] [--repeats R] [--family test] [--tree DIR] [--out FILE]
-    python tools/partial_backward_step.py --check NEW.jsonl --against PARENT.jsonl [PARENT2.jsonl ...]
+    python tools/partial_backward_step.py --check NEW.jsonl --against PARENT.jsonl [PARENT2.jsonl ...] [--same-pattern]
 
 Protocol (measuring guide): 8 input sets cycled, bench.PREHEAT_STEPS untimed steps, W warm-up steps, then K steps
 between two HIP events on the op's stream; R repeats per configuration, all kept.  ``--tree``: time another built
@@ -15,7 +15,9 @@ parent, in the same session:
   * this build's "all" pattern must be within the parent's own spread of the parent's,
 
 where the spread is max - min over the parent's repeated "all" runs (all files given to --against).  --check
-prints the table and exits 1 if a row misses."""
+prints the table and exits 1 if a row misses.  ``--same-pattern`` (a change that must leave every step as it is: the
+parent has the partial backward too) holds every row against the parent's row of the SAME pattern instead: this
+build's fastest repeat must not be slower than the parent's slowest."""
 import argparse
 import json
 import os
@@ -93,10 +95,11 @@ def load(paths):
 def check(args):
     new, parent = load([args.check]), load(args.against)
     bad = 0
-    print("| shape | type | pattern | parent all, us (min .. max) | this build, us (min .. max) | bound | |")
+    print("| shape | type | pattern | parent %s, us (min .. max) | this build, us (min .. max) | bound | |"
+          % ("same pattern" if args.same_pattern else "all"))
     print("|---|---|---|---|---|---|---|")
     for (workload, dtype, pattern), runs in sorted(new.items()):
-        base = parent[(workload, dtype, "all")]
+        base = parent[(workload, dtype, pattern if args.same_pattern else "all")]
         spread = max(base) - min(base)
         # each side by the fastest of its repeats (the least disturbed one); the parent's spread is the noise margin
         # -- i.e. the fastest repeat of this build against the SLOWEST all-gradients repeat of the parent
@@ -121,6 +124,7 @@ def main():
     ap.add_argument("--out", help="append the JSON lines to this file")
     ap.add_argument("--check", help="JSON lines of this build: evaluate the pass condition ...")
     ap.add_argument("--against", nargs="+", help="... against these JSON lines of the parent commit")
+    ap.add_argument("--same-pattern", action="store_true", help="--check: against the parent's row of the same pattern")
     args = ap.parse_args()
     sys.exit(check(args) if args.check else measure(args))
 
