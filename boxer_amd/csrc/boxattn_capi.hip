@@ -44,14 +44,19 @@ enum { kOptBinChunk = 10,     // records per work item of the accumulate kernels
        kOptRideShift = 20,    // where the riders sit: (s_count + 1) | (s_fill + 1) << 4, a rider group every 2^s groups
                               // of 8 workgroups (s = 0: all in front); | v << 8: 64 v bin workgroups (riders) in all;
                               // 0: defaults
-       kNumOpts = 21 };
+       kOptWideBox = 22,      // box attention with few (query, head) pairs and many points a pair (the mask model at
+                              // inference): 0 default (the wave-per-pair kernel where it measured faster, wide_box_ok),
+                              // 1 off (row-gather kernel: the parity cross-check of the two families), 2 on wherever
+                              // the instance flavour takes the family
+       kNumOpts = 23 };
 // (round 6 removed the keys whose non-default values had lost their A/B: 12 / 13 window margins, 17 staged forward off,
 // 21 staged float32 kernels off -- 11 = 1 switches every window-staged kernel off)
 std::atomic<int> g_opt[kNumOpts];      // 0 = default
 inline int opt(int k) { return g_opt[k].load(std::memory_order_relaxed); }
 inline bool opt_live(int k)
 {
-    return k == kOptBinChunk || k == kOptDense || k == kOptRiders || k == kOptAccF32 || k == kOptRideShift;
+    return k == kOptBinChunk || k == kOptDense || k == kOptRiders || k == kOptAccF32 || k == kOptRideShift ||
+           k == kOptWideBox;
 }
 #ifndef BOXATTN_RIDE_SHIFT_COUNT
 #define BOXATTN_RIDE_SHIFT_COUNT 0     // count riders: all in front of the forward kernel's grid (measured: interleaving
@@ -145,6 +150,10 @@ bool fast_ok(const Dims &d, const void *value, const void *loc, const void *a, c
     return aligned(value, va) && aligned(loc, 8) && aligned(a, va) && aligned(b, va) &&
            aligned(c, va);
 }
+// What the forward's choice of kernel sees of its tensors' addresses.  fast: fast_ok's alignments (value and the
+// outputs to 4 elements, loc to 8 bytes); rows16: value and the outputs to 16 bytes (8 channels a lane); staged:
+// what the window-staged kernels ask (value, out to 16 bytes, loc to 8)
+struct FwdAlign { bool fast, rows16, staged; };
 
 // Lanes per (query, head) pair and channels per lane of the gather kernels (boxattn_gather2.h):
 // 8 channels per lane when C allows and the rows can be fetched 16 bytes at a time.
@@ -167,11 +176,15 @@ bool fast_ok(const Dims &d, const void *value, const void *loc, const void *a, c
 #define BOXATTN_TUNE_U4_BF16 4
 #endif
 struct GatherCfg { int G, VEC; };
-template <typename ST> inline GatherCfg gather_cfg(const Dims &d, bool rows_16b_aligned)
+inline GatherCfg gather_cfg(int elem_bytes, const Dims &d, bool rows_16b_aligned)
 {
-    constexpr int want = sizeof(ST) == 2 ? BOXATTN_TUNE_VEC_BF16 : BOXATTN_TUNE_VEC_F32;
+    const int want = elem_bytes == 2 ? BOXATTN_TUNE_VEC_BF16 : BOXATTN_TUNE_VEC_F32;
     if (want == 8 && rows_16b_aligned && (d.C == 32 || d.C == 64)) return {d.C / 8, 8};
     return {fast_group(d), 4};
+}
+template <typename ST> inline GatherCfg gather_cfg(const Dims &d, bool rows_16b_aligned)
+{
+    return gather_cfg((int)sizeof(ST), d, rows_16b_aligned);
 }
 // points of a pair in flight per lane (loads issued before the first use)
 template <typename ST, int G, int VEC> struct GatherUnroll {
@@ -312,6 +325,59 @@ struct FwdExtras {
     bool allow_dense = true;
     unsigned long long *stats = nullptr;
 };
+// The forward's kernel families (BOXATTN_FWD_*), and the ONE function that chooses among them: launch_fwd launches
+// what it answers, boxattn_fwd_route reports it.
+enum { kFwdGeneric = BOXATTN_FWD_GENERIC, kFwdFast = BOXATTN_FWD_FAST, kFwdGather = BOXATTN_FWD_GATHER,
+       kFwdWide = BOXATTN_FWD_WIDE, kFwdStaged = BOXATTN_FWD_STAGED };
+struct FwdRoute {
+    GatherCfg cfg{0, 4};
+    GatherIdx ix{};
+    int blocks = 0;              // first generation / row gather: workgroups of 4 waves of 64 / G pairs
+    int wblocks = 0;             // wave per pair: workgroups, of 4 / ws pairs
+    unsigned ws = 1;             //                waves that share a pair
+};
+// Box attention on the wave-per-pair kernel (the instance flavour takes it from 64 / G points up): by default where
+// it measured faster than the row-gather kernel's walk of one lane group over the pair's points at every query count
+// and batch of the table (profiles/inference_forward_step.log) -- 16-bit storage from 64 points a level,
+// float32 from 196.  Below that it wins at few pairs and ties or loses at 14 400 of them.
+inline bool wide_box_ok(int elem_bytes, const Dims &d)
+{
+    const int o = opt(kOptWideBox);
+    if (o == 1 || o == 2) return o == 2;
+    return d.P >= (elem_bytes == 2 ? 64 : 196);
+}
+// -> family, or < 0: no kernel for these dimensions under the current switches (variant 2 and not eligible).
+// r: the launch geometry of the gather families; dp: the plan of the window-staged one
+inline int fwd_route(int elem_bytes, bool inst, const Dims &d, const FwdAlign &al, const int64_t *shapes_host,
+                     const int64_t *lsi_host, bool allow_dense, FwdRoute &r, DensePlan &dp)
+{
+    r = FwdRoute{};
+    if (elem_bytes == 8) return kFwdGeneric;                    // float64: the generic kernels, whatever the variant
+    if (g_variant == 1 || fast_group(d) == 0 || !al.fast) return g_variant == 2 ? -1 : kFwdGeneric;
+    // encoder case: window-staged forward
+    if (!inst && allow_dense && shapes_host && lsi_host && al.staged &&
+        make_dense_plan(d, shapes_host, lsi_host, dp, elem_bytes))
+        return kFwdStaged;
+    const size_t n_qh = d.n_qh(), vbytes = d.n_value() * (size_t)elem_bytes;
+    const bool gen2 = g_variant != 2 && vbytes < kOobOffset && gather_idx(d, r.ix, (size_t)elem_bytes);   // buffer-load kernels
+    r.cfg = gen2 ? gather_cfg(elem_bytes, d, al.rows16) : GatherCfg{fast_group(d), 4};
+    const int pairs = kWave / r.cfg.G;
+    r.blocks = gen2 ? gather_blocks(d, r.ix, pairs) : ceil_div_sz(n_qh, (size_t)pairs * 4);
+    if (!gen2) return kFwdFast;
+    // few (query, head) pairs and many points (the mask decoder): one wave per pair
+    if (r.blocks < 1024 && d.P >= pairs) {
+        // 8 or more point steps a pair: its points over the four waves of a workgroup
+        const int steps = ceil_div_sz((size_t)d.P, (size_t)pairs);
+        if (inst || wide_box_ok(elem_bytes, d)) {
+            r.ws = steps >= 8 ? 4 : steps >= 4 ? 2 : 1;
+            const size_t ppw = 4 / r.ws;
+            r.wblocks = r.ix.head_xcd ? 8 * ceil_div_sz((size_t)d.B * d.Lq, ppw) : ceil_div_sz(n_qh, ppw);
+            return kFwdWide;
+        }
+    }
+    return kFwdGather;
+}
+
 template <typename ST, bool INST>
 int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                const typename Storage<ST>::compute *loc,
@@ -334,56 +400,57 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
         return (int)e;
     }
     if (!value) return (int)hipErrorInvalidValue;
+    const size_t va = 4 * sizeof(ST);
+    FwdAlign al;
+    al.fast = aligned(value, va) && aligned(loc, 8) && aligned(out, va) && (!INST || aligned(mask, va));
+    al.rows16 = aligned(value, 16) && aligned(out, 16) && (!INST || aligned(mask, 16));
+    al.staged = aligned(value, 16) && aligned(out, 16) && aligned(loc, 8);
+    FwdRoute r;
+    DensePlan dp;
+    const int family = fwd_route((int)sizeof(ST), INST, d, al, x.shapes_host, x.lsi_host, x.allow_dense, r, dp);
+    if (family < 0) return (int)hipErrorInvalidValue;
     if constexpr (!std::is_same<ST, double>::value) {
-        if (fast_ok<ST>(d, value, loc, out, INST ? (const void *)mask : (const void *)out,
-                        out)) {
-            if constexpr (!INST) {     // encoder case: window-staged forward (16-bit: matrix cores; float32: VALU)
-                DensePlan dp;
-                if (x.allow_dense && x.shapes_host && x.lsi_host && aligned(value, 16) && aligned(out, 16) &&
-                    aligned(loc, 8) && make_dense_plan(d, x.shapes_host, x.lsi_host, dp, (int)sizeof(ST))) {
-                    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
-                    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST));
-                    const BinRide ride = count_ride ? *count_ride : BinRide{};
-                    if constexpr (IsHalf16<ST>::value) launch_fwd_dense<ST>(value, loc, w_sp, out, dp, vbytes, ride, x.stats, st);
-                    else launch_fwd_dense_f32(value, loc, w_sp, out, dp, vbytes, ride, x.stats, st);
-                    if (count_ride && ride_taken) *ride_taken = true;
-                    return finish();
-                }
-            }
-            const size_t vbytes = d.n_value() * sizeof(ST);
-            GatherIdx ix{};
-            const bool gen2 = g_variant != 2 && vbytes < kOobOffset && gather_idx(d, ix, sizeof(ST));   // buffer-load kernels
-            const GatherCfg cfg =
-                gen2 ? gather_cfg<ST>(d, aligned(value, 16) && aligned(out, 16) &&
-                                         (!INST || aligned(mask, 16)))
-                     : GatherCfg{fast_group(d), 4};
-            const int G = cfg.G;
-            const int pairs = kWave / G;
-            const int blocks = gen2 ? gather_blocks(d, ix, pairs) : ceil_div_sz(n_qh, (size_t)pairs * 4);
+        if (family != kFwdGeneric) {
             ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
-            // instance attention with few (query, head) pairs and many points (the mask decoder): one wave per
-            // pair, the points spread over the lane groups (any storage type, no atomics)
-            if constexpr (INST) {
-                if (gen2 && blocks < 1024 && d.P >= kWave / G) {
-                    // 8 or more point steps a pair: its points over the four waves of a workgroup
-                    const int steps = ceil_div_sz((size_t)d.P, (size_t)(kWave / G));
-                    const unsigned ws = steps >= 8 ? 4 : steps >= 4 ? 2 : 1;
-                    const size_t ppw = 4 / ws;
-                    const int wblocks = ix.head_xcd ? 8 * ceil_div_sz((size_t)d.B * d.Lq, ppw)
-                                                    : ceil_div_sz(n_qh, ppw);
-                    unsigned total = 0;
-                    const BinRide ride = place_riders(count_ride, (unsigned)wblocks, &total);
-#define BOXATTN_FWD_WIDE(GG, VV)                                                              \
-    hipLaunchKernelGGL((fwd_inst_wide_kernel<ST, GG, VV>), dim3(total), dim3(256), 0, st,     \
-                       value, shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.L, d.Lq, d.P, out,    \
-                       mask, with_grid(ix, wblocks, 1, 1), (unsigned)vbytes, ride, ws);
-                    BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_FWD_WIDE);
-#undef BOXATTN_FWD_WIDE
+            const size_t vbytes = d.n_value() * sizeof(ST);
+            const GatherCfg cfg = r.cfg;
+            const GatherIdx &ix = r.ix;
+            if constexpr (!INST) {     // encoder case: window-staged forward (16-bit: matrix cores; float32: VALU)
+                if (family == kFwdStaged) {
+                    const BinRide ride = count_ride ? *count_ride : BinRide{};
+                    if constexpr (IsHalf16<ST>::value)
+                        launch_fwd_dense<ST>(value, loc, w_sp, out, dp, (unsigned)vbytes, ride, x.stats, st);
+                    else launch_fwd_dense_f32(value, loc, w_sp, out, dp, (unsigned)vbytes, ride, x.stats, st);
                     if (count_ride && ride_taken) *ride_taken = true;
                     return finish();
                 }
             }
-            if (gen2) {
+            if (family == kFwdWide) {
+                // few (query, head) pairs and many points (the mask decoder): one wave per pair, the points spread
+                // over the lane groups (any storage type, no atomics); `ws` waves of a workgroup share a pair
+                unsigned total = 0;
+                const BinRide ride = place_riders(count_ride, (unsigned)r.wblocks, &total);
+                const unsigned ws = r.ws;
+                if constexpr (INST) {
+#define BOXATTN_LAUNCH_WIDE(GG, VV)                                                           \
+    hipLaunchKernelGGL((fwd_wide_kernel<ST, GG, VV, true>), dim3(total), dim3(256), 0, st,    \
+                       value, shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.L, d.Lq, d.P, out,    \
+                       mask, with_grid(ix, r.wblocks, 1, 1), (unsigned)vbytes, ride, ws);
+                    BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_WIDE);
+#undef BOXATTN_LAUNCH_WIDE
+                } else {
+#define BOXATTN_LAUNCH_WIDE(GG, VV)                                                           \
+    hipLaunchKernelGGL((fwd_wide_kernel<ST, GG, VV, false>), dim3(total), dim3(256), 0, st,   \
+                       value, shapes, lsi, loc, w_sp, NoArg{}, d.S, d.H, d.L, d.Lq, d.P, out, \
+                       NoArg{}, with_grid(ix, r.wblocks, 1, 1), (unsigned)vbytes, ride, ws);
+                    BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_WIDE);
+#undef BOXATTN_LAUNCH_WIDE
+                }
+                if (count_ride && ride_taken) *ride_taken = true;
+                return finish();
+            }
+            const int blocks = r.blocks;
+            if (family == kFwdGather) {
                 unsigned total = 0;
                 const BinRide ride = place_riders(count_ride, (unsigned)blocks, &total);
 #define BOXATTN_FWD2(GG, VV)                                                                  \
@@ -395,14 +462,13 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
 #undef BOXATTN_FWD2
                 if (count_ride && ride_taken) *ride_taken = true;
             } else {
-                for_group(G, [&](auto g) {
+                for_group(cfg.G, [&](auto g) {
                     hipLaunchKernelGGL((fwd_fast_kernel<ST, 4, decltype(g)::value, INST>), dim3(blocks), dim3(256), 0, st,
                                        value, shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.L, d.Lq, d.P, out, mask, n_qh);
                 });
             }
             return finish();
         }
-        if (g_variant == 2) return (int)hipErrorInvalidValue;
     }
     const size_t n = n_qh * d.C;
     const int blocks = (int)std::min<size_t>((n + 255) / 256, (size_t)1 << 20);
@@ -1300,6 +1366,19 @@ int boxattn_set_option(int key, int value)
     return g_opt[key].exchange(value);
 }
 
+
+int boxattn_fwd_route(int elem_bytes, int instance, int aligned, int B, int S, int H, int C, int L, int Lq, int P,
+                      const int64_t *shapes_host, const int64_t *lsi_host)
+{
+    const Dims d = DIMS;
+    if (!d.valid() || (elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8)) return -1;
+    // aligned: 0 nothing beyond the elements' own alignment, 8 every tensor to 8 bytes, else to 16 bytes
+    const int bytes = aligned == 0 ? elem_bytes : aligned == 8 ? 8 : 16;
+    const FwdAlign al{bytes >= 4 * elem_bytes && bytes >= 8, bytes >= 16, bytes >= 16};
+    FwdRoute r;
+    DensePlan dp;
+    return fwd_route(elem_bytes, instance != 0, d, al, shapes_host, lsi_host, true, r, dp);
+}
 
 int boxattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                     const float *loc, const float *attn, int B, int S, int H, int C, int L,

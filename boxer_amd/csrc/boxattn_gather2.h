@@ -546,13 +546,22 @@ template <int G> __device__ __forceinline__ unsigned group_bcast(unsigned v, int
     else return (unsigned)__shfl((int)v, (lane & ~(G - 1)) + t, kWave);
 }
 
-template <typename ST, int G, int VEC>
-__global__ __launch_bounds__(256) void fwd_inst_wide_kernel(
+// INST = false: the same walk for BOX attention with few pairs and many points (the mask model at inference, where
+// the mask decoder's layers run plain box attention on the 14 x 14 grid): no level weights, no mask rows, and neither
+// a w_lv nor a mask argument -- the flavour's kernel takes an empty NoArg in their places.  (One __global__ body, its
+// two parameter types chosen by the flag: behind a shared __device__ body the instance flavour came out with other
+// instructions than it had before there was a box flavour.)
+struct NoArg {};
+template <bool ON, typename T> struct ArgIf { typedef T type; };
+template <typename T> struct ArgIf<false, T> { typedef NoArg type; };
+
+template <typename ST, int G, int VEC, bool INST>
+__global__ __launch_bounds__(256) void fwd_wide_kernel(
     const ST *__restrict__ value, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ lsi, const float *__restrict__ loc,
-    const float *__restrict__ w_sp, const float *__restrict__ w_lv, int S, int H, int L, int Lq,
-    int P, ST *__restrict__ out, ST *__restrict__ mask, GatherIdx ix, unsigned value_bytes,
-    BinRide ride, unsigned ws)
+    const float *__restrict__ w_sp, typename ArgIf<INST, const float *__restrict__>::type w_lv, int S, int H, int L,
+    int Lq, int P, ST *__restrict__ out, typename ArgIf<INST, ST *__restrict__>::type mask, GatherIdx ix,
+    unsigned value_bytes, BinRide ride, unsigned ws)
 {
     constexpr int C = VEC * G, NG = kWave / G;
     typedef Row<ST, VEC> RowT;
@@ -590,7 +599,8 @@ __global__ __launch_bounds__(256) void fwd_inst_wide_kernel(
         __builtin_amdgcn_make_buffer_rsrc(const_cast<ST *>(value), 0, value_bytes, 0x00020000);
     const unsigned lane_off = (unsigned)(slot * RowT::kLaneBytes);
     const float2 *loc2 = reinterpret_cast<const float2 *>(loc);
-    ST *mk = mask + (size_t)bq * P * HC + (size_t)h * C + slot * LCH;
+    ST *mk = nullptr;
+    if constexpr (INST) mk = mask + (size_t)bq * P * HC + (size_t)h * C + slot * LCH;
 
     f32x2 acc[VEC / 2];
 #pragma unroll
@@ -603,7 +613,8 @@ __global__ __launch_bounds__(256) void fwd_inst_wide_kernel(
     auto request = [&](int p0) -> Ahead {
         const int p = min(p0 + grp, P - 1), lc = min(slot, L - 1);
         const size_t i = pt0 + (size_t)lc * P + p;
-        return Ahead{loc2[i], w_sp[i], w_lv[i]};
+        if constexpr (INST) return Ahead{loc2[i], w_sp[i], w_lv[i]};
+        else return Ahead{loc2[i], w_sp[i], 0.f};
     };
     const int pstep = (int)ws * NG;
     Ahead nxt = request((int)sub * NG);
@@ -615,9 +626,11 @@ __global__ __launch_bounds__(256) void fwd_inst_wide_kernel(
         const bool have_p = p < P;
         const Ahead cur = nxt;
         if (p0 + pstep < P) nxt = request(p0 + pstep);
-        f32x2 macc[VEC / 2];
+        f32x2 macc[INST ? VEC / 2 : 1];
+        if constexpr (INST) {
 #pragma unroll
-        for (int i = 0; i < VEC / 2; ++i) macc[i] = f32x2{0.f, 0.f};
+            for (int i = 0; i < VEC / 2; ++i) macc[i] = f32x2{0.f, 0.f};
+        }
         for (int l0 = 0; l0 < L; l0 += G) {
             // ---- step A: lane t of the group -> level l0 + t of point p
             const int l = l0 + slot;
@@ -629,7 +642,7 @@ __global__ __launch_bounds__(256) void fwd_inst_wide_kernel(
                 const size_t i = pt0 + (size_t)lc * P + (have_p ? p : P - 1);
                 xy = loc2[i];
                 as = w_sp[i];
-                al = w_lv[i];
+                if constexpr (INST) al = w_lv[i];
             }
             as = have ? as : 0.f;
             al = have ? al : 0.f;
@@ -654,7 +667,8 @@ __global__ __launch_bounds__(256) void fwd_inst_wide_kernel(
                     wt[u] = u32x4_t{group_bcast<G>(my_wt.x, t, lane), group_bcast<G>(my_wt.y, t, lane),
                                     group_bcast<G>(my_wt.z, t, lane), group_bcast<G>(my_wt.w, t, lane)};
                     aas[u] = group_bcast<G>(__float_as_uint(as), t, lane);
-                    aal[u] = group_bcast<G>(__float_as_uint(al), t, lane);
+                    if constexpr (INST) aal[u] = group_bcast<G>(__float_as_uint(al), t, lane);
+                    else aal[u] = 0u;
                     row_load<ST, VEC, PSB>(rs, off[u].x + lane_off, v[u][0]);
                     row_load<ST, VEC, PSB>(rs, off[u].y + lane_off, v[u][1]);
                     row_load<ST, VEC, PSB>(rs, off[u].z + lane_off, v[u][2]);
@@ -675,12 +689,14 @@ __global__ __launch_bounds__(256) void fwd_inst_wide_kernel(
 #pragma unroll
                     for (int k = 0; k < VEC / 2; ++k) {
                         acc[k] = __builtin_elementwise_fma(val[k], as2, acc[k]);
-                        macc[k] = __builtin_elementwise_fma(val[k], al2, macc[k]);
+                        if constexpr (INST) macc[k] = __builtin_elementwise_fma(val[k], al2, macc[k]);
                     }
                 }
             }
         }
-        if (have_p) row_store<ST, VEC, PSB>(mk + (size_t)p * HC, macc);
+        if constexpr (INST) {
+            if (have_p) row_store<ST, VEC, PSB>(mk + (size_t)p * HC, macc);
+        }
     }
     // out = sum over the lane groups (lanes with the same channel chunk: stride G)
 #pragma unroll

@@ -503,6 +503,21 @@ def box_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, att
     return out
 
 
+def forward_route(value, loc, shapes_host=None, lsi_host=None, instance=False):
+    """Which forward kernel family (``_lib.FWD_*``) the library launches for these tensors under the current switches:
+    ``boxattn_fwd_route`` with the dimensions, element size and alignment of ``value`` (B, S, H, C) and ``loc``
+    (B, Lq, H, L, P, 2).  ``shapes_host`` / ``lsi_host``: the level tables as int64 numpy arrays (or tensors, copied
+    to the host), as ``box_attn_forward`` hands them over; without them the answer is never window-staged.  The outputs
+    are taken as freshly allocated (aligned)."""
+    B, S, H, C = value.shape
+    Lq, L, P = loc.size(1), loc.size(3), loc.size(4)
+    host = lambda t: _host_table(t) if isinstance(t, torch.Tensor) else t
+    ptrs = (value.data_ptr(), loc.data_ptr())
+    aligned = 16 if all(p % 16 == 0 for p in ptrs) else 8 if all(p % 8 == 0 for p in ptrs) else 0
+    return _lib.fwd_route(value.element_size(), instance, aligned, (B, S, H, C, L, Lq, P), host(shapes_host),
+                          host(lsi_host))
+
+
 def box_attn_forward_train(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                            im2col_step):
     """Forward for training: -> (output, plan).  ``plan`` (or None) goes to

@@ -517,10 +517,30 @@ int instattn_weights_bwd_f16(const uint16_t *logits, const float *grad_spatial_w
  *      rider workgroups every 2^s groups of 8 workgroups (s = 0: all in front) -- | v << 8: 64 v bin workgroups
  *      (= riders) in all; 0 = defaults (all in front; 256, or one per ~600 (query, slice) pairs -- 256 ... 768 -- for the
  *      one-pass fill at encoder sizes).  Set before boxattn_plan_bytes.
+ *  22  box attention with few (query, head) pairs and many points a pair (the mask model at inference: 300 queries,
+ *      14 x 14 points on 4 levels) on the wave-per-pair forward kernel: 0 library default (the
+ *      kernel where it measured faster than the row-gather kernel), 1 off (row-gather kernel -- the parity
+ *      cross-check of the two kernel families), 2 on wherever instance attention takes that family.  Instance
+ *      attention does not read it.
  *  (ABI 8 removed 12 / 13 -- window margins --, 17 and 21 -- staged forward / staged float32 kernels off: 11 = 1
  *  switches every window-staged kernel off.)
  */
 int boxattn_set_option(int key, int value);
+
+/* The kernel families of the forward. */
+#define BOXATTN_FWD_GENERIC 0   /* any dimensions, any alignment, float64 */
+#define BOXATTN_FWD_FAST    1   /* first-generation fast kernels (boxattn_set_variant(2), or >= 2 GiB of value) */
+#define BOXATTN_FWD_GATHER  2   /* row gather: a lane group walks the points of its (query, head) pair */
+#define BOXATTN_FWD_WIDE    3   /* wave per pair: the lane groups of one to four waves share a pair's points */
+#define BOXATTN_FWD_STAGED  4   /* window-staged (the encoder case; needs the host tables) */
+/* Which forward kernel family the library would launch for these dimensions under the current
+ * switches (boxattn_set_variant / boxattn_set_option); the very function the forward entry points call.
+ * elem_bytes 2 / 4 / 8; instance 0 / 1; aligned != 0: every tensor 16-byte aligned (8: to 8 bytes only, 0: to
+ * nothing beyond its elements); shapes_host / lsi_host may be NULL (then never window-staged).  Pure host code:
+ * no device call.  < 0: invalid dimensions, or dimensions boxattn_set_variant(2) has no kernel for.
+ * (BOXATTN_HINT_NOT_LOCAL of a training forward is a per-call matter: the query answers for a call without it.) */
+int boxattn_fwd_route(int elem_bytes, int instance, int aligned, int B, int S, int H, int C, int L, int Lq, int P,
+                      const int64_t *shapes_host, const int64_t *lsi_host);
 /* Number of boxattn_set_variant / boxattn_set_option calls so far: lets a binding cache the size queries
  * (boxattn_plan_bytes, boxattn_bwd_workspace_bytes: pure functions of their arguments and the switches). */
 int boxattn_options_epoch(void);

@@ -10,7 +10,7 @@ n_steps = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 rows = con.execute("select name, start, end from kernels order by start").fetchall()
 rows = [(n, s, e) for n, s, e in rows if "boxattn" in n]
 # a step starts with the forward kernel
-starts = [i for i, r in enumerate(rows) if "fwd2_kernel" in r[0] or "fwd_inst_wide" in r[0]]
+starts = [i for i, r in enumerate(rows) if "fwd2_kernel" in r[0] or "fwd_wide" in r[0]]
 for si in starts[-n_steps:]:
     t0 = rows[si][1]
     nxt = [i for i in starts if i > si]
