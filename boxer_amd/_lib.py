@@ -89,7 +89,7 @@ _GRID_SIGNATURES = {
     "boxattn_grid_bwd_f32": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp, _vp],
 }
 EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "boxattn_set_option",
-           "boxattn_options_epoch", "boxattn_fwd_route",
+           "boxattn_options_epoch", "boxattn_fwd_route", "boxattn_bwd_accumulate_kind",
            "boxattn_set_debug_buffer",
            "boxattn_fwd_hl_f32", "boxattn_fwd_hl_bf16", "boxattn_fwd_hl_f16", *sorted(_POINTWISE_SIGNATURES),
            "boxattn_profile_begin", "boxattn_profile_end", "boxattn_bwd_workspace_bytes",
@@ -230,6 +230,8 @@ def load():
     lib.boxattn_options_epoch.restype = _i
     lib.boxattn_fwd_route.argtypes = [_i] * 10 + [_vp, _vp]
     lib.boxattn_fwd_route.restype = _i
+    lib.boxattn_bwd_accumulate_kind.argtypes = [_i] * 9
+    lib.boxattn_bwd_accumulate_kind.restype = _i
     for name, args in list(_GRID_SIGNATURES.items()) + list(_POINTWISE_SIGNATURES.items()):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = _i
@@ -260,7 +262,8 @@ def set_variant(v):
     return load().boxattn_set_variant(int(v))
 
 
-OPTIONS = {"bin_chunk": 10, "dense": 11, "riders": 15, "acc_f32": 19, "ride_shift": 20, "wide_box": 22}
+OPTIONS = {"bin_chunk": 10, "dense": 11, "riders": 15, "acc_f32": 19, "ride_shift": 20, "wide_box": 22,
+           "inst_acc16": 23}
 # boxattn_fwd_route: the forward's kernel families (BOXATTN_FWD_*)
 FWD_GENERIC, FWD_FAST, FWD_GATHER, FWD_WIDE, FWD_STAGED = range(5)
 FWD_FAMILIES = ("generic", "fast", "gather", "wide", "staged")
@@ -272,6 +275,17 @@ def fwd_route(elem_bytes, instance, aligned, dims, shapes_host=None, lsi_host=No
     ptr = lambda a: None if a is None else a.ctypes.data
     return load().boxattn_fwd_route(int(elem_bytes), int(instance), int(aligned), *[int(v) for v in dims],
                                     ptr(shapes_host), ptr(lsi_host))
+
+
+# boxattn_bwd_accumulate_kind: the grad_value accumulate kernels of the binned backward (BOXATTN_ACC_*)
+ACC_VALU, ACC_TR, ACC_F32, ACC_SPLIT = range(4)
+ACC_KINDS = ("valu", "tr", "f32", "split")
+
+
+def bwd_accumulate_kind(elem_bytes, instance, dims):
+    """boxattn_bwd_accumulate_kind(): the accumulate kernel (ACC_*) of a binned backward at ``dims`` = (B, S, H, C, L,
+    Lq, P) under the current switches; negative for invalid arguments or float64.  Pure host code (no GPU needed)."""
+    return load().boxattn_bwd_accumulate_kind(int(elem_bytes), int(instance), *[int(v) for v in dims])
 
 
 def set_option(name, value):

@@ -50,12 +50,27 @@ __device__ __forceinline__ uint2 lds_read_tr16(const unsigned short *base, unsig
     return __builtin_bit_cast(uint2, v);
 }
 
-template <typename ST, int C>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BOXATTN_TUNE_TR_WPE : 1))) void binned_accumulate_tr_kernel(
+// INST: instance attention.  A record {point id, x, y, a_s} contributes w_k (a_s g[query] + a_l g_mask[query, point]) to
+// each corner k (instance_attn_kernel.cuh:139).  Both upstream rows stay exact 16-bit operands: the round is TWO products,
+// the grad_out rows against A^T entries w_k a_s and the grad_mask rows against w_k a_l (a second G plane set and a second
+// A^T tile; one set of corner slots serves both), each entry a hi + lo term as for box attention.  a_l is gathered from
+// `level_w` by the record's point id when the record's rows are requested; grad_mask rows come through a buffer resource
+// of their own.  f16: at 14 x 14 points most w_k a_s lie below 2^-14, where an f16 pair only holds 2^-25 absolutely --
+// both weight sets are scaled by 2^8 before the split (they are <= 1) and the float32 sums scaled back before the store.
+template <typename T> struct InstRowsT {
+    const T *grad_mask;          // (B, Lq, P, H, C)
+    unsigned grad_mask_bytes;
+    const float *w_lv;           // (B, Lq, H, L, P)
+    int P;
+};
+// Two row sets and two A^T tiles in LDS (17.3 KB a wave at C <= 32, 25.3 KB at C = 64) leave room for two waves per SIMD
+// (one at C = 64), which is also what the flavour's registers are budgeted for (216 at C = 32).
+template <typename ST, int C, bool INST = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (INST ? 2 : BOXATTN_TUNE_TR_WPE) : 1))) void binned_accumulate_tr_kernel(
     const ST *__restrict__ grad_out, unsigned grad_out_bytes, BinPlan plan, int S, int H, int Lq,
     const int4 *__restrict__ items, const int *__restrict__ n_items,
     const int *__restrict__ records, ST *__restrict__ grad_value, float *__restrict__ partials, ChunkCombine cc,
-    ZeroRole zr)
+    ZeroRole zr, InstRowsT<ST> inst)
 {
     static_assert(IsHalf16<ST>::value, "16-bit storage");
     typedef Half16<ST> H16;
@@ -73,9 +88,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
     constexpr int ASB = AS * 2;
     constexpr int kDump = PB * ASB;                // byte offset of the row that takes the weights of corners outside the block
     constexpr int kBig = 1 << 20;
+    constexpr int NSRC = INST ? 2 : 1;             // upstream row sets: grad_out (+ grad_mask)
+    constexpr int kAtL = (PB + 1) * ASB;           // INST: byte offset of the A^T tile of the w_k a_l entries
+    constexpr int kGsM = NCB * GPL;                // INST: byte offset of the grad_mask planes
+    constexpr float kWScale = INST && std::is_same<ST, f16_t>::value ? 256.f : 1.f;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) unsigned short gs[NCB * GPL / 2];
-    __shared__ __attribute__((aligned(16))) unsigned short at[(PB + 1) * AS];
+    __shared__ __attribute__((aligned(16))) unsigned short gs[NSRC * NCB * GPL / 2];
+    __shared__ __attribute__((aligned(16))) unsigned short at[NSRC * (PB + 1) * AS];
     __shared__ int last_flag;
 
     // workgroup -> (slice, worker): all workers of a slice on one XCD (see binned_accumulate_kernel)
@@ -96,15 +115,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
     const int col = lane & 31, kb = lane >> 5;     // operand row / column, k-block
     const int n_it = n_items[2 * s];
 
-    for (int i = lane; i < (PB + 1) * AS / 2; i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
+    for (int i = lane; i < NSRC * (PB + 1) * AS / 2; i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
     if (C < CP)                                     // the padding channels stay zero
-        for (int i = lane; i < NCB * GPL / 4; i += 64) reinterpret_cast<unsigned int *>(gs)[i] = 0u;
+        for (int i = lane; i < NSRC * NCB * GPL / 4; i += 64) reinterpret_cast<unsigned int *>(gs)[i] = 0u;
     wave_lds_sync();
 
     const __amdgpu_buffer_rsrc_t rs =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<ST *>(grad_out), 0, grad_out_bytes, 0x00020000);
     const unsigned slice_off = (unsigned)((b * Lq) * H + h) * (unsigned)ROWB;   // byte offset of (b, query 0, h)
     const unsigned q_stride = (unsigned)(H * ROWB);
+    // INST: rows of grad_mask (b, q, p, h, :) and the level weights of this slice's points
+    const __amdgpu_buffer_rsrc_t rsm = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<ST *>(INST ? inst.grad_mask : grad_out), 0, INST ? inst.grad_mask_bytes : grad_out_bytes, 0x00020000);
+    const int P = INST ? inst.P : 1, LP = plan.L * P;
+    const unsigned m_slice_off = (unsigned)((b * Lq) * P * H + h) * (unsigned)ROWB;
+    const unsigned m_q_stride = (unsigned)(P * H * ROWB), m_p_stride = (unsigned)(H * ROWB);
+    const float rcp_p = 1.0f / (float)P;
+    const int lp_mask = (1 << plan.lp_bits) - 1;
     const int piece = lane % LPR, jrow = lane / LPR;
     // staging: record jrow (+ RPP per pass), 16-byte piece `piece` of its row -> plane piece / 4
     const unsigned stage_off = (unsigned)((piece >> 2) * GPL + jrow * 64 + (piece & 3) * 16);
@@ -129,11 +156,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
         const int oy = bg.oy, ox = bg.ox, bh = bg.bh, bw = bg.bw;
         const float Hf = (float)lvH, Wf = (float)lvW;
         const int4 *rec = reinterpret_cast<const int4 *>(records) + (size_t)s * plan.rec_cap;
-        tr_f32x16 acc[NCB];
+        tr_f32x16 acc[NCB], acc_m[INST ? NCB : 1];      // (INST: a chain of its own for the grad_mask products)
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[cb][r] = 0.f;
+        if constexpr (INST) {
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc_m[cb][r] = 0.f;
+        }
 
         // software pipeline over rounds of 64 records: the records are read three rounds ahead, their
         // upstream rows two (into registers; staged into LDS once the current round's operands have been
@@ -159,24 +192,54 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
             for (int ps = 0; ps < NPASS; ++ps)
                 *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(gs) + stage_off + ps * RPP * 64) = rows[ps];
         };
+        // INST: the grad_mask rows of a round's records, and the level weight a_l of this lane's record (0: idle lane)
+        auto fetch_rows_m = [&](const int4 &r, u32x4 (&rows)[NPASS]) -> float {
+            const unsigned q = (unsigned)max(r.x, 0) >> plan.lp_bits;
+            const int lp = max(r.x, 0) & lp_mask;
+            int l_, p_;
+            divmod_small(lp, P, rcp_p, l_, p_);
+            const unsigned off = r.x < 0 ? kNoRow : q * m_q_stride + (unsigned)p_ * m_p_stride + m_slice_off;
+            const float al = r.x < 0 ? 0.f : inst.w_lv[(((size_t)b * Lq + q) * H + h) * LP + lp];
+#pragma unroll
+            for (int ps = 0; ps < NPASS; ++ps) {
+                const unsigned oj = (unsigned)__shfl((int)off, ps * RPP + jrow, 64) + (unsigned)(piece * 16);
+                rows[ps] = __builtin_amdgcn_raw_buffer_load_b128(rsm, oj, 0, 0);
+            }
+            return al;
+        };
+        auto stage_rows_m = [&](const u32x4 (&rows)[NPASS]) {
+#pragma unroll
+            for (int ps = 0; ps < NPASS; ++ps)
+                *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(gs) + kGsM + stage_off + ps * RPP * 64) = rows[ps];
+        };
         // (requesting the NEXT item's first records here -- an item starts with two dependent round trips, and a
         // level-0 block at BoxeR-R50 shapes is under four rounds -- costs this kernel seven spilled registers and
         // 1-3 %; the float32 kernel below, which has the registers, gains 1 % from it)
         int4 rec_c = fetch_rec(item.y), rec_n = fetch_rec(item.y + R), rec_n2 = fetch_rec(item.y + 2 * R);
         u32x4 grow_a[NPASS], grow_b[NPASS];
+        u32x4 mrow_a[INST ? NPASS : 1], mrow_b[INST ? NPASS : 1];
+        float al_c = 0.f, al_n = 0.f, al_n2 = 0.f;      // INST: a_l of the records rec_c, rec_n, rec_n2
         fetch_rows(rec_c, grow_a);
+        if constexpr (INST) al_c = fetch_rows_m(rec_c, mrow_a);
         stage_rows(grow_a);
-        if (item.y + R < item.z) fetch_rows(rec_n, grow_a);
+        if constexpr (INST) stage_rows_m(mrow_a);
+        if (item.y + R < item.z) {
+            fetch_rows(rec_n, grow_a);
+            if constexpr (INST) al_n = fetch_rows_m(rec_n, mrow_a);
+        }
         // one round: `next` holds the rows of round rr + R (staged at the end), `ahead` receives those of rr + 2 R
-        auto round = [&](int rr, const u32x4 (&next)[NPASS], u32x4 (&ahead)[NPASS]) {
+        auto round = [&](int rr, const u32x4 (&next)[NPASS], u32x4 (&ahead)[NPASS],
+                         const u32x4 (&next_m)[INST ? NPASS : 1], u32x4 (&ahead_m)[INST ? NPASS : 1]) {
             const bool more = rr + R < item.z;     // wave-uniform
             int4 rec_n3 = make_int4(-1, 0, 0, 0);
             if (rr + 2 * R < item.z) {
                 fetch_rows(rec_n2, ahead);
+                if constexpr (INST) al_n2 = fetch_rows_m(rec_n2, ahead_m);
                 rec_n3 = fetch_rec(rr + 3 * R);
             }
             // ---- lane = record: its <= 4 weights go to A^T[pixel][lane] as hi + lo 16-bit terms
-            const float x = __int_as_float(rec_c.y), y = __int_as_float(rec_c.z), a = __int_as_float(rec_c.w);
+            const float x = __int_as_float(rec_c.y), y = __int_as_float(rec_c.z);
+            const float a = INST ? __int_as_float(rec_c.w) * kWScale : __int_as_float(rec_c.w);
             float h_im, w_im;
             {
 #pragma clang fp contract(off)                   // two roundings, as in locate()
@@ -193,6 +256,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
             const unsigned hi01 = H16::pack(w0, w1), hi23 = H16::pack(w2, w3);
             const unsigned lo01 = H16::pack(w0 - H16::lo(hi01), w1 - H16::hi(hi01));
             const unsigned lo23 = H16::pack(w2 - H16::lo(hi23), w3 - H16::hi(hi23));
+            // INST: the same four bilinear weights times a_l, for the grad_mask rows
+            unsigned mhi01 = 0u, mhi23 = 0u, mlo01 = 0u, mlo23 = 0u;
+            if constexpr (INST) {
+                const float am = al_c * kWScale;
+                const float hm = hh * am, lm = lh * am;
+                const float m0 = hm * hw, m1 = hm * lw, m2 = lm * hw, m3 = lm * lw;
+                mhi01 = H16::pack(m0, m1); mhi23 = H16::pack(m2, m3);
+                mlo01 = H16::pack(m0 - H16::lo(mhi01), m1 - H16::hi(mhi01));
+                mlo23 = H16::pack(m2 - H16::lo(mhi23), m3 - H16::hi(mhi23));
+            }
             // byte offsets of the corners' rows / columns inside A^T, kBig when outside the block (idle lanes: all)
             const int r0 = (unsigned)py < (unsigned)bh ? __mul24(py, BW * ASB) : kBig;
             const int r1 = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * ASB) + BW * ASB : kBig;
@@ -203,11 +276,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
             auto put = [&](int k, unsigned short v) {
                 *reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(at) + slot[k]) = v;
             };
+            auto put_m = [&](int k, unsigned short v) {      // INST: the tile of the w_k a_l entries, same slots
+                *reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(at) + kAtL + slot[k]) = v;
+            };
             put(0, (unsigned short)(hi01 & 0xffffu)); put(1, (unsigned short)(hi01 >> 16));
             put(2, (unsigned short)(hi23 & 0xffffu)); put(3, (unsigned short)(hi23 >> 16));
+            if constexpr (INST) {
+                put_m(0, (unsigned short)(mhi01 & 0xffffu)); put_m(1, (unsigned short)(mhi01 >> 16));
+                put_m(2, (unsigned short)(mhi23 & 0xffffu)); put_m(3, (unsigned short)(mhi23 >> 16));
+            }
             wave_lds_sync();
             // ---- the product: 4 K-steps of 16 records per 32-channel block, hi term then lo term
-            tr_h16x8 g[R / 16][NCB];
+            tr_h16x8 g[R / 16][NCB], gm[INST ? R / 16 : 1][NCB];
 #pragma unroll
             for (int t = 0; t < R / 16; ++t) {
                 const tr_h16x8 p_hi = __builtin_bit_cast(
@@ -219,10 +299,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
                     g[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
                     acc[cb] = H16::mfma32x32x16(g[t][cb], p_hi, acc[cb]);
                 }
+                if constexpr (INST) {
+                    const tr_h16x8 pm_hi = __builtin_bit_cast(
+                        tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + kAtL + a_off + 32 * t));
+#pragma unroll
+                    for (int cb = 0; cb < NCB; ++cb) {
+                        const uint2 g0 = lds_read_tr16(gs, kGsM + tr_off + cb * GPL + t * 1024);
+                        const uint2 g1 = lds_read_tr16(gs, kGsM + tr_off + cb * GPL + t * 1024 + 256);
+                        gm[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
+                        acc_m[cb] = H16::mfma32x32x16(gm[t][cb], pm_hi, acc_m[cb]);
+                    }
+                }
             }
             wave_lds_sync();                         // a wave's LDS operations execute in order
             put(0, (unsigned short)(lo01 & 0xffffu)); put(1, (unsigned short)(lo01 >> 16));
             put(2, (unsigned short)(lo23 & 0xffffu)); put(3, (unsigned short)(lo23 >> 16));
+            if constexpr (INST) {
+                put_m(0, (unsigned short)(mlo01 & 0xffffu)); put_m(1, (unsigned short)(mlo01 >> 16));
+                put_m(2, (unsigned short)(mlo23 & 0xffffu)); put_m(3, (unsigned short)(mlo23 >> 16));
+            }
             wave_lds_sync();
 #pragma unroll
             for (int t = 0; t < R / 16; ++t) {
@@ -231,21 +326,42 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb)
                     acc[cb] = H16::mfma32x32x16(g[t][cb], p_lo, acc[cb]);
+                if constexpr (INST) {
+                    const tr_h16x8 pm_lo = __builtin_bit_cast(
+                        tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + kAtL + a_off + 32 * t));
+#pragma unroll
+                    for (int cb = 0; cb < NCB; ++cb)
+                        acc_m[cb] = H16::mfma32x32x16(gm[t][cb], pm_lo, acc_m[cb]);
+                }
             }
             wave_lds_sync();
             // ---- clear this round's weights, stage the next round's rows (they have arrived)
 #pragma unroll
             for (int k = 0; k < 4; ++k) put(k, (unsigned short)0);
+            if constexpr (INST) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) put_m(k, (unsigned short)0);
+            }
             if (more) {
                 stage_rows(next);
+                if constexpr (INST) {
+                    stage_rows_m(next_m);
+                    al_c = al_n; al_n = al_n2;
+                }
                 rec_c = rec_n; rec_n = rec_n2; rec_n2 = rec_n3;
             }
             wave_lds_sync();
         };
         for (int rr = item.y; rr < item.z; rr += 2 * R) {       // (two rounds per trip: the row buffers swap roles, no copies)
-            round(rr, grow_a, grow_b);
+            round(rr, grow_a, grow_b, mrow_a, mrow_b);
             if (rr + R >= item.z) break;
-            round(rr + R, grow_b, grow_a);
+            round(rr + R, grow_b, grow_a, mrow_b, mrow_a);
+        }
+        if constexpr (INST) {          // one sum per pixel and channel; f16: the weights' scale taken back (exact)
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[cb][r] = (acc[cb][r] + acc_m[cb][r]) * (1.f / kWScale);
         }
         // ---- store.  Lane = pixel `col`; its registers hold channels 8 g + 4 kb + 0..3.
         if (item.w < 0) {
@@ -329,12 +445,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? BO
 // (instance_attn_kernel.cuh:139): both rows are gathered, combined in float32 as they arrive and THEN split -- the
 // bilinear weights go to A^T without an attention weight.  Records {point id, x, y, a_s} as for box attention (a_s = the
 // spatial weight); a_l is gathered from `level_w` by the record's point id.  Two row buffers in flight: 2 waves per SIMD.
-struct InstRows {
-    const float *grad_mask;      // (B, Lq, P, H, C)
-    unsigned grad_mask_bytes;
-    const float *w_lv;           // (B, Lq, H, L, P)
-    int P;
-};
+typedef InstRowsT<float> InstRows;
 template <int C, bool INST = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INST ? 2 : 3, INST ? 2 : 3))) void binned_accumulate_split_kernel(
     const float *__restrict__ grad_out, unsigned grad_out_bytes, BinPlan plan, int S, int H, int Lq,

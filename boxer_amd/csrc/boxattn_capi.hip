@@ -48,7 +48,10 @@ enum { kOptBinChunk = 10,     // records per work item of the accumulate kernels
                               // inference): 0 default (the wave-per-pair kernel where it measured faster, wide_box_ok),
                               // 1 off (row-gather kernel: the parity cross-check of the two families), 2 on wherever
                               // the instance flavour takes the family
-       kNumOpts = 23 };
+       kOptInstAcc16 = 23,    // 16-bit instance attention, C = 16 / 32 / 64, accumulate: 0 default (the matrix cores from
+                              // kInstTrMinPoints points a slice), 1 VALU list walk (4-byte records: the parity cross-check),
+                              // 2 the matrix cores (binned_accumulate_tr_kernel<ST, C, true>) wherever the shape is eligible
+       kNumOpts = 24 };
 // (round 6 removed the keys whose non-default values had lost their A/B: 12 / 13 window margins, 17 staged forward off,
 // 21 staged float32 kernels off -- 11 = 1 switches every window-staged kernel off)
 std::atomic<int> g_opt[kNumOpts];      // 0 = default
@@ -56,7 +59,7 @@ inline int opt(int k) { return g_opt[k].load(std::memory_order_relaxed); }
 inline bool opt_live(int k)
 {
     return k == kOptBinChunk || k == kOptDense || k == kOptRiders || k == kOptAccF32 || k == kOptRideShift ||
-           k == kOptWideBox;
+           k == kOptWideBox || k == kOptInstAcc16;
 }
 #ifndef BOXATTN_RIDE_SHIFT_COUNT
 #define BOXATTN_RIDE_SHIFT_COUNT 0     // count riders: all in front of the forward kernel's grid (measured: interleaving
@@ -595,10 +598,20 @@ int launch_bwd(const BwdIn<ST> &in, const BwdOut<ST> &out, typename Storage<ST>:
 #include "boxattn_host_plan.h"       // make_plan / make_dense_plan, plan_layout / scratch_layout, acc_kind, riders_ok
 
 // record format / query order / points per thread of the bin passes of a call
+// The accumulate kernel of a CALL: acc_kind of its dimensions, and for 16-bit instance attention the operands only that
+// route reads 16 bytes at a time -- a grad_mask view that is not 16-byte aligned (fast_ok asks 8) takes the VALU route
 template <typename ST, bool INST>
-inline int bin_flavour(const Dims &d, const float *loc, const float *w_sp)
+inline AccKind acc_kind_at(const Dims &d, const void *grad_mask, const void *w_lv)
 {
-    const bool wide = acc_kind<ST, INST>(d) != kAccValu;
+    const AccKind acc = acc_kind<ST, INST>(d);
+    if constexpr (INST && IsHalf16<ST>::value) {
+        if (acc == kAccTr && !(aligned(grad_mask, 16) && aligned(w_lv, 4))) return kAccValu;
+    }
+    return acc;
+}
+inline int bin_flavour(AccKind acc, const Dims &d, const float *loc, const float *w_sp)
+{
+    const bool wide = acc != kAccValu;
     // four points per thread where the layout allows 16-byte loads of a (query, level)'s points
     const bool pt4 = d.P % 4 == 0 && aligned(loc, 16) && (!wide || aligned(w_sp, 16));
     return (wide ? kRideWide : kRideInterleave) | (pt4 ? kRidePt4 : 0);
@@ -781,6 +794,14 @@ int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, cons
             return finish();
         }
     }
+    if constexpr (IsHalf16<ST>::value && INST) {
+        if (acc == kAccTr) {
+            launch_accumulate_tr_inst<ST>(C, grad_out, (size_t)d.B * d.Lq * d.H * C * sizeof(ST), plan, d.S, d.H, d.Lq, items,
+                                          n_items, records, grad_value, partials, wg_per_slice, ns8, cc, zr, st, grad_mask,
+                                          (size_t)d.B * d.Lq * d.P * d.H * C * sizeof(ST), w_lv, d.P);
+            return finish();
+        }
+    }
     if constexpr (std::is_same<ST, float>::value && !INST && C == 32) {
         if (acc == kAccSplit) {
             launch_accumulate_split(grad_out, (size_t)d.B * d.Lq * d.H * C * sizeof(float), plan, d.S, d.H, d.Lq, items,
@@ -816,14 +837,13 @@ int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, cons
 template <typename ST, int G, bool INST>
 int run_binned(const BwdIn<ST> &in, const BwdOut<ST> &out, const BinPlan &plan, const PlanLayout &pl, char *pbuf,
                const ScratchLayout &sl, char *sbuf, bool plan_ready, const DensePlan *dp, const SpecRide *spec,
-               bool spec_warm, int *spec_tickets, bool points)
+               bool spec_warm, int *spec_tickets, bool points, AccKind acc)
 {
     const Dims &d = in.d;
     const hipStream_t st = in.st;
     const float *loc = in.loc, *w_sp = in.w_sp;
     const int ns = d.B * d.H;
-    const AccKind acc = acc_kind<ST, INST>(d);
-    const int flavour = bin_flavour<ST, INST>(d, loc, w_sp);
+    const int flavour = bin_flavour(acc, d, loc, w_sp);
     int *records = (int *)(sbuf + sl.records);
     float *partials = (float *)(sbuf + sl.partials);
     const int *n_items = (const int *)(pbuf + pl.n_items), *offsets = (const int *)(pbuf + pl.offsets);
@@ -911,6 +931,7 @@ int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size
     if (!wp) out.grad_loc = out.grad_sp = out.grad_lv = nullptr;
     BinPlan plan;
     const size_t nv = d.n_value();
+    const AccKind acc = acc_kind_at<ST, INST>(d, in.grad_mask, in.w_lv);
     bool binned = (g_variant == 0 || g_variant == 3) && nv && d.n_qh() &&
                   make_plan(d, in.shapes_host, in.lsi_host, plan) &&
                   fast_ok<ST>(d, in.value, in.loc, in.grad_out,
@@ -922,7 +943,9 @@ int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size
     if (binned && wv) {
         pl = plan_layout(d, plan);
         sl = scratch_layout(d, plan, wide_workspace(kH16, d));
-        plan_ready = plan_buf && plan_bytes >= pl.total && aligned(plan_buf, 256);
+        // (a training forward plans for acc_kind's record order: a call that leaves that route for its operands'
+        // alignment plans for itself)
+        plan_ready = plan_buf && plan_bytes >= pl.total && aligned(plan_buf, 256) && acc == acc_kind<ST, INST>(d);
         binned = workspace && aligned(workspace, 256) && aligned(out.grad_value, 16) &&
                  workspace_bytes >= (plan_ready ? sl.total : pl.total + sl.total);
     }
@@ -978,7 +1001,7 @@ int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size
     int rc = 0;
     for_group(fast_group(d), [&](auto g) {
         rc = run_binned<ST, decltype(g)::value, INST>(in, out, plan, pl, pbuf, sl, sbuf, plan_ready, dp, sp, spec_warm,
-                                                      spec_tickets, wp);
+                                                      spec_tickets, wp, acc);
     });
     return rc;
 }
@@ -1028,7 +1051,7 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
     if (!ok)
         return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
     char *pbuf = (char *)plan_buf;
-    const int flavour = bin_flavour<ST, INST>(d, loc, w_sp);
+    const int flavour = bin_flavour(acc_kind<ST, INST>(d), d, loc, w_sp);
     bool taken = false;
     int rc = 0;
     if (riders_ok(plan, pl)) {
@@ -1366,6 +1389,16 @@ int boxattn_set_option(int key, int value)
     return g_opt[key].exchange(value);
 }
 
+
+int boxattn_bwd_accumulate_kind(int elem_bytes, int instance, int B, int S, int H, int C, int L, int Lq, int P)
+{
+    const Dims d = DIMS;
+    if (!d.valid()) return -1;
+    // (bf16 and f16 storage route alike: one answer for elem_bytes == 2)
+    if (elem_bytes == 2) return (int)(instance ? acc_kind<bf16_t, true>(d) : acc_kind<bf16_t, false>(d));
+    if (elem_bytes == 4) return (int)(instance ? acc_kind<float, true>(d) : acc_kind<float, false>(d));
+    return -1;          // float64 has no binned backward
+}
 
 int boxattn_fwd_route(int elem_bytes, int instance, int aligned, int B, int S, int H, int C, int L, int Lq, int P,
                       const int64_t *shapes_host, const int64_t *lsi_host)

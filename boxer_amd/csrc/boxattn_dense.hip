@@ -95,13 +95,34 @@ void launch_accumulate_tr(int C, const ST *grad_out, size_t grad_out_bytes, cons
 #define BOXATTN_ACC_TR(C_)                                                                              \
     hipLaunchKernelGGL((binned_accumulate_tr_kernel<ST, C_>), dim3(wg_per_slice + plan.zero_workers, ns8), dim3(64), 0, st, \
                        grad_out, (unsigned)grad_out_bytes, plan, S, H, Lq, items, n_items, records,     \
-                       grad_value, partials, cc, zr)
+                       grad_value, partials, cc, zr, InstRowsT<ST>{})
     switch (C) {
     case 16: BOXATTN_ACC_TR(16); break;
     case 32: BOXATTN_ACC_TR(32); break;
     case 64: BOXATTN_ACC_TR(64); break;
     }
 #undef BOXATTN_ACC_TR
+}
+
+// instance attention: two upstream rows per record (the kernel's INST flavour)
+template <typename ST>
+void launch_accumulate_tr_inst(int C, const ST *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
+                               int H, int Lq, const int4 *items, const int *n_items, const int *records,
+                               ST *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
+                               const ZeroRole &zr, hipStream_t st, const ST *grad_mask, size_t grad_mask_bytes,
+                               const float *w_lv, int P)
+{
+    const InstRowsT<ST> inst{grad_mask, (unsigned)grad_mask_bytes, w_lv, P};
+#define BOXATTN_ACC_TR_INST(C_)                                                                         \
+    hipLaunchKernelGGL((binned_accumulate_tr_kernel<ST, C_, true>), dim3(wg_per_slice + plan.zero_workers, ns8), dim3(64), 0, st, \
+                       grad_out, (unsigned)grad_out_bytes, plan, S, H, Lq, items, n_items, records,     \
+                       grad_value, partials, cc, zr, inst)
+    switch (C) {
+    case 16: BOXATTN_ACC_TR_INST(16); break;
+    case 32: BOXATTN_ACC_TR_INST(32); break;
+    case 64: BOXATTN_ACC_TR_INST(64); break;
+    }
+#undef BOXATTN_ACC_TR_INST
 }
 
 // one source per kernel family, instantiated for both 16-bit storage types
@@ -113,7 +134,11 @@ void launch_accumulate_tr(int C, const ST *grad_out, size_t grad_out_bytes, cons
                                         unsigned, const BinRide &, unsigned long long *, hipStream_t);      \
     template void launch_accumulate_tr<ST_>(int, const ST_ *, size_t, const BinPlan &, int, int, int,       \
                                             const int4 *, const int *, const int *, ST_ *, float *, int, int, \
-                                            const ChunkCombine &, const ZeroRole &, hipStream_t);
+                                            const ChunkCombine &, const ZeroRole &, hipStream_t);              \
+    template void launch_accumulate_tr_inst<ST_>(int, const ST_ *, size_t, const BinPlan &, int, int, int,  \
+                                                 const int4 *, const int *, const int *, ST_ *, float *, int, int, \
+                                                 const ChunkCombine &, const ZeroRole &, hipStream_t, const ST_ *, \
+                                                 size_t, const float *, int);
 BOXATTN_DENSE_H16(bf16_t)
 BOXATTN_DENSE_H16(f16_t)
 #undef BOXATTN_DENSE_H16

@@ -106,6 +106,14 @@ void launch_accumulate_tr(int C, const ST *grad_out, size_t grad_out_bytes, cons
                           int H, int Lq, const int4 *items, const int *n_items, const int *records,
                           ST *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
                           const ZeroRole &zr, hipStream_t st);
+// ... of 16-bit INSTANCE attention: a record's second row comes from grad_mask (B, Lq, P, H, C; below 2 GB too), its
+// second weight from level_w (B, Lq, H, L, P); grad_mask 16-byte aligned
+template <typename ST>
+void launch_accumulate_tr_inst(int C, const ST *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
+                               int H, int Lq, const int4 *items, const int *n_items, const int *records,
+                               ST *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
+                               const ZeroRole &zr, hipStream_t st, const ST *grad_mask, size_t grad_mask_bytes,
+                               const float *w_lv, int P);
 
 // float32 storage, C = 32: the accumulate on the bf16 matrix cores with exact three-term splits (boxattn_binned_tr.h:
 // binned_accumulate_split_kernel); grad_out below 2 GB

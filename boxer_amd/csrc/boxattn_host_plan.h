@@ -34,6 +34,11 @@ inline int bin_chunk(const Dims &d)
 //            interleaved over the bin workgroups.
 //   kAccSplit float32 box AND instance attention, C = 32 (default): binned_accumulate_split_kernel -- the bf16 matrix cores
 //            on exact three-term splits of rows and weights, 16-byte records; boxattn_set_option(19, 1) goes back to kAccValu.
+// 16-bit INSTANCE attention, C = 16 / 32 / 64: kAccTr is the INST flavour of that kernel -- two products a round, the
+//            grad_out rows against w_k a_s and the grad_mask rows against w_k a_l, 16-byte records {point id, x, y, a_s}.
+//            boxattn_set_option(23, v) ("inst_acc16"): 0 default (from kInstTrMinPoints = 235 200 points a slice: C3'), 1 the VALU list
+//            walk, 2 the matrix cores wherever the shape is eligible.  A grad_mask that is not 16-byte aligned takes
+//            the VALU route (acc_kind_at, boxattn_capi.hip).  boxattn_bwd_accumulate_kind() answers with acc_kind().
 enum AccKind { kAccValu = 0, kAccTr = 1, kAccF32 = 2, kAccSplit = 3 };
 inline bool accumulate_tr_ok(const Dims &d)          // 32-bit row offsets: grad_out below 2 GB
 {
@@ -46,11 +51,26 @@ inline bool f32_matrix_shape_ok(const Dims &d)
 }
 inline bool f32_mfma_ok(const Dims &d) { return opt(kOptAccF32) == 2 && f32_matrix_shape_ok(d); }
 constexpr size_t kInstSplitMinPoints = 65536;
+// 16-bit instance attention on the matrix cores from this many points a slice (Lq L P) by default: the smallest measured
+// size from which every larger cell passed the step rule against the VALU list walk (DESIGN.md 4.2.2,
+// profiles/instance_accumulate16_step.log).  C3' (235 k points): step 393 -> 360 us at B = 2, 224 -> 180 at B = 1, bf16 and
+// f16 alike (accumulate 137 -> 97 us, the fill riders' launch + 7 for the wide records); 77 k points (k = 8): 141 -> 147 at
+// B = 2; C3 (19 k): inside the spread of a host-bound step.
+constexpr size_t kInstTrMinPoints = 235200;
+inline bool inst_tr_ok(const Dims &d)
+{
+    const int o = opt(kOptInstAcc16);
+    if (o == 1 || !accumulate_tr_ok(d) || (size_t)d.B * d.Lq * d.P * d.H * d.C * 2 >= kAccTrMaxBytes) return false;
+    return o == 2 || (size_t)d.Lq * d.L * d.P >= kInstTrMinPoints;
+}
 inline bool f32_split_ok(const Dims &d) { return opt(kOptAccF32) == 0 && f32_matrix_shape_ok(d); }
 template <typename ST, bool INST> inline AccKind acc_kind(const Dims &d)
 {
     if constexpr (!INST && IsHalf16<ST>::value) {
         if (accumulate_tr_ok(d)) return kAccTr;
+    }
+    if constexpr (INST && IsHalf16<ST>::value) {
+        if (inst_tr_ok(d)) return kAccTr;
     }
     if constexpr (!INST && std::is_same<ST, float>::value) {
         if (f32_mfma_ok(d)) return kAccF32;

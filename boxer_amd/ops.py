@@ -518,6 +518,16 @@ def forward_route(value, loc, shapes_host=None, lsi_host=None, instance=False):
                           host(lsi_host))
 
 
+def backward_accumulate_kind(value, loc, instance=False):
+    """Which kernel (``_lib.ACC_*``) sums grad_value in a binned backward of these tensors under the current switches:
+    ``boxattn_bwd_accumulate_kind`` with the dimensions and element size of ``value`` (B, S, H, C) and ``loc``
+    (B, Lq, H, L, P, 2).  Negative for float64.  (A 16-bit instance-attention call whose ``grad_mask_output`` is not
+    16-byte aligned takes the VALU walk whatever this answers: the query sees no gradients.)"""
+    B, S, H, C = value.shape
+    Lq, L, P = loc.size(1), loc.size(3), loc.size(4)
+    return _lib.bwd_accumulate_kind(value.element_size(), instance, (B, S, H, C, L, Lq, P))
+
+
 def box_attn_forward_train(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                            im2col_step):
     """Forward for training: -> (output, plan).  ``plan`` (or None) goes to

@@ -522,6 +522,12 @@ int instattn_weights_bwd_f16(const uint16_t *logits, const float *grad_spatial_w
  *      kernel where it measured faster than the row-gather kernel), 1 off (row-gather kernel -- the parity
  *      cross-check of the two kernel families), 2 on wherever instance attention takes that family.  Instance
  *      attention does not read it.
+ *  23  "inst_acc16": instance attention in 16-bit storage, C = 16 / 32 / 64 -- the grad_value accumulate: 0 library
+ *      default (decided by measurement, DESIGN.md 4.2.2: the matrix cores from 235 200 points per (image, head) slice up
+ *      -- 300 queries, 14 x 14 points on four levels --, the VALU list walk below), 1 VALU list walk (4-byte
+ *      records; the parity cross-check), 2 the matrix cores wherever the shape is eligible (grad_out and grad_mask
+ *      below 2 GiB; a grad_mask that is not 16-byte aligned takes the VALU walk).  Box attention and float32 do not
+ *      read it.  Set before *_fwd_train_*: a plan made under another setting is not used.
  *  (ABI 8 removed 12 / 13 -- window margins --, 17 and 21 -- staged forward / staged float32 kernels off: 11 = 1
  *  switches every window-staged kernel off.)
  */
@@ -541,6 +547,16 @@ int boxattn_set_option(int key, int value);
  * (BOXATTN_HINT_NOT_LOCAL of a training forward is a per-call matter: the query answers for a call without it.) */
 int boxattn_fwd_route(int elem_bytes, int instance, int aligned, int B, int S, int H, int C, int L, int Lq, int P,
                       const int64_t *shapes_host, const int64_t *lsi_host);
+/* The grad_value accumulate kernels of the binned backward. */
+#define BOXATTN_ACC_VALU  0     /* VALU list walk over 4-byte records */
+#define BOXATTN_ACC_TR    1     /* 16-bit storage on v_mfma_f32_32x32x16_bf16 / _f16 (instance attention: option 23) */
+#define BOXATTN_ACC_F32   2     /* float32 on v_mfma_f32_32x32x2_f32 (option 19 = 2) */
+#define BOXATTN_ACC_SPLIT 3     /* float32 on the bf16 matrix cores over exact three-term splits */
+/* Which accumulate kernel a binned backward of these dimensions runs under the current switches: the very function
+ * the launch calls.  elem_bytes 2 / 4; instance 0 / 1.  Pure host code.  < 0: invalid dimensions or elem_bytes (8:
+ * float64 has no binned backward).  (Whether a call IS binned -- level tables, alignment, workspace -- and the
+ * alignment of grad_mask, which can send a 16-bit instance call to BOXATTN_ACC_VALU, are per-call matters.) */
+int boxattn_bwd_accumulate_kind(int elem_bytes, int instance, int B, int S, int H, int C, int L, int Lq, int P);
 /* Number of boxattn_set_variant / boxattn_set_option calls so far: lets a binding cache the size queries
  * (boxattn_plan_bytes, boxattn_bwd_workspace_bytes: pure functions of their arguments and the switches). */
 int boxattn_options_epoch(void);
