@@ -89,7 +89,7 @@ _GRID_SIGNATURES = {
     "boxattn_grid_bwd_f32": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp, _vp],
 }
 EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "boxattn_set_option",
-           "boxattn_options_epoch", "boxattn_fwd_route", "boxattn_bwd_accumulate_kind",
+           "boxattn_options_epoch", "boxattn_fwd_route", "boxattn_bwd_accumulate_kind", "boxattn_bwd_record_kind",
            "boxattn_set_debug_buffer",
            "boxattn_fwd_hl_f32", "boxattn_fwd_hl_bf16", "boxattn_fwd_hl_f16", *sorted(_POINTWISE_SIGNATURES),
            "boxattn_profile_begin", "boxattn_profile_end", "boxattn_bwd_workspace_bytes",
@@ -232,6 +232,8 @@ def load():
     lib.boxattn_fwd_route.restype = _i
     lib.boxattn_bwd_accumulate_kind.argtypes = [_i] * 9
     lib.boxattn_bwd_accumulate_kind.restype = _i
+    lib.boxattn_bwd_record_kind.argtypes = [_i] * 9
+    lib.boxattn_bwd_record_kind.restype = _i
     for name, args in list(_GRID_SIGNATURES.items()) + list(_POINTWISE_SIGNATURES.items()):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = _i
@@ -263,7 +265,7 @@ def set_variant(v):
 
 
 OPTIONS = {"bin_chunk": 10, "dense": 11, "riders": 15, "acc_f32": 19, "ride_shift": 20, "wide_box": 22,
-           "inst_acc16": 23}
+           "inst_acc16": 23, "group_records": 24}
 # boxattn_fwd_route: the forward's kernel families (BOXATTN_FWD_*)
 FWD_GENERIC, FWD_FAST, FWD_GATHER, FWD_WIDE, FWD_STAGED = range(5)
 FWD_FAMILIES = ("generic", "fast", "gather", "wide", "staged")
@@ -286,6 +288,17 @@ def bwd_accumulate_kind(elem_bytes, instance, dims):
     """boxattn_bwd_accumulate_kind(): the accumulate kernel (ACC_*) of a binned backward at ``dims`` = (B, S, H, C, L,
     Lq, P) under the current switches; negative for invalid arguments or float64.  Pure host code (no GPU needed)."""
     return load().boxattn_bwd_accumulate_kind(int(elem_bytes), int(instance), *[int(v) for v in dims])
+
+
+# boxattn_bwd_record_kind: the records of the binned backward (BOXATTN_REC_*)
+REC_POINT, REC_GROUP = range(2)
+REC_KINDS = ("point", "group")
+
+
+def bwd_record_kind(elem_bytes, instance, dims):
+    """boxattn_bwd_record_kind(): the records (REC_*) a binned backward at ``dims`` = (B, S, H, C, L, Lq, P) writes under
+    the current switches; negative for invalid arguments or float64.  Pure host code (no GPU needed)."""
+    return load().boxattn_bwd_record_kind(int(elem_bytes), int(instance), *[int(v) for v in dims])
 
 
 def set_option(name, value):

@@ -57,7 +57,7 @@ namespace boxattn {
 #define BOXATTN_TUNE_BIN_THREADS 512
 #endif
 constexpr int kBinThreads = BOXATTN_TUNE_BIN_THREADS;
-template <int BW, int BH, bool FILL, bool WIDE, int PT>
+template <int BW, int BH, bool FILL, bool WIDE, int PT, bool GRP = false>
 __global__ __launch_bounds__(kBinThreads) void bin_kernel(const float *__restrict__ loc,
                                                   const float *__restrict__ w_sp, BinPlan plan,
                                                   int H, int Lq, int P, int q_per_wg, int n_wg, int interleave,
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kBinThreads) void bin_kernel(const float *__restric
     extern __shared__ int sh_bins[];
     __shared__ BinLevel s_lv[kMaxBinLevels];       // indexed per lane (no select chains)
     const int s = blockIdx.y, wg = blockIdx.x;
-    bin_pass_body<kBinThreads, BW, BH, FILL, WIDE, PT>(sh_bins, s_lv, loc, w_sp, plan, H, Lq, P, q_per_wg, n_wg,
+    bin_pass_body<kBinThreads, BW, BH, FILL, WIDE, PT, GRP>(sh_bins, s_lv, loc, w_sp, plan, H, Lq, P, q_per_wg, n_wg,
                                                        interleave != 0, part, subtot, offsets, records, s, wg);
     if constexpr (!FILL) {
         int *mypart = part + ((size_t)s * n_wg + wg) * plan.nblk;

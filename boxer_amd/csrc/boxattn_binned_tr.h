@@ -65,13 +65,30 @@ template <typename T> struct InstRowsT {
 };
 // Two row sets and two A^T tiles in LDS (17.3 KB a wave at C <= 32, 25.3 KB at C = 64) leave room for two waves per SIMD
 // (one at C = 64), which is also what the flavour's registers are budgeted for (216 at C = 32).
-template <typename ST, int C, bool INST = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (INST ? 2 : BOXATTN_TUNE_TR_WPE) : 1))) void binned_accumulate_tr_kernel(
+// GRP: group records (boxattn_binplan.h: group_blocks), box attention with P == 4.  A record is one int -- (query, level,
+// mask) -- and a round is 64 GROUPS: with its upstream row a lane requests the group's 32 bytes of locations and 16 bytes
+// of attention weights (buffer resources; idle lanes read zeros from an offset outside them, as for kNoRow), forms the
+// <= 16 corner weights a_p w_k of the masked-in points and ADDS them, in float32, into its own column of a float32 tile
+// A^T[pixel][record] in LDS (read - add - store, point by point; corners outside the block go to a dump pixel): corners of different points on one
+// pixel -- a box of size 0 puts all sixteen on one pixel quad -- are summed before the hi / lo 16-bit split, which the
+// lanes do on the operand registers they read back (lane = pixel, 8 consecutive records a K-step).  The tile is
+// [16 record quads][32 pixels + dump][4 records] floats, 528 bytes a quad: the column writes of 64 lanes with one pixel
+// and the 16-byte operand reads of 32 pixels are both free of bank conflicts.  8.25 KB + the G planes: 12.3 KB a wave at
+// C <= 32, three waves per SIMD (12 waves x 12.5 KB of a CU's 160 KB).
+struct GroupPts {
+    const float *loc, *attn;     // (B, Lq, H, L, 4, 2), (B, Lq, H, L, 4)
+    unsigned loc_bytes;          // < 2^31 (record_kind); attn has half as many
+};
+constexpr int kGrpQuadB = 33 * 16;             // bytes of a record quad's row of the float32 tile: 32 pixels + the dump pixel
+constexpr int kGrpTileB = 16 * kGrpQuadB;
+template <typename ST, int C, bool INST = false, bool GRP = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (INST ? 2 : GRP ? 3 : BOXATTN_TUNE_TR_WPE) : 1))) void binned_accumulate_tr_kernel(
     const ST *__restrict__ grad_out, unsigned grad_out_bytes, BinPlan plan, int S, int H, int Lq,
     const int4 *__restrict__ items, const int *__restrict__ n_items,
     const int *__restrict__ records, ST *__restrict__ grad_value, float *__restrict__ partials, ChunkCombine cc,
-    ZeroRole zr, InstRowsT<ST> inst)
+    ZeroRole zr, InstRowsT<ST> inst, GroupPts gp)
 {
+    static_assert(!(GRP && INST), "group records: box attention");
     static_assert(IsHalf16<ST>::value, "16-bit storage");
     typedef Half16<ST> H16;
     typedef typename H16::x8 tr_h16x8;
@@ -94,7 +111,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
     constexpr float kWScale = INST && std::is_same<ST, f16_t>::value ? 256.f : 1.f;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) unsigned short gs[NSRC * NCB * GPL / 2];
-    __shared__ __attribute__((aligned(16))) unsigned short at[NSRC * (PB + 1) * AS];
+    __shared__ __attribute__((aligned(16))) unsigned short at[GRP ? kGrpTileB / 2 : NSRC * (PB + 1) * AS];
     __shared__ int last_flag;
 
     // workgroup -> (slice, worker): all workers of a slice on one XCD (see binned_accumulate_kernel)
@@ -115,7 +132,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
     const int col = lane & 31, kb = lane >> 5;     // operand row / column, k-block
     const int n_it = n_items[2 * s];
 
-    for (int i = lane; i < NSRC * (PB + 1) * AS / 2; i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
+    for (int i = lane; i < (int)(sizeof(at) / 4); i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
     if (C < CP)                                     // the padding channels stay zero
         for (int i = lane; i < NSRC * NCB * GPL / 4; i += 64) reinterpret_cast<unsigned int *>(gs)[i] = 0u;
     wave_lds_sync();
@@ -168,194 +185,353 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
                 for (int r = 0; r < 16; ++r) acc_m[cb][r] = 0.f;
         }
 
-        // software pipeline over rounds of 64 records: the records are read three rounds ahead, their
-        // upstream rows two (into registers; staged into LDS once the current round's operands have been
-        // read).  Idle lanes of an item's last round (id -1) fetch from an offset outside the buffer: the
-        // load returns ZEROS without touching memory, which is what they have to stage (0 * Inf = NaN: in a
-        // dense product any row that happened to be fetched there could poison the block).
-        constexpr unsigned kNoRow = 0x80000000u;
-        auto fetch_rec = [&](int rr) -> int4 {
-            if (rr + lane >= item.z) return make_int4(-1, 0, 0, 0);
-            return rec[rr + lane];
-        };
-        auto fetch_rows = [&](const int4 &r, u32x4 (&rows)[NPASS]) {
-            const unsigned id = (unsigned)r.x;
-            const unsigned off = r.x < 0 ? kNoRow : __umul24(id >> plan.lp_bits, q_stride) + slice_off;
+        if constexpr (GRP) {
+            // the same software pipeline: records three rounds ahead, rows two; the group's locations and weights ONE round
+            // ahead -- requested in front of the rows, so that waiting for them at the end of the round leaves the rows in
+            // flight -- because a second set in flight (12 registers) does not fit three waves per SIMD
+            constexpr unsigned kNoRow = 0x80000000u;
+            const int *grec = records + (size_t)s * plan.rec_cap;
+            struct Pts { u32x4 xa, xb, w; };         // x0 y0 x1 y1 | x2 y2 x3 y3 | a0 a1 a2 a3
+            const __amdgpu_buffer_rsrc_t rsl =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(gp.loc), 0, gp.loc_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rsa =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(gp.attn), 0, gp.loc_bytes / 2, 0x00020000);
+            // first point of (b, query 0, h, the block's level), points between queries
+            const unsigned pt_base = (unsigned)(((b * Lq) * H + h) * (plan.L * 4) + bg.level * 4);
+            const unsigned pt_q = (unsigned)(H * plan.L * 4);
+            auto fetch_rec = [&](int rr) -> int { return rr + lane < item.z ? grec[rr + lane] : -1; };
+            auto fetch_rows = [&](int r, u32x4 (&rows)[NPASS]) {
+                const unsigned off = r < 0 ? kNoRow : __umul24((unsigned)r >> plan.lp_bits, q_stride) + slice_off;
 #pragma unroll
-            for (int ps = 0; ps < NPASS; ++ps) {
-                const unsigned oj = (unsigned)__shfl((int)off, ps * RPP + jrow, 64) + (unsigned)(piece * 16);
-                rows[ps] = __builtin_amdgcn_raw_buffer_load_b128(rs, oj, 0, 0);
-            }
-        };
-        auto stage_rows = [&](const u32x4 (&rows)[NPASS]) {
-#pragma unroll
-            for (int ps = 0; ps < NPASS; ++ps)
-                *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(gs) + stage_off + ps * RPP * 64) = rows[ps];
-        };
-        // INST: the grad_mask rows of a round's records, and the level weight a_l of this lane's record (0: idle lane)
-        auto fetch_rows_m = [&](const int4 &r, u32x4 (&rows)[NPASS]) -> float {
-            const unsigned q = (unsigned)max(r.x, 0) >> plan.lp_bits;
-            const int lp = max(r.x, 0) & lp_mask;
-            int l_, p_;
-            divmod_small(lp, P, rcp_p, l_, p_);
-            const unsigned off = r.x < 0 ? kNoRow : q * m_q_stride + (unsigned)p_ * m_p_stride + m_slice_off;
-            const float al = r.x < 0 ? 0.f : inst.w_lv[(((size_t)b * Lq + q) * H + h) * LP + lp];
-#pragma unroll
-            for (int ps = 0; ps < NPASS; ++ps) {
-                const unsigned oj = (unsigned)__shfl((int)off, ps * RPP + jrow, 64) + (unsigned)(piece * 16);
-                rows[ps] = __builtin_amdgcn_raw_buffer_load_b128(rsm, oj, 0, 0);
-            }
-            return al;
-        };
-        auto stage_rows_m = [&](const u32x4 (&rows)[NPASS]) {
-#pragma unroll
-            for (int ps = 0; ps < NPASS; ++ps)
-                *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(gs) + kGsM + stage_off + ps * RPP * 64) = rows[ps];
-        };
-        // (requesting the NEXT item's first records here -- an item starts with two dependent round trips, and a
-        // level-0 block at BoxeR-R50 shapes is under four rounds -- costs this kernel seven spilled registers and
-        // 1-3 %; the float32 kernel below, which has the registers, gains 1 % from it)
-        int4 rec_c = fetch_rec(item.y), rec_n = fetch_rec(item.y + R), rec_n2 = fetch_rec(item.y + 2 * R);
-        u32x4 grow_a[NPASS], grow_b[NPASS];
-        u32x4 mrow_a[INST ? NPASS : 1], mrow_b[INST ? NPASS : 1];
-        float al_c = 0.f, al_n = 0.f, al_n2 = 0.f;      // INST: a_l of the records rec_c, rec_n, rec_n2
-        fetch_rows(rec_c, grow_a);
-        if constexpr (INST) al_c = fetch_rows_m(rec_c, mrow_a);
-        stage_rows(grow_a);
-        if constexpr (INST) stage_rows_m(mrow_a);
-        if (item.y + R < item.z) {
-            fetch_rows(rec_n, grow_a);
-            if constexpr (INST) al_n = fetch_rows_m(rec_n, mrow_a);
-        }
-        // one round: `next` holds the rows of round rr + R (staged at the end), `ahead` receives those of rr + 2 R
-        auto round = [&](int rr, const u32x4 (&next)[NPASS], u32x4 (&ahead)[NPASS],
-                         const u32x4 (&next_m)[INST ? NPASS : 1], u32x4 (&ahead_m)[INST ? NPASS : 1]) {
-            const bool more = rr + R < item.z;     // wave-uniform
-            int4 rec_n3 = make_int4(-1, 0, 0, 0);
-            if (rr + 2 * R < item.z) {
-                fetch_rows(rec_n2, ahead);
-                if constexpr (INST) al_n2 = fetch_rows_m(rec_n2, ahead_m);
-                rec_n3 = fetch_rec(rr + 3 * R);
-            }
-            // ---- lane = record: its <= 4 weights go to A^T[pixel][lane] as hi + lo 16-bit terms
-            const float x = __int_as_float(rec_c.y), y = __int_as_float(rec_c.z);
-            const float a = INST ? __int_as_float(rec_c.w) * kWScale : __int_as_float(rec_c.w);
-            float h_im, w_im;
-            {
-#pragma clang fp contract(off)                   // two roundings, as in locate()
-                h_im = y * Hf - 0.5f;
-                w_im = x * Wf - 0.5f;
-            }
-            const float yf = floorf(h_im), xf = floorf(w_im);
-            const float lh = h_im - yf, lw = w_im - xf;
-            // footprint corner relative to the block; idle lanes: outside
-            const int py = rec_c.x >= 0 ? (int)yf - oy : -2, px = (int)xf - ox;
-            const float hh = 1.f - lh, hw = 1.f - lw;
-            const float ha = hh * a, la = lh * a;
-            const float w0 = ha * hw, w1 = ha * lw, w2 = la * hw, w3 = la * lw;
-            const unsigned hi01 = H16::pack(w0, w1), hi23 = H16::pack(w2, w3);
-            const unsigned lo01 = H16::pack(w0 - H16::lo(hi01), w1 - H16::hi(hi01));
-            const unsigned lo23 = H16::pack(w2 - H16::lo(hi23), w3 - H16::hi(hi23));
-            // INST: the same four bilinear weights times a_l, for the grad_mask rows
-            unsigned mhi01 = 0u, mhi23 = 0u, mlo01 = 0u, mlo23 = 0u;
-            if constexpr (INST) {
-                const float am = al_c * kWScale;
-                const float hm = hh * am, lm = lh * am;
-                const float m0 = hm * hw, m1 = hm * lw, m2 = lm * hw, m3 = lm * lw;
-                mhi01 = H16::pack(m0, m1); mhi23 = H16::pack(m2, m3);
-                mlo01 = H16::pack(m0 - H16::lo(mhi01), m1 - H16::hi(mhi01));
-                mlo23 = H16::pack(m2 - H16::lo(mhi23), m3 - H16::hi(mhi23));
-            }
-            // byte offsets of the corners' rows / columns inside A^T, kBig when outside the block (idle lanes: all)
-            const int r0 = (unsigned)py < (unsigned)bh ? __mul24(py, BW * ASB) : kBig;
-            const int r1 = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * ASB) + BW * ASB : kBig;
-            const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, ASB) + 2 * lane : kBig;
-            const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, ASB) + 2 * lane + ASB : kBig;
-            const int dump = kDump + 2 * lane;
-            const int slot[4] = {min(r0 + c0, dump), min(r0 + c1, dump), min(r1 + c0, dump), min(r1 + c1, dump)};
-            auto put = [&](int k, unsigned short v) {
-                *reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(at) + slot[k]) = v;
-            };
-            auto put_m = [&](int k, unsigned short v) {      // INST: the tile of the w_k a_l entries, same slots
-                *reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(at) + kAtL + slot[k]) = v;
-            };
-            put(0, (unsigned short)(hi01 & 0xffffu)); put(1, (unsigned short)(hi01 >> 16));
-            put(2, (unsigned short)(hi23 & 0xffffu)); put(3, (unsigned short)(hi23 >> 16));
-            if constexpr (INST) {
-                put_m(0, (unsigned short)(mhi01 & 0xffffu)); put_m(1, (unsigned short)(mhi01 >> 16));
-                put_m(2, (unsigned short)(mhi23 & 0xffffu)); put_m(3, (unsigned short)(mhi23 >> 16));
-            }
-            wave_lds_sync();
-            // ---- the product: 4 K-steps of 16 records per 32-channel block, hi term then lo term
-            tr_h16x8 g[R / 16][NCB], gm[INST ? R / 16 : 1][NCB];
-#pragma unroll
-            for (int t = 0; t < R / 16; ++t) {
-                const tr_h16x8 p_hi = __builtin_bit_cast(
-                    tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + a_off + 32 * t));
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) {
-                    const uint2 g0 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024);
-                    const uint2 g1 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024 + 256);
-                    g[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
-                    acc[cb] = H16::mfma32x32x16(g[t][cb], p_hi, acc[cb]);
+                for (int ps = 0; ps < NPASS; ++ps) {
+                    const unsigned oj = (unsigned)__shfl((int)off, ps * RPP + jrow, 64) + (unsigned)(piece * 16);
+                    rows[ps] = __builtin_amdgcn_raw_buffer_load_b128(rs, oj, 0, 0);
                 }
-                if constexpr (INST) {
-                    const tr_h16x8 pm_hi = __builtin_bit_cast(
-                        tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + kAtL + a_off + 32 * t));
+            };
+            auto fetch_pts = [&](int r, Pts &p) {
+                const unsigned pt = __umul24((unsigned)r >> plan.lp_bits, pt_q) + pt_base;
+                const unsigned ol = r < 0 ? kNoRow : pt << 3, oa = r < 0 ? kNoRow : pt << 2;
+                p.xa = __builtin_amdgcn_raw_buffer_load_b128(rsl, ol, 0, 0);
+                p.xb = __builtin_amdgcn_raw_buffer_load_b128(rsl, ol + 16u, 0, 0);
+                p.w = __builtin_amdgcn_raw_buffer_load_b128(rsa, oa, 0, 0);
+            };
+            auto stage_rows = [&](const u32x4 (&rows)[NPASS]) {
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps)
+                    *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(gs) + stage_off + ps * RPP * 64) = rows[ps];
+            };
+            // this lane's column of the float32 tile (record = lane), and the 8 consecutive records of pixel `col` it reads
+            const int lane_at = (lane >> 2) * kGrpQuadB + (lane & 3) * 4;
+            unsigned f_off = (unsigned)(2 * kb * kGrpQuadB + col * 16);
+            asm volatile("" : "+v"(f_off));
+            int rec_c = fetch_rec(item.y), rec_n = fetch_rec(item.y + R), rec_n2 = fetch_rec(item.y + 2 * R);
+            u32x4 grow_a[NPASS], grow_b[NPASS];
+            Pts pc{}, pn{};
+            fetch_pts(rec_c, pc);
+            fetch_rows(rec_c, grow_a);
+            stage_rows(grow_a);
+            if (item.y + R < item.z) fetch_rows(rec_n, grow_a);
+            auto round = [&](int rr, const u32x4 (&next)[NPASS], u32x4 (&ahead)[NPASS]) {
+                const bool more = rr + R < item.z;     // wave-uniform
+                int rec_n3 = -1;
+                if (more) fetch_pts(rec_n, pn);
+                if (rr + 2 * R < item.z) {
+                    fetch_rows(rec_n2, ahead);
+                    rec_n3 = fetch_rec(rr + 3 * R);
+                }
+                // ---- lane = group: the corner weights of its masked-in points, summed per pixel in float32
+                const int mask = rec_c < 0 ? 0 : rec_c & ((1 << kGroupMaskBits) - 1);
+                const unsigned xs[4] = {pc.xa.x, pc.xa.z, pc.xb.x, pc.xb.z}, ys[4] = {pc.xa.y, pc.xa.w, pc.xb.y, pc.xb.w};
+                const unsigned as[4] = {pc.w.x, pc.w.y, pc.w.z, pc.w.w};
+                float w4[4][4];
+                int slot[4][4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float x = __uint_as_float(xs[k]), y = __uint_as_float(ys[k]), a = __uint_as_float(as[k]);
+                    float h_im, w_im;
+                    {
+#pragma clang fp contract(off)                   // two roundings, as in locate()
+                        h_im = y * Hf - 0.5f;
+                        w_im = x * Wf - 0.5f;
+                    }
+                    const float yf = floorf(h_im), xf = floorf(w_im);
+                    const float lh = h_im - yf, lw = w_im - xf;
+                    // footprint corner relative to the block; points the record does not speak for: outside
+                    const int py = (mask >> k & 1) ? (int)yf - oy : -2, px = (int)xf - ox;
+                    const float hh = 1.f - lh, hw = 1.f - lw;
+                    const float ha = hh * a, la = lh * a;
+                    w4[k][0] = ha * hw; w4[k][1] = ha * lw; w4[k][2] = la * hw; w4[k][3] = la * lw;
+                    // byte offsets of the corners' pixels (16 bytes each, 8 a block row), kBig when outside the block
+                    const int r0 = (unsigned)py < (unsigned)bh ? __mul24(py, BW * 16) : kBig;
+                    const int r1 = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * 16) + BW * 16 : kBig;
+                    const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, 16) : kBig;
+                    const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, 16) + 16 : kBig;
+                    slot[k][0] = lane_at + min(r0 + c0, PB * 16); slot[k][1] = lane_at + min(r0 + c1, PB * 16);
+                    slot[k][2] = lane_at + min(r1 + c0, PB * 16); slot[k][3] = lane_at + min(r1 + c1, PB * 16);
+                }
+                // The four corners of ONE point are four pixels (or the dump pixel, whose content nobody reads): point 0 is
+                // stored into the cleared column, every further point reads its four slots, adds and stores them -- three
+                // round trips of four independent LDS accesses, in the wave's issue order.  (ds_add_f32 instead -- sixteen
+                // LDS float atomics a round -- made this kernel four times slower than the point flavour.)
+                auto cell = [&](int k, int j) -> float * {
+                    return reinterpret_cast<float *>(__builtin_assume_aligned(reinterpret_cast<char *>(at) + slot[k][j], 4));
+                };
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *cell(0, j) = w4[0][j];
+#pragma unroll
+                for (int k = 1; k < 4; ++k) {
+                    wave_lds_sync();
+                    float old[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) old[j] = *cell(k, j);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) *cell(k, j) = old[j] + w4[k][j];
+                }
+                wave_lds_sync();
+                // ---- lane = pixel: its 8 records of every K-step, float32; the tile is cleared behind the read
+                float4 f[R / 16][2];
+#pragma unroll
+                for (int t = 0; t < R / 16; ++t)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        f[t][j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(at) + f_off +
+                                                                    (4 * t + j) * kGrpQuadB);
+                tr_h16x8 g[R / 16][NCB];
+#pragma unroll
+                for (int t = 0; t < R / 16; ++t)
 #pragma unroll
                     for (int cb = 0; cb < NCB; ++cb) {
-                        const uint2 g0 = lds_read_tr16(gs, kGsM + tr_off + cb * GPL + t * 1024);
-                        const uint2 g1 = lds_read_tr16(gs, kGsM + tr_off + cb * GPL + t * 1024 + 256);
-                        gm[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
-                        acc_m[cb] = H16::mfma32x32x16(gm[t][cb], pm_hi, acc_m[cb]);
+                        const uint2 g0 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024);
+                        const uint2 g1 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024 + 256);
+                        g[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
+                    }
+                wave_lds_sync();
+#pragma unroll
+                for (int t = 0; t < R / 16; ++t)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        *reinterpret_cast<float4 *>(reinterpret_cast<char *>(at) + f_off + (4 * t + j) * kGrpQuadB) =
+                            make_float4(0.f, 0.f, 0.f, 0.f);
+                // ---- hi / lo split of the sums, the product: 4 K-steps of 16 records per 32-channel block
+#pragma unroll
+                for (int t = 0; t < R / 16; ++t) {
+                    const float v[8] = {f[t][0].x, f[t][0].y, f[t][0].z, f[t][0].w, f[t][1].x, f[t][1].y, f[t][1].z, f[t][1].w};
+                    unsigned hi[4], lo[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        hi[i] = H16::pack(v[2 * i], v[2 * i + 1]);
+                        lo[i] = H16::pack(v[2 * i] - H16::lo(hi[i]), v[2 * i + 1] - H16::hi(hi[i]));
+                    }
+                    const tr_h16x8 p_hi = __builtin_bit_cast(tr_h16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
+                    const tr_h16x8 p_lo = __builtin_bit_cast(tr_h16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
+#pragma unroll
+                    for (int cb = 0; cb < NCB; ++cb) {
+                        acc[cb] = H16::mfma32x32x16(g[t][cb], p_hi, acc[cb]);
+                        acc[cb] = H16::mfma32x32x16(g[t][cb], p_lo, acc[cb]);
                     }
                 }
+                if (more) {          // the next round's rows and points have arrived
+                    stage_rows(next);
+                    pc = pn;
+                    rec_c = rec_n; rec_n = rec_n2; rec_n2 = rec_n3;
+                }
+                wave_lds_sync();
+            };
+            for (int rr = item.y; rr < item.z; rr += 2 * R) {
+                round(rr, grow_a, grow_b);
+                if (rr + R >= item.z) break;
+                round(rr + R, grow_b, grow_a);
             }
-            wave_lds_sync();                         // a wave's LDS operations execute in order
-            put(0, (unsigned short)(lo01 & 0xffffu)); put(1, (unsigned short)(lo01 >> 16));
-            put(2, (unsigned short)(lo23 & 0xffffu)); put(3, (unsigned short)(lo23 >> 16));
-            if constexpr (INST) {
-                put_m(0, (unsigned short)(mlo01 & 0xffffu)); put_m(1, (unsigned short)(mlo01 >> 16));
-                put_m(2, (unsigned short)(mlo23 & 0xffffu)); put_m(3, (unsigned short)(mlo23 >> 16));
+        } else {
+            // software pipeline over rounds of 64 records: the records are read three rounds ahead, their
+            // upstream rows two (into registers; staged into LDS once the current round's operands have been
+            // read).  Idle lanes of an item's last round (id -1) fetch from an offset outside the buffer: the
+            // load returns ZEROS without touching memory, which is what they have to stage (0 * Inf = NaN: in a
+            // dense product any row that happened to be fetched there could poison the block).
+            constexpr unsigned kNoRow = 0x80000000u;
+            auto fetch_rec = [&](int rr) -> int4 {
+                if (rr + lane >= item.z) return make_int4(-1, 0, 0, 0);
+                return rec[rr + lane];
+            };
+            auto fetch_rows = [&](const int4 &r, u32x4 (&rows)[NPASS]) {
+                const unsigned id = (unsigned)r.x;
+                const unsigned off = r.x < 0 ? kNoRow : __umul24(id >> plan.lp_bits, q_stride) + slice_off;
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps) {
+                    const unsigned oj = (unsigned)__shfl((int)off, ps * RPP + jrow, 64) + (unsigned)(piece * 16);
+                    rows[ps] = __builtin_amdgcn_raw_buffer_load_b128(rs, oj, 0, 0);
+                }
+            };
+            auto stage_rows = [&](const u32x4 (&rows)[NPASS]) {
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps)
+                    *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(gs) + stage_off + ps * RPP * 64) = rows[ps];
+            };
+            // INST: the grad_mask rows of a round's records, and the level weight a_l of this lane's record (0: idle lane)
+            auto fetch_rows_m = [&](const int4 &r, u32x4 (&rows)[NPASS]) -> float {
+                const unsigned q = (unsigned)max(r.x, 0) >> plan.lp_bits;
+                const int lp = max(r.x, 0) & lp_mask;
+                int l_, p_;
+                divmod_small(lp, P, rcp_p, l_, p_);
+                const unsigned off = r.x < 0 ? kNoRow : q * m_q_stride + (unsigned)p_ * m_p_stride + m_slice_off;
+                const float al = r.x < 0 ? 0.f : inst.w_lv[(((size_t)b * Lq + q) * H + h) * LP + lp];
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps) {
+                    const unsigned oj = (unsigned)__shfl((int)off, ps * RPP + jrow, 64) + (unsigned)(piece * 16);
+                    rows[ps] = __builtin_amdgcn_raw_buffer_load_b128(rsm, oj, 0, 0);
+                }
+                return al;
+            };
+            auto stage_rows_m = [&](const u32x4 (&rows)[NPASS]) {
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps)
+                    *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(gs) + kGsM + stage_off + ps * RPP * 64) = rows[ps];
+            };
+            // (requesting the NEXT item's first records here -- an item starts with two dependent round trips, and a
+            // level-0 block at BoxeR-R50 shapes is under four rounds -- costs this kernel seven spilled registers and
+            // 1-3 %; the float32 kernel below, which has the registers, gains 1 % from it)
+            int4 rec_c = fetch_rec(item.y), rec_n = fetch_rec(item.y + R), rec_n2 = fetch_rec(item.y + 2 * R);
+            u32x4 grow_a[NPASS], grow_b[NPASS];
+            u32x4 mrow_a[INST ? NPASS : 1], mrow_b[INST ? NPASS : 1];
+            float al_c = 0.f, al_n = 0.f, al_n2 = 0.f;      // INST: a_l of the records rec_c, rec_n, rec_n2
+            fetch_rows(rec_c, grow_a);
+            if constexpr (INST) al_c = fetch_rows_m(rec_c, mrow_a);
+            stage_rows(grow_a);
+            if constexpr (INST) stage_rows_m(mrow_a);
+            if (item.y + R < item.z) {
+                fetch_rows(rec_n, grow_a);
+                if constexpr (INST) al_n = fetch_rows_m(rec_n, mrow_a);
             }
-            wave_lds_sync();
-#pragma unroll
-            for (int t = 0; t < R / 16; ++t) {
-                const tr_h16x8 p_lo = __builtin_bit_cast(
-                    tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + a_off + 32 * t));
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb)
-                    acc[cb] = H16::mfma32x32x16(g[t][cb], p_lo, acc[cb]);
+            // one round: `next` holds the rows of round rr + R (staged at the end), `ahead` receives those of rr + 2 R
+            auto round = [&](int rr, const u32x4 (&next)[NPASS], u32x4 (&ahead)[NPASS],
+                             const u32x4 (&next_m)[INST ? NPASS : 1], u32x4 (&ahead_m)[INST ? NPASS : 1]) {
+                const bool more = rr + R < item.z;     // wave-uniform
+                int4 rec_n3 = make_int4(-1, 0, 0, 0);
+                if (rr + 2 * R < item.z) {
+                    fetch_rows(rec_n2, ahead);
+                    if constexpr (INST) al_n2 = fetch_rows_m(rec_n2, ahead_m);
+                    rec_n3 = fetch_rec(rr + 3 * R);
+                }
+                // ---- lane = record: its <= 4 weights go to A^T[pixel][lane] as hi + lo 16-bit terms
+                const float x = __int_as_float(rec_c.y), y = __int_as_float(rec_c.z);
+                const float a = INST ? __int_as_float(rec_c.w) * kWScale : __int_as_float(rec_c.w);
+                float h_im, w_im;
+                {
+#pragma clang fp contract(off)                   // two roundings, as in locate()
+                    h_im = y * Hf - 0.5f;
+                    w_im = x * Wf - 0.5f;
+                }
+                const float yf = floorf(h_im), xf = floorf(w_im);
+                const float lh = h_im - yf, lw = w_im - xf;
+                // footprint corner relative to the block; idle lanes: outside
+                const int py = rec_c.x >= 0 ? (int)yf - oy : -2, px = (int)xf - ox;
+                const float hh = 1.f - lh, hw = 1.f - lw;
+                const float ha = hh * a, la = lh * a;
+                const float w0 = ha * hw, w1 = ha * lw, w2 = la * hw, w3 = la * lw;
+                const unsigned hi01 = H16::pack(w0, w1), hi23 = H16::pack(w2, w3);
+                const unsigned lo01 = H16::pack(w0 - H16::lo(hi01), w1 - H16::hi(hi01));
+                const unsigned lo23 = H16::pack(w2 - H16::lo(hi23), w3 - H16::hi(hi23));
+                // INST: the same four bilinear weights times a_l, for the grad_mask rows
+                unsigned mhi01 = 0u, mhi23 = 0u, mlo01 = 0u, mlo23 = 0u;
                 if constexpr (INST) {
-                    const tr_h16x8 pm_lo = __builtin_bit_cast(
-                        tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + kAtL + a_off + 32 * t));
+                    const float am = al_c * kWScale;
+                    const float hm = hh * am, lm = lh * am;
+                    const float m0 = hm * hw, m1 = hm * lw, m2 = lm * hw, m3 = lm * lw;
+                    mhi01 = H16::pack(m0, m1); mhi23 = H16::pack(m2, m3);
+                    mlo01 = H16::pack(m0 - H16::lo(mhi01), m1 - H16::hi(mhi01));
+                    mlo23 = H16::pack(m2 - H16::lo(mhi23), m3 - H16::hi(mhi23));
+                }
+                // byte offsets of the corners' rows / columns inside A^T, kBig when outside the block (idle lanes: all)
+                const int r0 = (unsigned)py < (unsigned)bh ? __mul24(py, BW * ASB) : kBig;
+                const int r1 = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * ASB) + BW * ASB : kBig;
+                const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, ASB) + 2 * lane : kBig;
+                const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, ASB) + 2 * lane + ASB : kBig;
+                const int dump = kDump + 2 * lane;
+                const int slot[4] = {min(r0 + c0, dump), min(r0 + c1, dump), min(r1 + c0, dump), min(r1 + c1, dump)};
+                auto put = [&](int k, unsigned short v) {
+                    *reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(at) + slot[k]) = v;
+                };
+                auto put_m = [&](int k, unsigned short v) {      // INST: the tile of the w_k a_l entries, same slots
+                    *reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(at) + kAtL + slot[k]) = v;
+                };
+                put(0, (unsigned short)(hi01 & 0xffffu)); put(1, (unsigned short)(hi01 >> 16));
+                put(2, (unsigned short)(hi23 & 0xffffu)); put(3, (unsigned short)(hi23 >> 16));
+                if constexpr (INST) {
+                    put_m(0, (unsigned short)(mhi01 & 0xffffu)); put_m(1, (unsigned short)(mhi01 >> 16));
+                    put_m(2, (unsigned short)(mhi23 & 0xffffu)); put_m(3, (unsigned short)(mhi23 >> 16));
+                }
+                wave_lds_sync();
+                // ---- the product: 4 K-steps of 16 records per 32-channel block, hi term then lo term
+                tr_h16x8 g[R / 16][NCB], gm[INST ? R / 16 : 1][NCB];
+#pragma unroll
+                for (int t = 0; t < R / 16; ++t) {
+                    const tr_h16x8 p_hi = __builtin_bit_cast(
+                        tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + a_off + 32 * t));
+#pragma unroll
+                    for (int cb = 0; cb < NCB; ++cb) {
+                        const uint2 g0 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024);
+                        const uint2 g1 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024 + 256);
+                        g[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
+                        acc[cb] = H16::mfma32x32x16(g[t][cb], p_hi, acc[cb]);
+                    }
+                    if constexpr (INST) {
+                        const tr_h16x8 pm_hi = __builtin_bit_cast(
+                            tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + kAtL + a_off + 32 * t));
+#pragma unroll
+                        for (int cb = 0; cb < NCB; ++cb) {
+                            const uint2 g0 = lds_read_tr16(gs, kGsM + tr_off + cb * GPL + t * 1024);
+                            const uint2 g1 = lds_read_tr16(gs, kGsM + tr_off + cb * GPL + t * 1024 + 256);
+                            gm[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
+                            acc_m[cb] = H16::mfma32x32x16(gm[t][cb], pm_hi, acc_m[cb]);
+                        }
+                    }
+                }
+                wave_lds_sync();                         // a wave's LDS operations execute in order
+                put(0, (unsigned short)(lo01 & 0xffffu)); put(1, (unsigned short)(lo01 >> 16));
+                put(2, (unsigned short)(lo23 & 0xffffu)); put(3, (unsigned short)(lo23 >> 16));
+                if constexpr (INST) {
+                    put_m(0, (unsigned short)(mlo01 & 0xffffu)); put_m(1, (unsigned short)(mlo01 >> 16));
+                    put_m(2, (unsigned short)(mlo23 & 0xffffu)); put_m(3, (unsigned short)(mlo23 >> 16));
+                }
+                wave_lds_sync();
+#pragma unroll
+                for (int t = 0; t < R / 16; ++t) {
+                    const tr_h16x8 p_lo = __builtin_bit_cast(
+                        tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + a_off + 32 * t));
 #pragma unroll
                     for (int cb = 0; cb < NCB; ++cb)
-                        acc_m[cb] = H16::mfma32x32x16(gm[t][cb], pm_lo, acc_m[cb]);
+                        acc[cb] = H16::mfma32x32x16(g[t][cb], p_lo, acc[cb]);
+                    if constexpr (INST) {
+                        const tr_h16x8 pm_lo = __builtin_bit_cast(
+                            tr_h16x8, *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(at) + kAtL + a_off + 32 * t));
+#pragma unroll
+                        for (int cb = 0; cb < NCB; ++cb)
+                            acc_m[cb] = H16::mfma32x32x16(gm[t][cb], pm_lo, acc_m[cb]);
+                    }
                 }
-            }
-            wave_lds_sync();
-            // ---- clear this round's weights, stage the next round's rows (they have arrived)
+                wave_lds_sync();
+                // ---- clear this round's weights, stage the next round's rows (they have arrived)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) put(k, (unsigned short)0);
-            if constexpr (INST) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) put_m(k, (unsigned short)0);
-            }
-            if (more) {
-                stage_rows(next);
+                for (int k = 0; k < 4; ++k) put(k, (unsigned short)0);
                 if constexpr (INST) {
-                    stage_rows_m(next_m);
-                    al_c = al_n; al_n = al_n2;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) put_m(k, (unsigned short)0);
                 }
-                rec_c = rec_n; rec_n = rec_n2; rec_n2 = rec_n3;
+                if (more) {
+                    stage_rows(next);
+                    if constexpr (INST) {
+                        stage_rows_m(next_m);
+                        al_c = al_n; al_n = al_n2;
+                    }
+                    rec_c = rec_n; rec_n = rec_n2; rec_n2 = rec_n3;
+                }
+                wave_lds_sync();
+            };
+            for (int rr = item.y; rr < item.z; rr += 2 * R) {       // (two rounds per trip: the row buffers swap roles, no copies)
+                round(rr, grow_a, grow_b, mrow_a, mrow_b);
+                if (rr + R >= item.z) break;
+                round(rr + R, grow_b, grow_a, mrow_b, mrow_a);
             }
-            wave_lds_sync();
-        };
-        for (int rr = item.y; rr < item.z; rr += 2 * R) {       // (two rounds per trip: the row buffers swap roles, no copies)
-            round(rr, grow_a, grow_b, mrow_a, mrow_b);
-            if (rr + R >= item.z) break;
-            round(rr + R, grow_b, grow_a, mrow_b, mrow_a);
         }
         if constexpr (INST) {          // one sum per pixel and channel; f16: the weights' scale taken back (exact)
 #pragma unroll

@@ -28,7 +28,9 @@ namespace boxattn {
 // records land in few bins, in runs -- 27 -> 24 us for the fill pass.
 // No global atomics anywhere in the binning (they cost ~20 us per pass: ~200 k single-lane atomics on 226
 // cache lines), and the record order is deterministic.
-template <int THREADS, int BW, int BH, bool FILL, bool WIDE, int PT>
+// GRP (16-bit box attention, PT = 4): one 4-byte group record per (query, level, block) -- group_blocks
+// (boxattn_binplan.h) decides count and fill alike.
+template <int THREADS, int BW, int BH, bool FILL, bool WIDE, int PT, bool GRP = false>
 __device__ __forceinline__ void bin_pass_body(int *hist, BinLevel *s_lv, const float *__restrict__ loc,
                                               const float *__restrict__ w_sp, const BinPlan &plan, int H,
                                               int Lq, int P, int q_per_wg, int n_wg, bool interleave,
@@ -45,6 +47,7 @@ __device__ __forceinline__ void bin_pass_body(int *hist, BinLevel *s_lv, const f
 
     const float2 *loc2 = reinterpret_cast<const float2 *>(loc);
     static_assert(PT == 1 || PT == 4, "points per thread and step");
+    static_assert(!GRP || (PT == 4 && !WIDE), "a group is the four points of one (query, level)");
 #ifndef BOXATTN_TUNE_BIN_U
 #define BOXATTN_TUNE_BIN_U 2
 #endif
@@ -100,7 +103,20 @@ __device__ __forceinline__ void bin_pass_body(int *hist, BinLevel *s_lv, const f
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (g0 + u * THREADS >= n_grp) break;
-            const BinLevel lv = s_lv[(int)(((float)t.lp0[u] + 0.5f) * rcp_p)];   // level = lp / P
+            const int level = (int)(((float)t.lp0[u] + 0.5f) * rcp_p);            // level = lp / P
+            const BinLevel lv = s_lv[level];
+            if constexpr (GRP) {
+                unsigned set[4];
+                group_blocks(t.xy[u], lv, true, set);
+                const int idq = ((q0 + t.ql[u] * qstep) << plan.lp_bits) | (level << kGroupMaskBits);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    for_set_blocks(set[j], lv.nbx, [&](int blk, int mask) {
+                        const int slot = atomicAdd(&hist[blk], 1);                   // LDS
+                        if constexpr (FILL) rec[slot] = idq | mask;
+                    });
+                continue;
+            }
             // (One LDS atomic per touched block and (query, level) GROUP -- adding how many of its four points have a
             // record there -- instead of one per point and block was built and measured: the 2 x 2 block bookkeeping
             // costs more vector instructions than the atomics it saves; a fat rider's count pass 21 -> 26 us.)
@@ -152,7 +168,8 @@ __device__ __forceinline__ void bin_pass_body(int *hist, BinLevel *s_lv, const f
 // riders
 // ---------------------------------------------------------------------------------------
 enum { kRideWide = 1, kRideInterleave = 2, kRidePt4 = 4,
-       kRideSpec = 8 };     // one-pass fill into guessed bin ranges (boxattn_spec.h); wide records, contiguous queries
+       kRideSpec = 8,       // one-pass fill into guessed bin ranges (boxattn_spec.h); wide records, contiguous queries
+       kRideGroup = 16 };   // group records (with kRidePt4, without kRideWide): only host kernels instantiated with GRP carry the code
 constexpr int kRideMaxBlocks = 3072;      // blocks per slice the riders' LDS histogram is built for (12 KB; beyond kScanThreads the
                                           // slice's last arriver scans in two passes over it: scan_blocks_big_body)
 constexpr int kRideLdsInts = kRideMaxBlocks + 8 * (int)(sizeof(BinLevel) / sizeof(int)) + 4 * 4 + 2;
@@ -256,16 +273,18 @@ __device__ __forceinline__ void bin_count_ride(const BinRide r, unsigned id, int
     RIDE_STAMP(4);
 }
 
-template <int THREADS> __device__ __forceinline__ void bin_fill_spec_ride(const BinRide r, unsigned id, int *lds);   // boxattn_spec.h
+template <int THREADS, bool GRP = false>
+__device__ __forceinline__ void bin_fill_spec_ride(const BinRide r, unsigned id, int *lds);   // boxattn_spec.h
 
 // Fill rider `id` = (slice, bin workgroup); bin workgroup 0 of a slice also clears the slice's combine tickets.
-template <int THREADS>
+// GRP: the host kernel serves 16-bit box attention, whose calls may ask for group records (kRideGroup).
+template <int THREADS, bool GRP = false>
 __device__ __forceinline__ void bin_fill_ride(const BinRide r, unsigned id, int *lds)
 {
     if (id >= r.grid.n_riders) return;
     if (BOXATTN_TUNE_RIDE_PRIO) __builtin_amdgcn_s_setprio(BOXATTN_TUNE_RIDE_PRIO);
     if (r.flavour & kRideSpec) {        // one pass into guessed ranges, then the chain of the slice's last rider
-        bin_fill_spec_ride<THREADS>(r, id, lds);
+        bin_fill_spec_ride<THREADS, GRP>(r, id, lds);
         return;
     }
     RIDE_STAMP(5);
@@ -277,7 +296,10 @@ __device__ __forceinline__ void bin_fill_ride(const BinRide r, unsigned id, int 
     const bool inter = (r.flavour & kRideInterleave) != 0;
     if (wg == 0 && r.ctickets)
         for (int k = threadIdx.x; k < plan.nblk; k += THREADS) r.ctickets[(size_t)s * plan.nblk + k] = 0;
-    if ((r.flavour & kRideWide) && (r.flavour & kRidePt4))
+    if (GRP && (r.flavour & kRideGroup))
+        bin_pass_body<THREADS, 8, 4, true, false, 4, GRP>(m.hist, m.lv, r.loc, r.w_sp, plan, r.H, r.Lq, r.P, r.q_per_wg,
+                                                          r.n_wg, inter, r.part, r.subtot, r.offsets, r.records, s, wg);
+    else if ((r.flavour & kRideWide) && (r.flavour & kRidePt4))
         bin_pass_body<THREADS, 8, 4, true, true, 4>(m.hist, m.lv, r.loc, r.w_sp, plan, r.H, r.Lq, r.P, r.q_per_wg,
                                                    r.n_wg, inter, r.part, r.subtot, r.offsets, r.records, s, wg);
     else if (r.flavour & kRideWide)

@@ -87,4 +87,88 @@ __device__ __forceinline__ void touched_blocks(float x, float y, const BinLevel 
     blk[3] = inside && rb != ra && cb != ca ? base_b + cb : -1;
 }
 
+// ---------------------------------------------------------------------------------------
+// group records (16-bit box attention, P == 4): ONE 4-byte record per (query, level, block)
+//   record = (query << BinPlan::lp_bits) | (level << 4) | mask      (negative: idle)
+// mask: which of the group's four points the record speaks for in that block; the accumulate
+// kernel gathers the group's locations and weights by (query, level) and keeps the corners of
+// the masked-in points that lie inside the block.
+// ---------------------------------------------------------------------------------------
+constexpr int kGroupMaskBits = 4, kGroupLevelBits = 3;
+constexpr int kGroupBits = kGroupMaskBits + kGroupLevelBits;      // BinPlan::lp_bits of the group flavour
+static_assert(kMaxBinLevels <= (1 << kGroupLevelBits), "level field of a group record");
+
+// A candidate set: the <= 2 x 2 blocks b, b + 1 (kGrpCc), b + nbx (kGrpCr), b + nbx + 1 (both) and the mask their
+// records carry.  0: the set is empty.
+constexpr unsigned kGrpBlk = (1u << 13) - 1, kGrpIn = 1u << 13, kGrpCc = 1u << 14, kGrpCr = 1u << 15;
+constexpr int kGrpMaskShift = 16;
+
+// Block range of the pixel rectangle [ylo, yhi] x [xlo, xhi] (inside the map) as a candidate set without its mask;
+// wide: the rectangle spans more than 2 x 2 blocks (the set then says nothing).
+__device__ __forceinline__ unsigned rect_set(int ylo, int yhi, int xlo, int xhi, const BinLevel &lv, bool &wide)
+{
+    const int ra = blk_of(ylo, lv.nby, lv.mh), rb = blk_of(yhi, lv.nby, lv.mh);
+    const int ca = blk_of(xlo, lv.nbx, lv.mw), cb = blk_of(xhi, lv.nbx, lv.mw);
+    wide = rb - ra > 1 || cb - ca > 1;
+    return (unsigned)(lv.blk0 + ra * lv.nbx + ca) | kGrpIn | (cb != ca ? kGrpCc : 0u) | (rb != ra ? kGrpCr : 0u);
+}
+
+// THE decision of the group flavour, shared by the count pass, both fills and nothing else: which (block, mask)
+// records the four points xy[0..3] of one (query, level) group get.  Up to four candidate sets:
+//   fast  the bounding rectangle of the footprints of the points that pass the window test (the test that gives a point
+//         any record: touched_blocks) spans <= 2 x 2 blocks: set[0] = that range, mask = the passing points; a block
+//         of the range that no corner touches gets a record that adds nothing;
+//   slow  (wide or rotated boxes, i.i.d. locations) set[k] = touched_blocks of point k, mask = 1 << k: disjoint masks,
+//         so a block two points name is not counted twice.
+// `have` false: no records.  Returns whether the slow path was taken.
+__device__ __forceinline__ bool group_blocks(const float2 (&xy)[4], const BinLevel &lv, bool have, unsigned (&set)[4])
+{
+    int ylo[4], yhi[4], xlo[4], xhi[4];
+    unsigned pass = 0u;
+    int Ylo = INT32_MAX, Yhi = 0, Xlo = INT32_MAX, Xhi = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float h_im, w_im;
+        {
+#pragma clang fp contract(off)                   // two roundings, as in locate()
+            h_im = xy[k].y * (float)lv.H - 0.5f;
+            w_im = xy[k].x * (float)lv.W - 0.5f;
+        }
+        const bool inside = have && h_im > -1.f && w_im > -1.f && h_im < (float)lv.H && w_im < (float)lv.W &&
+                            lv.H > 0 && lv.W > 0;
+        const int y0 = (int)floorf(inside ? h_im : 0.f), x0 = (int)floorf(inside ? w_im : 0.f);
+        // the valid rows / columns of the footprint, as touched_blocks clamps them
+        ylo[k] = max(y0, 0); yhi[k] = min(y0 + 1, lv.H - 1);
+        xlo[k] = max(x0, 0); xhi[k] = min(x0 + 1, lv.W - 1);
+        pass |= inside ? 1u << k : 0u;
+        Ylo = inside ? min(Ylo, ylo[k]) : Ylo; Yhi = inside ? max(Yhi, yhi[k]) : Yhi;
+        Xlo = inside ? min(Xlo, xlo[k]) : Xlo; Xhi = inside ? max(Xhi, xhi[k]) : Xhi;
+    }
+    bool wide;
+    const unsigned fast = rect_set(pass ? Ylo : 0, Yhi, pass ? Xlo : 0, Xhi, lv, wide);
+    const bool slow = pass != 0u && wide;
+    set[0] = pass && !slow ? fast | pass << kGrpMaskShift : 0u;
+    set[1] = set[2] = set[3] = 0u;
+    if (__builtin_amdgcn_ballot_w64(slow) != 0ull) {      // wave-uniform: the model's groups are nearly all fast
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            bool w_;
+            const unsigned one = rect_set(ylo[k], yhi[k], xlo[k], xhi[k], lv, w_);
+            if (slow) set[k] = pass >> k & 1u ? one | 1u << (kGrpMaskShift + k) : 0u;
+        }
+    }
+    return slow;
+}
+
+// visits the blocks of a candidate set: f(block, mask)
+template <typename F> __device__ __forceinline__ void for_set_blocks(unsigned set, int nbx, F &&f)
+{
+    const int b0 = (int)(set & kGrpBlk), mask = (int)(set >> kGrpMaskShift);
+    const bool in = (set & kGrpIn) != 0u, cc = (set & kGrpCc) != 0u, cr = (set & kGrpCr) != 0u;
+    if (in) f(b0, mask);
+    if (in && cc) f(b0 + 1, mask);
+    if (in && cr) f(b0 + nbx, mask);
+    if (in && cc && cr) f(b0 + nbx + 1, mask);
+}
+
 }  // namespace boxattn

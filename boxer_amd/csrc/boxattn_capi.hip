@@ -51,7 +51,11 @@ enum { kOptBinChunk = 10,     // records per work item of the accumulate kernels
        kOptInstAcc16 = 23,    // 16-bit instance attention, C = 16 / 32 / 64, accumulate: 0 default (the matrix cores from
                               // kInstTrMinPoints points a slice), 1 VALU list walk (4-byte records: the parity cross-check),
                               // 2 the matrix cores (binned_accumulate_tr_kernel<ST, C, true>) wherever the shape is eligible
-       kNumOpts = 24 };
+       kOptGroupRecords = 24, // 16-bit box attention, P == 4, matrix-core accumulate: the records of the binned backward.  0 default
+                              // (group_default: the encoder shapes that passed the step rule),
+                              // 1 point records {id, x, y, weight}, 2 group records (one int per (query, level, block))
+                              // wherever the shape is eligible (record_kind)
+       kNumOpts = 25 };
 // (round 6 removed the keys whose non-default values had lost their A/B: 12 / 13 window margins, 17 staged forward off,
 // 21 staged float32 kernels off -- 11 = 1 switches every window-staged kernel off)
 std::atomic<int> g_opt[kNumOpts];      // 0 = default
@@ -59,7 +63,7 @@ inline int opt(int k) { return g_opt[k].load(std::memory_order_relaxed); }
 inline bool opt_live(int k)
 {
     return k == kOptBinChunk || k == kOptDense || k == kOptRiders || k == kOptAccF32 || k == kOptRideShift ||
-           k == kOptWideBox || k == kOptInstAcc16;
+           k == kOptWideBox || k == kOptInstAcc16 || k == kOptGroupRecords;
 }
 #ifndef BOXATTN_RIDE_SHIFT_COUNT
 #define BOXATTN_RIDE_SHIFT_COUNT 0     // count riders: all in front of the forward kernel's grid (measured: interleaving
@@ -609,12 +613,21 @@ inline AccKind acc_kind_at(const Dims &d, const void *grad_mask, const void *w_l
     }
     return acc;
 }
-inline int bin_flavour(AccKind acc, const Dims &d, const float *loc, const float *w_sp)
+inline int bin_flavour(AccKind acc, const Dims &d, const float *loc, const float *w_sp, RecKind rec = kRecPoint)
 {
     const bool wide = acc != kAccValu;
     // four points per thread where the layout allows 16-byte loads of a (query, level)'s points
     const bool pt4 = d.P % 4 == 0 && aligned(loc, 16) && (!wide || aligned(w_sp, 16));
+    if (rec == kRecGroup) return kRideGroup | kRidePt4;       // (record_kind_at asked for the alignment)
     return (wide ? kRideWide : kRideInterleave) | (pt4 ? kRidePt4 : 0);
+}
+// The record format of a CALL: record_kind of its dimensions where its locations and weights allow the 16-byte loads of
+// a whole group (the kRidePt4 condition); else point records
+template <typename ST, bool INST>
+inline RecKind record_kind_at(AccKind acc, const Dims &d, const float *loc, const float *w_sp)
+{
+    return acc == kAccTr && record_kind<ST, INST>(d) == kRecGroup && aligned(loc, 16) && aligned(w_sp, 16) ? kRecGroup
+                                                                                                           : kRecPoint;
 }
 inline BinRide make_ride(const float *loc, const float *w_sp, const Dims &d, const BinPlan &plan,
                          const PlanLayout &pl, char *pbuf, const ScratchLayout *sl, char *sbuf, int flavour,
@@ -652,13 +665,14 @@ inline void launch_binning(int flavour, const float *loc, const float *w_sp, con
     const dim3 bgrid(w.n_wg, ns);
     const size_t bsh = ((size_t)plan.nblk + 1) * sizeof(int);
     const int inter = (flavour & kRideInterleave) ? 1 : 0;
-    const bool wide = (flavour & kRideWide) != 0, pt4 = (flavour & kRidePt4) != 0;
+    const bool wide = (flavour & kRideWide) != 0, pt4 = (flavour & kRidePt4) != 0, grp = (flavour & kRideGroup) != 0;
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdBin], st);
-#define BOXATTN_BIN(FILL_, WIDE_, PT_)                                                              \
-    hipLaunchKernelGGL((bin_kernel<BW, BH, FILL_, WIDE_, PT_>), bgrid, dim3(kBinThreads), bsh, st, loc, w_sp, \
+#define BOXATTN_BIN(FILL_, WIDE_, PT_, ...)                                                         \
+    hipLaunchKernelGGL((bin_kernel<BW, BH, FILL_, WIDE_, PT_, ##__VA_ARGS__>), bgrid, dim3(kBinThreads), bsh, st, loc, w_sp, \
                        plan, d.H, d.Lq, d.P, w.q_per_wg, w.n_wg, inter, part, subtot, offsets, records, ctickets)
     if (stages & kBinCount) {
-        if (pt4) BOXATTN_BIN(false, false, 4); else BOXATTN_BIN(false, false, 1);
+        if (grp) BOXATTN_BIN(false, false, 4, true);
+        else if (pt4) BOXATTN_BIN(false, false, 4); else BOXATTN_BIN(false, false, 1);
         if (plan.zero_workers > 0)         // sparse map: the zero workers' geometry table is part of the plan
             hipLaunchKernelGGL(zero_geo_kernel, dim3((plan.nblk + 255) / 256), dim3(256), 0, st, plan,
                                (int2 *)(pbuf + w.zgeo));
@@ -689,7 +703,8 @@ inline void launch_binning(int flavour, const float *loc, const float *w_sp, con
     if (stages & kBinFill) {
         // (4-byte records: one point per thread -- neighbouring lanes then hold neighbouring slots and their
         // stores coalesce: 18.9 us against 23.0 with four)
-        if (wide && pt4) BOXATTN_BIN(true, true, 4);
+        if (grp) BOXATTN_BIN(true, false, 4, true);
+        else if (wide && pt4) BOXATTN_BIN(true, true, 4);
         else if (wide) BOXATTN_BIN(true, true, 1);
         else BOXATTN_BIN(true, false, 1);
     }
@@ -781,13 +796,19 @@ template <typename ST, int G, bool INST>
 int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, const float *loc, const float *w_sp,
                       const float *w_lv, const Dims &d, const BinPlan &plan, const int *offsets, const int4 *items,
                       const int *n_items, const int *records, ST *grad_value, float *partials,
-                      const ChunkCombine &cc, const ZeroRole &zr, hipStream_t st)
+                      const ChunkCombine &cc, const ZeroRole &zr, hipStream_t st, RecKind rec = kRecPoint)
 {
     constexpr int C = 4 * G;
     const int ns = d.B * d.H, ns8 = (ns + 7) / 8 * 8;
     const int wg_per_slice = std::min(kAccWgCap, std::max(1, plan.item_cap));
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdAccum], st);
     if constexpr (IsHalf16<ST>::value && !INST) {
+        if (acc == kAccTr && rec == kRecGroup) {
+            launch_accumulate_tr_group<ST>(C, grad_out, (size_t)d.B * d.Lq * d.H * C * sizeof(ST), plan, d.S, d.H, d.Lq, items,
+                                           n_items, records, grad_value, partials, wg_per_slice, ns8, cc, zr, st, loc, w_sp,
+                                           d.n_qh() * (size_t)d.L * 4 * 8);
+            return finish();
+        }
         if (acc == kAccTr) {
             launch_accumulate_tr<ST>(C, grad_out, (size_t)d.B * d.Lq * d.H * C * sizeof(ST), plan, d.S, d.H, d.Lq, items,
                                  n_items, records, grad_value, partials, wg_per_slice, ns8, cc, zr, st);
@@ -837,13 +858,13 @@ int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, cons
 template <typename ST, int G, bool INST>
 int run_binned(const BwdIn<ST> &in, const BwdOut<ST> &out, const BinPlan &plan, const PlanLayout &pl, char *pbuf,
                const ScratchLayout &sl, char *sbuf, bool plan_ready, const DensePlan *dp, const SpecRide *spec,
-               bool spec_warm, int *spec_tickets, bool points, AccKind acc)
+               bool spec_warm, int *spec_tickets, bool points, AccKind acc, RecKind rkind)
 {
     const Dims &d = in.d;
     const hipStream_t st = in.st;
     const float *loc = in.loc, *w_sp = in.w_sp;
     const int ns = d.B * d.H;
-    const int flavour = bin_flavour(acc, d, loc, w_sp);
+    const int flavour = bin_flavour(acc, d, loc, w_sp, rkind);
     int *records = (int *)(sbuf + sl.records);
     float *partials = (float *)(sbuf + sl.partials);
     const int *n_items = (const int *)(pbuf + pl.n_items), *offsets = (const int *)(pbuf + pl.offsets);
@@ -892,7 +913,7 @@ int run_binned(const BwdIn<ST> &in, const BwdOut<ST> &out, const BinPlan &plan, 
         plan_acc.zero_workers = kSpecRedoWorkers;
     }
     int rc = launch_accumulate<ST, G, INST>(acc, in.grad_out, in.grad_mask, loc, w_sp, in.w_lv, d, plan_acc, offsets, items,
-                                            n_items, records, out.grad_value, partials, cc, zr, st);
+                                            n_items, records, out.grad_value, partials, cc, zr, st, rkind);
     if (rc) return rc;
     if (spec && !(one_pass && filled))      // a cold state: the next call's ranges from this call's exact scan
         hipLaunchKernelGGL(spec_layout_kernel<256>, dim3(ns), dim3(256), 0, st, plan, offsets, spec->cursor, spec->cbase,
@@ -932,8 +953,9 @@ int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size
     BinPlan plan;
     const size_t nv = d.n_value();
     const AccKind acc = acc_kind_at<ST, INST>(d, in.grad_mask, in.w_lv);
+    const RecKind rkind = record_kind_at<ST, INST>(acc, d, in.loc, in.w_sp);
     bool binned = (g_variant == 0 || g_variant == 3) && nv && d.n_qh() &&
-                  make_plan(d, in.shapes_host, in.lsi_host, plan) &&
+                  make_plan(d, in.shapes_host, in.lsi_host, plan, rkind) &&
                   fast_ok<ST>(d, in.value, in.loc, in.grad_out,
                               INST ? (const void *)in.grad_mask : (const void *)in.grad_out,
                               wp ? (const void *)out.grad_loc : (const void *)in.grad_out);
@@ -942,10 +964,15 @@ int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size
     bool plan_ready = false;
     if (binned && wv) {
         pl = plan_layout(d, plan);
-        sl = scratch_layout(d, plan, wide_workspace(kH16, d));
+        // (the layout the workspace query sized: where the shape's box attention takes group records the query answered
+        // for those, and every other call of that shape -- instance attention -- is laid out for the records it writes)
+        sl = scratch_layout(d, plan, rkind == kRecGroup ? 4
+                                     : kH16 && record_kind<bf16_t, false>(d) == kRecGroup ? (acc != kAccValu ? 16 : 4)
+                                     : workspace_record_bytes(kH16, d));
         // (a training forward plans for acc_kind's record order: a call that leaves that route for its operands'
-        // alignment plans for itself)
-        plan_ready = plan_buf && plan_bytes >= pl.total && aligned(plan_buf, 256) && acc == acc_kind<ST, INST>(d);
+        // alignment plans for itself; it builds no plan for a shape that may take group records)
+        plan_ready = plan_buf && plan_bytes >= pl.total && aligned(plan_buf, 256) && acc == acc_kind<ST, INST>(d) &&
+                     record_kind<ST, INST>(d) == kRecPoint;
         binned = workspace && aligned(workspace, 256) && aligned(out.grad_value, 16) &&
                  workspace_bytes >= (plan_ready ? sl.total : pl.total + sl.total);
     }
@@ -986,7 +1013,8 @@ int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size
     int *spec_tickets = nullptr;
     if (wp && !plan_ready && spec_ok<ST, INST>(d, plan, pl)) {
         const StateLayout sy = state_layout(d, &plan);
-        const int chk = state_check(state, state_bytes, sy, d, in.shapes_host, in.st, (hints & BOXATTN_HINT_FRESH_STATE) != 0);
+        const int chk = state_check(state, state_bytes, sy, d, in.shapes_host, in.st, (hints & BOXATTN_HINT_FRESH_STATE) != 0,
+                                    (int)rkind);
         if (chk < 0) return (int)hipErrorInvalidValue;
         if (chk > 0) {
             char *sb = (char *)state;
@@ -1001,7 +1029,7 @@ int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size
     int rc = 0;
     for_group(fast_group(d), [&](auto g) {
         rc = run_binned<ST, decltype(g)::value, INST>(in, out, plan, pl, pbuf, sl, sbuf, plan_ready, dp, sp, spec_warm,
-                                                      spec_tickets, wp, acc);
+                                                      spec_tickets, wp, acc, rkind);
     });
     return rc;
 }
@@ -1049,6 +1077,9 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
         ok = plan_bytes >= pl.total;
     }
     if (!ok)
+        return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
+    // (a shape that may take group records: its backward counts groups, and plans for itself)
+    if (record_kind<ST, INST>(d) == kRecGroup)
         return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
     char *pbuf = (char *)plan_buf;
     const int flavour = bin_flavour(acc_kind<ST, INST>(d), d, loc, w_sp);
@@ -1154,11 +1185,14 @@ int instattn_fwd_train_f16(const uint16_t *value, const int64_t *shapes, const i
 size_t boxattn_plan_bytes(int is_16bit, int B, int S, int H, int C, int L, int Lq, int P,
                           const int64_t *shapes_host, const int64_t *lsi_host)
 {
-    (void)is_16bit;
     const Dims d = DIMS;
     BinPlan plan;
     if (!d.valid() || !make_plan(d, shapes_host, lsi_host, plan)) return 0;
-    return plan_layout(d, plan).total;
+    size_t need = plan_layout(d, plan).total;
+    BinPlan gplan;        // (group records cut more work items: boxattn_bwd_workspace_bytes)
+    if (is_16bit && record_kind<bf16_t, false>(d) == kRecGroup && make_plan(d, shapes_host, lsi_host, gplan, kRecGroup))
+        need = std::max(need, plan_layout(d, gplan).total);
+    return need;
 }
 
 size_t boxattn_state_bytes(int B, int S, int H, int C, int L, int Lq, int P, const int64_t *shapes_host,
@@ -1178,8 +1212,19 @@ size_t boxattn_bwd_workspace_bytes(int is_16bit, int B, int S, int H, int C, int
     const size_t fallback = is_16bit ? align_up(d.n_value() * sizeof(float)) : 0;
     BinPlan plan;
     if (!make_plan(d, shapes_host, lsi_host, plan)) return fallback;
-    return std::max(fallback, plan_layout(d, plan).total +
-                                  scratch_layout(d, plan, wide_workspace(is_16bit != 0, d)).total);
+    size_t need = plan_layout(d, plan).total + scratch_layout(d, plan, workspace_record_bytes(is_16bit != 0, d)).total;
+    // (a shape whose box attention takes group records: their plan -- smaller chunks, more partial tiles -- and 4-byte
+    // records; instance attention keeps the point flavour's sizes where those are larger.  A box-attention call whose
+    // locations are not 16-byte aligned would write 16-byte point records, which this area does not hold: it takes the
+    // atomic kernels, like any call the binned route's checks rule out)
+    BinPlan gplan;
+    if (is_16bit && record_kind<bf16_t, false>(d) == kRecGroup && make_plan(d, shapes_host, lsi_host, gplan, kRecGroup)) {
+        const size_t gneed = plan_layout(d, gplan).total + scratch_layout(d, gplan, 4).total;
+        const bool inst_wide = inst_tr_ok(d);
+        need = inst_wide ? std::max(need, gneed)
+                         : std::max(gneed, plan_layout(d, plan).total + scratch_layout(d, plan, 4).total);
+    }
+    return std::max(fallback, need);
 }
 
 int boxattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
@@ -1397,6 +1442,15 @@ int boxattn_bwd_accumulate_kind(int elem_bytes, int instance, int B, int S, int 
     // (bf16 and f16 storage route alike: one answer for elem_bytes == 2)
     if (elem_bytes == 2) return (int)(instance ? acc_kind<bf16_t, true>(d) : acc_kind<bf16_t, false>(d));
     if (elem_bytes == 4) return (int)(instance ? acc_kind<float, true>(d) : acc_kind<float, false>(d));
+    return -1;          // float64 has no binned backward
+}
+
+int boxattn_bwd_record_kind(int elem_bytes, int instance, int B, int S, int H, int C, int L, int Lq, int P)
+{
+    const Dims d = DIMS;
+    if (!d.valid()) return -1;
+    if (elem_bytes == 2) return (int)(instance ? record_kind<bf16_t, true>(d) : record_kind<bf16_t, false>(d));
+    if (elem_bytes == 4) return (int)(instance ? record_kind<float, true>(d) : record_kind<float, false>(d));
     return -1;          // float64 has no binned backward
 }
 

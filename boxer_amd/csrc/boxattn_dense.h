@@ -379,7 +379,7 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
     // records while the tiles' workgroups compute -- the one waits on memory, the other on issue slots
     const RideRole role = ride_role(blockIdx.x, ride.grid);
     if (role.rider) {
-        bin_fill_ride<256>(ride, role.id, reinterpret_cast<int *>(win_lds));
+        bin_fill_ride<256, true>(ride, role.id, reinterpret_cast<int *>(win_lds));
         return;
     }
 #ifdef BOXATTN_DEBUG_NO_TILES          // timing experiments only: the riders alone

@@ -95,13 +95,33 @@ void launch_accumulate_tr(int C, const ST *grad_out, size_t grad_out_bytes, cons
 #define BOXATTN_ACC_TR(C_)                                                                              \
     hipLaunchKernelGGL((binned_accumulate_tr_kernel<ST, C_>), dim3(wg_per_slice + plan.zero_workers, ns8), dim3(64), 0, st, \
                        grad_out, (unsigned)grad_out_bytes, plan, S, H, Lq, items, n_items, records,     \
-                       grad_value, partials, cc, zr, InstRowsT<ST>{})
+                       grad_value, partials, cc, zr, InstRowsT<ST>{}, GroupPts{})
     switch (C) {
     case 16: BOXATTN_ACC_TR(16); break;
     case 32: BOXATTN_ACC_TR(32); break;
     case 64: BOXATTN_ACC_TR(64); break;
     }
 #undef BOXATTN_ACC_TR
+}
+
+// group records (the kernel's GRP flavour): the group's locations and weights are gathered by the record's id
+template <typename ST>
+void launch_accumulate_tr_group(int C, const ST *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
+                                int H, int Lq, const int4 *items, const int *n_items, const int *records,
+                                ST *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
+                                const ZeroRole &zr, hipStream_t st, const float *loc, const float *attn, size_t loc_bytes)
+{
+    const GroupPts gp{loc, attn, (unsigned)loc_bytes};
+#define BOXATTN_ACC_TR_GRP(C_)                                                                          \
+    hipLaunchKernelGGL((binned_accumulate_tr_kernel<ST, C_, false, true>), dim3(wg_per_slice + plan.zero_workers, ns8), dim3(64), 0, st, \
+                       grad_out, (unsigned)grad_out_bytes, plan, S, H, Lq, items, n_items, records,     \
+                       grad_value, partials, cc, zr, InstRowsT<ST>{}, gp)
+    switch (C) {
+    case 16: BOXATTN_ACC_TR_GRP(16); break;
+    case 32: BOXATTN_ACC_TR_GRP(32); break;
+    case 64: BOXATTN_ACC_TR_GRP(64); break;
+    }
+#undef BOXATTN_ACC_TR_GRP
 }
 
 // instance attention: two upstream rows per record (the kernel's INST flavour)
@@ -116,7 +136,7 @@ void launch_accumulate_tr_inst(int C, const ST *grad_out, size_t grad_out_bytes,
 #define BOXATTN_ACC_TR_INST(C_)                                                                         \
     hipLaunchKernelGGL((binned_accumulate_tr_kernel<ST, C_, true>), dim3(wg_per_slice + plan.zero_workers, ns8), dim3(64), 0, st, \
                        grad_out, (unsigned)grad_out_bytes, plan, S, H, Lq, items, n_items, records,     \
-                       grad_value, partials, cc, zr, inst)
+                       grad_value, partials, cc, zr, inst, GroupPts{})
     switch (C) {
     case 16: BOXATTN_ACC_TR_INST(16); break;
     case 32: BOXATTN_ACC_TR_INST(32); break;
@@ -135,6 +155,10 @@ void launch_accumulate_tr_inst(int C, const ST *grad_out, size_t grad_out_bytes,
     template void launch_accumulate_tr<ST_>(int, const ST_ *, size_t, const BinPlan &, int, int, int,       \
                                             const int4 *, const int *, const int *, ST_ *, float *, int, int, \
                                             const ChunkCombine &, const ZeroRole &, hipStream_t);              \
+    template void launch_accumulate_tr_group<ST_>(int, const ST_ *, size_t, const BinPlan &, int, int, int, \
+                                                  const int4 *, const int *, const int *, ST_ *, float *, int, int, \
+                                                  const ChunkCombine &, const ZeroRole &, hipStream_t, const float *, \
+                                                  const float *, size_t);                                   \
     template void launch_accumulate_tr_inst<ST_>(int, const ST_ *, size_t, const BinPlan &, int, int, int,  \
                                                  const int4 *, const int *, const int *, ST_ *, float *, int, int, \
                                                  const ChunkCombine &, const ZeroRole &, hipStream_t, const ST_ *, \

@@ -114,6 +114,13 @@ void launch_accumulate_tr_inst(int C, const ST *grad_out, size_t grad_out_bytes,
                                ST *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
                                const ZeroRole &zr, hipStream_t st, const ST *grad_mask, size_t grad_mask_bytes,
                                const float *w_lv, int P);
+// ... from GROUP records (one int per (query, level, block), P == 4): the group's locations `loc` (B, Lq, H, L, 4, 2) and
+// weights `attn` are gathered by the record's id; loc below 2 GB (loc_bytes), both 16-byte aligned
+template <typename ST>
+void launch_accumulate_tr_group(int C, const ST *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
+                                int H, int Lq, const int4 *items, const int *n_items, const int *records,
+                                ST *grad_value, float *partials, int wg_per_slice, int ns8, const ChunkCombine &cc,
+                                const ZeroRole &zr, hipStream_t st, const float *loc, const float *attn, size_t loc_bytes);
 
 // float32 storage, C = 32: the accumulate on the bf16 matrix cores with exact three-term splits (boxattn_binned_tr.h:
 // binned_accumulate_split_kernel); grad_out below 2 GB

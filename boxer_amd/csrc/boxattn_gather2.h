@@ -748,7 +748,7 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
     __shared__ int ride_lds[kRideLdsInts];
     const RideRole role = ride_role(blockIdx.x, ride.grid);
     if (role.rider) {
-        if (blockIdx.y == 0) bin_fill_ride<256>(ride, role.id, ride_lds);
+        if (blockIdx.y == 0) bin_fill_ride<256, IsHalf16<ST>::value && !INST>(ride, role.id, ride_lds);
         return;
     }
     const unsigned blk = role.id;

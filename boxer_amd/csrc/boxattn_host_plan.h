@@ -11,10 +11,19 @@ constexpr int kChunk = 1024, kChunkBig = 1536;   // records per work item (upper
 // with few sample points (the decoders: 300 queries) 1 024-record items leave a handful of waves
 // running 16 rounds while the rest of the chip idles.  Aim at ~256 items per (image, head) slice
 // -- about the wave slots a slice gets -- between 128 and kChunk records.
-inline int bin_chunk(const Dims &d)
+// Group records (record_kind below): a record stands for the <= 4 points of a (query, level) in one block, ~2 records a
+// group -- and a round of 64 of them is about the work of 2.5 rounds of point records, so an item's two start-up round
+// trips and its tile store weigh more: ~128 items a slice, between 128 and kChunkGroup records (C2 bf16 accumulate with
+// 256 / 448 / 768 / 1 536 records an item: 60.7 / 50.8 / 48.7 / 49.8 us, profiles/group_records_step.log).
+constexpr int kChunkGroup = 1024;
+inline int bin_chunk(const Dims &d, bool group = false)
 {
     const int forced = opt(kOptBinChunk);
     if (forced > 0) return std::min(4096, std::max(64, (forced + 63) / 64 * 64));
+    if (group) {
+        const long long c = (2ll * d.Lq * d.L / 128 + 63) / 64 * 64;
+        return (int)std::min<long long>(kChunkGroup, std::max<long long>(128, c));
+    }
     const long long rec_est = 3ll * d.Lq * d.L * d.P / 2;          // ~1.4 records per point
     const long long c = (rec_est / 256 + 63) / 64 * 64;
     // (encoder-sized problems: 1 536 -- fewer partial tiles for the combine step, measured at C2 / C2' against
@@ -87,17 +96,59 @@ template <typename ST, bool INST> inline AccKind acc_kind(const Dims &d)
     }
     return kAccValu;
 }
+// The records of a binned backward (boxattn_bwd_record_kind() answers with record_kind()):
+//   kRecPoint  one record per sample point and touched block: 16 bytes {id, x, y, weight} for the matrix-core
+//              accumulates, the 4-byte point id for the VALU list walk;
+//   kRecGroup  16-bit box attention with P == 4 on the matrix cores (kAccTr): one int per (query, level, block)
+//              (boxattn_binplan.h: group_blocks), locations and weights gathered by id in the accumulate kernel.
+//              boxattn_set_option(24, v) ("group_records"): 0 default (group_default), 1 point records, 2 group records
+//              wherever the shape is eligible.  A call whose locations or weights are not 16-byte aligned keeps
+//              point records (record_kind_at, boxattn_capi.hip).
+enum RecKind { kRecPoint = 0, kRecGroup = 1 };
+inline bool group_records_ok(const Dims &d)
+{
+    // 32-bit byte offsets into loc (8 bytes a point) below 2 GB; the query field of a record (make_plan_blocks checks Lq)
+    return d.P == 4 && accumulate_tr_ok(d) && d.L <= kMaxBinLevels && d.n_qh() * (size_t)d.L * 4 * 8 < kAccTrMaxBytes &&
+           d.H * d.L * 4 < (1 << 24);
+}
+// The default, per shape class: group records where they passed the project's step rule -- this build's slowest repeat
+// faster than the parent's fastest (profiles/group_records_step.log; us a step, fastest .. slowest of
+// nine, bf16, f16 alike).  Passed: the encoders whose backward fills its bins in one pass, C2 (212 704 points a slice:
+// 131.9 .. 136.1 -> 127.2 .. 128.1) and C2' (355 568: 220.6 .. 222.9 -> 205.9 .. 207.4).  Did not: 300 decoder queries
+// (C3'': the training forward of a group shape builds no plan, 42.4 .. 45.3 -> 57.1 .. 58.6) and the BEV encoder with
+// rotated windows (C5': 68 445 pixels, 2 220 blocks a slice -- two-pass, its groups mostly on the slow path: 421.4 ..
+// 425.7 -> 456.5 .. 460.3).  So: one query per pixel, a map the one-pass fill takes (at most kSpecMaxBlocks blocks of
+// up to 32 pixels, option 15 leaving it on), from the smallest measured size that passed.  The rule is a function of the
+// dimensions alone -- the query and the training forward have no level tables -- so it restates spec_shape instead of
+// calling it: a shape just above kGroupMinPoints whose maps (many small levels) still land on the two-pass route gets
+// group records although nobody measured that combination.
+constexpr size_t kGroupMinPoints = 212704;
+inline bool group_default(const Dims &d)
+{
+    const int o = opt(kOptRiders);          // (the one-pass fill switched off -- 1, 4 -- keeps the parent's records and plans)
+    if (!(o == 0 || o == 2 || o == 3)) return false;
+    return d.Lq == d.S && (long long)d.S <= 32ll * kSpecMaxBlocks && (size_t)d.Lq * d.L * d.P >= kGroupMinPoints;
+}
+template <typename ST, bool INST> inline RecKind record_kind(const Dims &d)
+{
+    if constexpr (!INST && IsHalf16<ST>::value) {
+        const int o = opt(kOptGroupRecords);
+        if (o != 1 && group_records_ok(d) && (o == 2 || group_default(d))) return kRecGroup;
+    }
+    return kRecPoint;
+}
 // the workspace query only knows the storage type and the dimensions: room for 16-byte records
 // whenever a flavour of that type may write them (is_h16: bf16 or f16 storage, which plan alike)
 inline bool wide_workspace(bool is_h16, const Dims &d)
 {
     return is_h16 ? accumulate_tr_ok(d) : f32_mfma_ok(d) || f32_split_ok(d);
 }
+inline int workspace_record_bytes(bool is_h16, const Dims &d) { return wide_workspace(is_h16, d) ? 16 : 4; }
 constexpr int kMaxBlocks = 8192;      // per (image, head) slice: one LDS int each in bin_kernel
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-inline bool make_plan_blocks(const Dims &d, const int64_t *sh, const int64_t *ls, BinPlan &p)
+inline bool make_plan_blocks(const Dims &d, const int64_t *sh, const int64_t *ls, BinPlan &p, RecKind rec = kRecPoint)
 {
     constexpr int BW = 8, BH = 4;
     p.L = d.L;
@@ -150,13 +201,16 @@ inline bool make_plan_blocks(const Dims &d, const int64_t *sh, const int64_t *ls
         return false;
     int lp_bits = 0;
     while ((1ll << lp_bits) < (long long)d.L * d.P) ++lp_bits;
+    if (rec == kRecGroup) lp_bits = kGroupBits;         // record = (query << bits) | (level << 4) | mask
     if (((long long)d.Lq << lp_bits) > INT32_MAX) return false;
     if ((long long)d.L * d.P > (1 << 16)) return false;       // keeps per-workgroup point counts < 2^24
     p.lp_bits = lp_bits;
     p.n_slices = d.B * d.H;
     p.nblk = (int)blk0;
     p.rec_cap = (int)rec_cap;
-    p.chunk = bin_chunk(d);
+    // (group records: at most 16 a group -- four points on the slow path, four blocks each -- the same count bound as
+    // the point flavour's 4 a point, at 4 bytes instead of 16)
+    p.chunk = bin_chunk(d, rec == kRecGroup);
     p.item_cap = (int)(blk0 + rec_cap / p.chunk + 1);
     // sparse maps (fewer than ~2 expected records per block -- the BEV decoders: 1 000 queries against 468 x 468):
     // grad_value is zero-filled once and the empty blocks get no work item (BinPlan::min_items)
@@ -166,15 +220,19 @@ inline bool make_plan_blocks(const Dims &d, const int64_t *sh, const int64_t *ls
     p.zero_workers = p.min_items ? 0 : (int)((blk0 + kZeroPer - 1) / kZeroPer);
     // blocks with more than one chunk: sum of their chunk counts <= 2 * records / chunk
     p.pslot_cap = (int)std::min<long long>(2 * (rec_cap / p.chunk) + 2, blk0 + rec_cap / p.chunk + 1);
+    // (group records, whose chunks are smaller: a block of c > chunk records has ceil(c / chunk) <= c / chunk + 1 chunks,
+    // and no more than records / chunk blocks -- nor more than all blocks -- are that big)
+    if (rec == kRecGroup)
+        p.pslot_cap = (int)std::min<long long>(p.pslot_cap, rec_cap / p.chunk + std::min<long long>(blk0, rec_cap / p.chunk) + 2);
     // a chunk item carries {partial slot, ordinal of its block among the chunked ones} in one word (kItemSlotBits)
     if (p.pslot_cap >= (1 << kItemSlotBits) || blk0 >= (1 << (31 - kItemSlotBits))) return false;
     return true;
 }
 
-inline bool make_plan(const Dims &d, const int64_t *sh, const int64_t *ls, BinPlan &p)
+inline bool make_plan(const Dims &d, const int64_t *sh, const int64_t *ls, BinPlan &p, RecKind rec = kRecPoint)
 {
     if (!sh || !ls || !d.valid() || fast_group(d) == 0 || d.L > kMaxBinLevels) return false;
-    return make_plan_blocks(d, sh, ls, p);
+    return make_plan_blocks(d, sh, ls, p, rec);
 }
 
 std::atomic<float *> g_dense_dbg{nullptr};      // debugging aid: time stamps (boxattn_set_debug_buffer)
@@ -195,6 +253,8 @@ struct ScratchLayout { size_t records, partials, ctickets, total; };
 // call: many records a block (an encoder's one query per pixel: 660 a block at BoxeR-R50 shapes, fixed by the geometry).
 // 300 decoder queries leave ~9 records a block, anywhere: every call outgrows the ranges of the one before (measured, C3'':
 // 104 us a step over changing inputs against 52 with the two-pass riders, profiles/r06_onepass_ab.log).
+// (In group records -- ~2 a (query, level) group of four points instead of ~1.5 a point -- the same threshold reads 64
+// expected records a block: 2 Lq L >= 64 nblk is 3 Lq L P / 2 >= 192 nblk at P = 4, so both flavours share the test.)
 constexpr long long kSpecMinRecordsPerBlock = 192;
 inline bool spec_shape(const Dims &d, const BinPlan &p)
 {
@@ -238,14 +298,14 @@ inline PlanLayout plan_layout(const Dims &d, const BinPlan &p)
     w.total = o;
     return w;
 }
-// `wide`: 16-byte records {id, x, y, weight} instead of 4-byte point ids
-inline ScratchLayout scratch_layout(const Dims &d, const BinPlan &p, bool wide)
+// rec_bytes: 16 for records {id, x, y, weight}, 4 for point ids and for group records
+inline ScratchLayout scratch_layout(const Dims &d, const BinPlan &p, int rec_bytes)
 {
     const size_t ns = (size_t)d.B * d.H;
     ScratchLayout w;
     size_t o = 0;
     w.ctickets = o; o += align_up(ns * (size_t)p.nblk * 4);      // in-launch combine (chunk_finish)
-    w.records = o;  o += align_up(ns * (size_t)p.rec_cap * (wide ? 16 : 4));
+    w.records = o;  o += align_up(ns * (size_t)p.rec_cap * (size_t)rec_bytes);
     w.partials = o; o += align_up(ns * (size_t)p.pslot_cap * 32 * d.C * 4);
     w.total = o;
     return w;
@@ -299,7 +359,7 @@ inline StateLayout state_layout(const Dims &d, const BinPlan *plan)
 // zeroed buffer is a valid state (every range empty), so nothing here decides RESULTS: an unknown or forgotten buffer is
 // "cold" (the call runs the two-pass passes and plans the ranges), and a buffer that turns up with another shape is
 // zeroed first (its tickets and ranges mean nothing to this shape).
-struct StateShadow { Dims d; unsigned long long geo; bool learned; };
+struct StateShadow { Dims d; unsigned long long geo; bool learned; int rec; };      // rec: the record kind the ranges were learned under (-1: none yet)
 std::mutex g_state_mu;
 std::map<const void *, StateShadow> g_state_shadow;
 inline bool same_dims(const Dims &a, const Dims &b)
@@ -309,8 +369,10 @@ inline bool same_dims(const Dims &a, const Dims &b)
 // -> -1 unusable (misaligned / too small), 0 no state, 1 cold, 2 its ranges are planned
 // fresh (BOXATTN_HINT_FRESH_STATE): the caller has zeroed the buffer since its last call -- a new buffer, possibly at an
 // address another one had: whatever is remembered of the address is dropped
+// rec: the record kind of a backward call (ranges learned under the other kind count other records: they read as cold);
+// -1: a call that neither reads nor plans ranges (the training forward)
 inline int state_check(void *state, size_t bytes, const StateLayout &sy, const Dims &d, const int64_t *sh, hipStream_t st,
-                       bool fresh)
+                       bool fresh, int rec = -1)
 {
     if (!state) return 0;
     if (!aligned(state, 8) || bytes < sy.total) return -1;
@@ -321,12 +383,21 @@ inline int state_check(void *state, size_t bytes, const StateLayout &sy, const D
     const auto it = g_state_shadow.find(state);
     if (it == g_state_shadow.end()) {
         if (g_state_shadow.size() >= 4096) g_state_shadow.clear();
-        g_state_shadow[state] = StateShadow{d, geo, false};
+        g_state_shadow[state] = StateShadow{d, geo, false, rec};
         return 1;
     }
-    if (same_dims(it->second.d, d) && it->second.geo == geo) return it->second.learned ? 2 : 1;
+    if (same_dims(it->second.d, d) && it->second.geo == geo) {
+        if (rec < 0 || it->second.rec < 0 || it->second.rec == rec || !it->second.learned) {
+            if (rec >= 0) it->second.rec = rec;
+            return it->second.learned ? 2 : 1;
+        }
+        // the other record kind's ranges: cold (the two-pass passes of this call plan them anew and reset the cursors)
+        it->second.learned = false;
+        it->second.rec = rec;
+        return 1;
+    }
     if (zero_async((char *)state + kStatBytes, bytes - kStatBytes, st) != hipSuccess) return -1;
-    it->second = StateShadow{d, geo, false};
+    it->second = StateShadow{d, geo, false, rec};
     return 1;
 }
 inline void state_learned(const void *state)

@@ -280,6 +280,133 @@ __device__ __forceinline__ void spec_fill_body(int *hist, int *base, BinLevel *s
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// fill, group records (boxattn_binplan.h: group_blocks): a thread takes ONE (query, level) group a step and keeps, from
+// the rank phase to the store phase, the group's id, its candidate sets (one on the fast path) and their ranks --
+// not the four points' x, y and weight of the point flavour.  Rank / claim / store as in spec_fill_body.
+// ---------------------------------------------------------------------------------------------------------------
+template <int THREADS>
+__device__ __forceinline__ void spec_fill_group_body(int *hist, int *base, BinLevel *s_lv, const float *__restrict__ loc,
+                                                     const BinPlan &plan, int H, int Lq, int q_per_wg,
+                                                     int *__restrict__ cursor_s, const int *__restrict__ cbase_s,
+                                                     int *__restrict__ records, int s, int wg)
+{
+    constexpr int STRIDE = THREADS;
+    static_assert(STRIDE * 16 < (1 << kSpecRankBits), "ranks of a step");
+    const int b = s / H, h = s % H;
+    const int LG = plan.L, LP = plan.L * 4;           // groups / points per query (P == 4)
+    const int q0 = wg * q_per_wg;
+    const int n_q = max(0, min(q0 + q_per_wg, Lq) - q0);
+    const unsigned pid0 = (unsigned)(((b * Lq + q0) * H + h) * LP);
+    const unsigned qstride = (unsigned)(H * LP);
+    const int n_grp = n_q * LG;
+    const float rcp_lg = 1.0f / (float)LG;
+    int *rec = records + (size_t)s * plan.rec_cap;
+    struct Step {
+        float2 xy[4];
+        int level, ql;
+    };
+    auto load_step = [&](Step &t, int g0) {
+        const int g = min(g0, n_grp - 1);
+        divmod_small(g, LG, rcp_lg, t.ql, t.level);
+        const unsigned pbase = pid0 + (unsigned)t.ql * qstride + (unsigned)(t.level * 4);
+        const char *lp8 = reinterpret_cast<const char *>(loc) + (pbase << 3);
+        const float4 a = *reinterpret_cast<const float4 *>(lp8), c = *reinterpret_cast<const float4 *>(lp8 + 16);
+        t.xy[0] = make_float2(a.x, a.y); t.xy[1] = make_float2(a.z, a.w);
+        t.xy[2] = make_float2(c.x, c.y); t.xy[3] = make_float2(c.z, c.w);
+    };
+    auto work_step = [&](const Step &t, int g0) {
+        const BinLevel lv = s_lv[t.level];
+        unsigned set[4], rk[4][2];
+        const bool slow = group_blocks(t.xy, lv, g0 < n_grp, set);
+        const bool any_slow = __builtin_amdgcn_ballot_w64(slow) != 0ull;      // wave-uniform
+        // ---- rank: unconditional LDS atomics, a candidate that does not exist counts in the thread's own dump counter
+        const int dump = kSpecMaxBlocks + 1 + (int)threadIdx.x;
+        auto rank_set = [&](int j) {
+            const unsigned m = set[j];
+            const int b0 = (int)(m & kGrpBlk);
+            const bool in = (m & kGrpIn) != 0u, cc = (m & kGrpCc) != 0u, cr = (m & kGrpCr) != 0u;
+            const unsigned r0 = (unsigned)atomicAdd(&hist[in ? b0 : dump], 1);
+            const unsigned r1 = (unsigned)atomicAdd(&hist[cc ? b0 + 1 : dump], 1);
+            const unsigned r2 = (unsigned)atomicAdd(&hist[cr ? b0 + lv.nbx : dump], 1);
+            const unsigned r3 = (unsigned)atomicAdd(&hist[cc & cr ? b0 + lv.nbx + 1 : dump], 1);
+            rk[j][0] = (r0 & 0xFFFFu) | (r1 << 16);
+            rk[j][1] = (r2 & 0xFFFFu) | (r3 << 16);
+        };
+        rank_set(0);
+        if (any_slow) {
+#pragma unroll
+            for (int j = 1; j < 4; ++j) rank_set(j);
+        }
+        lds_barrier();
+        // ---- claim: as spec_fill_body
+        constexpr int KB = 2;
+        for (int k0 = (int)threadIdx.x; k0 < plan.nblk; k0 += KB * THREADS) {
+            int c[KB], old[KB], end[KB];
+#pragma unroll
+            for (int i = 0; i < KB; ++i) {
+                const int bk = k0 + i * THREADS;
+                c[i] = bk < plan.nblk ? hist[bk] : 0;
+                old[i] = end[i] = 0;
+            }
+#pragma unroll
+            for (int i = 0; i < KB; ++i)
+                if (c[i] > 0) {
+                    const unsigned bo = (unsigned)(k0 + i * THREADS) << 2;
+                    old[i] = __hip_atomic_fetch_add(reinterpret_cast<int *>(reinterpret_cast<char *>(cursor_s) + bo), c[i],
+                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    end[i] = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(cbase_s) + bo + 4u);
+                }
+#pragma unroll
+            for (int i = 0; i < KB; ++i)
+                if (c[i] > 0) {
+                    const int bk = k0 + i * THREADS;
+                    hist[bk] = 0;
+                    base[bk] = old[i] + c[i] <= end[i] ? old[i] : -1;
+                }
+        }
+        lds_barrier();
+        // ---- store (the neighbours' bases are read whether they exist or not: inside the LDS array, see spec_fill_body)
+        const int idq = ((q0 + t.ql) << plan.lp_bits) | (t.level << kGroupMaskBits);
+        auto store_set = [&](int j) {
+            const unsigned m = set[j];
+            const int b0 = (int)(m & kGrpBlk);
+            const int sb0 = base[b0], sb1 = base[b0 + 1], sb2 = base[b0 + lv.nbx], sb3 = base[b0 + lv.nbx + 1];
+            const int r = idq | (int)(m >> kGrpMaskShift);
+            char *rb8 = reinterpret_cast<char *>(rec);
+            if ((m & kGrpIn) && sb0 >= 0)
+                *reinterpret_cast<int *>(rb8 + ((unsigned)(sb0 + (int)(rk[j][0] & 0xFFFFu)) << 2)) = r;
+            if ((m & kGrpCc) && sb1 >= 0)
+                *reinterpret_cast<int *>(rb8 + ((unsigned)(sb1 + (int)(rk[j][0] >> 16)) << 2)) = r;
+            if ((m & kGrpCr) && sb2 >= 0)
+                *reinterpret_cast<int *>(rb8 + ((unsigned)(sb2 + (int)(rk[j][1] & 0xFFFFu)) << 2)) = r;
+            if ((m & kGrpCc) && (m & kGrpCr) && sb3 >= 0)
+                *reinterpret_cast<int *>(rb8 + ((unsigned)(sb3 + (int)(rk[j][1] >> 16)) << 2)) = r;
+        };
+        store_set(0);
+        if (any_slow) {
+#pragma unroll
+            for (int j = 1; j < 4; ++j) store_set(j);
+        }
+    };
+    Step sa, sb;
+    if (n_grp > 0) load_step(sa, (int)threadIdx.x);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kMaxBinLevels; ++k) s_lv[k] = plan.lv[k];
+    }
+    for (int k = threadIdx.x; k < plan.nblk; k += THREADS) hist[k] = 0;
+    __syncthreads();
+    for (int start = 0; start < n_grp; start += 2 * STRIDE) {           // workgroup-uniform trip count
+        const int g0 = start + (int)threadIdx.x;
+        if (start + STRIDE < n_grp) load_step(sb, g0 + STRIDE);
+        work_step(sa, g0);
+        if (start + STRIDE >= n_grp) break;
+        if (start + 2 * STRIDE < n_grp) load_step(sa, g0 + 2 * STRIDE);
+        work_step(sb, g0 + STRIDE);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // chain: the slice's last rider -- true counts -> work items, redo list, the next call's ranges
 // ---------------------------------------------------------------------------------------------------------------
 // cnt / cbl: nblk (+ 1) ints of LDS each (the fill's two arrays); wsum: 4 x THREADS / 64 ints.
@@ -444,7 +571,7 @@ __global__ __launch_bounds__(THREADS) void spec_layout_kernel(BinPlan plan, cons
 // ---------------------------------------------------------------------------------------------------------------
 // fill rider (the counterpart of bin_fill_ride for BinRide::flavour & kRideSpec)
 // ---------------------------------------------------------------------------------------------------------------
-template <int THREADS>
+template <int THREADS, bool GRP>
 __device__ __forceinline__ void bin_fill_spec_ride(const BinRide r, unsigned id, int *lds)
 {
     static_assert(THREADS == 256, "4 wave sums per scan quantity");
@@ -460,7 +587,9 @@ __device__ __forceinline__ void bin_fill_spec_ride(const BinRide r, unsigned id,
     int *cbase_s = r.spec.cbase + (size_t)s * (plan.nblk + 1);
     RIDE_STAMP(5);
     unsigned long long *tr = BOXATTN_RIDE_TRACE && r.trace ? r.trace + (size_t)id * 8 : nullptr;     // [0..3]: phase times
-    if (r.flavour & kRidePt4)
+    if (GRP && (r.flavour & kRideGroup))
+        spec_fill_group_body<THREADS>(hist, base, m.lv, r.loc, plan, r.H, r.Lq, r.q_per_wg, cursor_s, cbase_s, r.records, s, wg);
+    else if (r.flavour & kRidePt4)
         spec_fill_body<THREADS, 4>(hist, base, m.lv, r.loc, r.w_sp, plan, r.H, r.Lq, r.P, r.q_per_wg, cursor_s, cbase_s,
                                    r.records, s, wg, tr);
     else

@@ -332,6 +332,13 @@ def _workspace(lib, value, dims, sh, ls, stream):
     nbytes = max(_query_bytes(lib.boxattn_bwd_workspace_bytes, int(value.dtype in _H16), dims, sh, ls), 256)
     wkey = (value.device.index, stream)
     ws = _WORKSPACE.get(wkey)
+    # (a switch that changes the layouts -- group records: 285 -> 153 MB at C2 -- lets a cached buffer shrink too: a buffer
+    # that is too large after the options epoch moved is dropped; within one epoch the largest shape's buffer stays)
+    epoch = _lib.options_epoch()
+    if ws is not None and _WORKSPACE_EPOCH.get(wkey) != epoch and ws.numel() > nbytes and \
+            not torch.cuda.is_current_stream_capturing():
+        ws = None
+    _WORKSPACE_EPOCH[wkey] = epoch
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
         # cached per (device, stream) unless the caller opted out (set_workspace_caching(False): the scratch is then
@@ -339,12 +346,14 @@ def _workspace(lib, value, dims, sh, ls, stream):
         if _CACHE_WORKSPACE and not torch.cuda.is_current_stream_capturing():
             if len(_WORKSPACE) >= _WORKSPACE_CAP:          # streams come and go: start over rather than grow
                 _WORKSPACE.clear()
+                _WORKSPACE_EPOCH.clear()
             _WORKSPACE[wkey] = ws
     return ws
 
 
 _CACHE_WORKSPACE = os.environ.get("BOXATTN_CACHE_WORKSPACE", "1") != "0"
 _WORKSPACE_CAP = 64
+_WORKSPACE_EPOCH = {}          # (device, stream) -> options epoch its cached workspace was last sized under
 
 
 def set_workspace_caching(on):
@@ -526,6 +535,16 @@ def backward_accumulate_kind(value, loc, instance=False):
     B, S, H, C = value.shape
     Lq, L, P = loc.size(1), loc.size(3), loc.size(4)
     return _lib.bwd_accumulate_kind(value.element_size(), instance, (B, S, H, C, L, Lq, P))
+
+
+def backward_record_kind(value, loc, instance=False):
+    """Which records (``_lib.REC_*``) a binned backward of these tensors writes under the current switches:
+    ``boxattn_bwd_record_kind`` with the dimensions and element size of ``value`` (B, S, H, C) and ``loc``
+    (B, Lq, H, L, P, 2).  Negative for float64.  (A call whose ``loc`` or attention weights are not 16-byte aligned
+    keeps point records whatever this answers.)"""
+    B, S, H, C = value.shape
+    Lq, L, P = loc.size(1), loc.size(3), loc.size(4)
+    return _lib.bwd_record_kind(value.element_size(), instance, (B, S, H, C, L, Lq, P))
 
 
 def box_attn_forward_train(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,

@@ -528,6 +528,13 @@ int instattn_weights_bwd_f16(const uint16_t *logits, const float *grad_spatial_w
  *      records; the parity cross-check), 2 the matrix cores wherever the shape is eligible (grad_out and grad_mask
  *      below 2 GiB; a grad_mask that is not 16-byte aligned takes the VALU walk).  Box attention and float32 do not
  *      read it.  Set before *_fwd_train_*: a plan made under another setting is not used.
+ *  24  "group_records": box attention in 16-bit storage with P = 4 on the matrix-core accumulate -- the records of the
+ *      binned backward: 0 library default (decided by measurement per shape class), 1 point records
+ *      (16 bytes per sample point and touched block), 2 group records -- one int per (query, level, block), locations and
+ *      weights gathered by id in the accumulate kernel -- wherever the shape is eligible (C = 16 / 32 / 64, grad_out and
+ *      loc below 2 GiB; a call whose loc or attn is not 16-byte aligned keeps point records).  Instance attention and
+ *      float32 do not read it.  Set before boxattn_bwd_workspace_bytes / boxattn_plan_bytes / *_fwd_train_*: the
+ *      workspace of an eligible shape is smaller, and its training forward builds no plan.
  *  (ABI 8 removed 12 / 13 -- window margins --, 17 and 21 -- staged forward / staged float32 kernels off: 11 = 1
  *  switches every window-staged kernel off.)
  */
@@ -557,6 +564,13 @@ int boxattn_fwd_route(int elem_bytes, int instance, int aligned, int B, int S, i
  * float64 has no binned backward).  (Whether a call IS binned -- level tables, alignment, workspace -- and the
  * alignment of grad_mask, which can send a 16-bit instance call to BOXATTN_ACC_VALU, are per-call matters.) */
 int boxattn_bwd_accumulate_kind(int elem_bytes, int instance, int B, int S, int H, int C, int L, int Lq, int P);
+/* The records of the binned backward. */
+#define BOXATTN_REC_POINT 0     /* one record per sample point and touched block */
+#define BOXATTN_REC_GROUP 1     /* one 4-byte record per (query, level, block): 16-bit box attention, P = 4 (option 24) */
+/* Which records a binned backward of these dimensions writes under the current switches: the very function the launch
+ * calls.  Arguments and errors as boxattn_bwd_accumulate_kind.  (The alignment of loc / attn, which can send a call back
+ * to BOXATTN_REC_POINT, is a per-call matter.) */
+int boxattn_bwd_record_kind(int elem_bytes, int instance, int B, int S, int H, int C, int L, int Lq, int P);
 /* Number of boxattn_set_variant / boxattn_set_option calls so far: lets a binding cache the size queries
  * (boxattn_plan_bytes, boxattn_bwd_workspace_bytes: pure functions of their arguments and the switches). */
 int boxattn_options_epoch(void);
