@@ -37,6 +37,22 @@ namespace boxattn {
 #ifndef BOXATTN_TUNE_REC_AHEAD
 #define BOXATTN_TUNE_REC_AHEAD 1       // float32 kernel: request the next item's first records while the current item is summed
 #endif
+// The group-record round (GRP below), one switch per cut; every one leaves grad_value bitwise what it was
+#ifndef BOXATTN_TUNE_GRP_FOLD
+#define BOXATTN_TUNE_GRP_FOLD 1        // the lane's tile column folded into the column terms and ONE dump offset: 16 adds less
+#endif
+#ifndef BOXATTN_TUNE_GRP_ALIGNED
+#define BOXATTN_TUNE_GRP_ALIGNED 1     // a wave of axis-parallel 2 x 2 grids locates two x and two y, not eight coordinates
+#endif
+#ifndef BOXATTN_TUNE_GRP_TAIL
+#define BOXATTN_TUNE_GRP_TAIL 1        // an item's last round runs ceil(remaining / 16) K-steps, not four
+#endif
+#ifndef BOXATTN_TUNE_GRP_EARLY_EXIT
+#define BOXATTN_TUNE_GRP_EARLY_EXIT 1  // workgroups without an item leave before the tile is cleared; the clear in 16-byte stores
+#endif
+#ifndef BOXATTN_TUNE_GRP_PINGPONG
+#define BOXATTN_TUNE_GRP_PINGPONG 1    // the two point sets swap roles across the round pair instead of a 12-register copy
+#endif
 
 typedef __bf16 tr_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float tr_f32x16 __attribute__((ext_vector_type(16)));
@@ -132,7 +148,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
     const int col = lane & 31, kb = lane >> 5;     // operand row / column, k-block
     const int n_it = n_items[2 * s];
 
-    for (int i = lane; i < (int)(sizeof(at) / 4); i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
+    if constexpr (GRP) {
+        // The grid is sized by the host's bound on the items (kAccWgCap a slice); at BoxeR-R50 shapes more than half of its
+        // workgroups have no item.  Those leave here, before the 33 rounds of the dword clear below, and the others clear
+        // the tile sixteen bytes a lane (the surplus waves issued a tenth of the kernel's instructions).
+        if (BOXATTN_TUNE_GRP_EARLY_EXIT && worker >= n_it) return;
+        if (BOXATTN_TUNE_GRP_EARLY_EXIT) {
+            for (int i = lane; i < kGrpTileB / 16; i += 64) reinterpret_cast<u32x4 *>(at)[i] = u32x4{0u, 0u, 0u, 0u};
+        } else {
+            for (int i = lane; i < (int)(sizeof(at) / 4); i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
+        }
+    } else {
+        for (int i = lane; i < (int)(sizeof(at) / 4); i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
+    }
     if (C < CP)                                     // the padding channels stay zero
         for (int i = lane; i < NSRC * NCB * GPL / 4; i += 64) reinterpret_cast<unsigned int *>(gs)[i] = 0u;
     wave_lds_sync();
@@ -226,12 +254,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
             asm volatile("" : "+v"(f_off));
             int rec_c = fetch_rec(item.y), rec_n = fetch_rec(item.y + R), rec_n2 = fetch_rec(item.y + 2 * R);
             u32x4 grow_a[NPASS], grow_b[NPASS];
-            Pts pc{}, pn{};
-            fetch_pts(rec_c, pc);
+            Pts pts_a{}, pts_b{};
+            fetch_pts(rec_c, pts_a);
             fetch_rows(rec_c, grow_a);
             stage_rows(grow_a);
             if (item.y + R < item.z) fetch_rows(rec_n, grow_a);
-            auto round = [&](int rr, const u32x4 (&next)[NPASS], u32x4 (&ahead)[NPASS]) {
+            const int dump_lane = PB * 16 + lane_at;
+            // Product masks: (rows of the 2 x 2 grid the record speaks for) x (columns) -- every mask of a fast record whose
+            // grid is axis-parallel (a point passes the window test by its row AND its column), and the single-point masks
+            constexpr unsigned kProductMasks = 0x953Fu;
+            auto round = [&](int rr, const u32x4 (&next)[NPASS], u32x4 (&ahead)[NPASS], Pts &pc, Pts &pn) {
                 const bool more = rr + R < item.z;     // wave-uniform
                 int rec_n3 = -1;
                 if (more) fetch_pts(rec_n, pn);
@@ -241,43 +273,95 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
                 }
                 // ---- lane = group: the corner weights of its masked-in points, summed per pixel in float32
                 const int mask = rec_c < 0 ? 0 : rec_c & ((1 << kGroupMaskBits) - 1);
-                const unsigned xs[4] = {pc.xa.x, pc.xa.z, pc.xb.x, pc.xb.z}, ys[4] = {pc.xa.y, pc.xa.w, pc.xb.y, pc.xb.w};
                 const unsigned as[4] = {pc.w.x, pc.w.y, pc.w.z, pc.w.w};
-                float w4[4][4];
+                float fa[4][2], fb[4][2];        // corner weight j of point k: fa[k][j >> 1] * fb[k][j & 1] = {hh a, lh a} x {hw, lw}
                 int slot[4][4];
+                // BoxeR's grid is centre +- size / 4: points 0, 2 share x, 1, 3 share x, 0, 1 share y and 2, 3 share y BIT FOR
+                // BIT (idle lanes: all zeros).  A wave of such groups locates two rows and two columns; the sixteen slots are
+                // row[i] + col[j], the products of the weights those of the per-point code below on the same numbers.
+                bool aligned = false;
+                if (BOXATTN_TUNE_GRP_ALIGNED) {
+                    const bool same = pc.xa.x == pc.xb.x && pc.xa.z == pc.xb.z && pc.xa.y == pc.xa.w && pc.xb.y == pc.xb.w &&
+                                      (kProductMasks >> mask & 1u) != 0u;
+                    aligned = __builtin_amdgcn_ballot_w64(!same) == 0ull;
+                }
+                if (aligned) {
+                    const unsigned ys2[2] = {pc.xa.y, pc.xb.y}, xs2[2] = {pc.xa.x, pc.xa.z};
+                    float hh[2], lh[2], hw[2], lw[2];
+                    int rt[2][2], ct[2][2];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float x = __uint_as_float(xs[k]), y = __uint_as_float(ys[k]), a = __uint_as_float(as[k]);
-                    float h_im, w_im;
-                    {
+                    for (int i = 0; i < 2; ++i) {
+                        const float x = __uint_as_float(xs2[i]), y = __uint_as_float(ys2[i]);
+                        float h_im, w_im;
+                        {
 #pragma clang fp contract(off)                   // two roundings, as in locate()
-                        h_im = y * Hf - 0.5f;
-                        w_im = x * Wf - 0.5f;
+                            h_im = y * Hf - 0.5f;
+                            w_im = x * Wf - 0.5f;
+                        }
+                        const float yf = floorf(h_im), xf = floorf(w_im);
+                        lh[i] = h_im - yf; lw[i] = w_im - xf;
+                        hh[i] = 1.f - lh[i]; hw[i] = 1.f - lw[i];
+                        // row i: points 2 i, 2 i + 1; column i: points i, i + 2 -- outside when the record speaks for neither
+                        const int py = (mask >> (2 * i) & 3) ? (int)yf - oy : -2, px = (mask >> i & 5) ? (int)xf - ox : -2;
+                        rt[i][0] = (unsigned)py < (unsigned)bh ? __mul24(py, BW * 16) : kBig;
+                        rt[i][1] = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * 16) + BW * 16 : kBig;
+                        ct[i][0] = (unsigned)px < (unsigned)bw ? __mul24(px, 16) + lane_at : kBig;
+                        ct[i][1] = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, 16) + lane_at + 16 : kBig;
                     }
-                    const float yf = floorf(h_im), xf = floorf(w_im);
-                    const float lh = h_im - yf, lw = w_im - xf;
-                    // footprint corner relative to the block; points the record does not speak for: outside
-                    const int py = (mask >> k & 1) ? (int)yf - oy : -2, px = (int)xf - ox;
-                    const float hh = 1.f - lh, hw = 1.f - lw;
-                    const float ha = hh * a, la = lh * a;
-                    w4[k][0] = ha * hw; w4[k][1] = ha * lw; w4[k][2] = la * hw; w4[k][3] = la * lw;
-                    // byte offsets of the corners' pixels (16 bytes each, 8 a block row), kBig when outside the block
-                    const int r0 = (unsigned)py < (unsigned)bh ? __mul24(py, BW * 16) : kBig;
-                    const int r1 = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * 16) + BW * 16 : kBig;
-                    const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, 16) : kBig;
-                    const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, 16) + 16 : kBig;
-                    slot[k][0] = lane_at + min(r0 + c0, PB * 16); slot[k][1] = lane_at + min(r0 + c1, PB * 16);
-                    slot[k][2] = lane_at + min(r1 + c0, PB * 16); slot[k][3] = lane_at + min(r1 + c1, PB * 16);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = k >> 1, j = k & 1;
+                        const float a = __uint_as_float(as[k]);
+                        fa[k][0] = hh[i] * a; fa[k][1] = lh[i] * a;
+                        fb[k][0] = hw[j]; fb[k][1] = lw[j];
+                        slot[k][0] = min(rt[i][0] + ct[j][0], dump_lane); slot[k][1] = min(rt[i][0] + ct[j][1], dump_lane);
+                        slot[k][2] = min(rt[i][1] + ct[j][0], dump_lane); slot[k][3] = min(rt[i][1] + ct[j][1], dump_lane);
+                    }
+                } else {
+                    const unsigned xs[4] = {pc.xa.x, pc.xa.z, pc.xb.x, pc.xb.z}, ys[4] = {pc.xa.y, pc.xa.w, pc.xb.y, pc.xb.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float x = __uint_as_float(xs[k]), y = __uint_as_float(ys[k]), a = __uint_as_float(as[k]);
+                        float h_im, w_im;
+                        {
+#pragma clang fp contract(off)                   // two roundings, as in locate()
+                            h_im = y * Hf - 0.5f;
+                            w_im = x * Wf - 0.5f;
+                        }
+                        const float yf = floorf(h_im), xf = floorf(w_im);
+                        const float lh = h_im - yf, lw = w_im - xf;
+                        // footprint corner relative to the block; points the record does not speak for: outside
+                        const int py = (mask >> k & 1) ? (int)yf - oy : -2, px = (int)xf - ox;
+                        const float hh = 1.f - lh, hw = 1.f - lw;
+                        fa[k][0] = hh * a; fa[k][1] = lh * a;
+                        fb[k][0] = hw; fb[k][1] = lw;
+                        // byte offsets of the corners' pixels (16 bytes each, 8 a block row), kBig when outside the block
+                        const int r0 = (unsigned)py < (unsigned)bh ? __mul24(py, BW * 16) : kBig;
+                        const int r1 = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * 16) + BW * 16 : kBig;
+                        if (BOXATTN_TUNE_GRP_FOLD) {       // the lane's column inside the column terms; one dump offset per lane
+                            const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, 16) + lane_at : kBig;
+                            const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, 16) + lane_at + 16 : kBig;
+                            slot[k][0] = min(r0 + c0, dump_lane); slot[k][1] = min(r0 + c1, dump_lane);
+                            slot[k][2] = min(r1 + c0, dump_lane); slot[k][3] = min(r1 + c1, dump_lane);
+                        } else {
+                            const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, 16) : kBig;
+                            const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, 16) + 16 : kBig;
+                            slot[k][0] = lane_at + min(r0 + c0, PB * 16); slot[k][1] = lane_at + min(r0 + c1, PB * 16);
+                            slot[k][2] = lane_at + min(r1 + c0, PB * 16); slot[k][3] = lane_at + min(r1 + c1, PB * 16);
+                        }
+                    }
                 }
                 // The four corners of ONE point are four pixels (or the dump pixel, whose content nobody reads): point 0 is
                 // stored into the cleared column, every further point reads its four slots, adds and stores them -- three
                 // round trips of four independent LDS accesses, in the wave's issue order.  (ds_add_f32 instead -- sixteen
-                // LDS float atomics a round -- made this kernel four times slower than the point flavour.)
+                // LDS float atomics a round -- made this kernel four times slower than the point flavour.)  The sum of a further
+                // point is ONE rounding of old + (hh a) hw, a fused multiply-add -- written out, so that no change of the code
+                // around it changes what the compiler contracts.
                 auto cell = [&](int k, int j) -> float * {
                     return reinterpret_cast<float *>(__builtin_assume_aligned(reinterpret_cast<char *>(at) + slot[k][j], 4));
                 };
 #pragma unroll
-                for (int j = 0; j < 4; ++j) *cell(0, j) = w4[0][j];
+                for (int j = 0; j < 4; ++j) *cell(0, j) = fa[0][j >> 1] * fb[0][j & 1];
 #pragma unroll
                 for (int k = 1; k < 4; ++k) {
                     wave_lds_sync();
@@ -285,37 +369,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
 #pragma unroll
                     for (int j = 0; j < 4; ++j) old[j] = *cell(k, j);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) *cell(k, j) = old[j] + w4[k][j];
+                    for (int j = 0; j < 4; ++j) *cell(k, j) = __builtin_fmaf(fa[k][j >> 1], fb[k][j & 1], old[j]);
                 }
                 wave_lds_sync();
-                // ---- lane = pixel: its 8 records of every K-step, float32; the tile is cleared behind the read
-                float4 f[R / 16][2];
-#pragma unroll
-                for (int t = 0; t < R / 16; ++t)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        f[t][j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(at) + f_off +
-                                                                    (4 * t + j) * kGrpQuadB);
-                tr_h16x8 g[R / 16][NCB];
-#pragma unroll
-                for (int t = 0; t < R / 16; ++t)
-#pragma unroll
-                    for (int cb = 0; cb < NCB; ++cb) {
-                        const uint2 g0 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024);
-                        const uint2 g1 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024 + 256);
-                        g[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
-                    }
-                wave_lds_sync();
-#pragma unroll
-                for (int t = 0; t < R / 16; ++t)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        *reinterpret_cast<float4 *>(reinterpret_cast<char *>(at) + f_off + (4 * t + j) * kGrpQuadB) =
-                            make_float4(0.f, 0.f, 0.f, 0.f);
-                // ---- hi / lo split of the sums, the product: 4 K-steps of 16 records per 32-channel block
-#pragma unroll
-                for (int t = 0; t < R / 16; ++t) {
-                    const float v[8] = {f[t][0].x, f[t][0].y, f[t][0].z, f[t][0].w, f[t][1].x, f[t][1].y, f[t][1].z, f[t][1].w};
+                // ---- hi / lo split of 8 float32 sums, the product of one K-step of 16 records per 32-channel block
+                auto k_step = [&](const float4 &f0, const float4 &f1, const tr_h16x8 (&gt)[NCB]) {
+                    const float v[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
                     unsigned hi[4], lo[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -326,21 +385,71 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
                     const tr_h16x8 p_lo = __builtin_bit_cast(tr_h16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
 #pragma unroll
                     for (int cb = 0; cb < NCB; ++cb) {
-                        acc[cb] = H16::mfma32x32x16(g[t][cb], p_hi, acc[cb]);
-                        acc[cb] = H16::mfma32x32x16(g[t][cb], p_lo, acc[cb]);
+                        acc[cb] = H16::mfma32x32x16(gt[cb], p_hi, acc[cb]);
+                        acc[cb] = H16::mfma32x32x16(gt[cb], p_lo, acc[cb]);
                     }
+                };
+                // An item's last round holds item.z - rr records: the columns of the K-steps behind them were written by
+                // idle lanes only -- to the dump pixel -- and their rows are zeros: no tile read, split, clear, operand
+                // read or product for them (a product of zeros leaves the sums what they are).
+                const int n_k = more ? R / 16 : (item.z - rr + 15) >> 4;      // wave-uniform
+                if (BOXATTN_TUNE_GRP_TAIL && n_k < R / 16) {
+                    for (int t = 0; t < n_k; ++t) {
+                        char *fp = reinterpret_cast<char *>(at) + f_off + 4 * t * kGrpQuadB;
+                        const float4 f0 = *reinterpret_cast<const float4 *>(fp);
+                        const float4 f1 = *reinterpret_cast<const float4 *>(fp + kGrpQuadB);
+                        tr_h16x8 gt[NCB];
+#pragma unroll
+                        for (int cb = 0; cb < NCB; ++cb) {
+                            const uint2 g0 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024);
+                            const uint2 g1 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024 + 256);
+                            gt[cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
+                        }
+                        wave_lds_sync();
+                        *reinterpret_cast<float4 *>(fp) = make_float4(0.f, 0.f, 0.f, 0.f);
+                        *reinterpret_cast<float4 *>(fp + kGrpQuadB) = make_float4(0.f, 0.f, 0.f, 0.f);
+                        k_step(f0, f1, gt);
+                    }
+                } else {
+                    // ---- lane = pixel: its 8 records of every K-step, float32; the tile is cleared behind the read
+                    float4 f[R / 16][2];
+#pragma unroll
+                    for (int t = 0; t < R / 16; ++t)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            f[t][j] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(at) + f_off +
+                                                                        (4 * t + j) * kGrpQuadB);
+                    tr_h16x8 g[R / 16][NCB];
+#pragma unroll
+                    for (int t = 0; t < R / 16; ++t)
+#pragma unroll
+                        for (int cb = 0; cb < NCB; ++cb) {
+                            const uint2 g0 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024);
+                            const uint2 g1 = lds_read_tr16(gs, tr_off + cb * GPL + t * 1024 + 256);
+                            g[t][cb] = __builtin_bit_cast(tr_h16x8, u32x4{g0.x, g0.y, g1.x, g1.y});
+                        }
+                    wave_lds_sync();
+#pragma unroll
+                    for (int t = 0; t < R / 16; ++t)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            *reinterpret_cast<float4 *>(reinterpret_cast<char *>(at) + f_off + (4 * t + j) * kGrpQuadB) =
+                                make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int t = 0; t < R / 16; ++t) k_step(f[t][0], f[t][1], g[t]);
                 }
                 if (more) {          // the next round's rows and points have arrived
                     stage_rows(next);
-                    pc = pn;
+                    if (!BOXATTN_TUNE_GRP_PINGPONG) pc = pn;
                     rec_c = rec_n; rec_n = rec_n2; rec_n2 = rec_n3;
                 }
                 wave_lds_sync();
             };
             for (int rr = item.y; rr < item.z; rr += 2 * R) {
-                round(rr, grow_a, grow_b);
+                round(rr, grow_a, grow_b, pts_a, pts_b);
                 if (rr + R >= item.z) break;
-                round(rr + R, grow_b, grow_a);
+                if (BOXATTN_TUNE_GRP_PINGPONG) round(rr + R, grow_b, grow_a, pts_b, pts_a);
+                else round(rr + R, grow_b, grow_a, pts_a, pts_b);
             }
         } else {
             // software pipeline over rounds of 64 records: the records are read three rounds ahead, their

@@ -792,6 +792,9 @@ hipLaunchKernelGGL((pointgrad2_kernel<ST, GG, INST, GatherUnroll<ST, GG, VV>::va
 // worker) themselves (XCD affinity), hence the 8-aligned grid.
 constexpr int kAccWgCap = 1024;   // accumulate workgroups per slice; beyond that a workgroup takes several items (its next one in
                                   // flight); 256 / 512 / 1024 / 3072 / 6144: C5 99 / 85 / 83 / 93 / 111 us, C2 67 / 54 / 54 / 55 / 54
+#ifndef BOXATTN_TUNE_GRP_WG_CAP
+#define BOXATTN_TUNE_GRP_WG_CAP kAccWgCap      // the same bound for the group-record flavour (sweep: DESIGN.md 4.2.3)
+#endif
 template <typename ST, int G, bool INST>
 int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, const float *loc, const float *w_sp,
                       const float *w_lv, const Dims &d, const BinPlan &plan, const int *offsets, const int4 *items,
@@ -800,7 +803,7 @@ int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, cons
 {
     constexpr int C = 4 * G;
     const int ns = d.B * d.H, ns8 = (ns + 7) / 8 * 8;
-    const int wg_per_slice = std::min(kAccWgCap, std::max(1, plan.item_cap));
+    const int wg_per_slice = std::min(rec == kRecGroup ? (int)(BOXATTN_TUNE_GRP_WG_CAP) : kAccWgCap, std::max(1, plan.item_cap));
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdAccum], st);
     if constexpr (IsHalf16<ST>::value && !INST) {
         if (acc == kAccTr && rec == kRecGroup) {
