@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "boxattn_binned.h"
+#include "boxattn_boxes.h"
 #include "boxattn_fast.h"
 #include "boxattn_gather2.h"
 #include "boxattn_dense_plan.h"
@@ -483,6 +484,69 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
     hipLaunchKernelGGL((fwd_generic_kernel<ST, INST>), dim3(blocks), dim3(256), 0, st, value,
                        shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.C, d.L, d.Lq, d.P, out, mask,
                        n);
+    return finish();
+}
+
+// ---- instance attention at inference from boxes and 2x2 logits (boxattn_boxes.h) ----------------------------
+// Whether fwd_wide_boxes_kernel runs these dimensions (P = k * k points a level): where the instance flavour of
+// fwd_route takes the wave-per-pair family, for the k and L of the weight kernels (k even, 2 ... 32; L <= 16: the
+// 4 L cells of a pair fit the lanes of a wave).  The ONE function behind instattn_fwd_boxes_ok and the entry points;
+// r: the launch geometry.  Option key 22 is not read (the instance flavour does not read it).
+inline bool boxes_route(int elem_bytes, const Dims &d, int k, const FwdAlign &al, FwdRoute &r)
+{
+    if ((elem_bytes != 2 && elem_bytes != 4) || !d.valid()) return false;
+    if (k < 2 || k > 32 || k % 2 != 0 || d.P != k * k || d.L > 16) return false;
+    DensePlan dp;
+    return fwd_route(elem_bytes, true, d, al, nullptr, nullptr, false, r, dp) == kFwdWide;
+}
+
+template <typename ST>
+int launch_fwd_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
+                     int ref_per_head, const float *offsets, const float *kernel_idx, const float *valid_ratios,
+                     const float *logits, int B, int S, int H, int C, int L, int Lq, int k, ST *out, ST *mask,
+                     hipStream_t st)
+{
+    if (k < 2 || k > 32 || k % 2 != 0 || ref_dim < 4) return (int)hipErrorInvalidValue;
+    const Dims d{B, S, H, C, L, Lq, k * k};
+    if (!d.valid() || L > 16) return (int)hipErrorInvalidValue;
+    if (d.empty()) return 0;                                   // no queries: nothing to write
+    if (!shapes || !lsi || !ref || !offsets || !kernel_idx || !logits || !out) return (int)hipErrorInvalidValue;
+    const size_t n_qh = d.n_qh();
+    if (d.n_value() == 0) {                                    // no pixels: every sample is 0
+        hipError_t e = zero_async(out, n_qh * d.C * sizeof(ST), st);
+        if (e == hipSuccess && mask) e = zero_async(mask, n_qh * d.C * d.P * sizeof(ST), st);
+        return (int)e;
+    }
+    if (!value) return (int)hipErrorInvalidValue;
+    const size_t va = 4 * sizeof(ST);
+    FwdAlign al;
+    al.fast = aligned(value, va) && aligned(out, va) && aligned(mask, va);
+    al.rows16 = aligned(value, 16) && aligned(out, 16) && aligned(mask, 16);
+    al.staged = false;
+    FwdRoute r;
+    if (!boxes_route((int)sizeof(ST), d, k, al, r)) return (int)hipErrorInvalidValue;   // no other kernel behind this entry
+    const GridDims gd{Lq, H, L, d.P, 4, ref_dim, ref_per_head ? 1 : 0, 0};
+    const float m = (float)(k / 2);
+    const BoxesDims bd{k, k / 2, 1.f / (float)k, 1.f / (m * m)};
+    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST)), ws = r.ws;
+    const GatherIdx ix = with_grid(r.ix, r.wblocks, 1, 1);
+    const GatherCfg cfg = r.cfg;
+    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
+    if (mask) {
+#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                  \
+    hipLaunchKernelGGL((fwd_wide_boxes_kernel<ST, GG, VV, true>), dim3(r.wblocks), dim3(256), 0, st,  \
+                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, d.S, d.H,  \
+                       d.L, d.Lq, d.P, out, mask, gd, bd, ix, vbytes, ws);
+        BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
+#undef BOXATTN_LAUNCH_BOXES
+    } else {
+#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                  \
+    hipLaunchKernelGGL((fwd_wide_boxes_kernel<ST, GG, VV, false>), dim3(r.wblocks), dim3(256), 0, st, \
+                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, d.S, d.H,  \
+                       d.L, d.Lq, d.P, out, NoArg{}, gd, bd, ix, vbytes, ws);
+        BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
+#undef BOXATTN_LAUNCH_BOXES
+    }
     return finish();
 }
 
@@ -1468,6 +1532,40 @@ int boxattn_fwd_route(int elem_bytes, int instance, int aligned, int B, int S, i
     FwdRoute r;
     DensePlan dp;
     return fwd_route(elem_bytes, instance != 0, d, al, shapes_host, lsi_host, true, r, dp);
+}
+
+int instattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k)
+{
+    if (k < 2 || k > 32) return 0;
+    const Dims d{B, S, H, C, L, Lq, k * k};
+    const int bytes = aligned == 0 ? elem_bytes : aligned == 8 ? 8 : 16;          // as boxattn_fwd_route
+    const FwdAlign al{bytes >= 4 * elem_bytes && bytes >= 8, bytes >= 16, false};
+    FwdRoute r;
+    return boxes_route(elem_bytes, d, k, al, r) ? 1 : 0;
+}
+int instattn_fwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                           int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
+                           const float *valid_ratios, const float *logits, int B, int S, int H, int C, int L,
+                           int Lq, int k, float *out, float *mask_out, void *stream)
+{
+    return launch_fwd_boxes<float>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios,
+                                   logits, B, S, H, C, L, Lq, k, out, mask_out, ST_);
+}
+int instattn_fwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                            int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
+                            const float *valid_ratios, const float *logits, int B, int S, int H, int C, int L,
+                            int Lq, int k, uint16_t *out, uint16_t *mask_out, void *stream)
+{
+    return launch_fwd_boxes<bf16_t>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios,
+                                    logits, B, S, H, C, L, Lq, k, out, mask_out, ST_);
+}
+int instattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                           int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
+                           const float *valid_ratios, const float *logits, int B, int S, int H, int C, int L,
+                           int Lq, int k, uint16_t *out, uint16_t *mask_out, void *stream)
+{
+    return launch_fwd_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx,
+                                   valid_ratios, logits, B, S, H, C, L, Lq, k, as_f16(out), as_f16(mask_out), ST_);
 }
 
 int boxattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,

@@ -4,6 +4,7 @@
 // mask-fill + bf16 cast (N3).  The device helpers they share with the sampling kernels (grid_box, grid_point,
 // grid_grad_*) live in boxattn_grid.h.
 #pragma once
+#include "boxattn_cells.h"
 #include "boxattn_grid.h"
 
 namespace boxattn {
@@ -66,10 +67,6 @@ __global__ __launch_bounds__(256) void grid_bwd_kernel(const float *__restrict__
 // (element index = 4 * thread) and the row max / sum are cross-lane butterflies.  Any other
 // length <= 64: one thread per row (strided accesses; the rare shapes).
 // ---------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ float pw_ld(const T *p);
-template <> __device__ __forceinline__ float pw_ld<float>(const float *p) { return *p; }
-template <> __device__ __forceinline__ float pw_ld<bf16_t>(const bf16_t *p) { return bf16_bits_to_f32(*p); }
-template <> __device__ __forceinline__ float pw_ld<f16_t>(const f16_t *p) { return (float)*p; }
 template <typename T> __device__ __forceinline__ void pw_st(T *p, float v);
 template <> __device__ __forceinline__ void pw_st<float>(float *p, float v) { *p = v; }
 template <> __device__ __forceinline__ void pw_st<bf16_t>(bf16_t *p, float v) { *p = f32_to_bf16(v); }
@@ -191,44 +188,12 @@ __global__ __launch_bounds__(256) void softmax_vec_bwd_kernel(const float *__res
 // level) and must be 16-byte aligned -- the entry points reject other pointers; the logits and their gradient are
 // accessed element by element (consecutive lanes, consecutive elements) and need no alignment.
 // ---------------------------------------------------------------------------------------
-template <int FROM, int G> __device__ __forceinline__ float lanes_max(float v)   // over lanes FROM, 2 FROM, .. G/2 apart
-{
-#pragma unroll
-    for (int o = FROM; o < G; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-template <int FROM, int G> __device__ __forceinline__ float lanes_add(float v)
-{
-#pragma unroll
-    for (int o = FROM; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// q / d for q < 2^20 from rcp = 1.f / d: (q + 0.5) / d is at least 0.5 / d away from an integer, the two
-// roundings (rcp, the product) move it by less than (q + 0.5) / d * 2^-22
-__device__ __forceinline__ unsigned small_div(unsigned q, float rcp)
-{
-    return (unsigned)(((float)q + 0.5f) * rcp);
-}
-
 struct InstDims {
     int L, k;
     unsigned n4_level, n4_row;             // float4s per level (k^2 / 4) and per row
     float rcp_k, rcp_n4_level, rcp_n4_row;
     float inv_m2;                          // 1 / m^2
 };
-
-// this lane's cell: a (softmax over the row, not yet divided by m^2) and t (softmax over the levels)
-template <typename T, int G>
-__device__ __forceinline__ void inst_cell_softmax(const T *__restrict__ logits, size_t row, int c, int L,
-                                                  float &a, float &t)
-{
-    const float z = c < 4 * L ? pw_ld<T>(logits + row * (size_t)(4 * L) + c) : -INFINITY;
-    const float ea = __expf(z - lanes_max<1, G>(z));
-    a = ea * (1.f / lanes_add<1, G>(ea));
-    const float et = __expf(z - lanes_max<4, G>(z));          // (level 0 is always there: the maxima are finite)
-    t = et * (1.f / lanes_add<4, G>(et));
-}
 
 __device__ __forceinline__ float inst_pick(bool hi_y, bool hi_x, float c0, float c1, float c2, float c3)
 {

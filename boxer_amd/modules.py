@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import dense
+from . import dense, ops
 from .functions import (BoxAttnBF16Function, BoxAttnF16Function, BoxAttnFunction, BoxGridFunction,
                         InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
                         InstanceWeightsFunction, LogitSoftmaxFunction, ValueMaskCastFunction)
@@ -61,6 +61,10 @@ class _BoxAttentionBase(nn.Module):
         # (InstanceWeightsFunction) -- and, in the 16-bit storage modes, the value mask-fill + 16-bit cast
         # (ValueMaskCastFunction) as single HIP passes
         self.fused_pointwise = False
+        # opt-in, InstanceAttention at inference only (no grad): the whole of forward between the projections as ONE
+        # HIP launch from the predicted boxes and 2x2 logits (ops.instance_attn_forward_boxes) -- no sampling grid, no
+        # per-point weights; the third element of the return is then the empty tuple
+        self.fused_boxes = False
 
         self.linear_box_weight = nn.Parameter(torch.zeros(num_level * num_head * box_vars, d_model))
         self.linear_box_bias = nn.Parameter(torch.zeros(num_head * num_level * box_vars))
@@ -231,6 +235,37 @@ class InstanceAttention(_BoxAttentionBase):
 
     _where_to_attend = BoxAttention._where_to_attend
 
+    def _boxes_value(self, query, value, v_valid_ratios):
+        """The projected ``value`` as the one-launch inference forward takes it (the storage mode's type, float32
+        without one), or None: that path is not taken -- flag off, grad mode, CPU / float64 tensors, ``v_valid_ratios``
+        of another shape than the reference's, or no kernel for the shape (ops.forward_boxes_ok)."""
+        if not self.fused_boxes or torch.is_grad_enabled() or not (query.is_cuda and value.is_cuda):
+            return None
+        if torch.float64 in (query.dtype, value.dtype):
+            return None                       # (the kernel computes in float32)
+        if v_valid_ratios is not None and not (
+                v_valid_ratios.dim() == 6 and v_valid_ratios.size(0) == query.size(0)
+                and tuple(v_valid_ratios.shape[1:]) == (1, 1, self.num_level, 1, 2)):
+            return None
+        k = self.kernel_size
+        if not (isinstance(k, int) and k % 2 == 0 and 2 <= k <= 32):
+            return None
+        value = value.to(self._storage_dtype() or torch.float32).contiguous()
+        return value if ops.forward_boxes_ok(value, self.num_level, query.size(1), k) else None
+
+    def _forward_boxes(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows, logits):
+        b, l1 = query.shape[:2]
+        k = self.kernel_size
+        f32 = lambda t: t.float().contiguous()
+        offsets = f32(self._box_offsets(query, ref_windows, 4))
+        output, mask_output = ops.instance_attn_forward_boxes(
+            value, v_shape, v_start_index, f32(ref_windows), offsets, f32(self.kernel_indices),
+            None if v_valid_ratios is None else f32(v_valid_ratios).view(b, self.num_level, 2), f32(logits), k,
+            need_mask=not self.inferencing)
+        if mask_output is not None:
+            mask_output = self.out_proj(mask_output.view(b, l1, k, k, self.d_model))
+        return self.out_proj(output), mask_output, ()
+
     def forward(self, query, value, v_shape, v_mask, v_start_index, v_valid_ratios, ref_windows):
         b, l1 = query.shape[:2]
         k = self.kernel_size
@@ -238,6 +273,10 @@ class InstanceAttention(_BoxAttentionBase):
 
         logits = dense.linear(query, self.linear_attn_weight, self.linear_attn_bias)
         logits = logits.view(b, l1, self.num_head, self.num_level, 2, 2)
+        boxes_value = self._boxes_value(query, value, v_valid_ratios)
+        if boxes_value is not None:
+            return self._forward_boxes(query, boxes_value, v_shape, v_start_index, v_valid_ratios, ref_windows,
+                                       logits)
         # (the kernels' shapes: k even, 2 ... 32, at most 16 levels)
         fused = (k % 2 == 0 and 2 <= k <= 32 and self.num_level <= 16 and self._fused_logits(logits))
         if fused:

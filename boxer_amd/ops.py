@@ -844,3 +844,61 @@ def instance_weights_backward(logits, grad_spatial, grad_level=None):
                _aligned16(grad_spatial) if grad_spatial is not None else 0,
                _aligned16(grad_level) if grad_level is not None else 0, rows, L, k, out)
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# instance attention at inference straight from boxes and 2x2 logits (opt-in; SURVEY.md 8(f) N1 + N3 inside the
+# operator: include/boxattn.h, instattn_fwd_boxes_*)
+# ---------------------------------------------------------------------------------------
+def _align_of(*tensors):
+    ptrs = [t.data_ptr() for t in tensors]
+    return 16 if all(p % 16 == 0 for p in ptrs) else 8 if all(p % 8 == 0 for p in ptrs) else 0
+
+
+def forward_boxes_ok(value, num_level, num_query, kernel_size):
+    """Whether ``instance_attn_forward_boxes`` has its kernel under the current switches: ``instattn_fwd_boxes_ok``
+    with the dimensions, element size and alignment of ``value`` (B, S, H, C), ``num_level`` levels, ``num_query``
+    queries an image and ``kernel_size`` x ``kernel_size`` points a level.  The outputs are taken as freshly
+    allocated (aligned).  Pure host code."""
+    if value.dim() != 4 or value.dtype not in (torch.float32,) + _H16:
+        return False
+    B, S, H, C = value.shape
+    return _lib.fwd_boxes_ok(value.element_size(), _align_of(value), (B, S, H, C, num_level, num_query), kernel_size)
+
+
+def instance_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                                valid_ratios, logits, kernel_size, need_mask=True):
+    """InstanceAttention's inference forward in one launch, from what the module predicts:
+    ``value`` (B,S,H,C) float32 / bfloat16 / float16, ``ref_windows`` (B,Lq,D) or (B,Lq,H,D), ``offsets``
+    (B,Lq,H,L,4), ``kernel_indices`` (k*k,2), ``valid_ratios`` None or B*L*2 values, ``logits`` (B,Lq,H,L,2,2) -- all
+    float32 but ``value`` -> ``(output (B,Lq,H*C), mask_output (B,Lq,k*k,H*C) or None)`` in the type of ``value``:
+    what ``box_grid_forward`` -> ``instance_weights_forward`` -> ``instance_attn_forward`` (``need_mask``) or
+    ``box_attn_forward`` on the spatial weights (not ``need_mask``) return, without the per-point tensors in
+    between.  No backward.  Raises where ``forward_boxes_ok`` says no: there is no other kernel behind it."""
+    (B, Lq, H, L, P), (D, per_head, _, _) = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios, 0)
+    _check(value, "value")
+    _check(spatial_shapes, "spatial_shapes")
+    _check(level_start_index, "level_start_index")
+    _check(logits, "logits")
+    k = int(kernel_size)
+    if value.dtype not in (torch.float32,) + _H16:
+        raise RuntimeError("instance_attn_forward_boxes: float32, bfloat16 or float16 value expected, got %s" % value.dtype)
+    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
+        raise RuntimeError("spatial_shapes / level_start_index must be int64")
+    if logits.dtype != torch.float32 or tuple(logits.shape) != (B, Lq, H, L, 2, 2):
+        raise RuntimeError("expected logits (B,Lq,H,L,2,2) float32 matching offsets")
+    if value.dim() != 4 or value.size(0) != B or value.size(2) != H or spatial_shapes.size(0) != L or \
+            level_start_index.numel() != L:
+        raise RuntimeError("offsets / spatial_shapes do not match value (B,S,H,C)")
+    if P != k * k:
+        raise RuntimeError("kernel_indices must have kernel_size**2 rows")
+    if not forward_boxes_ok(value, L, Lq, k):
+        raise RuntimeError("instance_attn_forward_boxes: no kernel for value %s, %d levels, %d queries, kernel_size %d "
+                           "(forward_boxes_ok)" % (tuple(value.shape), L, Lq, k))
+    S, C = value.size(1), value.size(3)
+    out = torch.empty((B, Lq, H * C), dtype=value.dtype, device=value.device)
+    mask = torch.empty((B, Lq, P, H * C), dtype=value.dtype, device=value.device) if need_mask else None
+    _grid_call("instattn_fwd_boxes_" + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index,
+               ref_windows, D, per_head, offsets, kernel_indices, valid_ratios if valid_ratios is not None else 0,
+               logits, B, S, H, C, L, Lq, k, out, mask if need_mask else 0)
+    return out, mask

@@ -490,6 +490,43 @@ int instattn_weights_bwd_f16(const uint16_t *logits, const float *grad_spatial_w
                              uint16_t *grad_logits, void *stream);
 
 /*
+ * Instance attention at INFERENCE straight from what the module predicts per (batch, query, head, level) -- one box and
+ * 2x2 logits -- in one launch: what boxattn_grid_fwd_f32 (angle_mode 0, V = 4), instattn_weights_fwd_f32 and
+ * instattn_fwd_* compute in three, without the (B,Lq,H,L,k*k,2) sampling grid and the (B,Lq,H,L,k,k) weight tensors
+ * in between.  Locations and weights are made by the device functions those kernels use, in their
+ * operation order, in float32.  ref / ref_dim / ref_per_head / offsets / kernel_idx / valid_ratios as
+ * boxattn_grid_fwd_f32, logits as instattn_weights_fwd_f32; P = k * k points a level, row-major over (y, x).
+ *   mask_out given: out and mask_out of instattn_fwd_*;
+ *   mask_out NULL:  out of boxattn_fwd_* with the spatial weights (the module with `inferencing` set).
+ * Forward only (training keeps the per-point tensors: the backward reads them).  One wave-per-pair kernel and no other
+ * behind these entries: dimensions for which instattn_fwd_boxes_ok answers 0 -- with `aligned` what value, out and
+ * mask_out are aligned to -- are hipErrorInvalidValue, and so is a NULL among value, shapes, lsi, ref, offsets,
+ * kernel_idx, logits, out; nothing is launched then.  No queries: nothing is written; no pixels: the outputs are
+ * zero-filled.  No atomics (bitwise reproducible), no host reads, no allocation: capturable.  Profile slot 0.
+ */
+int instattn_fwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *ref, int ref_dim, int ref_per_head, const float *offsets,
+                           const float *kernel_idx, const float *valid_ratios, const float *logits,
+                           int B, int S, int H, int C, int L, int Lq, int k, float *out, float *mask_out,
+                           void *stream);
+int instattn_fwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                            const float *ref, int ref_dim, int ref_per_head, const float *offsets,
+                            const float *kernel_idx, const float *valid_ratios, const float *logits,
+                            int B, int S, int H, int C, int L, int Lq, int k, uint16_t *out,
+                            uint16_t *mask_out, void *stream);
+int instattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *ref, int ref_dim, int ref_per_head, const float *offsets,
+                           const float *kernel_idx, const float *valid_ratios, const float *logits,
+                           int B, int S, int H, int C, int L, int Lq, int k, uint16_t *out,
+                           uint16_t *mask_out, void *stream);
+/* 1 where the entry points above have their kernel: boxattn_fwd_route answers BOXATTN_FWD_WIDE for the instance flavour
+ * of these dimensions with P = k * k (that covers boxattn_set_variant, the alignment and value < 2 GiB), k is even,
+ * 2 <= k <= 32, and L <= 16; else 0.  elem_bytes 2 / 4; aligned as boxattn_fwd_route.  The same answer with and
+ * without mask_out; option key 22 is not read.  Pure host code: no device call; the entry points call the same
+ * function. */
+int instattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k);
+
+/*
  * Tuning options for A/B runs (process-wide, relaxed atomics; 0 = default).  Returns the
  * previous value, -1 for an unknown key.  (The key numbers of earlier ABI versions are kept; the keys
  * of kernels that were removed are gone.)
