@@ -13,13 +13,14 @@ DESIGN.md and INTEGRATION.md.  There is no CPU fallback: ops raise if the librar
 from . import _lib, ops
 from .functions import (BoxAttnBF16Function, BoxAttnF16Function, BoxAttnFunction, BoxGridFunction,
                         InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
-                        InstanceWeightsFunction, LogitSoftmaxFunction, ValueMaskCastFunction)
+                        InstanceAttnBoxesFunction, InstanceWeightsFunction, LogitSoftmaxFunction,
+                        ValueMaskCastFunction)
 from .modules import Box3dAttention, BoxAttention, InstanceAttention
 
 __all__ = [
     "ops", "BoxAttnFunction", "InstanceAttnFunction", "BoxAttnBF16Function",
     "InstanceAttnBF16Function", "BoxAttnF16Function", "InstanceAttnF16Function", "BoxGridFunction", "LogitSoftmaxFunction", "ValueMaskCastFunction",
-    "InstanceWeightsFunction",
+    "InstanceWeightsFunction", "InstanceAttnBoxesFunction",
     "BoxAttention", "InstanceAttention", "Box3dAttention",
     "build", "build_info",
 ]

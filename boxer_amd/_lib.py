@@ -92,13 +92,18 @@ _GRID_SIGNATURES = {
 # B, S, H, C, L, Lq, k, out, mask_out | NULL, stream
 _BOXES_SIGNATURES = {"instattn_fwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_vp] * 4 + [_i] * 7 + [_vp] * 3
                      for suf in ("f32", "bf16", "f16")}
+# value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios | NULL, logits, grad_out,
+# grad_mask | NULL, B, S, H, C, L, Lq, k, grad_offsets, grad_ref_rows | NULL, grad_logits, stream
+_BOXES_BWD_SIGNATURES = {"instattn_bwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_vp] * 6 + [_i] * 7 + [_vp] * 4
+                         for suf in ("f32", "bf16", "f16")}
 EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "boxattn_set_option",
            "boxattn_options_epoch", "boxattn_fwd_route", "boxattn_bwd_accumulate_kind", "boxattn_bwd_record_kind",
            "boxattn_set_debug_buffer",
            "boxattn_fwd_hl_f32", "boxattn_fwd_hl_bf16", "boxattn_fwd_hl_f16", *sorted(_POINTWISE_SIGNATURES),
            "boxattn_profile_begin", "boxattn_profile_end", "boxattn_bwd_workspace_bytes",
            "boxattn_plan_bytes", "boxattn_state_bytes",
-           "boxattn_grid_fwd_f32", "boxattn_grid_bwd_f32", "instattn_fwd_boxes_ok", *sorted(_BOXES_SIGNATURES)] + [
+           "boxattn_grid_fwd_f32", "boxattn_grid_bwd_f32", "instattn_fwd_boxes_ok", *sorted(_BOXES_SIGNATURES),
+           "instattn_bwd_boxes_ok", *sorted(_BOXES_BWD_SIGNATURES)] + [
     "%s_%s" % (stem, suf) for stem in _SIGNATURES for suf in ("f32", "f64", "bf16", "f16")] + [
     "%s_%s" % (stem, suf) for stem in _WS_SIGNATURES for suf in ("f32", "bf16", "f16")] + [
     "%s_%s" % (stem, suf) for stem in _PART_SIGNATURES for suf in ("f32", "bf16", "f16")] + sorted(_PART_F64_SIGNATURES)
@@ -239,11 +244,13 @@ def load():
     lib.boxattn_bwd_record_kind.argtypes = [_i] * 9
     lib.boxattn_bwd_record_kind.restype = _i
     for name, args in (list(_GRID_SIGNATURES.items()) + list(_POINTWISE_SIGNATURES.items()) +
-                       list(_BOXES_SIGNATURES.items())):
+                       list(_BOXES_SIGNATURES.items()) + list(_BOXES_BWD_SIGNATURES.items())):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = _i
     lib.instattn_fwd_boxes_ok.argtypes = [_i] * 9
     lib.instattn_fwd_boxes_ok.restype = _i
+    lib.instattn_bwd_boxes_ok.argtypes = [_i] * 9
+    lib.instattn_bwd_boxes_ok.restype = _i
     lib.boxattn_state_bytes.argtypes = [_i] * 7 + [_vp, _vp]
     lib.boxattn_state_bytes.restype = ctypes.c_size_t
     for name in ("boxattn_bwd_workspace_bytes", "boxattn_plan_bytes"):
@@ -290,6 +297,12 @@ def fwd_boxes_ok(elem_bytes, aligned, dims, k):
     """instattn_fwd_boxes_ok(): whether the instattn_fwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
     C, L, Lq) and ``k`` x ``k`` points a level under the current switches.  Pure host code (no GPU needed)."""
     return bool(load().instattn_fwd_boxes_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims], int(k)))
+
+
+def bwd_boxes_ok(elem_bytes, aligned, dims, k):
+    """instattn_bwd_boxes_ok(): whether the instattn_bwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
+    C, L, Lq) and ``k`` x ``k`` points a level under the current switches.  Pure host code (no GPU needed)."""
+    return bool(load().instattn_bwd_boxes_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims], int(k)))
 
 
 # boxattn_bwd_accumulate_kind: the grad_value accumulate kernels of the binned backward (BOXATTN_ACC_*)

@@ -17,6 +17,7 @@
 
 #include "boxattn_binned.h"
 #include "boxattn_boxes.h"
+#include "boxattn_boxes_bwd.h"
 #include "boxattn_fast.h"
 #include "boxattn_gather2.h"
 #include "boxattn_dense_plan.h"
@@ -544,6 +545,64 @@ int launch_fwd_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi,
     hipLaunchKernelGGL((fwd_wide_boxes_kernel<ST, GG, VV, false>), dim3(r.wblocks), dim3(256), 0, st, \
                        value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, d.S, d.H,  \
                        d.L, d.Lq, d.P, out, NoArg{}, gd, bd, ix, vbytes, ws);
+        BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
+#undef BOXATTN_LAUNCH_BOXES
+    }
+    return finish();
+}
+
+// ---- instance attention's box and logit gradients from boxes and 2x2 logits (boxattn_boxes_bwd.h) -----------
+// Eligibility is boxes_route, with grad_out / grad_mask in the place of the forward's out / mask_out in the row
+// alignment: the ONE function behind instattn_bwd_boxes_ok and the entry points.  grad_mask NULL: the flavour
+// without the level term.  No other kernel behind this entry.
+template <typename ST>
+int launch_bwd_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
+                     int ref_per_head, const float *offsets, const float *kernel_idx, const float *valid_ratios,
+                     const float *logits, const ST *grad_out, const ST *grad_mask, int B, int S, int H, int C, int L,
+                     int Lq, int k, float *grad_offsets, float *grad_ref_rows, float *grad_logits, hipStream_t st)
+{
+    if (k < 2 || k > 32 || k % 2 != 0 || ref_dim < 4) return (int)hipErrorInvalidValue;
+    const Dims d{B, S, H, C, L, Lq, k * k};
+    if (!d.valid() || L > 16) return (int)hipErrorInvalidValue;
+    if (d.empty()) return 0;                                   // no queries: nothing to write
+    if (!shapes || !lsi || !ref || !offsets || !kernel_idx || !logits || !grad_out || !grad_offsets || !grad_logits)
+        return (int)hipErrorInvalidValue;
+    const size_t n_rows = d.n_qh() * (size_t)L;
+    if (d.n_value() == 0) {                                    // no pixels: every gradient is 0
+        hipError_t e = zero_async(grad_offsets, n_rows * 4 * sizeof(float), st);
+        if (e == hipSuccess && grad_ref_rows) e = zero_async(grad_ref_rows, n_rows * 5 * sizeof(float), st);
+        if (e == hipSuccess) e = zero_async(grad_logits, n_rows * 4 * sizeof(float), st);
+        return (int)e;
+    }
+    if (!value) return (int)hipErrorInvalidValue;
+    const size_t va = 4 * sizeof(ST);
+    FwdAlign al;
+    al.fast = aligned(value, va) && aligned(grad_out, va) && aligned(grad_mask, va);
+    al.rows16 = aligned(value, 16) && aligned(grad_out, 16) && aligned(grad_mask, 16);
+    al.staged = false;
+    FwdRoute r;
+    if (!boxes_route((int)sizeof(ST), d, k, al, r)) return (int)hipErrorInvalidValue;
+    const GridDims gd{Lq, H, L, d.P, 4, ref_dim, ref_per_head ? 1 : 0, 0};
+    const float m = (float)(k / 2);
+    const BoxesDims bd{k, k / 2, 1.f / (float)k, 1.f / (m * m)};
+    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST)), ws = r.ws;
+    const GatherIdx ix = with_grid(r.ix, r.wblocks, 1, 1);
+    const GatherCfg cfg = r.cfg;
+    ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], st);
+    if (grad_mask) {
+#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                    \
+    hipLaunchKernelGGL((pointgrad_boxes_kernel<ST, GG, VV, true>), dim3(r.wblocks), dim3(256), 0, st,   \
+                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, grad_out,    \
+                       grad_mask, d.S, d.H, d.L, d.Lq, d.P, grad_offsets, grad_ref_rows, grad_logits,   \
+                       gd, bd, ix, vbytes, ws);
+        BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
+#undef BOXATTN_LAUNCH_BOXES
+    } else {
+#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                    \
+    hipLaunchKernelGGL((pointgrad_boxes_kernel<ST, GG, VV, false>), dim3(r.wblocks), dim3(256), 0, st,  \
+                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, grad_out,    \
+                       NoArg{}, d.S, d.H, d.L, d.Lq, d.P, grad_offsets, grad_ref_rows, grad_logits,     \
+                       gd, bd, ix, vbytes, ws);
         BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
 #undef BOXATTN_LAUNCH_BOXES
     }
@@ -1566,6 +1625,41 @@ int instattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const i
 {
     return launch_fwd_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx,
                                    valid_ratios, logits, B, S, H, C, L, Lq, k, as_f16(out), as_f16(mask_out), ST_);
+}
+
+int instattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k)
+{
+    return instattn_fwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, k);   // boxes_route: one eligibility
+}
+int instattn_bwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                           int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
+                           const float *valid_ratios, const float *logits, const float *grad_out,
+                           const float *grad_mask, int B, int S, int H, int C, int L, int Lq, int k,
+                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
+{
+    return launch_bwd_boxes<float>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios,
+                                   logits, grad_out, grad_mask, B, S, H, C, L, Lq, k, grad_offsets, grad_ref_rows,
+                                   grad_logits, ST_);
+}
+int instattn_bwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                            int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
+                            const float *valid_ratios, const float *logits, const uint16_t *grad_out,
+                            const uint16_t *grad_mask, int B, int S, int H, int C, int L, int Lq, int k,
+                            float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
+{
+    return launch_bwd_boxes<bf16_t>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios,
+                                    logits, grad_out, grad_mask, B, S, H, C, L, Lq, k, grad_offsets, grad_ref_rows,
+                                    grad_logits, ST_);
+}
+int instattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                           int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
+                           const float *valid_ratios, const float *logits, const uint16_t *grad_out,
+                           const uint16_t *grad_mask, int B, int S, int H, int C, int L, int Lq, int k,
+                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
+{
+    return launch_bwd_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx,
+                                   valid_ratios, logits, as_f16(grad_out), as_f16(grad_mask), B, S, H, C, L, Lq, k,
+                                   grad_offsets, grad_ref_rows, grad_logits, ST_);
 }
 
 int boxattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,

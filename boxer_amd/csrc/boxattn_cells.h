@@ -1,6 +1,6 @@
-// Instance attention's 2x2 cells: the softmaxes over a row's 4 L logits that the weight kernels (boxattn_pointwise.h,
-// translation unit boxattn_extras.hip) and the forward that takes boxes and logits (boxattn_boxes.h, translation unit
-// boxattn_capi.hip) share -- one text, so both make the same numbers.  Device helpers only: no kernel is defined here.
+// Instance attention's 2x2 cells: the softmaxes over a row's 4 L logits and the per-cell gradient sums that the weight
+// kernels (boxattn_pointwise.h, translation unit boxattn_extras.hip) and the kernels that take boxes and logits
+// (boxattn_boxes.h, boxattn_boxes_bwd.h, translation unit boxattn_capi.hip) share -- one text, so both make the same numbers.  Device helpers only: no kernel is defined here.
 #pragma once
 #include "boxattn_device.h"
 
@@ -43,6 +43,23 @@ __device__ __forceinline__ void inst_cell_softmax(const T *__restrict__ logits, 
     a = ea * (1.f / lanes_add<1, G>(ea));
     const float et = __expf(z - lanes_max<4, G>(z));          // (level 0 is always there: the maxima are finite)
     t = et * (1.f / lanes_add<4, G>(et));
+}
+
+// per-cell sums of a level's upstream weight gradients (the weight backward, and the backward that takes boxes)
+struct InstCellSums { float c0, c1, c2, c3; };
+__device__ __forceinline__ void inst_cell_add(InstCellSums &s, bool hi_y, bool hi_x, float g)
+{
+    s.c0 += !hi_y && !hi_x ? g : 0.f;
+    s.c1 += !hi_y && hi_x ? g : 0.f;
+    s.c2 += hi_y && !hi_x ? g : 0.f;
+    s.c3 += hi_y && hi_x ? g : 0.f;
+}
+// the four lanes of a level: sum the partial cell sums over them (DPP quad), lane s keeps cell s
+__device__ __forceinline__ float inst_cell_total(const InstCellSums &s, int sub)
+{
+    const float c0 = lanes_add<1, 4>(s.c0), c1 = lanes_add<1, 4>(s.c1), c2 = lanes_add<1, 4>(s.c2),
+                c3 = lanes_add<1, 4>(s.c3);
+    return sub == 0 ? c0 : sub == 1 ? c1 : sub == 2 ? c2 : c3;
 }
 
 }  // namespace boxattn

@@ -253,22 +253,6 @@ __global__ __launch_bounds__(256) void inst_weights_fwd_kernel(const T *__restri
     }
 }
 
-struct InstCellSums { float c0, c1, c2, c3; };
-__device__ __forceinline__ void inst_cell_add(InstCellSums &s, bool hi_y, bool hi_x, float g)
-{
-    s.c0 += !hi_y && !hi_x ? g : 0.f;
-    s.c1 += !hi_y && hi_x ? g : 0.f;
-    s.c2 += hi_y && !hi_x ? g : 0.f;
-    s.c3 += hi_y && hi_x ? g : 0.f;
-}
-// the four lanes of a level: sum the partial cell sums over them (DPP quad), lane s keeps cell s
-__device__ __forceinline__ float inst_cell_total(const InstCellSums &s, int sub)
-{
-    const float c0 = lanes_add<1, 4>(s.c0), c1 = lanes_add<1, 4>(s.c1), c2 = lanes_add<1, 4>(s.c2),
-                c3 = lanes_add<1, 4>(s.c3);
-    return sub == 0 ? c0 : sub == 1 ? c1 : sub == 2 ? c2 : c3;
-}
-
 // Load-bound: the four lanes of a (row, level) walk that level's k^2 / 4 float4s of each upstream gradient (a
 // quad reads 64 consecutive bytes), every lane keeps four per-cell sums per gradient, chosen by predicate; quad
 // sums, then lane c holds Gs[c] and Gt[c] next to its a[c] and t[c].  Either gradient may be NULL (= zeros).

@@ -329,3 +329,77 @@ def _ref_grad(ref_windows, rows):
     n = min(5, ref_windows.size(-1))
     grad_ref[..., :n] = rows[..., :n]
     return grad_ref
+
+
+_H16 = (torch.bfloat16, torch.float16)
+
+
+class InstanceAttnBoxesFunction(Function):
+    """(value (B,S,H,C), spatial_shapes, level_start_index, ref_windows (B,Lq,D) / (B,Lq,H,D), offsets (B,Lq,H,L,4),
+    kernel_indices (k*k,2), valid_ratios None / B*L*2 values, logits (B,Lq,H,L,2,2), kernel_size) ->
+    (output (B,Lq,H*C), mask_output (B,Lq,k,k,H*C)): InstanceAttention's training step from what the module predicts
+    (``module.fused_boxes_train``).  The forward is ``ops.instance_attn_forward_boxes``; nothing per point is saved.
+    The gradients of ``offsets``, ``ref_windows`` and ``logits`` come from one ``ops.instance_attn_backward_boxes``
+    call; ``grad_value`` comes from the destination-binned backward, whose records need the per-point tensors: they
+    are rebuilt for that call (same device functions: bit for bit what the forward sampled) and dropped after it.
+    ``value`` is float32, or bfloat16 / float16: that is then the storage type -- outputs in it, upstream gradients
+    cast to it, ``grad_value`` in the caller's type (the conventions of the 16-bit Functions above).  A mask output
+    the loss did not use arrives as None and reaches the kernels as NULL."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios,
+                logits, kernel_size):
+        ctx.set_materialize_grads(False)
+        storage = value.dtype if value.dtype in _H16 else torch.float32
+        ctx.value_dtype, ctx.k = value.dtype, int(kernel_size)
+        ctx.in_dtypes = (ref_windows.dtype, offsets.dtype, logits.dtype)
+        f32 = lambda t: t.detach().float().contiguous()
+        value = value.detach().to(storage).contiguous()
+        ref_windows, offsets, kernel_indices, logits = f32(ref_windows), f32(offsets), f32(kernel_indices), f32(logits)
+        if valid_ratios is not None:
+            valid_ratios = f32(valid_ratios)
+        output, mask_output = ops.instance_attn_forward_boxes(
+            value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits,
+            ctx.k, need_mask=True)
+        # (the (k*k, 2) buffer is kept flat: nothing saved here has a point axis)
+        ctx.save_for_backward(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices.view(-1),
+                              valid_ratios, logits)
+        b, l, _, c = mask_output.shape
+        return output, mask_output.view(b, l, ctx.k, ctx.k, c)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output, grad_mask_output):
+        none = (None,) * 9
+        if grad_output is None and grad_mask_output is None:
+            return none
+        value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits = ctx.saved_tensors
+        kernel_indices = kernel_indices.view(-1, 2)
+        need_v, _, _, need_r, need_o, _, _, need_l = ctx.needs_input_grad[:8]
+        B, Lq, H, L = offsets.shape[:4]
+        if grad_output is None:
+            grad_output = value.new_zeros((B, Lq, H * value.size(3)))
+        grad_output = grad_output.to(value.dtype).contiguous()
+        if grad_mask_output is not None:
+            grad_mask_output = grad_mask_output.to(value.dtype).contiguous()
+        grad_value = grad_ref = grad_offsets = grad_logits = None
+        if need_r or need_o or need_l:
+            grad_offsets, rows, grad_logits = ops.instance_attn_backward_boxes(
+                value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits, ctx.k, grad_output,
+                grad_mask_output, need_ref_grad=need_r)
+            rdt, odt, ldt = ctx.in_dtypes
+            grad_ref = _ref_grad(ref_windows, rows).to(rdt) if need_r else None
+            grad_offsets = grad_offsets.to(odt) if need_o else None
+            grad_logits = grad_logits.to(ldt) if need_l else None
+        if need_v:
+            # the per-point tensors, for this call only
+            loc = ops.box_grid_forward(ref_windows, offsets, kernel_indices, valid_ratios, 0)
+            sw, lw = ops.instance_weights_forward(logits, ctx.k, grad_mask_output is not None)
+            if grad_mask_output is not None:
+                grad_value = ops.instance_attn_backward(value, shapes, lsi, loc, sw, lw, grad_output,
+                                                        grad_mask_output, B, plan=None, want=1)[0]
+            else:
+                grad_value = ops.box_attn_backward(value, shapes, lsi, loc, sw, grad_output, B, plan=None, want=1)[0]
+            del loc, sw, lw
+            grad_value = grad_value.to(ctx.value_dtype)
+        return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)

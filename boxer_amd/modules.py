@@ -23,8 +23,8 @@ import torch.nn.functional as F
 
 from . import dense, ops
 from .functions import (BoxAttnBF16Function, BoxAttnF16Function, BoxAttnFunction, BoxGridFunction,
-                        InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
-                        InstanceWeightsFunction, LogitSoftmaxFunction, ValueMaskCastFunction)
+                        InstanceAttnBF16Function, InstanceAttnBoxesFunction, InstanceAttnF16Function,
+                        InstanceAttnFunction, InstanceWeightsFunction, LogitSoftmaxFunction, ValueMaskCastFunction)
 
 
 def _kernel_offsets(kernel_size, divisor):
@@ -65,6 +65,10 @@ class _BoxAttentionBase(nn.Module):
         # HIP launch from the predicted boxes and 2x2 logits (ops.instance_attn_forward_boxes) -- no sampling grid, no
         # per-point weights; the third element of the return is then the empty tuple
         self.fused_boxes = False
+        # opt-in, InstanceAttention in training (grad mode, `inferencing` false): forward and backward from the boxes
+        # and 2x2 logits (InstanceAttnBoxesFunction) -- no per-point tensor is built in the forward or kept for the
+        # backward; the third element of the return is then the empty tuple.  `fused_boxes` does not imply it.
+        self.fused_boxes_train = False
 
         self.linear_box_weight = nn.Parameter(torch.zeros(num_level * num_head * box_vars, d_model))
         self.linear_box_bias = nn.Parameter(torch.zeros(num_head * num_level * box_vars))
@@ -239,7 +243,38 @@ class InstanceAttention(_BoxAttentionBase):
         """The projected ``value`` as the one-launch inference forward takes it (the storage mode's type, float32
         without one), or None: that path is not taken -- flag off, grad mode, CPU / float64 tensors, ``v_valid_ratios``
         of another shape than the reference's, or no kernel for the shape (ops.forward_boxes_ok)."""
-        if not self.fused_boxes or torch.is_grad_enabled() or not (query.is_cuda and value.is_cuda):
+        if not self.fused_boxes or torch.is_grad_enabled():
+            return None
+        value = self._boxes_operand(query, value, v_valid_ratios)
+        return value if value is not None and ops.forward_boxes_ok(value, self.num_level, query.size(1),
+                                                                   self.kernel_size) else None
+
+    def _boxes_train(self, query, value, v_valid_ratios):
+        """``value`` as the training step from boxes and logits takes it (a differentiable cast), or None: that path
+        is not taken -- ``fused_boxes_train`` off, no grad mode, ``inferencing``, what ``_boxes_operand`` refuses, or
+        no kernel for the shape one way or the other."""
+        if not self.fused_boxes_train or not torch.is_grad_enabled() or self.inferencing:
+            return None
+        value = self._boxes_operand(query, value, v_valid_ratios)
+        if value is None:
+            return None
+        n, k = query.size(1), self.kernel_size
+        ok = ops.backward_boxes_ok(value, self.num_level, n, k) and ops.forward_boxes_ok(value, self.num_level, n, k)
+        return value if ok else None
+
+    def _forward_boxes_train(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows, logits):
+        b, l1 = query.shape[:2]
+        # (differentiable casts: the gradients flow on to the projections, the query and the reference windows)
+        output, mask_output = InstanceAttnBoxesFunction.apply(
+            value, v_shape, v_start_index, ref_windows.float(), self._box_offsets(query, ref_windows, 4).float(),
+            self.kernel_indices, None if v_valid_ratios is None else v_valid_ratios.view(b, self.num_level, 2),
+            logits.float(), self.kernel_size)
+        return self.out_proj(output), self.out_proj(mask_output), ()
+
+    def _boxes_operand(self, query, value, v_valid_ratios):
+        """``value`` in the type the kernels from boxes take it, or None where they do not run: CPU / float64 tensors,
+        ``v_valid_ratios`` of another shape than the reference's, k odd or out of 2 ... 32."""
+        if not (query.is_cuda and value.is_cuda):
             return None
         if torch.float64 in (query.dtype, value.dtype):
             return None                       # (the kernel computes in float32)
@@ -250,8 +285,7 @@ class InstanceAttention(_BoxAttentionBase):
         k = self.kernel_size
         if not (isinstance(k, int) and k % 2 == 0 and 2 <= k <= 32):
             return None
-        value = value.to(self._storage_dtype() or torch.float32).contiguous()
-        return value if ops.forward_boxes_ok(value, self.num_level, query.size(1), k) else None
+        return value.to(self._storage_dtype() or torch.float32).contiguous()
 
     def _forward_boxes(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows, logits):
         b, l1 = query.shape[:2]
@@ -277,6 +311,10 @@ class InstanceAttention(_BoxAttentionBase):
         if boxes_value is not None:
             return self._forward_boxes(query, boxes_value, v_shape, v_start_index, v_valid_ratios, ref_windows,
                                        logits)
+        boxes_value = self._boxes_train(query, value, v_valid_ratios)
+        if boxes_value is not None:
+            return self._forward_boxes_train(query, boxes_value, v_shape, v_start_index, v_valid_ratios, ref_windows,
+                                             logits)
         # (the kernels' shapes: k even, 2 ... 32, at most 16 levels)
         fused = (k % 2 == 0 and 2 <= k <= 32 and self.num_level <= 16 and self._fused_logits(logits))
         if fused:

@@ -855,6 +855,29 @@ def _align_of(*tensors):
     return 16 if all(p % 16 == 0 for p in ptrs) else 8 if all(p % 8 == 0 for p in ptrs) else 0
 
 
+def _boxes_args(what, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios,
+                logits, kernel_size):
+    """The argument checks the calls from boxes share -> (B, Lq, H, L, P), D, per_head, k."""
+    (B, Lq, H, L, P), (D, per_head, _, _) = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios, 0)
+    _check(value, "value")
+    _check(spatial_shapes, "spatial_shapes")
+    _check(level_start_index, "level_start_index")
+    _check(logits, "logits")
+    k = int(kernel_size)
+    if value.dtype not in (torch.float32,) + _H16:
+        raise RuntimeError("%s: float32, bfloat16 or float16 value expected, got %s" % (what, value.dtype))
+    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
+        raise RuntimeError("spatial_shapes / level_start_index must be int64")
+    if logits.dtype != torch.float32 or tuple(logits.shape) != (B, Lq, H, L, 2, 2):
+        raise RuntimeError("expected logits (B,Lq,H,L,2,2) float32 matching offsets")
+    if value.dim() != 4 or value.size(0) != B or value.size(2) != H or spatial_shapes.size(0) != L or \
+            level_start_index.numel() != L:
+        raise RuntimeError("offsets / spatial_shapes do not match value (B,S,H,C)")
+    if P != k * k:
+        raise RuntimeError("kernel_indices must have kernel_size**2 rows")
+    return (B, Lq, H, L, P), D, per_head, k
+
+
 def forward_boxes_ok(value, num_level, num_query, kernel_size):
     """Whether ``instance_attn_forward_boxes`` has its kernel under the current switches: ``instattn_fwd_boxes_ok``
     with the dimensions, element size and alignment of ``value`` (B, S, H, C), ``num_level`` levels, ``num_query``
@@ -874,24 +897,11 @@ def instance_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_wi
     float32 but ``value`` -> ``(output (B,Lq,H*C), mask_output (B,Lq,k*k,H*C) or None)`` in the type of ``value``:
     what ``box_grid_forward`` -> ``instance_weights_forward`` -> ``instance_attn_forward`` (``need_mask``) or
     ``box_attn_forward`` on the spatial weights (not ``need_mask``) return, without the per-point tensors in
-    between.  No backward.  Raises where ``forward_boxes_ok`` says no: there is no other kernel behind it."""
-    (B, Lq, H, L, P), (D, per_head, _, _) = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios, 0)
-    _check(value, "value")
-    _check(spatial_shapes, "spatial_shapes")
-    _check(level_start_index, "level_start_index")
-    _check(logits, "logits")
-    k = int(kernel_size)
-    if value.dtype not in (torch.float32,) + _H16:
-        raise RuntimeError("instance_attn_forward_boxes: float32, bfloat16 or float16 value expected, got %s" % value.dtype)
-    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
-        raise RuntimeError("spatial_shapes / level_start_index must be int64")
-    if logits.dtype != torch.float32 or tuple(logits.shape) != (B, Lq, H, L, 2, 2):
-        raise RuntimeError("expected logits (B,Lq,H,L,2,2) float32 matching offsets")
-    if value.dim() != 4 or value.size(0) != B or value.size(2) != H or spatial_shapes.size(0) != L or \
-            level_start_index.numel() != L:
-        raise RuntimeError("offsets / spatial_shapes do not match value (B,S,H,C)")
-    if P != k * k:
-        raise RuntimeError("kernel_indices must have kernel_size**2 rows")
+    between.  No backward here (``instance_attn_backward_boxes``).  Raises where ``forward_boxes_ok`` says no: there
+    is no other kernel behind it."""
+    (B, Lq, H, L, P), D, per_head, k = _boxes_args(
+        "instance_attn_forward_boxes", value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+        valid_ratios, logits, kernel_size)
     if not forward_boxes_ok(value, L, Lq, k):
         raise RuntimeError("instance_attn_forward_boxes: no kernel for value %s, %d levels, %d queries, kernel_size %d "
                            "(forward_boxes_ok)" % (tuple(value.shape), L, Lq, k))
@@ -902,3 +912,49 @@ def instance_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_wi
                ref_windows, D, per_head, offsets, kernel_indices, valid_ratios if valid_ratios is not None else 0,
                logits, B, S, H, C, L, Lq, k, out, mask if need_mask else 0)
     return out, mask
+
+
+def backward_boxes_ok(value, num_level, num_query, kernel_size):
+    """Whether ``instance_attn_backward_boxes`` has its kernel under the current switches: ``instattn_bwd_boxes_ok``
+    (the eligibility of ``forward_boxes_ok``) with the dimensions, element size and alignment of ``value`` (B, S, H,
+    C).  The upstream gradients are taken as aligned like ``value``; ``instance_attn_backward_boxes`` asks again with
+    their addresses.  Pure host code."""
+    if value.dim() != 4 or value.dtype not in (torch.float32,) + _H16:
+        return False
+    B, S, H, C = value.shape
+    return _lib.bwd_boxes_ok(value.element_size(), _align_of(value), (B, S, H, C, num_level, num_query), kernel_size)
+
+
+def instance_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                                 valid_ratios, logits, kernel_size, grad_output, grad_mask_output, need_ref_grad=False):
+    """The box and logit gradients of InstanceAttention's training step in one launch, from the operands of
+    ``instance_attn_forward_boxes`` and the upstream gradients ``grad_output`` (B,Lq,H*C) and ``grad_mask_output``
+    (B,Lq,k*k,H*C), or None where the mask output took no part in the loss, both in the type of ``value`` ->
+    ``(grad_offsets (B,Lq,H,L,4), grad_ref_rows (B,Lq,H,L,5) or None, grad_logits (B,Lq,H,L,2,2))``, float32: what
+    ``instance_attn_backward(want=2)`` -> ``box_grid_backward`` + ``instance_weights_backward`` return, without the
+    per-point tensors in between.  ``grad_value`` is not computed.  Raises where ``backward_boxes_ok`` says no:
+    there is no other kernel behind it."""
+    (B, Lq, H, L, P), D, per_head, k = _boxes_args(
+        "instance_attn_backward_boxes", value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+        valid_ratios, logits, kernel_size)
+    S, C = value.size(1), value.size(3)
+    grads = [("grad_output", grad_output, B * Lq * H * C)]
+    if grad_mask_output is not None:
+        grads.append(("grad_mask_output", grad_mask_output, B * Lq * P * H * C))
+    for name, g, n in grads:
+        _check(g, name)
+        if g.dtype != value.dtype or g.numel() != n:
+            raise RuntimeError("%s: %d elements of type %s expected" % (name, n, value.dtype))
+    given = [value, grad_output] + ([grad_mask_output] if grad_mask_output is not None else [])
+    if not _lib.bwd_boxes_ok(value.element_size(), _align_of(*given), (B, S, H, C, L, Lq), k):
+        raise RuntimeError("instance_attn_backward_boxes: no kernel for value %s, %d levels, %d queries, kernel_size "
+                           "%d at the alignment of value and the gradients (backward_boxes_ok)"
+                           % (tuple(value.shape), L, Lq, k))
+    grad_offsets = torch.empty((B, Lq, H, L, 4), dtype=torch.float32, device=value.device)
+    grad_rows = torch.empty((B, Lq, H, L, 5), dtype=torch.float32, device=value.device) if need_ref_grad else None
+    grad_logits = torch.empty((B, Lq, H, L, 2, 2), dtype=torch.float32, device=value.device)
+    _grid_call("instattn_bwd_boxes_" + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index,
+               ref_windows, D, per_head, offsets, kernel_indices, valid_ratios if valid_ratios is not None else 0,
+               logits, grad_output, grad_mask_output if grad_mask_output is not None else 0, B, S, H, C, L, Lq, k,
+               grad_offsets, grad_rows if need_ref_grad else 0, grad_logits)
+    return grad_offsets, grad_rows, grad_logits

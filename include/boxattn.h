@@ -498,7 +498,7 @@ int instattn_weights_bwd_f16(const uint16_t *logits, const float *grad_spatial_w
  * boxattn_grid_fwd_f32, logits as instattn_weights_fwd_f32; P = k * k points a level, row-major over (y, x).
  *   mask_out given: out and mask_out of instattn_fwd_*;
  *   mask_out NULL:  out of boxattn_fwd_* with the spatial weights (the module with `inferencing` set).
- * Forward only (training keeps the per-point tensors: the backward reads them).  One wave-per-pair kernel and no other
+ * Forward only (the box and logit gradients: instattn_bwd_boxes_* below).  One wave-per-pair kernel and no other
  * behind these entries: dimensions for which instattn_fwd_boxes_ok answers 0 -- with `aligned` what value, out and
  * mask_out are aligned to -- are hipErrorInvalidValue, and so is a NULL among value, shapes, lsi, ref, offsets,
  * kernel_idx, logits, out; nothing is launched then.  No queries: nothing is written; no pixels: the outputs are
@@ -525,6 +525,47 @@ int instattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const i
  * without mask_out; option key 22 is not read.  Pure host code: no device call; the entry points call the same
  * function. */
 int instattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k);
+
+/*
+ * Instance attention's TRAINING step from the same operands: the gradients the module needs per (batch, query, head,
+ * level) -- of the box offsets, of the reference window (rows, summed by the caller as after boxattn_grid_bwd_f32) and
+ * of the 2x2 logits -- in one launch: what instattn_bwd_part_* (want = BOXATTN_WANT_POINTS), boxattn_grid_bwd_f32
+ * (angle_mode 0, V = 4) and instattn_weights_bwd_f32 compute in three, without reading the sampling grid and the two
+ * weight tensors and without writing grad_loc / grad_spatial_w / grad_level_w in between.  Locations
+ * and weights are recomputed by the device functions of the forward above; everything is float32 except value and the
+ * upstream gradients, which are in the storage type.  grad_value is NOT computed here.
+ *   grad_out  (B,Lq,H,C), grad_mask (B,Lq,k*k,H,C) or NULL
+ *   grad_mask given: the gradients of instattn_fwd_* (both outputs took part in the loss);
+ *   grad_mask NULL:  those of boxattn_fwd_* with the spatial weights: grad_logits has the spatial term only.
+ *   grad_offsets (B,Lq,H,L,4), grad_ref_rows (B,Lq,H,L,5) or NULL, grad_logits (B,Lq,H,L,2,2): float32, every element
+ *   written.
+ * One wave-per-pair kernel and no other behind these entries: dimensions for which instattn_bwd_boxes_ok answers 0 --
+ * with `aligned` what value, grad_out and grad_mask are aligned to -- are hipErrorInvalidValue, and so are ref_dim < 4
+ * and a NULL among value, shapes, lsi, ref, offsets, kernel_idx, logits, grad_out, grad_offsets, grad_logits; nothing
+ * is launched then.  No queries: nothing is written; no pixels: the outputs are zero-filled.  No atomics and a fixed
+ * summation order (bitwise reproducible), no host reads, no allocation: capturable.  Profile slot 1.
+ */
+int instattn_bwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *ref, int ref_dim, int ref_per_head, const float *offsets,
+                           const float *kernel_idx, const float *valid_ratios, const float *logits,
+                           const float *grad_out, const float *grad_mask,
+                           int B, int S, int H, int C, int L, int Lq, int k,
+                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+int instattn_bwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                            const float *ref, int ref_dim, int ref_per_head, const float *offsets,
+                            const float *kernel_idx, const float *valid_ratios, const float *logits,
+                            const uint16_t *grad_out, const uint16_t *grad_mask,
+                            int B, int S, int H, int C, int L, int Lq, int k,
+                            float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+int instattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *ref, int ref_dim, int ref_per_head, const float *offsets,
+                           const float *kernel_idx, const float *valid_ratios, const float *logits,
+                           const uint16_t *grad_out, const uint16_t *grad_mask,
+                           int B, int S, int H, int C, int L, int Lq, int k,
+                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+/* 1 where the entry points above have their kernel: exactly where instattn_fwd_boxes_ok answers 1 (the same host
+ * function), `aligned` now speaking of value, grad_out and grad_mask.  Pure host code: no device call. */
+int instattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k);
 
 /*
  * Tuning options for A/B runs (process-wide, relaxed atomics; 0 = default).  Returns the
