@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import error_bounds as eb
 from oracle import boxattn_oracle as oc
 from test_gpu_f16 import check as check_f16
 from test_gpu_parity import close as close_parity
@@ -152,6 +153,15 @@ def compare_routes(g, dtype, what, t=None, want=None):
     assert e_new <= 2.0 * e_old, (what, e_new, e_old)
     for a, b, name in zip(new[1:], old[1:], ("grad_loc", "grad_spatial", "grad_level")):
         assert torch.equal(a, b), (what, name)
+    # every element inside the bound of tests/error_bounds.py on both routes: the matrix cores with the
+    # weights in two 16-bit terms, the VALU walk with float32 weights (the uniform locations of ``problem`` keep the
+    # cell-edge share of grad_loc under its cap: asserted)
+    if "_ref" not in g:
+        g["_ref"] = eb.instance_reference(g["value"], g["shapes"], g["lsi"], g["loc"], g["spatial_w"], g["level_w"],
+                                          g["grad_out"], g["grad_mask"])
+    names = ("grad_value", "grad_loc", "grad_spatial", "grad_level")
+    for route, grads, split in (("matrix cores", new, eb.store_name(dtype)), ("VALU", old, "none")):
+        eb.hold_all(dict(zip(names, grads)), g["_ref"], dtype, split, "%s (%s)" % (what, route))
     return new, old, want
 
 
