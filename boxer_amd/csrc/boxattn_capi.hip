@@ -18,6 +18,7 @@
 #include "boxattn_binned.h"
 #include "boxattn_boxes.h"
 #include "boxattn_boxes_bwd.h"
+#include "boxattn_gather2_boxes.h"
 #include "boxattn_fast.h"
 #include "boxattn_gather2.h"
 #include "boxattn_dense_plan.h"
@@ -548,6 +549,56 @@ int launch_fwd_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi,
         BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
 #undef BOXATTN_LAUNCH_BOXES
     }
+    return finish();
+}
+
+// ---- box attention at inference from boxes and L P logits (boxattn_gather2_boxes.h) -------------------------
+// Whether fwd2_boxes_kernel runs these dimensions: where the box flavour of fwd_route, without host tables, takes the
+// row gather, for the L of the level table and the L P of the softmax kernels (the pair's logits fit 64 / G rounds of
+// a lane group).  The ONE function behind boxattn_fwd_boxes_ok and the entry points; r: the launch geometry.
+inline bool box_boxes_route(int elem_bytes, const Dims &d, const FwdAlign &al, FwdRoute &r)
+{
+    if ((elem_bytes != 2 && elem_bytes != 4) || !d.valid()) return false;
+    if (d.L > 16 || (long long)d.L * d.P > kBoxesMaxLP) return false;
+    DensePlan dp;
+    return fwd_route(elem_bytes, false, d, al, nullptr, nullptr, false, r, dp) == kFwdGather;
+}
+
+template <typename ST>
+int launch_fwd_box_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
+                         int ref_per_head, const float *offsets, int V, int angle_mode, const float *kernel_idx,
+                         const float *valid_ratios, const float *logits, int B, int S, int H, int C, int L, int Lq,
+                         int P, ST *out, hipStream_t st)
+{
+    const Dims d{B, S, H, C, L, Lq, P};
+    if (!d.valid() || L > 16 || (long long)L * P > kBoxesMaxLP) return (int)hipErrorInvalidValue;
+    if (angle_mode < 0 || angle_mode > 2 || V != (angle_mode == 1 ? 5 : 4) || ref_dim < (angle_mode ? 5 : 4))
+        return (int)hipErrorInvalidValue;
+    if (d.empty()) return 0;                                   // no queries: nothing to write
+    if (!shapes || !lsi || !ref || !offsets || !kernel_idx || !logits || !out) return (int)hipErrorInvalidValue;
+    if (d.n_value() == 0)                                      // no pixels: every sample is 0
+        return (int)zero_async(out, d.n_qh() * d.C * sizeof(ST), st);
+    if (!value) return (int)hipErrorInvalidValue;
+    const size_t va = 4 * sizeof(ST);
+    FwdAlign al;
+    al.fast = aligned(value, va) && aligned(out, va);
+    al.rows16 = aligned(value, 16) && aligned(out, 16);
+    al.staged = false;
+    FwdRoute r;
+    if (!box_boxes_route((int)sizeof(ST), d, al, r)) return (int)hipErrorInvalidValue;   // no other kernel behind this entry
+    const GridDims gd{Lq, H, L, P, V, ref_dim, ref_per_head ? 1 : 0, angle_mode};
+    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST));
+    const unsigned stride = fwd2_boxes_pair_stride(L, L * P);
+    const GatherCfg cfg = r.cfg;
+    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
+#define BOXATTN_FWD2_BOXES(GG, VV)                                                                        \
+    hipLaunchKernelGGL((fwd2_boxes_kernel<ST, GG, GatherUnroll<ST, GG, VV>::value, VV>), dim3(r.blocks),  \
+                       dim3(256), (size_t)kGatherWaves * (kWave / GG) * stride * sizeof(u32x4_t), st,     \
+                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, d.S, d.H, d.L, \
+                       d.Lq, d.P, out, gd, with_grid(r.ix, r.blocks, 1, (L * P + GG - 1) / GG), vbytes,   \
+                       stride);
+    BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_FWD2_BOXES);
+#undef BOXATTN_FWD2_BOXES
     return finish();
 }
 
@@ -1625,6 +1676,39 @@ int instattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const i
 {
     return launch_fwd_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx,
                                    valid_ratios, logits, B, S, H, C, L, Lq, k, as_f16(out), as_f16(mask_out), ST_);
+}
+
+int boxattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P)
+{
+    const Dims d = DIMS;
+    const int bytes = aligned == 0 ? elem_bytes : aligned == 8 ? 8 : 16;          // as boxattn_fwd_route
+    const FwdAlign al{bytes >= 4 * elem_bytes && bytes >= 8, bytes >= 16, false};
+    FwdRoute r;
+    return box_boxes_route(elem_bytes, d, al, r) ? 1 : 0;
+}
+int boxattn_fwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                          int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
+                          const float *kernel_idx, const float *valid_ratios, const float *logits, int B, int S,
+                          int H, int C, int L, int Lq, int P, float *out, void *stream)
+{
+    return launch_fwd_box_boxes<float>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
+                                       kernel_idx, valid_ratios, logits, B, S, H, C, L, Lq, P, out, ST_);
+}
+int boxattn_fwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                           int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
+                           const float *kernel_idx, const float *valid_ratios, const float *logits, int B, int S,
+                           int H, int C, int L, int Lq, int P, uint16_t *out, void *stream)
+{
+    return launch_fwd_box_boxes<bf16_t>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
+                                        kernel_idx, valid_ratios, logits, B, S, H, C, L, Lq, P, out, ST_);
+}
+int boxattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                          int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
+                          const float *kernel_idx, const float *valid_ratios, const float *logits, int B, int S,
+                          int H, int C, int L, int Lq, int P, uint16_t *out, void *stream)
+{
+    return launch_fwd_box_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
+                                       kernel_idx, valid_ratios, logits, B, S, H, C, L, Lq, P, as_f16(out), ST_);
 }
 
 int instattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k)

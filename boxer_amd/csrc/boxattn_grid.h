@@ -55,6 +55,30 @@ __device__ __forceinline__ GridBox grid_box(const float *__restrict__ ref,
     return g;
 }
 
+// grid_box for a caller that already holds the row's indices (grid_box finds them by 64-bit division): the box of one
+// (b, q, h, l) row from its three rows -- r the reference window, o the predicted offsets, v the level's valid ratios
+// (or null).  The same operations in the same order; kept beside grid_box, not under it: routed through here, the
+// kernels that call grid_box came out with other instructions than they had.
+__device__ __forceinline__ GridBox grid_box_rows(const float *__restrict__ r, const float *__restrict__ o,
+                                                 const float *__restrict__ v, int angle_mode)
+{
+#pragma clang fp contract(off)
+    GridBox g;
+    g.rw = r[2];
+    g.rh = r[3];
+    g.cx = r[0] + o[0] / 8.f * g.rw;
+    g.cy = r[1] + o[1] / 8.f * g.rh;
+    g.w = g.rw + o[2] / 8.f * g.rw;
+    g.h = g.rh + o[3] / 8.f * g.rh;
+    g.sn = 0.f;
+    g.cs = 1.f;
+    if (angle_mode == 1) sincosf((r[4] + o[4] / 16.f) * 2.f * 3.14159265358979323846f, &g.sn, &g.cs);
+    else if (angle_mode == 2) sincosf(r[4], &g.sn, &g.cs);
+    g.vx = v ? v[0] : 1.f;
+    g.vy = v ? v[1] : 1.f;
+    return g;
+}
+
 // grid point p of a decoded box (the body of grid_fwd_kernel, shared with the sampling kernels
 // that take boxes instead of a grid: same operations, same order, no FMA contraction)
 __device__ __forceinline__ float2 grid_point(const GridBox &g, const float *__restrict__ kidx,

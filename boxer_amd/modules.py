@@ -61,9 +61,10 @@ class _BoxAttentionBase(nn.Module):
         # (InstanceWeightsFunction) -- and, in the 16-bit storage modes, the value mask-fill + 16-bit cast
         # (ValueMaskCastFunction) as single HIP passes
         self.fused_pointwise = False
-        # opt-in, InstanceAttention at inference only (no grad): the whole of forward between the projections as ONE
-        # HIP launch from the predicted boxes and 2x2 logits (ops.instance_attn_forward_boxes) -- no sampling grid, no
-        # per-point weights; the third element of the return is then the empty tuple
+        # opt-in, at inference only (no grad): the whole of forward between the projections as ONE HIP launch from the
+        # predicted boxes and logits -- no sampling grid, no per-point weights.  InstanceAttention:
+        # ops.instance_attn_forward_boxes, the third element of the return is then the empty tuple; BoxAttention /
+        # Box3dAttention: ops.box_attn_forward_boxes, the second element of the return is then the empty tuple
         self.fused_boxes = False
         # opt-in, InstanceAttention in training (grad mode, `inferencing` false): forward and backward from the boxes
         # and 2x2 logits (InstanceAttnBoxesFunction) -- no per-point tensor is built in the forward or kept for the
@@ -156,6 +157,19 @@ class _BoxAttentionBase(nn.Module):
             and tuple(v_valid_ratios.shape[1:]) == (1, 1, self.num_level, 1, 2)
             and v_valid_ratios.size(0) == query.size(0))
 
+    def _boxes_operand(self, query, value, v_valid_ratios):
+        """``value`` in the type the kernels from boxes take it, or None where they do not run: CPU / float64 tensors,
+        ``v_valid_ratios`` of another shape than the reference's."""
+        if not (query.is_cuda and value.is_cuda):
+            return None
+        if torch.float64 in (query.dtype, value.dtype):
+            return None                       # (the kernel computes in float32)
+        if v_valid_ratios is not None and not (
+                v_valid_ratios.dim() == 6 and v_valid_ratios.size(0) == query.size(0)
+                and tuple(v_valid_ratios.shape[1:]) == (1, 1, self.num_level, 1, 2)):
+            return None
+        return value.to(self._storage_dtype() or torch.float32).contiguous()
+
 
 class BoxAttention(_BoxAttentionBase):
     def __init__(self, d_model, num_level, num_head, kernel_size=2):
@@ -183,8 +197,33 @@ class BoxAttention(_BoxAttentionBase):
     def _angle_mode(self):
         return 0
 
+    def _boxes_value(self, query, value, v_valid_ratios):
+        """The projected ``value`` as the one-launch inference forward takes it (the storage mode's type, float32
+        without one), or None: that path is not taken -- flag off, grad mode, what ``_boxes_operand`` refuses, or no
+        kernel for the shape (ops.box_forward_boxes_ok)."""
+        if not self.fused_boxes or torch.is_grad_enabled():
+            return None
+        value = self._boxes_operand(query, value, v_valid_ratios)
+        return value if value is not None and ops.box_forward_boxes_ok(value, self.num_level, query.size(1),
+                                                                       self.num_point) else None
+
+    def _forward_boxes(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows):
+        b, l1 = query.shape[:2]
+        f32 = lambda t: t.float().contiguous()
+        mode = self._angle_mode()
+        logits = dense.linear(query, self.linear_attn_weight, self.linear_attn_bias)
+        offsets = self._box_offsets(query, ref_windows, 5 if mode == 1 else 4)
+        output = ops.box_attn_forward_boxes(
+            value, v_shape, v_start_index, f32(ref_windows), f32(offsets), f32(self.kernel_indices),
+            None if v_valid_ratios is None else f32(v_valid_ratios).view(b, self.num_level, 2),
+            f32(logits).view(b, l1, self.num_head, -1), mode)
+        return dense.linear(output, self.out_proj.weight, self.out_proj.bias), ()
+
     def forward(self, query, value, v_shape, v_mask, v_start_index, v_valid_ratios, ref_windows):
         value = self._project_value(value, v_mask)
+        boxes_value = self._boxes_value(query, value, v_valid_ratios)
+        if boxes_value is not None:
+            return self._forward_boxes(query, boxes_value, v_shape, v_start_index, v_valid_ratios, ref_windows)
         attn_weights = self._softmax_weights(query)
         sampled_grid = self._where_to_attend(query, v_valid_ratios, ref_windows)
         output = self._box_function().apply(value, v_shape, v_start_index, sampled_grid,
@@ -272,20 +311,11 @@ class InstanceAttention(_BoxAttentionBase):
         return self.out_proj(output), self.out_proj(mask_output), ()
 
     def _boxes_operand(self, query, value, v_valid_ratios):
-        """``value`` in the type the kernels from boxes take it, or None where they do not run: CPU / float64 tensors,
-        ``v_valid_ratios`` of another shape than the reference's, k odd or out of 2 ... 32."""
-        if not (query.is_cuda and value.is_cuda):
-            return None
-        if torch.float64 in (query.dtype, value.dtype):
-            return None                       # (the kernel computes in float32)
-        if v_valid_ratios is not None and not (
-                v_valid_ratios.dim() == 6 and v_valid_ratios.size(0) == query.size(0)
-                and tuple(v_valid_ratios.shape[1:]) == (1, 1, self.num_level, 1, 2)):
-            return None
+        """``_BoxAttentionBase._boxes_operand`` where the instance weights exist: k even, 2 ... 32; else None."""
         k = self.kernel_size
         if not (isinstance(k, int) and k % 2 == 0 and 2 <= k <= 32):
             return None
-        return value.to(self._storage_dtype() or torch.float32).contiguous()
+        return super()._boxes_operand(query, value, v_valid_ratios)
 
     def _forward_boxes(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows, logits):
         b, l1 = query.shape[:2]

@@ -958,3 +958,54 @@ def instance_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_w
                logits, grad_output, grad_mask_output if grad_mask_output is not None else 0, B, S, H, C, L, Lq, k,
                grad_offsets, grad_rows if need_ref_grad else 0, grad_logits)
     return grad_offsets, grad_rows, grad_logits
+
+
+# ---------------------------------------------------------------------------------------
+# box attention at inference straight from boxes and L*P logits (opt-in; SURVEY.md 8(f) N1 + N3 inside the operator:
+# include/boxattn.h, boxattn_fwd_boxes_*)
+# ---------------------------------------------------------------------------------------
+def box_forward_boxes_ok(value, num_level, num_query, num_point):
+    """Whether ``box_attn_forward_boxes`` has its kernel under the current switches: ``boxattn_fwd_boxes_ok`` with the
+    dimensions, element size and alignment of ``value`` (B, S, H, C), ``num_level`` levels, ``num_query`` queries an
+    image and ``num_point`` points a level.  The output is taken as freshly allocated (aligned).  Pure host code."""
+    if not isinstance(value, torch.Tensor) or value.dim() != 4 or value.dtype not in (torch.float32,) + _H16:
+        return False
+    B, S, H, C = value.shape
+    return _lib.box_fwd_boxes_ok(value.element_size(), _align_of(value), (B, S, H, C, num_level, num_query, num_point))
+
+
+def box_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                           valid_ratios, logits, angle_mode=0):
+    """BoxAttention's / Box3dAttention's inference forward in one launch, from what the module predicts: ``value``
+    (B,S,H,C) float32 / bfloat16 / float16, ``ref_windows`` (B,Lq,D) or (B,Lq,H,D), ``offsets`` (B,Lq,H,L,V) with V = 5
+    for ``angle_mode`` 1 and 4 otherwise, ``kernel_indices`` (P,2), ``valid_ratios`` None or B*L*2 values, ``logits``
+    B*Lq*H*L*P values -- all float32 but ``value`` -> ``output`` (B,Lq,H*C) in the type of ``value``: what
+    ``box_grid_forward`` -> ``softmax_forward`` -> ``box_attn_forward`` return, without the sampling grid and the
+    weights in between.  No backward.  Raises ValueError, before any device call, for arguments that do not fit and
+    where ``box_forward_boxes_ok`` says no: there is no other kernel behind it."""
+    try:
+        (B, Lq, H, L, P), (D, per_head, V, mode) = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios,
+                                                              angle_mode)
+        for t, name in ((value, "value"), (spatial_shapes, "spatial_shapes"),
+                        (level_start_index, "level_start_index"), (logits, "logits")):
+            _check(t, name)
+    except RuntimeError as e:
+        raise ValueError("box_attn_forward_boxes: %s" % e) from None
+    if value.dtype not in (torch.float32,) + _H16:
+        raise ValueError("box_attn_forward_boxes: float32, bfloat16 or float16 value expected, got %s" % value.dtype)
+    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
+        raise ValueError("box_attn_forward_boxes: spatial_shapes / level_start_index must be int64")
+    if logits.dtype != torch.float32 or logits.numel() != B * Lq * H * L * P:
+        raise ValueError("box_attn_forward_boxes: expected B*Lq*H*L*P float32 logits matching offsets")
+    if value.dim() != 4 or value.size(0) != B or value.size(2) != H or spatial_shapes.size(0) != L or \
+            level_start_index.numel() != L:
+        raise ValueError("box_attn_forward_boxes: offsets / spatial_shapes do not match value (B,S,H,C)")
+    if not box_forward_boxes_ok(value, L, Lq, P):
+        raise ValueError("box_attn_forward_boxes: no kernel for value %s, %d levels, %d queries, %d points a level "
+                         "(box_forward_boxes_ok)" % (tuple(value.shape), L, Lq, P))
+    S, C = value.size(1), value.size(3)
+    out = torch.empty((B, Lq, H * C), dtype=value.dtype, device=value.device)
+    _grid_call("boxattn_fwd_boxes_" + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index,
+               ref_windows, D, per_head, offsets, V, mode, kernel_indices,
+               valid_ratios if valid_ratios is not None else 0, logits, B, S, H, C, L, Lq, P, out)
+    return out

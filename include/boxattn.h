@@ -527,6 +527,40 @@ int instattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const i
 int instattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k);
 
 /*
+ * BOX attention at INFERENCE straight from what BoxAttention / Box3dAttention predict per (batch, query, head) -- L
+ * boxes and L*P logits -- in one launch: what boxattn_grid_fwd_f32, boxattn_softmax_fwd_f32 and boxattn_fwd_* compute
+ * in three, without the (B,Lq,H,L,P,2) sampling grid and the (B,Lq,H,L*P) weights in between.  ref /
+ * ref_dim / ref_per_head / offsets / V / angle_mode / kernel_idx / valid_ratios as boxattn_grid_fwd_f32 (all three
+ * angle modes); logits (B,Lq,H,L*P) float32; out as boxattn_fwd_*.  The locations are made by the grid kernel's device
+ * functions in its operation order; the weights are exp(z - max) * (1 / sum) in float32, summed over a lane group.
+ * Forward only.  One row-gather kernel and no other behind these entries: dimensions for which boxattn_fwd_boxes_ok
+ * answers 0 -- with `aligned` what value and out are aligned to --, ref_dim < 4 (< 5 with an angle), V other than 4
+ * (5 for angle_mode 1), and a NULL among value, shapes, lsi, ref, offsets, kernel_idx, logits, out are
+ * hipErrorInvalidValue; nothing is launched then.  No queries: nothing is written; no pixels: out is zero-filled.
+ * No atomics (bitwise reproducible), no host reads, no allocation: capturable, on the one stream.  Profile slot 0.
+ */
+int boxattn_fwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                          int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                          const float *logits, int B, int S, int H, int C, int L, int Lq, int P, float *out,
+                          void *stream);
+int boxattn_fwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                           int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                           const float *logits, int B, int S, int H, int C, int L, int Lq, int P, uint16_t *out,
+                           void *stream);
+int boxattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                          int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                          const float *logits, int B, int S, int H, int C, int L, int Lq, int P, uint16_t *out,
+                          void *stream);
+/* 1 where the entry points above have their kernel: boxattn_fwd_route answers BOXATTN_FWD_GATHER for the box flavour of
+ * these dimensions without host tables (that covers boxattn_set_variant, option key 22, the alignment and value <
+ * 2 GiB), L <= 16 and L*P <= 64 (the limit of the softmax kernels; P itself is free); else 0.  elem_bytes 2 / 4;
+ * aligned as boxattn_fwd_route.  Pure host code: no device call; the entry points call the same function. */
+int boxattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P);
+
+/*
  * Instance attention's TRAINING step from the same operands: the gradients the module needs per (batch, query, head,
  * level) -- of the box offsets, of the reference window (rows, summed by the caller as after boxattn_grid_bwd_f32) and
  * of the 2x2 logits -- in one launch: what instattn_bwd_part_* (want = BOXATTN_WANT_POINTS), boxattn_grid_bwd_f32
