@@ -32,6 +32,54 @@ evaluated exactly, as half the type's spacing at |want| + R (half_ulp): u x is t
 twice it at the top, where a result one whole step off the correctly rounded one would still pass -- with u x a dropped
 corner went unnoticed in 5.5 % of the cases on all-positive bf16 data, with half_ulp in 2.0 %
 (tests/test_error_bounds.py).  Whatever passes this passes the formula above.
+
+From boxes (``boxes_reference``): the kernels that take reference windows, offsets, kernel_indices, valid ratios and
+logits instead of a sampling grid and weights are held against a model that starts from those inputs -- the modules'
+_where_to_attend and softmaxes restated from DESIGN.md 1 / 4.4 / 4.6 and the reference's module code, in float64.
+float32 locations and weights are not the float64 ones, so two allowances join the bound; u = 2^-24 below.
+
+  dloc   (grid_reference) per point and axis, normalised units: what a float32 evaluation in the documented order
+         (every operation rounded once, no fused multiply-add) may differ by.  Without rotation the chain to a
+         coordinate is  off / 8 * size (/ 8 is exact; 1 rounding), + centre (1), off / 8 * size, + size (2),
+         kidx * relu(size) (1), the sum (1): n = 6 roundings, each of a partial result that is at most
+         T = |centre| + |off / 8 size_ref| + |kidx| (|size_ref| + |off / 8 size_ref|) in magnitude (the last term only
+         where the float64 size is positive), so dloc = 6 u T to first order; the cancellation in a size near zero is
+         covered because T sums absolute values.  With rotation both local coordinates enter either axis: T takes both
+         |kidx| terms (|cos|, |sin| <= 1) and n = 9 (two more products, the difference).  The sine and cosine are each off
+         by at most dtheta + 2^-22: dtheta = 3 u (|ref angle| + |off / 16|) 2 pi in mode 1 (the sum, the product with
+         float32's 2 pi, that constant's own representation error; / 16 and * 2 are exact), 0 in mode 2 (theta is an input);
+         2^-22 = 4 ulp at 1.0 is an ALLOWANCE for the device sincosf at any argument, not a measurement -- no
+         accuracy statement for it was found in the ROCm documentation installed beside this project, so none is cited;
+         profiles/boxes_error_bounds.log records how much of dloc the kernel uses.  They multiply the local coordinates:
+         (dtheta + 2^-22) (|lx| + |ly|) on either axis.  Valid ratios: one more rounding, everything times |vr|.
+  dw     (softmax_reference, instance_weights_reference) per weight, relative.  exp(d), d = z - max, is formed as
+         exp2(d log2 e): the subtraction (1 rounding of |d|), the constant log2 e (relative u) and the product (1) move
+         the exponent by at most 3 u |d| log2 e, the result by the factor 2^that = 1 +- 3 u |d|; the exp2 instruction adds
+         an ulp (2 u, relative): de = (3 |d| + 2) u.  The float32 sum of N positive terms, in any order, is off by at
+         most (N - 1) u relatively plus the weighted mean of its terms' de, sum_j a_j de_j; the reciprocal (a division:
+         1 rounding) and the product (1).  dw_i = de_i + sum_j a_j de_j + (N + 1) u; the spatial weights of instance
+         attention -- a softmax over the row's 4 L cells, times 1 / m^2 -- take 2 u more (that constant, the product).
+         A logit more than 87 below its row's maximum would leave float32's normal range, where a relative allowance
+         means nothing: the reference refuses such a row (no case has one; the widest spread tested is 60).
+
+How they enter.  level_terms / _reference take the locations' ``slack`` = dloc: a point's coordinate allowance becomes
+3 size u + size dloc (it was 3 size u), its eps the sum of the two axes', and the alternative cells are searched with it.
+A weight a_i off by dw_i |a_i| moves a term by dw_i |term|: the plane W sums that per element and is added to R beside the
+split term (``bound``); the constants of R are untouched, and without slack / dws nothing changes, bit for bit.
+
+The three gradients of the backward from boxes are linear in the per-point grad_loc, grad_spatial, grad_level:
+  grad_offsets[0:2] = size_ref / 8 sum_p g_p,   [2:4] = relu'(size) size_ref / 8 sum_p kidx_p g_p    (g = grad_loc vr)
+  grad_ref_rows[0:2] = sum_p g_p,   [2:4] = off[0:2] / 8 sum_p g_p + relu'(size) (1 + off[2:4] / 8) sum_p kidx_p g_p,  [4] = 0
+  grad_logits[c] = a_c / m^2 (Gs_c - sum_c' a_c' Gs_c') + t_c (Gt_c - sum_l' t_l' Gt_l')        (Gs, Gt: the cells' sums)
+(d grid / d box and the Jacobians of the two softmaxes, from the definitions).  want reduces in float64; A and E (with
+W) with the absolute values of the same coefficients, every difference as a sum; n is the largest n of the points plus
+the reduction's own roundings (P + 6 for the box rows: the vr and kidx products, a P-term sum, the row's last few;
+m^2 + 4 L + 8 for the logits); a weight a_c off by da_c adds (da_c + max da) times the A of its bracket to E.  A size whose
+float32 sign is not certain (|size| <= 2 u (|size_ref| + |off / 8 size_ref|), not exactly 0) allows either relu'.
+grad_loc jumps at cell edges and a sum cannot leave a point out: a point within EDGE_PX + its coordinate allowance of
+an integer coordinate has two legitimate own-axis gradients; want takes the float64 side, J = |the neighbouring
+cell's - that| goes into E of every element the point feeds (times the coefficient).  ``edge_share`` is the share of
+such points (callers assert <= EDGE_CAP), ``edge_dominated`` the share of elements whose bound is more than half J.
 """
 
 import numpy as np
@@ -81,11 +129,11 @@ def round_to(x, store):
 class _Acc:
     """want / A / E / n / G of one output, as (rows, C) float64 planes summed into by row index."""
 
-    def __init__(self, shape, with_g):
+    def __init__(self, shape, with_g, more=()):
         self.shape = shape
         self.C = shape[-1]
         self.rows = int(np.prod(shape[:-1]))
-        names = ("want", "A", "E", "n") + (("G",) if with_g else ())
+        names = ("want", "A", "E", "n") + (("G",) if with_g else ()) + more
         self.planes = {k: np.zeros(self.rows * self.C) for k in names}
 
     def add(self, idx, **vals):
@@ -107,11 +155,13 @@ def _corners(y0, x0, Hl, Wl):
     return np.clip(ys, 0, Hl - 1) * Wl + np.clip(xs, 0, Wl - 1), ok
 
 
-def level_terms(value, shapes, lsi, loc, l, frac_hook=None):
+def level_terms(value, shapes, lsi, loc, l, frac_hook=None, slack=None):
     """The sample points of level ``l`` that pass the window test (-1, H) x (-1, W) (a coordinate of exactly -1 is
     outside, as in the reference kernels): dict of b, q, h, p (m,), rows / ok (m, 4), w (m, 4) bilinear weights,
     v (m, 4, C) corner rows (zeros outside the map), fy, fx, eps.  Also ``alts``: the (point, cell) pairs float32 could
-    take instead (see the module docstring), each b, q, h, p, rows, ok, v."""
+    take instead (see the module docstring), each b, q, h, p, rows, ok, v.  ``slack`` (B, Lq, H, L, P, 2), normalised
+    units: what the location itself may be off by (grid_reference's dloc); a point's coordinate allowance is then
+    3 size 2^-24 + size slack, its eps (an (m, 1) column in every returned entry) the sum of the two axes'."""
     B, S, Hh, C = value.shape
     Lq, P = loc.shape[1], loc.shape[4]
     Hl, Wl = int(shapes[l][0]), int(shapes[l][1])
@@ -123,8 +173,16 @@ def level_terms(value, shapes, lsi, loc, l, frac_hook=None):
     def gather(sel, y0, x0):
         rows, ok = _corners(y0, x0, Hl, Wl)
         v = vlev[b[sel][:, None], rows, h[sel][:, None]] * ok[:, :, None]
-        return dict(b=b[sel], q=q[sel], h=h[sel], p=p[sel], rows=rows, ok=ok, v=v)
+        d = dict(b=b[sel], q=q[sel], h=h[sel], p=p[sel], rows=rows, ok=ok, v=v)
+        if slack is not None:
+            d["eps"] = (dx + dy)[sel][:, None]
+        return d
 
+    # what float32 may do instead: both coordinates moved by +- 3 size 2^-24 (plus the location's own slack)
+    dx, dy = 3.0 * Wl * 2.0 ** -24, 3.0 * Hl * 2.0 ** -24
+    if slack is not None:
+        dx = dx + Wl * slack[:, :, :, l, :, 0].ravel()
+        dy = dy + Hl * slack[:, :, :, l, :, 1].ravel()
     inside = (y > -1) & (x > -1) & (y < Hl) & (x < Wl)
     sel = np.nonzero(inside)[0]
     y0, x0 = np.floor(y[sel]).astype(np.int64), np.floor(x[sel]).astype(np.int64)
@@ -133,9 +191,9 @@ def level_terms(value, shapes, lsi, loc, l, frac_hook=None):
         fy, fx = frac_hook(l, sel, fy, fx)
     t = gather(sel, y0, x0)
     t.update(fy=fy, fx=fx, w=np.stack([(1 - fy) * (1 - fx), (1 - fy) * fx, fy * (1 - fx), fy * fx], 1),
-             eps=3.0 * (Wl + Hl) * 2.0 ** -24, Hl=Hl, Wl=Wl, sel=sel)
-    # what float32 may do instead: both coordinates moved by +- 3 size 2^-24
-    dx, dy = 3.0 * Wl * 2.0 ** -24, 3.0 * Hl * 2.0 ** -24
+             Hl=Hl, Wl=Wl, sel=sel)
+    if slack is None:
+        t["eps"] = 3.0 * (Wl + Hl) * 2.0 ** -24
     cand = {}
     for name, c, d, size in (("x", x, dx, Wl), ("y", y, dy, Hl)):
         for s in (-1, 1):
@@ -167,24 +225,75 @@ def on_edge(loc, shapes):
     return (np.abs(pix - np.round(pix)) < EDGE_PX).any(-1, keepdims=True)
 
 
-def _reference(value, shapes, lsi, loc, weights, ups, instance, frac_hook=None, weight_hook=None):
+def _edge_jumps(gloc, value, shapes, lsi, loc, l, weights, ups, instance, slack):
+    """grad_loc of level ``l``: for every point and axis whose pixel coordinate is within EDGE_PX + its slack of an
+    integer (a cell edge, -1 or the far side of the window test) the own-axis gradient has two legitimate values;
+    J gets |the value in the neighbouring cell - the float64 side's| (the gradient along an axis does not depend on that
+    axis' fraction, so any coordinate inside the neighbouring cell gives it)."""
+    B, S, Hh, C = value.shape
+    Lq, P = loc.shape[1], loc.shape[4]
+    Hl, Wl = int(shapes[l][0]), int(shapes[l][1])
+    vlev = value[:, int(lsi[l]):int(lsi[l]) + Hl * Wl]
+    pix = [loc[:, :, :, l, :, 0] * Wl - 0.5, loc[:, :, :, l, :, 1] * Hl - 0.5]
+    sl = np.zeros(loc.shape[:3] + (P, 2)) if slack is None else slack[:, :, :, l]
+    near_all = gloc.setdefault("near", np.zeros(gloc["want"].shape, dtype=bool))
+
+    def grad(b, q, h, p, x, y, axis):
+        inside = (y > -1) & (x > -1) & (y < Hl) & (x < Wl)
+        y0, x0 = np.floor(y).astype(np.int64), np.floor(x).astype(np.int64)
+        fy, fx = (y - y0)[:, None], (x - x0)[:, None]
+        rows, ok = _corners(y0, x0, Hl, Wl)
+        v = vlev[b[:, None], rows, h[:, None]] * ok[:, :, None]
+        tt = weights[0][b, q, h, l, p][:, None] * ups[0][b, q, h]
+        if instance:
+            tt = tt + weights[1][b, q, h, l, p][:, None] * ups[1][b, q, p, h]
+        dv = (1 - fy) * (v[:, 1] - v[:, 0]) + fy * (v[:, 3] - v[:, 2]) if axis == 0 else \
+            (1 - fx) * (v[:, 2] - v[:, 0]) + fx * (v[:, 3] - v[:, 1])
+        return np.where(inside, (Wl, Hl)[axis] * (tt * dv).sum(1), 0.0)
+
+    for axis, size in ((0, Wl), (1, Hl)):
+        c = pix[axis]
+        r = np.round(c)
+        near = np.abs(c - r) < EDGE_PX + (3.0 * size * 2.0 ** -24 + size * sl[..., axis])
+        near_all[:, :, :, l, :, axis] = near
+        b, q, h, p = np.nonzero(near)
+        if not b.size:
+            continue
+        xy = [pix[0][b, q, h, p], pix[1][b, q, h, p]]
+        here = grad(b, q, h, p, xy[0], xy[1], axis)
+        xy[axis] = np.where(c[b, q, h, p] >= r[b, q, h, p], r[b, q, h, p] - 0.5, r[b, q, h, p] + 0.5)
+        gloc["J"][b, q, h, l, p, axis] = np.abs(grad(b, q, h, p, xy[0], xy[1], axis) - here)
+
+
+def _reference(value, shapes, lsi, loc, weights, ups, instance, frac_hook=None, weight_hook=None, slack=None, dws=None):
     """weights: [attn] or [spatial_w, level_w], (B, Lq, H, L, P); ups: [grad_out (B, Lq, H, C)] or that and grad_mask
     (B, Lq, P, H, C).  The hooks mutate what goes into ``want`` only (tests of the bound itself): frac_hook(l, sel, fy,
-    fx) -> fy, fx; weight_hook(a w_k) -> the weight products the sums of out / mask_out / grad_value use."""
+    fx) -> fy, fx; weight_hook(a w_k) -> the weight products the sums of out / mask_out / grad_value use.
+    slack: level_terms' (the locations' own allowance); dws: one relative allowance (B, Lq, H, L, P) per weight set.
+    With either, every output that multiplies a weight gets a plane W = sum of dw |term| (beside the split term in
+    R), and grad_loc no ``skip``: its points within EDGE_PX + slack of a cell edge get ``J``, the size of the jump of
+    the own-axis gradient to the other side of the edge (also added to E; want stays on the float64 side)."""
     B, S, Hh, C = value.shape
+    ext = slack is not None or dws is not None
+    if ext and dws is None:
+        dws = [np.zeros(loc.shape[:5]) for _ in weights]
+    _AccW = (lambda shape, g: _Acc(shape, g, ("W",))) if ext else _Acc
     Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
-    out = _Acc((B, Lq, Hh, C), True)
-    mask = _Acc((B, Lq, P, Hh, C), True) if instance else None
-    gval = _Acc((B, S, Hh, C), True)
+    out = _AccW((B, Lq, Hh, C), True)
+    mask = _AccW((B, Lq, P, Hh, C), True) if instance else None
+    gval = _AccW((B, S, Hh, C), True)
     point = {k: {m: np.zeros((B, Lq, Hh, L, P)) for m in ("want", "A", "E", "n")}
              for k in (("grad_spatial", "grad_level") if instance else ("grad_attn",))}
-    gloc = {m: np.zeros((B, Lq, Hh, L, P, 2)) for m in ("want", "A", "E", "n")}
+    gloc = {m: np.zeros((B, Lq, Hh, L, P, 2)) for m in ("want", "A", "E", "n") + (("W", "J") if ext else ())}
     wh = weight_hook if weight_hook is not None else (lambda aw: aw)
     for l in range(L):
-        t = level_terms(value, shapes, lsi, loc, l, frac_hook)
+        t = level_terms(value, shapes, lsi, loc, l, frac_hook, slack)
         for alt, u in enumerate([t] + t["alts"]):
             b, q, h, p, ok, v = u["b"], u["q"], u["h"], u["p"], u["ok"], u["v"]
-            eps = t["eps"]
+            eps = u["eps"] if slack is not None else t["eps"]          # a scalar, or an (m, 1) column
+            eps1 = eps[:, 0] if slack is not None else eps
+            sub = (lambda e, m: e[m]) if slack is not None else (lambda e, m: e)
+            dw = [d[b, q, h, l, p] for d in dws] if ext else None
             av = np.abs(v)
             qh = (b * Lq + q) * Hh + h
             a = [w[b, q, h, l, p] for w in weights]
@@ -196,32 +305,36 @@ def _reference(value, shapes, lsi, loc, weights, ups, instance, frac_hook=None, 
             for k in range(4):
                 idx = ((b * S + int(lsi[l]) + u["rows"][:, k]) * Hh + h)[ok[:, k]]
                 if alt:
-                    gval.add(idx, E=eps * abs_t[ok[:, k]])
+                    gval.add(idx, E=sub(eps, ok[:, k]) * abs_t[ok[:, k]])
                     continue
-                for ai, gi in zip(a, g):
+                for j, (ai, gi) in enumerate(zip(a, g)):
                     aw = (ai * t["w"][:, k])[ok[:, k]]
                     gk = gi[ok[:, k]]
                     gval.add(idx, want=wh(aw)[:, None] * gk, A=np.abs(aw)[:, None] * np.abs(gk),
                              n=np.ones((idx.size, 1)), G=np.abs(gk))
-                gval.add(idx, E=eps * abs_t[ok[:, k]])
-            for (acc, idx), ai in zip(outs, a):
+                    if ext:
+                        gval.add(idx, W=(dw[j][ok[:, k]] * np.abs(aw))[:, None] * np.abs(gk))
+                gval.add(idx, E=sub(eps, ok[:, k]) * abs_t[ok[:, k]])
+            for j, ((acc, idx), ai) in enumerate(zip(outs, a)):
                 if alt:
                     acc.add(idx, E=eps * np.abs(ai)[:, None] * sum_av)
                     continue
                 aw = ai[:, None] * t["w"]                                                # (m, 4)
                 acc.add(idx, want=(wh(aw)[:, :, None] * v).sum(1), A=(np.abs(aw)[:, :, None] * av).sum(1),
                         E=eps * np.abs(ai)[:, None] * sum_av, n=ok.sum(1)[:, None].astype(np.float64), G=sum_av)
+                if ext:
+                    acc.add(idx, W=dw[j][:, None] * (np.abs(aw)[:, :, None] * av).sum(1))
             at = (b, q, h, l, p)
             for name, gi in zip(sorted(point, reverse=True) if instance else ["grad_attn"], g):   # spatial, then level
                 d = point[name]
-                d["E"][at] += eps * (np.abs(gi) * sum_av).sum(1)
+                d["E"][at] += eps1 * (np.abs(gi) * sum_av).sum(1)
                 if alt:
                     continue
                 d["want"][at] = (gi * (t["w"][:, :, None] * v).sum(1)).sum(1)
                 d["A"][at] = (np.abs(gi) * (t["w"][:, :, None] * av).sum(1)).sum(1)
                 d["n"][at] = C * ok.sum(1)
             if alt:
-                continue                       # (such a point is within EDGE_PX of an edge: skipped in grad_loc)
+                continue                       # (such a point is within EDGE_PX of an edge: skipped in grad_loc, or given J)
             tt = sum(ai[:, None] * gi for ai, gi in zip(a, g))                           # (m, C)
             fy, fx = t["fy"][:, None], t["fx"][:, None]
             dxv = (1 - fy) * (v[:, 1] - v[:, 0]) + fy * (v[:, 3] - v[:, 2])
@@ -231,11 +344,20 @@ def _reference(value, shapes, lsi, loc, weights, ups, instance, frac_hook=None, 
             for j, (size, dv, da) in enumerate(((t["Wl"], dxv, dxa), (t["Hl"], dyv, dya))):
                 gloc["want"][at + (j,)] = size * (tt * dv).sum(1)
                 gloc["A"][at + (j,)] = size * (abs_t * da).sum(1)
-                gloc["E"][at + (j,)] = size * eps * (abs_t * sum_av).sum(1)
+                gloc["E"][at + (j,)] = size * eps1 * (abs_t * sum_av).sum(1)
                 gloc["n"][at + (j,)] = C * ok.sum(1) * len(a)
-    edge = on_edge(loc, shapes)
-    gloc["skip"] = np.broadcast_to(edge, gloc["want"].shape)
-    gloc["edge_share"] = float(edge.mean())
+                if ext:
+                    dw_t = sum((di * np.abs(ai))[:, None] * np.abs(gi) for di, ai, gi in zip(dw, a, g))
+                    gloc["W"][at + (j,)] = size * (dw_t * da).sum(1)
+        if ext:
+            _edge_jumps(gloc, value, shapes, lsi, loc, l, weights, ups, instance, slack)
+    if ext:
+        gloc["E"] += gloc["J"]
+        gloc["edge_share"] = float(gloc.pop("near").any(-1).mean())
+    else:
+        edge = on_edge(loc, shapes)
+        gloc["skip"] = np.broadcast_to(edge, gloc["want"].shape)
+        gloc["edge_share"] = float(edge.mean())
     ref = {"out": out.result(), "grad_value": gval.result(), "grad_loc": gloc}
     ref["out"] = {k: a.reshape(B, Lq, Hh * C) for k, a in ref["out"].items()}
     if instance:
@@ -284,6 +406,8 @@ def bound(ref, store, split="none"):
     R = ((ref["n"] + 8.0) * 2.0 ** -24 + SPLIT[split]) * ref["A"] + ref["E"]
     if split == "f16":
         R = R + 2.0 ** -25 * ref["G"]
+    if "W" in ref:                                     # the weights' own allowance (boxes_reference): sum of dw |term|
+        R = R + ref["W"]
     return np.where(ref["A"] + ref["E"] > 0, half_ulp(np.abs(ref["want"]) + R, store) + R, 0.0)
 
 
@@ -375,3 +499,212 @@ def numpy_inputs(inp):
     if inp["kind"] == "instance":
         d["spatial_w"], d["level_w"], d["grad_mask"] = d["attn"], f64(inp["level_w"]), f64(inp["grad_mask"])
     return d
+
+
+# ------------------------------------------------------------------ from boxes and logits (see "From boxes" in the module docstring)
+U32 = 2.0 ** -24                 # one float32 rounding, relative
+SINCOS_ABS = 2.0 ** -22          # the device sincosf: an allowance of 4 ulp at 1.0, absolute (not a measurement)
+LOG2E = 1.4426950408889634
+EXP_MIN = -87.0                  # z - max below this: exp leaves float32's normal range, a relative dw means nothing
+
+
+def grid_reference(ref, off, kidx, vr, angle_mode):
+    """The modules' _where_to_attend after the offset projection, float64.  ref (B, Lq, D) or (B, Lq, H, D), off
+    (B, Lq, H, L, V), kidx (P, 2), vr (B, 1, 1, L, 1, 2) or None; angle_mode 0: no rotation, 1: theta = (ref[4] +
+    off[4] / 16) 2 pi, 2: theta = ref[4].  -> loc (B, Lq, H, L, P, 2), dloc (the same shape, normalised units)."""
+    ref, off, kidx = f64(ref), f64(off), f64(kidx)
+    lead = off.shape[:4]
+    r = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]                 # (B, Lq, 1 | H, 1, D)
+    col = lambda j: np.broadcast_to(r[..., j], lead)
+    centre = [col(j) + off[..., j] / 8 * col(2 + j) for j in (0, 1)]
+    size = [col(2 + j) + off[..., 2 + j] / 8 * col(2 + j) for j in (0, 1)]
+    local = [kidx[:, j] * np.maximum(size[j], 0.0)[..., None] for j in (0, 1)]           # (B, Lq, H, L, P)
+    # the absolute values of the terms the roundings act on, per axis
+    t_centre = [np.abs(col(j)) + np.abs(off[..., j] / 8 * col(2 + j)) for j in (0, 1)]
+    t_local = [np.abs(kidx[:, j]) * ((np.abs(col(2 + j)) + np.abs(off[..., 2 + j] / 8 * col(2 + j)))
+                                     * (size[j] > 0))[..., None] for j in (0, 1)]
+    if angle_mode:
+        if angle_mode == 1:
+            theta = (col(4) + off[..., 4] / 16) * 2 * np.pi
+            # the sum ref[4] + off[4] / 16, the product with float32's 2 pi, that constant itself: 3 roundings
+            dtheta = 3 * U32 * (np.abs(col(4)) + np.abs(off[..., 4] / 16)) * 2 * np.pi
+        else:
+            theta, dtheta = col(4), np.zeros(lead)
+        cs, sn = np.cos(theta)[..., None], np.sin(theta)[..., None]
+        rot = [local[0] * cs - local[1] * sn, local[0] * sn + local[1] * cs]
+        dsc = (dtheta + SINCOS_ABS)[..., None] * (np.abs(local[0]) + np.abs(local[1]))
+        # product, sum (centre); product, sum, product (size, local) on either axis; two products, the difference, the sum
+        terms = [t_centre[j][..., None] + t_local[0] + t_local[1] for j in (0, 1)]
+        n, local = 9, rot
+    else:
+        dsc = 0.0
+        terms = [t_centre[j][..., None] + t_local[j] for j in (0, 1)]
+        n = 6                     # product, sum (centre); product, sum (size); kidx relu(size); the sum
+    loc = np.stack([centre[j][..., None] + local[j] for j in (0, 1)], -1)
+    dloc = np.stack([n * U32 * terms[j] + dsc for j in (0, 1)], -1)
+    if vr is not None:
+        v = np.abs(f64(vr))
+        loc, dloc = loc * f64(vr), (dloc + U32 * np.stack(terms, -1)) * v                # one more rounding
+    return loc, dloc
+
+
+def _softmax(z, axes, count, more=0):
+    """float64 softmax of ``z`` over ``axes`` and its relative allowance (``count`` terms in the sum, ``more`` further
+    roundings of the result)."""
+    d = z - z.max(axes, keepdims=True)
+    assert d.min() >= EXP_MIN, "a logit %.1f below its row's maximum" % -d.min()
+    e = np.exp(d)
+    a = e / e.sum(axes, keepdims=True)
+    de = (3.0 * np.abs(d) + 2.0) * U32                      # the exponent's three roundings, the instruction's ulp
+    dw = de + (a * de).sum(axes, keepdims=True) + (count - 1 + 1 + 1 + more) * U32      # sum, reciprocal, product
+    return a, np.broadcast_to(dw, a.shape)
+
+
+def softmax_reference(logits):
+    """logits (..., N) -> (softmax over the last axis in float64, dw)."""
+    z = f64(logits)
+    return _softmax(z, (-1,), z.shape[-1])
+
+
+def cell_weights_reference(logits):
+    """logits (B, Lq, H, L, 2, 2) -> a (softmax over the row's 4 L cells), da, t (softmax over the levels), dt."""
+    z = f64(logits)
+    L = z.shape[3]
+    a, da = _softmax(z, (-1, -2, -3), 4 * L, more=2)       # ... / m^2: the constant and the product
+    t, dt = _softmax(z, (-3,), L)
+    return a, da, t, dt
+
+
+def _expand(cells, k):
+    """(B, Lq, H, L, 2, 2) -> (B, Lq, H, L, k * k): repeat_interleave by k / 2 along both axes, row-major (y, x)."""
+    m = k // 2
+    return np.repeat(np.repeat(cells, m, -2), m, -1).reshape(cells.shape[:4] + (k * k,))
+
+
+def instance_weights_reference(logits, k, need_level=True):
+    """The spatial weights -- softmax over all L k k repeated logits = a[cell] / m^2 -- and, with need_level, the level
+    weights t[cell], (B, Lq, H, L, k * k) each, float64 -> (spatial, level | None, dw_spatial, dw_level | None)."""
+    a, da, t, dt = cell_weights_reference(logits)
+    m = k // 2
+    sw, dsw = _expand(a / (m * m), k), _expand(da, k)
+    return (sw, _expand(t, k), dsw, _expand(dt, k)) if need_level else (sw, None, dsw, None)
+
+
+def _reduce_boxes(r, names, ref, off, kidx, vr, logits, k):
+    """The per-point planes of ``_reference`` -> grad_offsets (B, Lq, H, L, 4), grad_ref_rows (B, Lq, H, L, 5),
+    grad_logits (B, Lq, H, L, 2, 2), angle mode 0.  want reduces in float64; A, E (with W and the edge jumps) and J with
+    the absolute values of the same coefficients; n is the largest n of the points plus the reduction's own roundings.
+    grad_offsets also gets ``unmasked``: its exact value with relu' left out (a mutation, for the tests of the bound)."""
+    ref, off, kidx = f64(ref), f64(off), f64(kidx)
+    lead = off.shape[:4]
+    P = kidx.shape[0]
+    rr = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]
+    col = lambda j: np.broadcast_to(rr[..., j], lead)
+    g = r["grad_loc"]
+    scale = f64(vr) if vr is not None else 1.0                       # d / d (unscaled grid)
+    pl = {"want": g["want"] * scale, "A": g["A"] * np.abs(scale), "E": (g["E"] + g["W"]) * np.abs(scale),
+          "J": g["J"] * np.abs(scale)}
+    n_out = g["n"].max((-1, -2)) + P + 6             # the vr product, kidx product, P-term sum, and the row's few
+    goff = {m: np.zeros(lead + (4,)) for m in ("want", "A", "E", "J", "n", "unmasked")}
+    rows = {m: np.zeros(lead + (5,)) for m in ("want", "A", "E", "J", "n")}
+    for j in (0, 1):
+        sz = col(2 + j) + off[..., 2 + j] / 8 * col(2 + j)
+        dsz = 2 * U32 * (np.abs(col(2 + j)) + np.abs(off[..., 2 + j] / 8 * col(2 + j)))
+        pos = sz > 0
+        unsure = (np.abs(sz) <= dsz) & (sz != 0)     # the sign of a float32 size may differ: either relu' is legitimate
+        for m, p in pl.items():
+            kj = kidx[:, j] if m == "want" else np.abs(kidx[:, j])
+            ab = (lambda x: x) if m == "want" else np.abs
+            s_c, s_k = p[..., j].sum(-1), (kj * p[..., j]).sum(-1)
+            goff[m][..., j] = s_c * ab(col(2 + j)) / 8
+            goff[m][..., 2 + j] = pos * s_k * ab(col(2 + j)) / 8
+            if m == "want":
+                goff["unmasked"][..., j], goff["unmasked"][..., 2 + j] = goff[m][..., j], s_k * col(2 + j) / 8
+            rows[m][..., j] = s_c
+            rows[m][..., 2 + j] = s_c * ab(off[..., j] / 8) + pos * s_k * ab(1 + off[..., 2 + j] / 8)
+            if m == "A":
+                goff["E"][..., 2 + j] += unsure * s_k * np.abs(col(2 + j)) / 8
+                rows["E"][..., 2 + j] += unsure * s_k * np.abs(1 + off[..., 2 + j] / 8)
+    for d in (goff, rows):
+        d["n"][...] = n_out[..., None]
+    rows["n"][..., 4] = 0
+    # ---- the 2 x 2 logits
+    a, da, t, dt = cell_weights_reference(logits)
+    m2 = (k // 2) ** 2
+    L = a.shape[3]
+    cells = lambda x: x.reshape(lead + (2, k // 2, 2, k // 2)).sum((-1, -3))
+    row, lev = (-1, -2, -3), (-3,)
+    glog = {}
+    sp = r[names[0]]
+    lvp = r[names[1]] if len(names) > 1 else None
+    for m in ("want", "A", "E"):
+        Gs = cells(sp[m])
+        if m == "want":
+            x = a / m2 * (Gs - (a * Gs).sum(row, keepdims=True))
+        else:
+            x = a / m2 * (Gs + (a * Gs).sum(row, keepdims=True))
+        if m == "E":       # the weights' own allowance: a is within da of its value, every a of the row within the largest
+            As = cells(sp["A"])
+            x = x + (da + da.max(row, keepdims=True)) * a / m2 * (As + (a * As).sum(row, keepdims=True))
+        if lvp is not None:
+            Gt = cells(lvp[m])
+            if m == "want":
+                x = x + t * (Gt - (t * Gt).sum(lev, keepdims=True))
+            else:
+                x = x + t * (Gt + (t * Gt).sum(lev, keepdims=True))
+            if m == "E":
+                At = cells(lvp["A"])
+                x = x + (dt + dt.max(lev, keepdims=True)) * t * (At + (t * At).sum(lev, keepdims=True))
+        glog[m] = x
+    n_pt = sp["n"].max(-1) if lvp is None else np.maximum(sp["n"].max(-1), lvp["n"].max(-1))
+    glog["n"] = np.broadcast_to((n_pt + m2 + 4 * L + 8)[..., None, None], glog["want"].shape).copy()
+    glog["J"] = np.zeros_like(glog["want"])
+    return {"grad_offsets": goff, "grad_ref_rows": rows, "grad_logits": glog}
+
+
+def boxes_reference(kind, value, shapes, lsi, ref, off, kidx, vr, logits, angle_mode=0, k=None, grad_out=None,
+                    grad_mask=None, loc=None, weights=None):
+    """What the kernels that take boxes and logits must give, from their own inputs (float32 ref, off, kidx, vr,
+    logits; ``value`` and the upstream gradients as stored).  kind "box": logits (B, Lq, H, L P) -> {out}; kind
+    "instance": logits (B, Lq, H, L, 2, 2), k -> {out, mask_out} and, with grad_out (grad_mask None: the mask output took
+    no part), {grad_offsets, grad_ref_rows, grad_logits}.  ``loc`` / ``weights`` (a list) replace the model's own in
+    ``want``: mutations, for the tests of the bound itself.  Also "grid" and
+    "weights": (loc, dloc) and [(w, dw), ...] of the model."""
+    value = f64(value)
+    B, S, Hh, C = value.shape
+    shapes, lsi = f64(shapes).astype(np.int64), f64(lsi).astype(np.int64)
+    loc0, dloc = grid_reference(ref, off, kidx, vr, angle_mode)
+    Lq, L, P = loc0.shape[1], loc0.shape[3], loc0.shape[4]
+    if kind == "box":
+        w, dw = softmax_reference(logits)
+        ws, dws = [w.reshape(B, Lq, Hh, L, P)], [dw.reshape(B, Lq, Hh, L, P)]
+    else:
+        sw, lw, dsw, dlw = instance_weights_reference(logits, k, True)
+        ws, dws = [sw, lw], [dsw, dlw]
+    res = {"grid": (loc0, dloc), "weights": list(zip(ws, dws))}
+    ws = ws if weights is None else [f64(w).reshape(B, Lq, Hh, L, P) for w in weights]
+    loc = loc0 if loc is None else f64(loc)
+    gout = np.zeros((B, Lq, Hh, C)) if grad_out is None else f64(grad_out).reshape(B, Lq, Hh, C)
+    if kind == "box":
+        r = _reference(value, shapes, lsi, loc, ws, [gout], False, slack=dloc, dws=dws)
+        res["out"] = r["out"]
+        return res
+    if grad_out is None or grad_mask is not None:
+        gmask = np.zeros((B, Lq, P, Hh, C)) if grad_mask is None else f64(grad_mask).reshape(B, Lq, P, Hh, C)
+        r = _reference(value, shapes, lsi, loc, ws, [gout, gmask], True, slack=dloc, dws=dws)
+        res.update(out=r["out"], mask_out=r["mask_out"])
+        names = ("grad_spatial", "grad_level")
+    else:
+        r = _reference(value, shapes, lsi, loc, ws[:1], [gout], False, slack=dloc, dws=dws[:1])
+        res["out"] = r["out"]
+        names = ("grad_attn",)
+    if grad_out is not None:
+        res.update(_reduce_boxes(r, names, ref, off, kidx, vr, logits, k))
+        res["edge_share"] = r["grad_loc"]["edge_share"]
+    return res
+
+
+def edge_dominated(ref, store="float32"):
+    """The share of an output's elements whose bound is more than half edge allowance (the J plane)."""
+    bnd = bound(ref, store)
+    return float((ref["J"] > 0.5 * bnd).mean()) if bnd.size else 0.0

@@ -1,0 +1,315 @@
+"""GPU: the three kernels that take boxes and logits -- ``ops.box_attn_forward_boxes``,
+``ops.instance_attn_forward_boxes``, ``ops.instance_attn_backward_boxes`` -- and their building blocks
+(``ops.box_grid_forward``, ``ops.softmax_forward``, ``ops.instance_weights_forward``) held per element against
+``error_bounds.boxes_reference``: a float64 model that starts from what the kernel receives (reference windows,
+offsets, kernel_indices, valid ratios, logits), with nothing taken from a GPU chain.
+
+The problems are those of tests/test_gpu_box_boxes_forward.py, tests/test_gpu_boxes_forward.py and
+tests/test_gpu_boxes_backward.py (imported, not copied).  ``value`` and the upstream gradients are rounded to bf16 and
+then to f16: numbers every storage type holds exactly, so one reference serves the three types.  A case of the instance
+matrix whose share of points within EDGE_PX + slack of a cell edge is above EDGE_CAP takes another seed (RESEED;
+tests/test_boxes_error_bounds.py checks every input here without a GPU).  Each case prints ``error-bound | route | type
+| output | worst err / bound``; profiles/boxes_error_bounds.log is that table from one run."""
+import functools
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+import error_bounds as eb
+import test_gpu_box_boxes_forward as box_cases
+import test_gpu_boxes_forward as inst_cases
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+BOX_GEOMETRIES = ["model", "ragged", "one_level", "odd_k", "sixteen_levels", "k4", "encoder"]
+CHANNELS = [16, 32, 64]
+INST_FLAVOURS = list(itertools.product((False, True), (False, True)))          # per_head, with_vr
+# (geometry, C, k, per_head, with_vr) -> what is added to the seed of test_gpu_boxes_forward.problem
+RESEED = {}
+
+
+def kernel_offsets(k):
+    """The modules' kernel_indices buffer of a k x k kernel, float32 numpy."""
+    from boxer_amd.modules import _kernel_offsets
+    return _kernel_offsets(k, k).float().numpy()
+
+
+def every_type(a):
+    """float64 numbers that float32, bf16 and f16 all hold exactly: rounded to bf16, then to f16 (which changes a bf16
+    number only below 2^-17, to a multiple of 2^-24 of at most 7 bits)."""
+    return eb.round_to(eb.round_to(a, "bf16"), "f16")
+
+
+def report(route, dtype, name, worst):
+    print("error-bound | %s | %s | %s | %.3f" % (route, eb.store_name(dtype), name, worst))
+
+
+# ------------------------------------------------------------------ inputs and references (CPU)
+def box_problem(geometry, C, flavour):
+    (angle_mode, ref_dim), per_head, with_vr = flavour
+    return box_cases.problem(geometry, C, angle_mode, ref_dim, per_head, with_vr)
+
+
+@functools.lru_cache(maxsize=16)
+def box_reference(geometry, C, flavour):
+    g = box_problem(geometry, C, flavour)
+    P = g["dims"][6]
+    return eb.boxes_reference("box", every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
+                              kernel_offsets(int(round(P ** 0.5))), g["vr"], g["logits"], g["angle_mode"])
+
+
+@functools.lru_cache(maxsize=None)
+def inst_problem(geometry, C, k, per_head, with_vr):
+    """test_gpu_boxes_backward.case (test_gpu_boxes_forward.problem, re-seeded where that file had to), re-seeded again
+    where the condition with the locations' own slack asks for it."""
+    from test_gpu_boxes_backward import case
+    bump = RESEED.get((geometry, C, k, per_head, with_vr))
+    if bump is None:
+        return case(geometry, C, k, per_head, with_vr)
+    make = np.random.default_rng
+    np.random.default_rng = lambda seed: make(seed + bump)
+    try:
+        return inst_cases.problem.__wrapped__(geometry, C, k, per_head, with_vr)
+    finally:
+        np.random.default_rng = make
+
+
+def inst_upstream(g, k):
+    B, S, H, C, L, Lq = g["dims"]
+    rng = np.random.default_rng(100)
+    return every_type(rng.standard_normal((B, Lq, H * C))), every_type(rng.standard_normal((B, Lq, k * k, H * C)))
+
+
+@functools.lru_cache(maxsize=8)
+def inst_reference(geometry, C, k, per_head, with_vr, with_mask):
+    """with_mask: {out, mask_out, the three gradients with grad_mask}; without: {out, the gradients without}."""
+    g = inst_problem(geometry, C, k, per_head, with_vr)
+    gout, gmask = inst_upstream(g, k)
+    return eb.boxes_reference("instance", every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
+                              kernel_offsets(k), g["vr"], g["logits"], 0, k, gout, gmask if with_mask else None)
+
+
+GRAD_NAMES = ("grad_offsets", "grad_ref_rows", "grad_logits")
+GRID_POINTS = [1, 4, 9, 196]
+GRID_FLAVOURS = list(itertools.product((0, 1, 2), (False, True), (False, True)))   # angle_mode, per_head, with_vr
+
+
+@functools.lru_cache(maxsize=None)
+def grid_problem(P, angle_mode, per_head, with_vr):
+    """A few boxes for ops.box_grid_forward on its own: windows inside, partly and wholly outside the map, sizes below
+    and exactly zero, angles of 23 and -7.25 (turns in mode 1, radians in mode 2) and an offset angle of 77 / 16 turns."""
+    B, Lq, H, L = 2, 5, 3, 2
+    D, V = (7 if angle_mode else 4), (5 if angle_mode == 1 else 4)
+    rng = np.random.default_rng(500 + 10 * P + 3 * angle_mode + per_head)
+    rshape = (B, Lq, H) if per_head else (B, Lq)
+    ref = np.concatenate([rng.uniform(0.05, 0.95, rshape + (2,)), rng.uniform(0.05, 0.7, rshape + (2,)),
+                          rng.uniform(-3.0, 3.0, rshape + (D - 4,))], -1)
+    flat = ref.reshape(-1, D)
+    flat[0, :4] = (2.6, 2.4, 0.2, 0.3)
+    flat[1, :4] = (0.97, 0.02, 0.5, 0.4)
+    flat[-1, :4] = (-0.7, 0.5, 0.3, 0.3)
+    if D > 4:
+        flat[2, 4], flat[3, 4] = 23.0, -7.25
+    off = 3.0 * rng.standard_normal((B, Lq, H, L, V))
+    rows = off.reshape(-1, V)
+    rows[rng.random(len(rows)) < 0.15, 2] = -12.0
+    rows[0, 2:4] = -8.0
+    if V == 5:
+        rows[1, 4] = 77.0
+    k = int(round(P ** 0.5))
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    return dict(ref=f32(ref), off=f32(off), kidx=kernel_offsets(k), angle_mode=angle_mode,
+                vr=f32(rng.uniform(0.5, 1.0, (B, 1, 1, L, 1, 2))) if with_vr else None)
+
+
+@functools.lru_cache(maxsize=None)
+def softmax_rows(n):
+    """Rows of n logits: 3 randn; the same with a shared shift of +- 30; a spread of 60 (one logit on top, the others
+    60 and 30 below); all equal; float32."""
+    rng = np.random.default_rng(n)
+    z = 3.0 * rng.standard_normal((8, n))
+    z[2:4] += np.asarray([[30.0], [-30.0]])
+    z[4] = np.where(np.arange(n) % 2 == 0, -60.0, -30.0)
+    z[4, n // 2] = 0.0
+    z[5] = 1.25
+    z[6] = np.linspace(-60.0, 0.0, n)
+    return np.ascontiguousarray(z, dtype=np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def cell_rows(L):
+    """(1, 8, 1, L, 2, 2) logits of the same kinds for ops.instance_weights_forward."""
+    return softmax_rows(4 * L).reshape(1, 8, 1, L, 2, 2)
+
+
+def within(got, want, allowance, what):
+    """Assert |got - want| <= allowance per element; -> the worst ratio."""
+    got = eb.f64(got).reshape(want.shape)
+    err = np.abs(got - want)
+    assert np.isfinite(got).all(), what
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, 0.0, err / allowance)
+    worst = float(r.max()) if r.size else 0.0
+    at = np.unravel_index(int(np.argmax(r)), r.shape)
+    assert worst <= 1.0, "%s: %d of %d elements outside the allowance; worst at %s: got %.9g, want %.9g, allowed %.3e" \
+        % (what, int((r > 1).sum()), r.size, at, got[at], want[at], np.broadcast_to(allowance, want.shape)[at])
+    return worst
+
+
+# ------------------------------------------------------------------ running
+def dev(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return t.to(dtype) if dtype is not None else t
+
+
+def offset_by_eight(t):
+    flat = torch.zeros(t.numel() + 4, dtype=t.dtype, device="cuda")
+    out = flat[4:].view(t.shape)
+    out.copy_(t)
+    assert out.data_ptr() % 16 == 8 and out.is_contiguous()
+    return out
+
+
+def box_args(g, dt, value=None):
+    B, S, H, C, L, Lq, P = g["dims"]
+    value = dev(every_type(g["value"]), dt) if value is None else value
+    return (value, dev(g["shapes"]), dev(g["lsi"]), dev(g["ref"]), dev(g["off"]),
+            dev(kernel_offsets(int(round(P ** 0.5)))), None if g["vr"] is None else dev(g["vr"]), dev(g["logits"]),
+            g["angle_mode"])
+
+
+def run_box(g, dt, value=None):
+    from boxer_amd import ops
+    B, S, H, C, L, Lq, P = g["dims"]
+    args = box_args(g, dt, value)
+    assert ops.box_forward_boxes_ok(args[0], L, Lq, P), "not eligible: %s %s" % (g["dims"], dt)
+    out = ops.box_attn_forward_boxes(*args)
+    torch.cuda.synchronize()
+    assert out.dtype == dt
+    return out
+
+
+@pytest.mark.parametrize("dtype", sorted(DTYPES))
+@pytest.mark.parametrize("C", CHANNELS)
+@pytest.mark.parametrize("geometry", BOX_GEOMETRIES)
+def test_box_forward_from_boxes(geometry, C, dtype):
+    """fwd2_boxes_kernel over every flavour (angle modes 0, 1 with 5 and 7 reference values, 2 x windows shared and per
+    head x valid ratios None and given).  The split is "none": float32 weights on the VALU."""
+    from boxer_amd import ops
+    dt = DTYPES[dtype]
+    worst, zeros = 0.0, 0
+    for flavour in box_cases.FLAVOURS:
+        g = box_problem(geometry, C, flavour)
+        B, S, H, _, L, Lq, P = g["dims"]
+        if geometry == "k4" and not ops.box_forward_boxes_ok(torch.empty(B, S, H, C, dtype=dt, device="cuda"), L, Lq, P):
+            with pytest.raises(ValueError):          # no row gather for this type at this C: an error, not a fall-back
+                ops.box_attn_forward_boxes(*box_args(g, dt))
+            continue
+        ref = box_reference(geometry, C, flavour)["out"]
+        what = "box from boxes: %s C=%d angle=%d D=%d per_head=%d vr=%d" % ((geometry, C) + flavour[0] + flavour[1:])
+        worst = max(worst, eb.hold(run_box(g, dt), ref, dt, "none", what))
+        zeros += int(((ref["A"] + ref["E"]) == 0).sum())
+    report("box from boxes: %s C=%d (%d must-be-zero elements)" % (geometry, C, zeros), dt, "out", worst)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+@pytest.mark.parametrize("geometry", ["model", "ragged"])
+def test_box_forward_value_offset_by_eight_bytes(geometry, dtype):
+    """A 16-bit ``value`` 8 bytes off a 16-byte boundary: 4 channels a lane instead of 8."""
+    dt = DTYPES[dtype]
+    flavour = ((1, 5), True, True)
+    g = box_problem(geometry, 32, flavour)
+    value = offset_by_eight(dev(every_type(g["value"]), dt))
+    worst = eb.hold(run_box(g, dt, value=value), box_reference(geometry, 32, flavour)["out"], dt, "none",
+                    "box from boxes, value offset: %s" % geometry)
+    report("box from boxes: %s C=32, value 8 bytes off" % geometry, dt, "out", worst)
+
+
+@pytest.mark.parametrize("dtype", sorted(DTYPES))
+@pytest.mark.parametrize("k", inst_cases.KERNEL_SIZES)
+@pytest.mark.parametrize("C", CHANNELS)
+@pytest.mark.parametrize("geometry", sorted(inst_cases.GEOMETRY))
+def test_instance_forward_and_backward_from_boxes(geometry, C, k, dtype):
+    """ops.instance_attn_forward_boxes with and without mask_out and ops.instance_attn_backward_boxes with and without
+    grad_mask (need_ref_grad), windows shared and per head x valid ratios None and given; the gradients are float32 in
+    every storage type.  (One test for both: they share the reference.)"""
+    from boxer_amd import ops
+    dt = DTYPES[dtype]
+    worst, edge = {}, {}
+    for per_head, with_vr in INST_FLAVOURS:
+        g = inst_problem(geometry, C, k, per_head, with_vr)
+        B, S, H, _, L, Lq = g["dims"]
+        gout64, gmask64 = inst_upstream(g, k)
+        value, gout, gmask = dev(every_type(g["value"]), dt), dev(gout64, dt), dev(gmask64, dt)
+        a = (value, dev(g["shapes"]), dev(g["lsi"]), dev(g["ref"]), dev(g["off"]), dev(kernel_offsets(k)),
+             None if g["vr"] is None else dev(g["vr"]), dev(g["logits"]), k)
+        assert ops.forward_boxes_ok(value, L, Lq, k) and ops.backward_boxes_ok(value, L, Lq, k), \
+            "not eligible: %s k=%d %s" % (g["dims"], k, dt)
+        for with_mask in (True, False):
+            ref = inst_reference(geometry, C, k, per_head, with_vr, with_mask)
+            what = "instance from boxes: %s C=%d k=%d per_head=%d vr=%d mask=%d" % (geometry, C, k, per_head, with_vr,
+                                                                                     with_mask)
+            assert ref["edge_share"] <= eb.EDGE_CAP, "%s: %.4f %% of the points on a cell edge" % (
+                what, 100 * ref["edge_share"])
+            out, mask = ops.instance_attn_forward_boxes(*a, with_mask)
+            grads = ops.instance_attn_backward_boxes(*a, gout, gmask if with_mask else None, need_ref_grad=True)
+            torch.cuda.synchronize()
+            assert (mask is None) == (not with_mask) and out.dtype == dt
+            got = dict(zip(GRAD_NAMES, grads), out=out, **({"mask_out": mask} if with_mask else {}))
+            for name, t in got.items():
+                store = dt if name in ("out", "mask_out") else torch.float32
+                assert t.dtype == store, name
+                key = "%s%s" % (name, "" if with_mask or name == "out" else " (no grad_mask)")
+                worst[key] = max(worst.get(key, 0.0), eb.hold(t, ref[name], store, "none", "%s: %s" % (what, name)))
+                if name in GRAD_NAMES:
+                    edge[key] = max(edge.get(key, 0.0), eb.edge_dominated(ref[name]))
+    route = "instance from boxes: %s C=%d k=%d" % (geometry, C, k)
+    for name, w in worst.items():
+        report(route, dt if name.split()[0] in ("out", "mask_out") else torch.float32, name, w)
+    print("%s: share of elements whose bound is more than half edge allowance: %s"
+          % (route, ", ".join("%s %.4f" % kv for kv in edge.items())))
+
+
+# ------------------------------------------------------------------ the building blocks on their own
+@pytest.mark.parametrize("P", GRID_POINTS)
+def test_box_grid_forward_is_within_dloc(P):
+    """ops.box_grid_forward against grid_reference within dloc: the three angle modes x windows shared and per head x
+    valid ratios None and given, angles of several turns."""
+    from boxer_amd import ops
+    worst = {}
+    for angle_mode, per_head, with_vr in GRID_FLAVOURS:
+        g = grid_problem(P, angle_mode, per_head, with_vr)
+        loc, dloc = eb.grid_reference(g["ref"], g["off"], g["kidx"], g["vr"], angle_mode)
+        got = ops.box_grid_forward(dev(g["ref"]), dev(g["off"]), dev(g["kidx"]),
+                                   None if g["vr"] is None else dev(g["vr"]), angle_mode)
+        torch.cuda.synchronize()
+        w = within(got, loc, dloc, "grid P=%d angle=%d per_head=%d vr=%d" % (P, angle_mode, per_head, with_vr))
+        worst[angle_mode] = max(worst.get(angle_mode, 0.0), w)
+    for angle_mode, w in sorted(worst.items()):
+        report("box_grid_forward P=%d angle mode %d" % (P, angle_mode), torch.float32, "grid / dloc", w)
+
+
+@pytest.mark.parametrize("n", [1, 4, 12, 18, 64])
+def test_softmax_forward_is_within_dw(n):
+    from boxer_amd import ops
+    z = softmax_rows(n)
+    want, dw = eb.softmax_reference(z)
+    got = ops.softmax_forward(dev(z))
+    torch.cuda.synchronize()
+    report("softmax_forward n=%d" % n, torch.float32, "weights / dw", within(got, want, dw * want, "softmax n=%d" % n))
+
+
+@pytest.mark.parametrize("k", inst_cases.KERNEL_SIZES)
+@pytest.mark.parametrize("L", [1, 5, 16])
+def test_instance_weights_forward_is_within_dw(L, k):
+    from boxer_amd import ops
+    z = cell_rows(L)
+    sw, lw, dsw, dlw = eb.instance_weights_reference(z, k, True)
+    got_s, got_l = ops.instance_weights_forward(dev(z), k, need_level=True)
+    torch.cuda.synchronize()
+    route = "instance_weights_forward L=%d k=%d" % (L, k)
+    report(route, torch.float32, "spatial / dw", within(got_s, sw, dsw * sw, route + " spatial"))
+    report(route, torch.float32, "level / dw", within(got_l, lw, dlw * lw, route + " level"))
