@@ -14,7 +14,7 @@ class and box heads).  One process per GPU; gradients are all-reduced by Distrib
 (RCCL with backend "nccl", gloo in the CPU test) -- the operator itself never communicates.
 
   python bench_train.py [--steps 30 --warmup 10 --dtype bf16|fp16|fp32 --fused-grid --fused-pointwise
-                         --model 2d|3d --mask-decoder --split-k-wgrad --graph]
+                         --fused-boxes-train --model 2d|3d --mask-decoder --split-k-wgrad --graph]
   python bench_train.py --gpus N          (starts its own N ranks; or under torch.distributed.run)
 prints ONE JSON line on rank 0: ms per step (MAX over ranks), images/s, operator share.
 """
@@ -166,6 +166,9 @@ def main():
                          "(boxer_amd.dense)")
     ap.add_argument("--fused-pointwise", action="store_true",
                     help="softmax and value mask + cast as single HIP passes (module.fused_pointwise)")
+    ap.add_argument("--fused-boxes-train", action="store_true",
+                    help="the attention step from the predicted boxes and logits, no per-point tensors kept "
+                         "(module.fused_boxes_train, on every attention module that has the flag)")
     ap.add_argument("--mask-decoder", action="store_true",
                     help="InstanceAttention (14x14) in the decoder: the instance-segmentation model")
     ap.add_argument("--layers", type=int, default=None, help="encoder = decoder layers (2d: 6, 3d: 2)")
@@ -202,6 +205,8 @@ def main():
         m.native_f16 = args.dtype == "fp16"
         m.fused_grid = args.fused_grid
         m.fused_pointwise = args.fused_pointwise
+        if hasattr(m, "fused_boxes_train"):
+            m.fused_boxes_train = args.fused_boxes_train
         with torch.no_grad():                                # trained-like box offsets
             m.linear_box_weight.normal_(0, 0.02)
     from boxer_amd import dense
@@ -271,7 +276,7 @@ def main():
                 args.model.upper(), args.layers, args.layers, "/".join("%dx%d" % hw for hw in levels)),
             "ms_per_step": round(ms_step, 3), "images_per_s": round(world * args.batch / ms_step * 1e3, 2),
             "n_gpus": world, "batch_per_gpu": args.batch, "dtype": args.dtype,
-            "fused_grid": args.fused_grid, "fused_pointwise": args.fused_pointwise, "split_k_wgrad": args.split_k_wgrad, "graph": args.graph, "mask_decoder": args.mask_decoder, "params_M": round(n_params / 1e6, 2),
+            "fused_grid": args.fused_grid, "fused_pointwise": args.fused_pointwise, "fused_boxes_train": args.fused_boxes_train, "split_k_wgrad": args.split_k_wgrad, "graph": args.graph, "mask_decoder": args.mask_decoder, "params_M": round(n_params / 1e6, 2),
             "operator_kernels_ms_per_step": round(op_ms, 3),
             "peak_mem_GB": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 2),
             "operator_share": round(op_ms / ms_step, 3), "loss": round(float(loss), 4),

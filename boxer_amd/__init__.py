@@ -11,8 +11,8 @@ The compute lives in a C-ABI HIP library (``include/boxattn.h``, ``boxer_amd/csr
 DESIGN.md and INTEGRATION.md.  There is no CPU fallback: ops raise if the library is missing.
 """
 from . import _lib, ops
-from .functions import (BoxAttnBF16Function, BoxAttnF16Function, BoxAttnFunction, BoxGridFunction,
-                        InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
+from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnF16Function, BoxAttnFunction,
+                        BoxGridFunction, InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
                         InstanceAttnBoxesFunction, InstanceWeightsFunction, LogitSoftmaxFunction,
                         ValueMaskCastFunction)
 from .modules import Box3dAttention, BoxAttention, InstanceAttention
@@ -20,7 +20,7 @@ from .modules import Box3dAttention, BoxAttention, InstanceAttention
 __all__ = [
     "ops", "BoxAttnFunction", "InstanceAttnFunction", "BoxAttnBF16Function",
     "InstanceAttnBF16Function", "BoxAttnF16Function", "InstanceAttnF16Function", "BoxGridFunction", "LogitSoftmaxFunction", "ValueMaskCastFunction",
-    "InstanceWeightsFunction", "InstanceAttnBoxesFunction",
+    "InstanceWeightsFunction", "InstanceAttnBoxesFunction", "BoxAttnBoxesFunction",
     "BoxAttention", "InstanceAttention", "Box3dAttention",
     "build", "build_info",
 ]

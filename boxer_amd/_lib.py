@@ -100,6 +100,10 @@ _BOXES_BWD_SIGNATURES = {"instattn_bwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_v
 # B, S, H, C, L, Lq, P, out, stream
 _BOX_BOXES_SIGNATURES = {"boxattn_fwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_vp] + [_i, _i] + [_vp] * 3 + [_i] * 7 +
                          [_vp] * 2 for suf in ("f32", "bf16", "f16")}
+# value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode, kernel_idx, valid_ratios | NULL, logits,
+# grad_out, B, S, H, C, L, Lq, P, grad_offsets, grad_ref_rows | NULL, grad_logits, stream
+_BOX_BOXES_BWD_SIGNATURES = {"boxattn_bwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_vp] + [_i, _i] + [_vp] * 4 +
+                             [_i] * 7 + [_vp] * 4 for suf in ("f32", "bf16", "f16")}
 EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "boxattn_set_option",
            "boxattn_options_epoch", "boxattn_fwd_route", "boxattn_bwd_accumulate_kind", "boxattn_bwd_record_kind",
            "boxattn_set_debug_buffer",
@@ -108,7 +112,8 @@ EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "
            "boxattn_plan_bytes", "boxattn_state_bytes",
            "boxattn_grid_fwd_f32", "boxattn_grid_bwd_f32", "instattn_fwd_boxes_ok", *sorted(_BOXES_SIGNATURES),
            "instattn_bwd_boxes_ok", *sorted(_BOXES_BWD_SIGNATURES),
-           "boxattn_fwd_boxes_ok", *sorted(_BOX_BOXES_SIGNATURES)] + [
+           "boxattn_fwd_boxes_ok", *sorted(_BOX_BOXES_SIGNATURES),
+           "boxattn_bwd_boxes_ok", *sorted(_BOX_BOXES_BWD_SIGNATURES)] + [
     "%s_%s" % (stem, suf) for stem in _SIGNATURES for suf in ("f32", "f64", "bf16", "f16")] + [
     "%s_%s" % (stem, suf) for stem in _WS_SIGNATURES for suf in ("f32", "bf16", "f16")] + [
     "%s_%s" % (stem, suf) for stem in _PART_SIGNATURES for suf in ("f32", "bf16", "f16")] + sorted(_PART_F64_SIGNATURES)
@@ -250,7 +255,7 @@ def load():
     lib.boxattn_bwd_record_kind.restype = _i
     for name, args in (list(_GRID_SIGNATURES.items()) + list(_POINTWISE_SIGNATURES.items()) +
                        list(_BOXES_SIGNATURES.items()) + list(_BOXES_BWD_SIGNATURES.items()) +
-                       list(_BOX_BOXES_SIGNATURES.items())):
+                       list(_BOX_BOXES_SIGNATURES.items()) + list(_BOX_BOXES_BWD_SIGNATURES.items())):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = _i
     lib.instattn_fwd_boxes_ok.argtypes = [_i] * 9
@@ -259,6 +264,8 @@ def load():
     lib.instattn_bwd_boxes_ok.restype = _i
     lib.boxattn_fwd_boxes_ok.argtypes = [_i] * 9
     lib.boxattn_fwd_boxes_ok.restype = _i
+    lib.boxattn_bwd_boxes_ok.argtypes = [_i] * 9
+    lib.boxattn_bwd_boxes_ok.restype = _i
     lib.boxattn_state_bytes.argtypes = [_i] * 7 + [_vp, _vp]
     lib.boxattn_state_bytes.restype = ctypes.c_size_t
     for name in ("boxattn_bwd_workspace_bytes", "boxattn_plan_bytes"):
@@ -311,6 +318,12 @@ def box_fwd_boxes_ok(elem_bytes, aligned, dims):
     """boxattn_fwd_boxes_ok(): whether the boxattn_fwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
     C, L, Lq, P) under the current switches.  Pure host code (no GPU needed)."""
     return bool(load().boxattn_fwd_boxes_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims]))
+
+
+def box_bwd_boxes_ok(elem_bytes, aligned, dims):
+    """boxattn_bwd_boxes_ok(): whether the boxattn_bwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
+    C, L, Lq, P) under the current switches.  Pure host code (no GPU needed)."""
+    return bool(load().boxattn_bwd_boxes_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims]))
 
 
 def bwd_boxes_ok(elem_bytes, aligned, dims, k):

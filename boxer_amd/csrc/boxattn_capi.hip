@@ -19,6 +19,7 @@
 #include "boxattn_boxes.h"
 #include "boxattn_boxes_bwd.h"
 #include "boxattn_gather2_boxes.h"
+#include "boxattn_gather2_boxes_bwd.h"
 #include "boxattn_fast.h"
 #include "boxattn_gather2.h"
 #include "boxattn_dense_plan.h"
@@ -657,6 +658,54 @@ int launch_bwd_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi,
         BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
 #undef BOXATTN_LAUNCH_BOXES
     }
+    return finish();
+}
+
+// ---- box attention's box and logit gradients from boxes and L P logits (boxattn_gather2_boxes_bwd.h) --------
+// Eligibility is box_boxes_route, with grad_out in the place of the forward's out in the row alignment: the ONE
+// function behind boxattn_bwd_boxes_ok and the entry points.  No other kernel behind this entry.
+template <typename ST>
+int launch_bwd_box_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
+                         int ref_per_head, const float *offsets, int V, int angle_mode, const float *kernel_idx,
+                         const float *valid_ratios, const float *logits, const ST *grad_out, int B, int S, int H,
+                         int C, int L, int Lq, int P, float *grad_offsets, float *grad_ref_rows, float *grad_logits,
+                         hipStream_t st)
+{
+    const Dims d{B, S, H, C, L, Lq, P};
+    if (!d.valid() || L > 16 || (long long)L * P > kBoxesMaxLP) return (int)hipErrorInvalidValue;
+    if (angle_mode < 0 || angle_mode > 2 || V != (angle_mode == 1 ? 5 : 4) || ref_dim < (angle_mode ? 5 : 4))
+        return (int)hipErrorInvalidValue;
+    if (d.empty()) return 0;                                   // no queries: nothing to write
+    if (!shapes || !lsi || !ref || !offsets || !kernel_idx || !logits || !grad_out || !grad_offsets || !grad_logits)
+        return (int)hipErrorInvalidValue;
+    const size_t n_rows = d.n_qh() * (size_t)L;
+    if (d.n_value() == 0) {                                    // no pixels: every gradient is 0
+        hipError_t e = zero_async(grad_offsets, n_rows * (size_t)V * sizeof(float), st);
+        if (e == hipSuccess && grad_ref_rows) e = zero_async(grad_ref_rows, n_rows * 5 * sizeof(float), st);
+        if (e == hipSuccess) e = zero_async(grad_logits, n_rows * (size_t)P * sizeof(float), st);
+        return (int)e;
+    }
+    if (!value) return (int)hipErrorInvalidValue;
+    const size_t va = 4 * sizeof(ST);
+    FwdAlign al;
+    al.fast = aligned(value, va) && aligned(grad_out, va);
+    al.rows16 = aligned(value, 16) && aligned(grad_out, 16);
+    al.staged = false;
+    FwdRoute r;
+    if (!box_boxes_route((int)sizeof(ST), d, al, r)) return (int)hipErrorInvalidValue;
+    const GridDims gd{Lq, H, L, P, V, ref_dim, ref_per_head ? 1 : 0, angle_mode};
+    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST));
+    const unsigned stride = bwd2_boxes_pair_stride(L * P);
+    const GatherCfg cfg = r.cfg;
+    ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], st);
+#define BOXATTN_BWD2_BOXES(GG, VV)                                                                        \
+    hipLaunchKernelGGL((bwd2_boxes_kernel<ST, GG, GatherUnroll<ST, GG, VV>::value, VV>), dim3(r.blocks),  \
+                       dim3(256), (size_t)kGatherWaves * (kWave / GG) * stride * sizeof(float), st,       \
+                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, grad_out, d.S, \
+                       d.H, d.L, d.Lq, d.P, grad_offsets, grad_ref_rows, grad_logits, gd,                 \
+                       with_grid(r.ix, r.blocks, 1, (L * P + GG - 1) / GG), vbytes, stride);
+    BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_BWD2_BOXES);
+#undef BOXATTN_BWD2_BOXES
     return finish();
 }
 
@@ -1744,6 +1793,41 @@ int instattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const i
     return launch_bwd_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx,
                                    valid_ratios, logits, as_f16(grad_out), as_f16(grad_mask), B, S, H, C, L, Lq, k,
                                    grad_offsets, grad_ref_rows, grad_logits, ST_);
+}
+
+int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P)
+{
+    return boxattn_fwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P);   // box_boxes_route: one eligibility
+}
+int boxattn_bwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                          int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
+                          const float *kernel_idx, const float *valid_ratios, const float *logits,
+                          const float *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
+                          float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
+{
+    return launch_bwd_box_boxes<float>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
+                                       kernel_idx, valid_ratios, logits, grad_out, B, S, H, C, L, Lq, P,
+                                       grad_offsets, grad_ref_rows, grad_logits, ST_);
+}
+int boxattn_bwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                           int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
+                           const float *kernel_idx, const float *valid_ratios, const float *logits,
+                           const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
+                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
+{
+    return launch_bwd_box_boxes<bf16_t>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
+                                        kernel_idx, valid_ratios, logits, grad_out, B, S, H, C, L, Lq, P,
+                                        grad_offsets, grad_ref_rows, grad_logits, ST_);
+}
+int boxattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
+                          int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
+                          const float *kernel_idx, const float *valid_ratios, const float *logits,
+                          const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
+                          float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
+{
+    return launch_bwd_box_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, V,
+                                       angle_mode, kernel_idx, valid_ratios, logits, as_f16(grad_out), B, S, H, C,
+                                       L, Lq, P, grad_offsets, grad_ref_rows, grad_logits, ST_);
 }
 
 int boxattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,

@@ -403,3 +403,62 @@ class InstanceAttnBoxesFunction(Function):
             del loc, sw, lw
             grad_value = grad_value.to(ctx.value_dtype)
         return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)
+
+
+class BoxAttnBoxesFunction(Function):
+    """(value (B,S,H,C), spatial_shapes, level_start_index, ref_windows (B,Lq,D) / (B,Lq,H,D), offsets (B,Lq,H,L,V),
+    kernel_indices (P,2), valid_ratios None / B*L*2 values, logits B*Lq*H*L*P values, angle_mode) -> output
+    (B,Lq,H*C): BoxAttention's / Box3dAttention's training step from what the module predicts
+    (``module.fused_boxes_train``).  The forward is ``ops.box_attn_forward_boxes``; nothing per point is saved.  The
+    gradients of ``offsets``, ``ref_windows`` and ``logits`` come from one ``ops.box_attn_backward_boxes`` call;
+    ``grad_value`` comes from the destination-binned backward, whose records need the per-point tensors: they are
+    rebuilt for that call (same device functions: bit for bit the locations the forward sampled) and dropped after it.
+    ``value`` is float32, or bfloat16 / float16: that is then the storage type -- output in it, the upstream gradient
+    cast to it, ``grad_value`` in the caller's type (the conventions of ``InstanceAttnBoxesFunction``)."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios,
+                logits, angle_mode):
+        storage = value.dtype if value.dtype in _H16 else torch.float32
+        ctx.value_dtype, ctx.angle_mode = value.dtype, int(angle_mode)
+        ctx.in_dtypes = (ref_windows.dtype, offsets.dtype, logits.dtype)
+        ctx.logits_shape = tuple(logits.shape)
+        f32 = lambda t: t.detach().float().contiguous()
+        value = value.detach().to(storage).contiguous()
+        ref_windows, offsets, kernel_indices, logits = f32(ref_windows), f32(offsets), f32(kernel_indices), f32(logits)
+        b, lq, h = offsets.shape[:3]
+        logits = logits.view(b, lq, h, -1)
+        if valid_ratios is not None:
+            valid_ratios = f32(valid_ratios)
+        output = ops.box_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets,
+                                            kernel_indices, valid_ratios, logits, ctx.angle_mode)
+        # (the (P, 2) buffer is kept flat: nothing saved here has a point axis)
+        ctx.save_for_backward(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices.view(-1),
+                              valid_ratios, logits)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits = ctx.saved_tensors
+        kernel_indices = kernel_indices.view(-1, 2)
+        need_v, _, _, need_r, need_o, _, _, need_l = ctx.needs_input_grad[:8]
+        B, Lq, H, L = offsets.shape[:4]
+        grad_output = grad_output.to(value.dtype).contiguous()
+        grad_value = grad_ref = grad_offsets = grad_logits = None
+        if need_r or need_o or need_l:
+            grad_offsets, rows, grad_logits = ops.box_attn_backward_boxes(
+                value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits, ctx.angle_mode,
+                grad_output, need_ref_grad=need_r)
+            rdt, odt, ldt = ctx.in_dtypes
+            grad_ref = _ref_grad(ref_windows, rows).to(rdt) if need_r else None
+            grad_offsets = grad_offsets.to(odt) if need_o else None
+            grad_logits = grad_logits.to(ldt).view(ctx.logits_shape) if need_l else None
+        if need_v:
+            # the per-point tensors, for this call only
+            loc = ops.box_grid_forward(ref_windows, offsets, kernel_indices, valid_ratios, ctx.angle_mode)
+            attn = ops.softmax_forward(logits).view(B, Lq, H, L, -1)
+            grad_value = ops.box_attn_backward(value, shapes, lsi, loc, attn, grad_output, B, plan=None, want=1)[0]
+            del loc, attn
+            grad_value = grad_value.to(ctx.value_dtype)
+        return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)

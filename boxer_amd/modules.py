@@ -22,8 +22,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import dense, ops
-from .functions import (BoxAttnBF16Function, BoxAttnF16Function, BoxAttnFunction, BoxGridFunction,
-                        InstanceAttnBF16Function, InstanceAttnBoxesFunction, InstanceAttnF16Function,
+from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnF16Function, BoxAttnFunction,
+                        BoxGridFunction, InstanceAttnBF16Function, InstanceAttnBoxesFunction, InstanceAttnF16Function,
                         InstanceAttnFunction, InstanceWeightsFunction, LogitSoftmaxFunction, ValueMaskCastFunction)
 
 
@@ -66,9 +66,11 @@ class _BoxAttentionBase(nn.Module):
         # ops.instance_attn_forward_boxes, the third element of the return is then the empty tuple; BoxAttention /
         # Box3dAttention: ops.box_attn_forward_boxes, the second element of the return is then the empty tuple
         self.fused_boxes = False
-        # opt-in, InstanceAttention in training (grad mode, `inferencing` false): forward and backward from the boxes
-        # and 2x2 logits (InstanceAttnBoxesFunction) -- no per-point tensor is built in the forward or kept for the
-        # backward; the third element of the return is then the empty tuple.  `fused_boxes` does not imply it.
+        # opt-in, in training (grad mode): forward and backward from the boxes and logits -- no per-point tensor is built
+        # in the forward or kept for the backward.  InstanceAttention (`inferencing` false): InstanceAttnBoxesFunction,
+        # the third element of the return is then the empty tuple; BoxAttention / Box3dAttention:
+        # BoxAttnBoxesFunction, the second element of the return is then the empty tuple.  `fused_boxes` does not
+        # imply it.
         self.fused_boxes_train = False
 
         self.linear_box_weight = nn.Parameter(torch.zeros(num_level * num_head * box_vars, d_model))
@@ -219,11 +221,40 @@ class BoxAttention(_BoxAttentionBase):
             f32(logits).view(b, l1, self.num_head, -1), mode)
         return dense.linear(output, self.out_proj.weight, self.out_proj.bias), ()
 
+    def _boxes_train(self, query, value, v_valid_ratios):
+        """``value`` as the training step from boxes and logits takes it (a differentiable cast), or None: that path
+        is not taken -- ``fused_boxes_train`` off, no grad mode, what ``_boxes_operand`` refuses, or no kernel for the
+        shape one way or the other."""
+        if not self.fused_boxes_train or not torch.is_grad_enabled():
+            return None
+        value = self._boxes_operand(query, value, v_valid_ratios)
+        if value is None:
+            return None
+        n = query.size(1)
+        ok = ops.box_backward_boxes_ok(value, self.num_level, n, self.num_point) and \
+            ops.box_forward_boxes_ok(value, self.num_level, n, self.num_point)
+        return value if ok else None
+
+    def _forward_boxes_train(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows):
+        b, l1 = query.shape[:2]
+        mode = self._angle_mode()
+        logits = dense.linear(query, self.linear_attn_weight, self.linear_attn_bias)
+        # (differentiable casts: the gradients flow on to the projections, the query and the reference windows)
+        output = BoxAttnBoxesFunction.apply(
+            value, v_shape, v_start_index, ref_windows.float(),
+            self._box_offsets(query, ref_windows, 5 if mode == 1 else 4).float(), self.kernel_indices,
+            None if v_valid_ratios is None else v_valid_ratios.view(b, self.num_level, 2),
+            logits.float().view(b, l1, self.num_head, -1), mode)
+        return dense.linear(output, self.out_proj.weight, self.out_proj.bias), ()
+
     def forward(self, query, value, v_shape, v_mask, v_start_index, v_valid_ratios, ref_windows):
         value = self._project_value(value, v_mask)
         boxes_value = self._boxes_value(query, value, v_valid_ratios)
         if boxes_value is not None:
             return self._forward_boxes(query, boxes_value, v_shape, v_start_index, v_valid_ratios, ref_windows)
+        boxes_value = self._boxes_train(query, value, v_valid_ratios)
+        if boxes_value is not None:
+            return self._forward_boxes_train(query, boxes_value, v_shape, v_start_index, v_valid_ratios, ref_windows)
         attn_weights = self._softmax_weights(query)
         sampled_grid = self._where_to_attend(query, v_valid_ratios, ref_windows)
         output = self._box_function().apply(value, v_shape, v_start_index, sampled_grid,

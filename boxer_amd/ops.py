@@ -1009,3 +1009,60 @@ def box_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows
                ref_windows, D, per_head, offsets, V, mode, kernel_indices,
                valid_ratios if valid_ratios is not None else 0, logits, B, S, H, C, L, Lq, P, out)
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# box attention's training step from the same operands (opt-in; include/boxattn.h, boxattn_bwd_boxes_*)
+# ---------------------------------------------------------------------------------------
+def box_backward_boxes_ok(value, num_level, num_query, num_point):
+    """Whether ``box_attn_backward_boxes`` has its kernel under the current switches: ``boxattn_bwd_boxes_ok`` (the
+    eligibility of ``box_forward_boxes_ok``) with the dimensions, element size and alignment of ``value`` (B, S, H,
+    C).  The upstream gradient is taken as aligned like ``value``; ``box_attn_backward_boxes`` asks again with its
+    address.  Pure host code."""
+    if not isinstance(value, torch.Tensor) or value.dim() != 4 or value.dtype not in (torch.float32,) + _H16:
+        return False
+    B, S, H, C = value.shape
+    return _lib.box_bwd_boxes_ok(value.element_size(), _align_of(value), (B, S, H, C, num_level, num_query, num_point))
+
+
+def box_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                            valid_ratios, logits, angle_mode, grad_output, need_ref_grad=False):
+    """The box and logit gradients of BoxAttention's / Box3dAttention's training step in one launch, from the operands
+    of ``box_attn_forward_boxes`` and the upstream gradient ``grad_output`` (B,Lq,H*C) in the type of ``value`` ->
+    ``(grad_offsets (B,Lq,H,L,V), grad_ref_rows (B,Lq,H,L,5) or None, grad_logits (B,Lq,H,L*P))``, float32: what
+    ``box_attn_backward(want=2)`` -> ``box_grid_backward`` + ``softmax_backward`` return, without the sampling grid, the
+    weights and their per-point gradients in between.  ``grad_value`` is not computed.  Raises ValueError, before any
+    device call, for arguments that do not fit and where ``boxattn_bwd_boxes_ok`` says no at the alignment of
+    ``value`` and ``grad_output``: there is no other kernel behind it."""
+    what = "box_attn_backward_boxes"
+    try:
+        (B, Lq, H, L, P), (D, per_head, V, mode) = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios,
+                                                              angle_mode)
+        for t, name in ((value, "value"), (spatial_shapes, "spatial_shapes"),
+                        (level_start_index, "level_start_index"), (logits, "logits"), (grad_output, "grad_output")):
+            _check(t, name)
+    except RuntimeError as e:
+        raise ValueError("%s: %s" % (what, e)) from None
+    if value.dtype not in (torch.float32,) + _H16:
+        raise ValueError("%s: float32, bfloat16 or float16 value expected, got %s" % (what, value.dtype))
+    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
+        raise ValueError("%s: spatial_shapes / level_start_index must be int64" % what)
+    if logits.dtype != torch.float32 or logits.numel() != B * Lq * H * L * P:
+        raise ValueError("%s: expected B*Lq*H*L*P float32 logits matching offsets" % what)
+    if value.dim() != 4 or value.size(0) != B or value.size(2) != H or spatial_shapes.size(0) != L or \
+            level_start_index.numel() != L:
+        raise ValueError("%s: offsets / spatial_shapes do not match value (B,S,H,C)" % what)
+    S, C = value.size(1), value.size(3)
+    if grad_output.dtype != value.dtype or grad_output.numel() != B * Lq * H * C:
+        raise ValueError("%s: grad_output: %d elements of type %s expected" % (what, B * Lq * H * C, value.dtype))
+    if not _lib.box_bwd_boxes_ok(value.element_size(), _align_of(value, grad_output), (B, S, H, C, L, Lq, P)):
+        raise ValueError("%s: no kernel for value %s, %d levels, %d queries, %d points a level at the alignment of "
+                         "value and grad_output (box_backward_boxes_ok)" % (what, tuple(value.shape), L, Lq, P))
+    grad_offsets = torch.empty((B, Lq, H, L, V), dtype=torch.float32, device=value.device)
+    grad_rows = torch.empty((B, Lq, H, L, 5), dtype=torch.float32, device=value.device) if need_ref_grad else None
+    grad_logits = torch.empty((B, Lq, H, L * P), dtype=torch.float32, device=value.device)
+    _grid_call("boxattn_bwd_boxes_" + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index,
+               ref_windows, D, per_head, offsets, V, mode, kernel_indices,
+               valid_ratios if valid_ratios is not None else 0, logits, grad_output, B, S, H, C, L, Lq, P,
+               grad_offsets, grad_rows if need_ref_grad else 0, grad_logits)
+    return grad_offsets, grad_rows, grad_logits

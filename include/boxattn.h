@@ -602,6 +602,46 @@ int instattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const i
 int instattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k);
 
 /*
+ * Box attention's TRAINING step from the operands of boxattn_fwd_boxes_*: the gradients BoxAttention / Box3dAttention
+ * need per (batch, query, head) -- of the box offsets, of the reference window (rows, summed by the caller as after
+ * boxattn_grid_bwd_f32) and of the L*P logits -- in one launch: what boxattn_bwd_part_* (want = BOXATTN_WANT_POINTS),
+ * boxattn_grid_bwd_f32 (all three angle modes) and boxattn_softmax_bwd_f32 compute in three, without reading a sampling
+ * grid or a weights tensor and without writing grad_loc / grad_attn in between.  Locations and weights
+ * are recomputed by the device functions of the forward above, in its operation order; everything is float32 except
+ * value and the upstream gradient, which are in the storage type.  grad_value is NOT computed here.
+ *   grad_out  (B,Lq,H,C)
+ *   grad_offsets (B,Lq,H,L,V), grad_ref_rows (B,Lq,H,L,5) or NULL, grad_logits (B,Lq,H,L*P): float32, every element
+ *   written; element 4 of a grad_ref_rows row as boxattn_grid_bwd_f32 writes it in each angle mode.
+ * One row-gather kernel and no other behind these entries: dimensions for which boxattn_bwd_boxes_ok answers 0 -- with
+ * `aligned` what value and grad_out are aligned to --, ref_dim < 4 (< 5 with an angle), V other than 4 (5 for
+ * angle_mode 1), and a NULL among value, shapes, lsi, ref, offsets, kernel_idx, logits, grad_out, grad_offsets,
+ * grad_logits are hipErrorInvalidValue; nothing is launched then.  No queries: nothing is written; no pixels: the
+ * outputs are zero-filled.  No atomics and a fixed summation order (bitwise reproducible), no host reads, no
+ * allocation: capturable, on the one stream.  Profile slot 1.
+ */
+int boxattn_bwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                          int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                          const float *logits, const float *grad_out,
+                          int B, int S, int H, int C, int L, int Lq, int P,
+                          float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+int boxattn_bwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                           int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                           const float *logits, const uint16_t *grad_out,
+                           int B, int S, int H, int C, int L, int Lq, int P,
+                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+int boxattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                          int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                          const float *logits, const uint16_t *grad_out,
+                          int B, int S, int H, int C, int L, int Lq, int P,
+                          float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+/* 1 where the entry points above have their kernel: exactly where boxattn_fwd_boxes_ok answers 1 (the same host
+ * function), `aligned` now speaking of value and grad_out.  Pure host code: no device call. */
+int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P);
+
+/*
  * Tuning options for A/B runs (process-wide, relaxed atomics; 0 = default).  Returns the
  * previous value, -1 for an unknown key.  (The key numbers of earlier ABI versions are kept; the keys
  * of kernels that were removed are gone.)

@@ -1,0 +1,145 @@
+"""CPU: box attention's training step from boxes and L*P logits at the C ABI -- boxattn_bwd_boxes_{f32, bf16, f16} and
+the eligibility query boxattn_bwd_boxes_ok are declared in include/boxattn.h, exported and bound, the query answers
+exactly what boxattn_fwd_boxes_ok answers (one host function), the entry points refuse what the query refuses, a
+reference window or offsets that do not fit the angle mode, and NULL required pointers, with hipErrorInvalidValue
+before any device call, and ``BoxAttnBoxesFunction`` is part of the package.  No compute calls: there is no GPU here."""
+import ctypes
+import itertools
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "boxattn.h")
+ENTRY_POINTS = ["boxattn_bwd_boxes_" + suf for suf in ("f32", "bf16", "f16")]
+INVALID_VALUE = 1                        # hipErrorInvalidValue
+# (levels, B, Lq, H): a decoder-like and an encoder-like (one query a pixel) geometry
+GEOMETRIES = [([(9, 11), (4, 5), (3, 3), (2, 2)], 2, 5, 8), ([(6, 5)], 1, 30, 2)]
+
+
+def declarations():
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return {m.group(1): " ".join(m.group(2).split())
+            for m in re.finditer(r"\b((?:boxattn|instattn)_\w+)\s*\(([^;{]*?)\)\s*;", text, re.S)}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from boxer_amd import _lib
+    _lib.build()
+    _lib.set_variant(0)
+    yield _lib
+    _lib.set_variant(0)
+
+
+def test_header_declares_the_four_names_and_the_bindings_know_them(lib):
+    decl = declarations()
+    for name in ENTRY_POINTS + ["boxattn_bwd_boxes_ok"]:
+        assert name in decl, "missing declaration: " + name
+        assert name in lib.EXPORTS, "not bound: " + name
+        assert hasattr(ctypes.CDLL(lib.LIB_PATH), name), "missing export: " + name
+    assert decl["boxattn_bwd_boxes_ok"] == "int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P"
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    for name in ENTRY_POINTS:
+        st = "float" if name.endswith("f32") else "uint16_t"
+        assert decl[name] == (
+            "const %s *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim, "
+            "int ref_per_head, const float *offsets, int V, int angle_mode, const float *kernel_idx, "
+            "const float *valid_ratios, const float *logits, const %s *grad_out, int B, int S, int H, int C, int L, "
+            "int Lq, int P, float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream" % (st, st)), name
+        fn = getattr(lib.load(), name)
+        assert list(fn.argtypes) == [vp] * 4 + [i, i] + [vp] + [i, i] + [vp] * 4 + [i] * 7 + [vp] * 4
+        assert fn.restype is ctypes.c_int
+    ok = lib.load().boxattn_bwd_boxes_ok
+    assert list(ok.argtypes) == [i] * 9 and ok.restype is ctypes.c_int
+    assert re.search(r"#define BOXATTN_ABI_VERSION 8\b", open(HEADER).read())        # nothing existing changed
+    assert lib.load().boxattn_abi_version() == 8 and lib.ABI_VERSION == 8
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+def test_query_answers_what_the_forwards_query_answers(lib, variant):
+    """Element sizes 2 / 4 / 8, alignments 16 / 8 / 4 (and 0: none), L = 17 and L P = 65 among the dimensions, under
+    the default switches and boxattn_set_variant(1)."""
+    lib.set_variant(variant)
+    try:
+        seen = {True: 0, False: 0}
+        for (levels, B, Lq, H), C, P, L, elem, aligned in itertools.product(
+                GEOMETRIES, (8, 16, 32, 64), (1, 4, 9, 16, 64, 65), (1, 4, 16, 17), (2, 4, 8), (16, 8, 4, 0)):
+            S = sum(h * w for h, w in levels)
+            dims = (B, S, H, C, L, Lq, P)
+            want = lib.box_fwd_boxes_ok(elem, aligned, dims)
+            assert lib.box_bwd_boxes_ok(elem, aligned, dims) == want, (dims, elem, aligned)
+            if L == 17 or L * P > 64 or elem == 8:
+                assert not want, (dims, elem, aligned)
+            seen[want] += 1
+        if variant == 0:
+            assert seen[True] >= 20 and seen[False] >= 20, seen      # the grid holds both answers
+        else:
+            assert seen[True] == 0, seen                             # variant 1: the generic kernels only
+    finally:
+        lib.set_variant(0)
+
+
+def call(lib, name, ptrs, dims, ref_dim=4, V=4, angle_mode=0):
+    """An entry call with fake (never dereferenced) pointers; ptrs: value, shapes, lsi, ref, offsets, kernel_idx,
+    valid_ratios, logits, grad_out, grad_offsets, grad_ref_rows, grad_logits."""
+    v, sh, ls, ref, off, kid, vr, lg, go, goff, grow, glog = ptrs
+    return getattr(lib.load(), name)(v, sh, ls, ref, ref_dim, 0, off, V, angle_mode, kid, vr, lg, go, *dims, goff,
+                                     grow, glog, None)
+
+
+@pytest.mark.parametrize("name", ENTRY_POINTS)
+def test_entry_points_refuse_before_any_device_call(lib, name):
+    """hipErrorInvalidValue for dimensions the query refuses, for a reference window or offsets that do not fit the
+    angle mode and for NULL required pointers; a call without queries returns 0 having done nothing.  (An accepted
+    call would launch: there is none here.)"""
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+    p -= p % 16
+    p += 16
+    all_ptrs = [p] * 12
+    S = 9 * 11 + 4 * 5
+    good = (2, S, 8, 32, 2, 4, 4)
+    elem = 4 if name.endswith("f32") else 2
+    assert lib.box_bwd_boxes_ok(elem, 16, good)
+    refused = [(2, S, 8, 8, 2, 4, 4), (2, S, 8, 32, 1, 4, 65), (2, S, 8, 32, 17, 4, 1), (2, S, 8, 32, 4, 4, 17),
+               (2, S, 8, 32, 2, 4, 0), (2, S, 0, 32, 2, 4, 4), (-1, S, 8, 32, 2, 4, 4)]
+    for dims in refused:
+        assert not lib.box_bwd_boxes_ok(elem, 16, dims), dims
+        assert call(lib, name, all_ptrs, dims) == INVALID_VALUE, dims
+    assert call(lib, name, all_ptrs, good, ref_dim=3) == INVALID_VALUE
+    assert call(lib, name, all_ptrs, good, ref_dim=4, angle_mode=2) == INVALID_VALUE      # an angle needs ref_dim 5
+    assert call(lib, name, all_ptrs, good, ref_dim=5, V=4, angle_mode=1) == INVALID_VALUE
+    assert call(lib, name, all_ptrs, good, ref_dim=5, V=5, angle_mode=0) == INVALID_VALUE
+    assert call(lib, name, all_ptrs, good, ref_dim=5, V=5, angle_mode=3) == INVALID_VALUE
+    for missing in (0, 1, 2, 3, 4, 5, 7, 8, 9, 11):                        # every required pointer (6, 10: optional)
+        ptrs = list(all_ptrs)
+        ptrs[missing] = None
+        assert call(lib, name, ptrs, good) == INVALID_VALUE, missing
+    lib.set_variant(1)
+    try:
+        assert not lib.box_bwd_boxes_ok(elem, 16, good)
+        assert call(lib, name, all_ptrs, good) == INVALID_VALUE             # no generic fallback behind this entry
+    finally:
+        lib.set_variant(0)
+    assert call(lib, name, [None] * 12, (2, S, 8, 32, 2, 0, 4)) == 0        # no queries: nothing to do
+
+
+def test_python_surface():
+    import inspect
+    import boxer_amd
+    from boxer_amd import BoxAttnBoxesFunction, ops
+    from boxer_amd.modules import Box3dAttention, BoxAttention
+    assert "BoxAttnBoxesFunction" in boxer_amd.__all__ and issubclass(BoxAttnBoxesFunction, boxer_amd.functions.Function)
+    p = inspect.signature(ops.box_attn_backward_boxes).parameters
+    assert list(p) == ["value", "spatial_shapes", "level_start_index", "ref_windows", "offsets", "kernel_indices",
+                       "valid_ratios", "logits", "angle_mode", "grad_output", "need_ref_grad"]
+    assert p["need_ref_grad"].default is False
+    assert list(inspect.signature(ops.box_backward_boxes_ok).parameters) == ["value", "num_level", "num_query",
+                                                                             "num_point"]
+    assert list(inspect.signature(BoxAttnBoxesFunction.forward).parameters)[1:] == [
+        "value", "spatial_shapes", "level_start_index", "ref_windows", "offsets", "kernel_indices", "valid_ratios",
+        "logits", "angle_mode"]
+    for m in (BoxAttention(32, 1, 2), Box3dAttention(32, 1, 2)):
+        assert m.fused_boxes_train is False and m.fused_boxes is False
