@@ -88,22 +88,22 @@ _GRID_SIGNATURES = {
     "boxattn_grid_fwd_f32": [_vp, _i, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp],
     "boxattn_grid_bwd_f32": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp, _vp],
 }
-# value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios | NULL, logits,
-# B, S, H, C, L, Lq, k, out, mask_out | NULL, stream
-_BOXES_SIGNATURES = {"instattn_fwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_vp] * 4 + [_i] * 7 + [_vp] * 3
-                     for suf in ("f32", "bf16", "f16")}
-# value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios | NULL, logits, grad_out,
-# grad_mask | NULL, B, S, H, C, L, Lq, k, grad_offsets, grad_ref_rows | NULL, grad_logits, stream
-_BOXES_BWD_SIGNATURES = {"instattn_bwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_vp] * 6 + [_i] * 7 + [_vp] * 4
-                         for suf in ("f32", "bf16", "f16")}
-# value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode, kernel_idx, valid_ratios | NULL, logits,
-# B, S, H, C, L, Lq, P, out, stream
-_BOX_BOXES_SIGNATURES = {"boxattn_fwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_vp] + [_i, _i] + [_vp] * 3 + [_i] * 7 +
-                         [_vp] * 2 for suf in ("f32", "bf16", "f16")}
-# value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode, kernel_idx, valid_ratios | NULL, logits,
-# grad_out, B, S, H, C, L, Lq, P, grad_offsets, grad_ref_rows | NULL, grad_logits, stream
-_BOX_BOXES_BWD_SIGNATURES = {"boxattn_bwd_boxes_" + suf: [_vp] * 4 + [_i, _i] + [_vp] + [_i, _i] + [_vp] * 4 +
-                             [_i] * 7 + [_vp] * 4 for suf in ("f32", "bf16", "f16")}
+# The calls from boxes and logits: value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, [V, angle_mode: the box
+# flavour,] kernel_idx, valid_ratios | NULL, logits, <upstream gradients>, B, S, H, C, L, Lq, k | P, <outputs>, stream
+def _boxes_signatures(stem, box, upstream, outputs):
+    args = ([_vp] * 4 + [_i, _i] + [_vp] + ([_i, _i] if box else []) + [_vp] * 3 + [_vp] * upstream + _DIMS +
+            [_vp] * outputs + [_vp])
+    return {stem + suf: args for suf in ("f32", "bf16", "f16")}
+
+
+# out, mask_out | NULL
+_BOXES_SIGNATURES = _boxes_signatures("instattn_fwd_boxes_", False, 0, 2)
+# grad_out, grad_mask | NULL; grad_offsets, grad_ref_rows | NULL, grad_logits
+_BOXES_BWD_SIGNATURES = _boxes_signatures("instattn_bwd_boxes_", False, 2, 3)
+# out
+_BOX_BOXES_SIGNATURES = _boxes_signatures("boxattn_fwd_boxes_", True, 0, 1)
+# grad_out; grad_offsets, grad_ref_rows | NULL, grad_logits
+_BOX_BOXES_BWD_SIGNATURES = _boxes_signatures("boxattn_bwd_boxes_", True, 1, 3)
 EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "boxattn_set_option",
            "boxattn_options_epoch", "boxattn_fwd_route", "boxattn_bwd_accumulate_kind", "boxattn_bwd_record_kind",
            "boxattn_set_debug_buffer",
@@ -258,14 +258,9 @@ def load():
                        list(_BOX_BOXES_SIGNATURES.items()) + list(_BOX_BOXES_BWD_SIGNATURES.items())):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = _i
-    lib.instattn_fwd_boxes_ok.argtypes = [_i] * 9
-    lib.instattn_fwd_boxes_ok.restype = _i
-    lib.instattn_bwd_boxes_ok.argtypes = [_i] * 9
-    lib.instattn_bwd_boxes_ok.restype = _i
-    lib.boxattn_fwd_boxes_ok.argtypes = [_i] * 9
-    lib.boxattn_fwd_boxes_ok.restype = _i
-    lib.boxattn_bwd_boxes_ok.argtypes = [_i] * 9
-    lib.boxattn_bwd_boxes_ok.restype = _i
+    for name in ("instattn_fwd_boxes_ok", "instattn_bwd_boxes_ok", "boxattn_fwd_boxes_ok", "boxattn_bwd_boxes_ok"):
+        getattr(lib, name).argtypes = [_i] * 9
+        getattr(lib, name).restype = _i
     lib.boxattn_state_bytes.argtypes = [_i] * 7 + [_vp, _vp]
     lib.boxattn_state_bytes.restype = ctypes.c_size_t
     for name in ("boxattn_bwd_workspace_bytes", "boxattn_plan_bytes"):
@@ -308,28 +303,33 @@ def fwd_route(elem_bytes, instance, aligned, dims, shapes_host=None, lsi_host=No
                                     ptr(shapes_host), ptr(lsi_host))
 
 
+def _boxes_ok(name, elem_bytes, aligned, dims):
+    """The eligibility queries of the calls from boxes: ``dims`` = (B, S, H, C, L, Lq, k or P)."""
+    return bool(getattr(load(), name)(int(elem_bytes), int(aligned), *[int(v) for v in dims]))
+
+
 def fwd_boxes_ok(elem_bytes, aligned, dims, k):
     """instattn_fwd_boxes_ok(): whether the instattn_fwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
     C, L, Lq) and ``k`` x ``k`` points a level under the current switches.  Pure host code (no GPU needed)."""
-    return bool(load().instattn_fwd_boxes_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims], int(k)))
+    return _boxes_ok("instattn_fwd_boxes_ok", elem_bytes, aligned, tuple(dims) + (k,))
 
 
 def box_fwd_boxes_ok(elem_bytes, aligned, dims):
     """boxattn_fwd_boxes_ok(): whether the boxattn_fwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
     C, L, Lq, P) under the current switches.  Pure host code (no GPU needed)."""
-    return bool(load().boxattn_fwd_boxes_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims]))
+    return _boxes_ok("boxattn_fwd_boxes_ok", elem_bytes, aligned, dims)
 
 
 def box_bwd_boxes_ok(elem_bytes, aligned, dims):
     """boxattn_bwd_boxes_ok(): whether the boxattn_bwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
     C, L, Lq, P) under the current switches.  Pure host code (no GPU needed)."""
-    return bool(load().boxattn_bwd_boxes_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims]))
+    return _boxes_ok("boxattn_bwd_boxes_ok", elem_bytes, aligned, dims)
 
 
 def bwd_boxes_ok(elem_bytes, aligned, dims, k):
     """instattn_bwd_boxes_ok(): whether the instattn_bwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
     C, L, Lq) and ``k`` x ``k`` points a level under the current switches.  Pure host code (no GPU needed)."""
-    return bool(load().instattn_bwd_boxes_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims], int(k)))
+    return _boxes_ok("instattn_bwd_boxes_ok", elem_bytes, aligned, tuple(dims) + (k,))
 
 
 # boxattn_bwd_accumulate_kind: the grad_value accumulate kernels of the binned backward (BOXATTN_ACC_*)

@@ -490,11 +490,23 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
     return finish();
 }
 
-// ---- instance attention at inference from boxes and 2x2 logits (boxattn_boxes.h) ----------------------------
-// Whether fwd_wide_boxes_kernel runs these dimensions (P = k * k points a level): where the instance flavour of
+// ---- attention from boxes and logits: the four routes and the host path they share --------------------------
+// instance flavour (k x k points a level, 2x2 logits): fwd_wide_boxes_kernel (boxattn_boxes.h) and
+// pointgrad_boxes_kernel (boxattn_boxes_bwd.h); box flavour (P points a level, L P logits): fwd2_boxes_kernel
+// (boxattn_gather2_boxes.h) and bwd2_boxes_kernel (boxattn_gather2_boxes_bwd.h).  No other kernel behind these entries.
+
+// What the eligibility queries know of the tensors' addresses.  aligned: 0 nothing beyond the elements' own alignment,
+// 8 every tensor to 8 bytes, else to 16 bytes (staged: left false, boxattn_fwd_route sets it)
+inline FwdAlign align_from_bytes(int elem_bytes, int aligned)
+{
+    const int bytes = aligned == 0 ? elem_bytes : aligned == 8 ? 8 : 16;
+    return FwdAlign{bytes >= 4 * elem_bytes && bytes >= 8, bytes >= 16, false};
+}
+
+// Whether the instance kernels run these dimensions (P = k * k points a level): where the instance flavour of
 // fwd_route takes the wave-per-pair family, for the k and L of the weight kernels (k even, 2 ... 32; L <= 16: the
-// 4 L cells of a pair fit the lanes of a wave).  The ONE function behind instattn_fwd_boxes_ok and the entry points;
-// r: the launch geometry.  Option key 22 is not read (the instance flavour does not read it).
+// 4 L cells of a pair fit the lanes of a wave).  The ONE function behind instattn_{fwd,bwd}_boxes_ok and the entry
+// points; r: the launch geometry.  Option key 22 is not read (the instance flavour does not read it).
 inline bool boxes_route(int elem_bytes, const Dims &d, int k, const FwdAlign &al, FwdRoute &r)
 {
     if ((elem_bytes != 2 && elem_bytes != 4) || !d.valid()) return false;
@@ -503,60 +515,9 @@ inline bool boxes_route(int elem_bytes, const Dims &d, int k, const FwdAlign &al
     return fwd_route(elem_bytes, true, d, al, nullptr, nullptr, false, r, dp) == kFwdWide;
 }
 
-template <typename ST>
-int launch_fwd_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
-                     int ref_per_head, const float *offsets, const float *kernel_idx, const float *valid_ratios,
-                     const float *logits, int B, int S, int H, int C, int L, int Lq, int k, ST *out, ST *mask,
-                     hipStream_t st)
-{
-    if (k < 2 || k > 32 || k % 2 != 0 || ref_dim < 4) return (int)hipErrorInvalidValue;
-    const Dims d{B, S, H, C, L, Lq, k * k};
-    if (!d.valid() || L > 16) return (int)hipErrorInvalidValue;
-    if (d.empty()) return 0;                                   // no queries: nothing to write
-    if (!shapes || !lsi || !ref || !offsets || !kernel_idx || !logits || !out) return (int)hipErrorInvalidValue;
-    const size_t n_qh = d.n_qh();
-    if (d.n_value() == 0) {                                    // no pixels: every sample is 0
-        hipError_t e = zero_async(out, n_qh * d.C * sizeof(ST), st);
-        if (e == hipSuccess && mask) e = zero_async(mask, n_qh * d.C * d.P * sizeof(ST), st);
-        return (int)e;
-    }
-    if (!value) return (int)hipErrorInvalidValue;
-    const size_t va = 4 * sizeof(ST);
-    FwdAlign al;
-    al.fast = aligned(value, va) && aligned(out, va) && aligned(mask, va);
-    al.rows16 = aligned(value, 16) && aligned(out, 16) && aligned(mask, 16);
-    al.staged = false;
-    FwdRoute r;
-    if (!boxes_route((int)sizeof(ST), d, k, al, r)) return (int)hipErrorInvalidValue;   // no other kernel behind this entry
-    const GridDims gd{Lq, H, L, d.P, 4, ref_dim, ref_per_head ? 1 : 0, 0};
-    const float m = (float)(k / 2);
-    const BoxesDims bd{k, k / 2, 1.f / (float)k, 1.f / (m * m)};
-    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST)), ws = r.ws;
-    const GatherIdx ix = with_grid(r.ix, r.wblocks, 1, 1);
-    const GatherCfg cfg = r.cfg;
-    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
-    if (mask) {
-#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                  \
-    hipLaunchKernelGGL((fwd_wide_boxes_kernel<ST, GG, VV, true>), dim3(r.wblocks), dim3(256), 0, st,  \
-                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, d.S, d.H,  \
-                       d.L, d.Lq, d.P, out, mask, gd, bd, ix, vbytes, ws);
-        BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
-#undef BOXATTN_LAUNCH_BOXES
-    } else {
-#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                  \
-    hipLaunchKernelGGL((fwd_wide_boxes_kernel<ST, GG, VV, false>), dim3(r.wblocks), dim3(256), 0, st, \
-                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, d.S, d.H,  \
-                       d.L, d.Lq, d.P, out, NoArg{}, gd, bd, ix, vbytes, ws);
-        BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
-#undef BOXATTN_LAUNCH_BOXES
-    }
-    return finish();
-}
-
-// ---- box attention at inference from boxes and L P logits (boxattn_gather2_boxes.h) -------------------------
-// Whether fwd2_boxes_kernel runs these dimensions: where the box flavour of fwd_route, without host tables, takes the
+// Whether the box kernels run these dimensions: where the box flavour of fwd_route, without host tables, takes the
 // row gather, for the L of the level table and the L P of the softmax kernels (the pair's logits fit 64 / G rounds of
-// a lane group).  The ONE function behind boxattn_fwd_boxes_ok and the entry points; r: the launch geometry.
+// a lane group).  The ONE function behind boxattn_{fwd,bwd}_boxes_ok and the entry points; r: the launch geometry.
 inline bool box_boxes_route(int elem_bytes, const Dims &d, const FwdAlign &al, FwdRoute &r)
 {
     if ((elem_bytes != 2 && elem_bytes != 4) || !d.valid()) return false;
@@ -565,146 +526,177 @@ inline bool box_boxes_route(int elem_bytes, const Dims &d, const FwdAlign &al, F
     return fwd_route(elem_bytes, false, d, al, nullptr, nullptr, false, r, dp) == kFwdGather;
 }
 
-template <typename ST>
-int launch_fwd_box_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
-                         int ref_per_head, const float *offsets, int V, int angle_mode, const float *kernel_idx,
-                         const float *valid_ratios, const float *logits, int B, int S, int H, int C, int L, int Lq,
-                         int P, ST *out, hipStream_t st)
-{
-    const Dims d{B, S, H, C, L, Lq, P};
-    if (!d.valid() || L > 16 || (long long)L * P > kBoxesMaxLP) return (int)hipErrorInvalidValue;
-    if (angle_mode < 0 || angle_mode > 2 || V != (angle_mode == 1 ? 5 : 4) || ref_dim < (angle_mode ? 5 : 4))
-        return (int)hipErrorInvalidValue;
-    if (d.empty()) return 0;                                   // no queries: nothing to write
-    if (!shapes || !lsi || !ref || !offsets || !kernel_idx || !logits || !out) return (int)hipErrorInvalidValue;
-    if (d.n_value() == 0)                                      // no pixels: every sample is 0
-        return (int)zero_async(out, d.n_qh() * d.C * sizeof(ST), st);
-    if (!value) return (int)hipErrorInvalidValue;
-    const size_t va = 4 * sizeof(ST);
-    FwdAlign al;
-    al.fast = aligned(value, va) && aligned(out, va);
-    al.rows16 = aligned(value, 16) && aligned(out, 16);
-    al.staged = false;
+// A from-boxes call's operands, filled by the extern "C" wrappers.  Instance flavour: k x k points a level (d.P is
+// not read: boxes_prepare sets it), V 4, angle_mode 0; box flavour: d.P points a level (k is not read).
+template <typename ST> struct BoxesIn {
+    const ST *value;
+    const int64_t *shapes, *lsi;
+    const float *ref;
+    int ref_dim, ref_per_head;
+    const float *offsets;
+    int V, angle_mode;
+    const float *kernel_idx, *valid_ratios, *logits;
+    Dims d;
+    int k;
+    hipStream_t st;
+};
+// An output of a from-boxes call (p NULL: an optional one that is absent) and its bytes a (query, head) pair
+struct BoxesOutput { void *p; size_t pair_bytes; };
+// What boxes_prepare hands a launcher: the dimensions (with P), the route's launch geometry and the kernels' arguments
+struct BoxesLaunch {
+    Dims d;
     FwdRoute r;
-    if (!box_boxes_route((int)sizeof(ST), d, al, r)) return (int)hipErrorInvalidValue;   // no other kernel behind this entry
-    const GridDims gd{Lq, H, L, P, V, ref_dim, ref_per_head ? 1 : 0, angle_mode};
-    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST));
-    const unsigned stride = fwd2_boxes_pair_stride(L, L * P);
-    const GatherCfg cfg = r.cfg;
-    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
-#define BOXATTN_FWD2_BOXES(GG, VV)                                                                        \
-    hipLaunchKernelGGL((fwd2_boxes_kernel<ST, GG, GatherUnroll<ST, GG, VV>::value, VV>), dim3(r.blocks),  \
-                       dim3(256), (size_t)kGatherWaves * (kWave / GG) * stride * sizeof(u32x4_t), st,     \
-                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, d.S, d.H, d.L, \
-                       d.Lq, d.P, out, gd, with_grid(r.ix, r.blocks, 1, (L * P + GG - 1) / GG), vbytes,   \
-                       stride);
-    BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_FWD2_BOXES);
+    GridDims gd;
+    BoxesDims bd;           // instance flavour
+    unsigned vbytes;
+};
+
+// Everything a from-boxes launcher does before its launch; false: the call ends here with rc.  The order shows in
+// the return codes: the dimensions and the flavour's limit, no queries -> 0 before any pointer is looked at, the
+// required pointers (have_required: those of the launcher's own), no pixels -> the outputs zero-filled, value, the
+// route (rows / rows_opt: the row-sized tensors next to value, out / mask_out or grad_out / grad_mask; NULL: aligned).
+template <typename ST, bool INST>
+bool boxes_prepare(const BoxesIn<ST> &in, const ST *rows, const ST *rows_opt, bool have_required,
+                   std::initializer_list<BoxesOutput> outputs, BoxesLaunch &l, int &rc)
+{
+    rc = (int)hipErrorInvalidValue;
+    Dims &d = l.d = in.d;
+    if constexpr (INST) {
+        if (in.k < 2 || in.k > 32 || in.k % 2 != 0 || in.ref_dim < 4) return false;
+        d.P = in.k * in.k;
+    }
+    if (!d.valid() || d.L > 16) return false;
+    if constexpr (!INST) {
+        if ((long long)d.L * d.P > kBoxesMaxLP) return false;
+        if (in.angle_mode < 0 || in.angle_mode > 2 || in.V != (in.angle_mode == 1 ? 5 : 4) ||
+            in.ref_dim < (in.angle_mode ? 5 : 4))
+            return false;
+    }
+    if (d.empty()) {                                           // no queries: nothing to write
+        rc = 0;
+        return false;
+    }
+    if (!in.shapes || !in.lsi || !in.ref || !in.offsets || !in.kernel_idx || !in.logits || !have_required) return false;
+    if (d.n_value() == 0) {                                    // no pixels: every sample and every gradient is 0
+        hipError_t e = hipSuccess;
+        for (const BoxesOutput &o : outputs)
+            if (e == hipSuccess && o.p) e = zero_async(o.p, d.n_qh() * o.pair_bytes, in.st);
+        rc = (int)e;
+        return false;
+    }
+    if (!in.value) return false;
+    const size_t va = 4 * sizeof(ST);
+    const FwdAlign al{aligned(in.value, va) && aligned(rows, va) && aligned(rows_opt, va),
+                      aligned(in.value, 16) && aligned(rows, 16) && aligned(rows_opt, 16), false};
+    if (!(INST ? boxes_route((int)sizeof(ST), d, in.k, al, l.r) : box_boxes_route((int)sizeof(ST), d, al, l.r)))
+        return false;
+    l.gd = GridDims{d.Lq, d.H, d.L, d.P, in.V, in.ref_dim, in.ref_per_head ? 1 : 0, in.angle_mode};
+    if constexpr (INST) {
+        const float m = (float)(in.k / 2);
+        l.bd = BoxesDims{in.k, in.k / 2, 1.f / (float)in.k, 1.f / (m * m)};
+    }
+    l.vbytes = (unsigned)(d.n_value() * sizeof(ST));
+    return true;
+}
+
+// The gradients of a from-boxes backward: per (query, head, level) row V offsets, 5 window terms (optional) and the
+// row's logits (instance flavour: 2x2; box flavour: P)
+struct BoxesGrads { float *offsets, *ref_rows, *logits; };
+template <typename ST, bool INST>
+bool boxes_prepare_bwd(const BoxesIn<ST> &in, const ST *grad_out, const ST *grad_mask, const BoxesGrads &g,
+                       BoxesLaunch &l, int &rc)
+{
+    const size_t row = (size_t)in.d.L * sizeof(float);
+    return boxes_prepare<ST, INST>(
+        in, grad_out, grad_mask, grad_out && g.offsets && g.logits,
+        {{g.offsets, row * in.V}, {g.ref_rows, row * 5}, {g.logits, row * (INST ? 4 : in.d.P)}}, l, rc);
+}
+
+// mask NULL: the flavour without the mask output
+template <typename ST> int launch_fwd_boxes(const BoxesIn<ST> &in, ST *out, ST *mask)
+{
+    // (pair_bytes are read after the dimensions and k have passed)
+    const size_t row = (size_t)in.d.C * sizeof(ST);
+    BoxesLaunch l;
+    int rc;
+    if (!boxes_prepare<ST, true>(in, out, mask, out != nullptr, {{out, row}, {mask, row * in.k * in.k}}, l, rc))
+        return rc;
+    const Dims &d = l.d;
+    const GatherIdx ix = with_grid(l.r.ix, l.r.wblocks, 1, 1);
+    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], in.st);
+    const auto launch = [&](auto inst, auto mask_arg) {
+#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                             \
+    hipLaunchKernelGGL((fwd_wide_boxes_kernel<ST, GG, VV, decltype(inst)::value>), dim3(l.r.wblocks), dim3(256), \
+                       0, in.st, in.value, in.shapes, in.lsi, in.ref, in.offsets, in.kernel_idx,                 \
+                       in.valid_ratios, in.logits, d.S, d.H, d.L, d.Lq, d.P, out, mask_arg, l.gd, l.bd, ix,      \
+                       l.vbytes, (unsigned)l.r.ws);
+        BOXATTN_GATHER_DISPATCH(l.r.cfg, BOXATTN_LAUNCH_BOXES);
+#undef BOXATTN_LAUNCH_BOXES
+    };
+    if (mask) launch(std::true_type{}, mask);
+    else launch(std::false_type{}, NoArg{});
+    return finish();
+}
+
+template <typename ST> int launch_fwd_box_boxes(const BoxesIn<ST> &in, ST *out)
+{
+    BoxesLaunch l;
+    int rc;
+    if (!boxes_prepare<ST, false>(in, out, nullptr, out != nullptr, {{out, (size_t)in.d.C * sizeof(ST)}}, l, rc))
+        return rc;
+    const Dims &d = l.d;
+    const unsigned stride = fwd2_boxes_pair_stride(d.L, d.L * d.P);
+    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], in.st);
+#define BOXATTN_FWD2_BOXES(GG, VV)                                                                          \
+    hipLaunchKernelGGL((fwd2_boxes_kernel<ST, GG, GatherUnroll<ST, GG, VV>::value, VV>), dim3(l.r.blocks),  \
+                       dim3(256), (size_t)kGatherWaves * (kWave / GG) * stride * sizeof(u32x4_t), in.st,    \
+                       in.value, in.shapes, in.lsi, in.ref, in.offsets, in.kernel_idx, in.valid_ratios,     \
+                       in.logits, d.S, d.H, d.L, d.Lq, d.P, out, l.gd,                                      \
+                       with_grid(l.r.ix, l.r.blocks, 1, (d.L * d.P + GG - 1) / GG), l.vbytes, stride);
+    BOXATTN_GATHER_DISPATCH(l.r.cfg, BOXATTN_FWD2_BOXES);
 #undef BOXATTN_FWD2_BOXES
     return finish();
 }
 
-// ---- instance attention's box and logit gradients from boxes and 2x2 logits (boxattn_boxes_bwd.h) -----------
-// Eligibility is boxes_route, with grad_out / grad_mask in the place of the forward's out / mask_out in the row
-// alignment: the ONE function behind instattn_bwd_boxes_ok and the entry points.  grad_mask NULL: the flavour
-// without the level term.  No other kernel behind this entry.
+// grad_mask NULL: the flavour without the level term
 template <typename ST>
-int launch_bwd_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
-                     int ref_per_head, const float *offsets, const float *kernel_idx, const float *valid_ratios,
-                     const float *logits, const ST *grad_out, const ST *grad_mask, int B, int S, int H, int C, int L,
-                     int Lq, int k, float *grad_offsets, float *grad_ref_rows, float *grad_logits, hipStream_t st)
+int launch_bwd_boxes(const BoxesIn<ST> &in, const ST *grad_out, const ST *grad_mask, const BoxesGrads &g)
 {
-    if (k < 2 || k > 32 || k % 2 != 0 || ref_dim < 4) return (int)hipErrorInvalidValue;
-    const Dims d{B, S, H, C, L, Lq, k * k};
-    if (!d.valid() || L > 16) return (int)hipErrorInvalidValue;
-    if (d.empty()) return 0;                                   // no queries: nothing to write
-    if (!shapes || !lsi || !ref || !offsets || !kernel_idx || !logits || !grad_out || !grad_offsets || !grad_logits)
-        return (int)hipErrorInvalidValue;
-    const size_t n_rows = d.n_qh() * (size_t)L;
-    if (d.n_value() == 0) {                                    // no pixels: every gradient is 0
-        hipError_t e = zero_async(grad_offsets, n_rows * 4 * sizeof(float), st);
-        if (e == hipSuccess && grad_ref_rows) e = zero_async(grad_ref_rows, n_rows * 5 * sizeof(float), st);
-        if (e == hipSuccess) e = zero_async(grad_logits, n_rows * 4 * sizeof(float), st);
-        return (int)e;
-    }
-    if (!value) return (int)hipErrorInvalidValue;
-    const size_t va = 4 * sizeof(ST);
-    FwdAlign al;
-    al.fast = aligned(value, va) && aligned(grad_out, va) && aligned(grad_mask, va);
-    al.rows16 = aligned(value, 16) && aligned(grad_out, 16) && aligned(grad_mask, 16);
-    al.staged = false;
-    FwdRoute r;
-    if (!boxes_route((int)sizeof(ST), d, k, al, r)) return (int)hipErrorInvalidValue;
-    const GridDims gd{Lq, H, L, d.P, 4, ref_dim, ref_per_head ? 1 : 0, 0};
-    const float m = (float)(k / 2);
-    const BoxesDims bd{k, k / 2, 1.f / (float)k, 1.f / (m * m)};
-    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST)), ws = r.ws;
-    const GatherIdx ix = with_grid(r.ix, r.wblocks, 1, 1);
-    const GatherCfg cfg = r.cfg;
-    ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], st);
-    if (grad_mask) {
-#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                    \
-    hipLaunchKernelGGL((pointgrad_boxes_kernel<ST, GG, VV, true>), dim3(r.wblocks), dim3(256), 0, st,   \
-                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, grad_out,    \
-                       grad_mask, d.S, d.H, d.L, d.Lq, d.P, grad_offsets, grad_ref_rows, grad_logits,   \
-                       gd, bd, ix, vbytes, ws);
-        BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
+    BoxesLaunch l;
+    int rc;
+    if (!boxes_prepare_bwd<ST, true>(in, grad_out, grad_mask, g, l, rc)) return rc;
+    const Dims &d = l.d;
+    const GatherIdx ix = with_grid(l.r.ix, l.r.wblocks, 1, 1);
+    ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], in.st);
+    const auto launch = [&](auto inst, auto grad_mask_arg) {
+#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                              \
+    hipLaunchKernelGGL((pointgrad_boxes_kernel<ST, GG, VV, decltype(inst)::value>), dim3(l.r.wblocks), dim3(256), \
+                       0, in.st, in.value, in.shapes, in.lsi, in.ref, in.offsets, in.kernel_idx,                  \
+                       in.valid_ratios, in.logits, grad_out, grad_mask_arg, d.S, d.H, d.L, d.Lq, d.P, g.offsets,  \
+                       g.ref_rows, g.logits, l.gd, l.bd, ix, l.vbytes, (unsigned)l.r.ws);
+        BOXATTN_GATHER_DISPATCH(l.r.cfg, BOXATTN_LAUNCH_BOXES);
 #undef BOXATTN_LAUNCH_BOXES
-    } else {
-#define BOXATTN_LAUNCH_BOXES(GG, VV)                                                                    \
-    hipLaunchKernelGGL((pointgrad_boxes_kernel<ST, GG, VV, false>), dim3(r.wblocks), dim3(256), 0, st,  \
-                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, grad_out,    \
-                       NoArg{}, d.S, d.H, d.L, d.Lq, d.P, grad_offsets, grad_ref_rows, grad_logits,     \
-                       gd, bd, ix, vbytes, ws);
-        BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_BOXES);
-#undef BOXATTN_LAUNCH_BOXES
-    }
+    };
+    if (grad_mask) launch(std::true_type{}, grad_mask);
+    else launch(std::false_type{}, NoArg{});
     return finish();
 }
 
-// ---- box attention's box and logit gradients from boxes and L P logits (boxattn_gather2_boxes_bwd.h) --------
-// Eligibility is box_boxes_route, with grad_out in the place of the forward's out in the row alignment: the ONE
-// function behind boxattn_bwd_boxes_ok and the entry points.  No other kernel behind this entry.
-template <typename ST>
-int launch_bwd_box_boxes(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
-                         int ref_per_head, const float *offsets, int V, int angle_mode, const float *kernel_idx,
-                         const float *valid_ratios, const float *logits, const ST *grad_out, int B, int S, int H,
-                         int C, int L, int Lq, int P, float *grad_offsets, float *grad_ref_rows, float *grad_logits,
-                         hipStream_t st)
+template <typename ST> int launch_bwd_box_boxes(const BoxesIn<ST> &in, const ST *grad_out, const BoxesGrads &g)
 {
-    const Dims d{B, S, H, C, L, Lq, P};
-    if (!d.valid() || L > 16 || (long long)L * P > kBoxesMaxLP) return (int)hipErrorInvalidValue;
-    if (angle_mode < 0 || angle_mode > 2 || V != (angle_mode == 1 ? 5 : 4) || ref_dim < (angle_mode ? 5 : 4))
-        return (int)hipErrorInvalidValue;
-    if (d.empty()) return 0;                                   // no queries: nothing to write
-    if (!shapes || !lsi || !ref || !offsets || !kernel_idx || !logits || !grad_out || !grad_offsets || !grad_logits)
-        return (int)hipErrorInvalidValue;
-    const size_t n_rows = d.n_qh() * (size_t)L;
-    if (d.n_value() == 0) {                                    // no pixels: every gradient is 0
-        hipError_t e = zero_async(grad_offsets, n_rows * (size_t)V * sizeof(float), st);
-        if (e == hipSuccess && grad_ref_rows) e = zero_async(grad_ref_rows, n_rows * 5 * sizeof(float), st);
-        if (e == hipSuccess) e = zero_async(grad_logits, n_rows * (size_t)P * sizeof(float), st);
-        return (int)e;
-    }
-    if (!value) return (int)hipErrorInvalidValue;
-    const size_t va = 4 * sizeof(ST);
-    FwdAlign al;
-    al.fast = aligned(value, va) && aligned(grad_out, va);
-    al.rows16 = aligned(value, 16) && aligned(grad_out, 16);
-    al.staged = false;
-    FwdRoute r;
-    if (!box_boxes_route((int)sizeof(ST), d, al, r)) return (int)hipErrorInvalidValue;
-    const GridDims gd{Lq, H, L, P, V, ref_dim, ref_per_head ? 1 : 0, angle_mode};
-    const unsigned vbytes = (unsigned)(d.n_value() * sizeof(ST));
-    const unsigned stride = bwd2_boxes_pair_stride(L * P);
-    const GatherCfg cfg = r.cfg;
-    ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], st);
-#define BOXATTN_BWD2_BOXES(GG, VV)                                                                        \
-    hipLaunchKernelGGL((bwd2_boxes_kernel<ST, GG, GatherUnroll<ST, GG, VV>::value, VV>), dim3(r.blocks),  \
-                       dim3(256), (size_t)kGatherWaves * (kWave / GG) * stride * sizeof(float), st,       \
-                       value, shapes, lsi, ref, offsets, kernel_idx, valid_ratios, logits, grad_out, d.S, \
-                       d.H, d.L, d.Lq, d.P, grad_offsets, grad_ref_rows, grad_logits, gd,                 \
-                       with_grid(r.ix, r.blocks, 1, (L * P + GG - 1) / GG), vbytes, stride);
-    BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_BWD2_BOXES);
+    BoxesLaunch l;
+    int rc;
+    if (!boxes_prepare_bwd<ST, false>(in, grad_out, nullptr, g, l, rc)) return rc;
+    const Dims &d = l.d;
+    const unsigned stride = bwd2_boxes_pair_stride(d.L * d.P);
+    ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], in.st);
+#define BOXATTN_BWD2_BOXES(GG, VV)                                                                          \
+    hipLaunchKernelGGL((bwd2_boxes_kernel<ST, GG, GatherUnroll<ST, GG, VV>::value, VV>), dim3(l.r.blocks),  \
+                       dim3(256), (size_t)kGatherWaves * (kWave / GG) * stride * sizeof(float), in.st,      \
+                       in.value, in.shapes, in.lsi, in.ref, in.offsets, in.kernel_idx, in.valid_ratios,     \
+                       in.logits, grad_out, d.S, d.H, d.L, d.Lq, d.P, g.offsets, g.ref_rows, g.logits,      \
+                       l.gd, with_grid(l.r.ix, l.r.blocks, 1, (d.L * d.P + GG - 1) / GG), l.vbytes, stride);
+    BOXATTN_GATHER_DISPATCH(l.r.cfg, BOXATTN_BWD2_BOXES);
 #undef BOXATTN_BWD2_BOXES
     return finish();
 }
@@ -1685,150 +1677,93 @@ int boxattn_fwd_route(int elem_bytes, int instance, int aligned, int B, int S, i
 {
     const Dims d = DIMS;
     if (!d.valid() || (elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8)) return -1;
-    // aligned: 0 nothing beyond the elements' own alignment, 8 every tensor to 8 bytes, else to 16 bytes
-    const int bytes = aligned == 0 ? elem_bytes : aligned == 8 ? 8 : 16;
-    const FwdAlign al{bytes >= 4 * elem_bytes && bytes >= 8, bytes >= 16, bytes >= 16};
+    FwdAlign al = align_from_bytes(elem_bytes, aligned);
+    al.staged = al.rows16;
     FwdRoute r;
     DensePlan dp;
     return fwd_route(elem_bytes, instance != 0, d, al, shapes_host, lsi_host, true, r, dp);
 }
 
+// ---- attention from boxes and logits: two eligibility queries a flavour (one answer) and an entry point per route
+// and storage type
 int instattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k)
 {
-    if (k < 2 || k > 32) return 0;
-    const Dims d{B, S, H, C, L, Lq, k * k};
-    const int bytes = aligned == 0 ? elem_bytes : aligned == 8 ? 8 : 16;          // as boxattn_fwd_route
-    const FwdAlign al{bytes >= 4 * elem_bytes && bytes >= 8, bytes >= 16, false};
+    const Dims d{B, S, H, C, L, Lq, (int)((unsigned)k * (unsigned)k)};     // (any k: boxes_route tests it)
     FwdRoute r;
-    return boxes_route(elem_bytes, d, k, al, r) ? 1 : 0;
+    return boxes_route(elem_bytes, d, k, align_from_bytes(elem_bytes, aligned), r) ? 1 : 0;
 }
-int instattn_fwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                           int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
-                           const float *valid_ratios, const float *logits, int B, int S, int H, int C, int L,
-                           int Lq, int k, float *out, float *mask_out, void *stream)
-{
-    return launch_fwd_boxes<float>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios,
-                                   logits, B, S, H, C, L, Lq, k, out, mask_out, ST_);
-}
-int instattn_fwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                            int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
-                            const float *valid_ratios, const float *logits, int B, int S, int H, int C, int L,
-                            int Lq, int k, uint16_t *out, uint16_t *mask_out, void *stream)
-{
-    return launch_fwd_boxes<bf16_t>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios,
-                                    logits, B, S, H, C, L, Lq, k, out, mask_out, ST_);
-}
-int instattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                           int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
-                           const float *valid_ratios, const float *logits, int B, int S, int H, int C, int L,
-                           int Lq, int k, uint16_t *out, uint16_t *mask_out, void *stream)
-{
-    return launch_fwd_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx,
-                                   valid_ratios, logits, B, S, H, C, L, Lq, k, as_f16(out), as_f16(mask_out), ST_);
-}
-
-int boxattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P)
-{
-    const Dims d = DIMS;
-    const int bytes = aligned == 0 ? elem_bytes : aligned == 8 ? 8 : 16;          // as boxattn_fwd_route
-    const FwdAlign al{bytes >= 4 * elem_bytes && bytes >= 8, bytes >= 16, false};
-    FwdRoute r;
-    return box_boxes_route(elem_bytes, d, al, r) ? 1 : 0;
-}
-int boxattn_fwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                          int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
-                          const float *kernel_idx, const float *valid_ratios, const float *logits, int B, int S,
-                          int H, int C, int L, int Lq, int P, float *out, void *stream)
-{
-    return launch_fwd_box_boxes<float>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
-                                       kernel_idx, valid_ratios, logits, B, S, H, C, L, Lq, P, out, ST_);
-}
-int boxattn_fwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                           int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
-                           const float *kernel_idx, const float *valid_ratios, const float *logits, int B, int S,
-                           int H, int C, int L, int Lq, int P, uint16_t *out, void *stream)
-{
-    return launch_fwd_box_boxes<bf16_t>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
-                                        kernel_idx, valid_ratios, logits, B, S, H, C, L, Lq, P, out, ST_);
-}
-int boxattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                          int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
-                          const float *kernel_idx, const float *valid_ratios, const float *logits, int B, int S,
-                          int H, int C, int L, int Lq, int P, uint16_t *out, void *stream)
-{
-    return launch_fwd_box_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
-                                       kernel_idx, valid_ratios, logits, B, S, H, C, L, Lq, P, as_f16(out), ST_);
-}
-
 int instattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int k)
 {
     return instattn_fwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, k);   // boxes_route: one eligibility
 }
-int instattn_bwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                           int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
-                           const float *valid_ratios, const float *logits, const float *grad_out,
-                           const float *grad_mask, int B, int S, int H, int C, int L, int Lq, int k,
-                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
+int boxattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P)
 {
-    return launch_bwd_boxes<float>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios,
-                                   logits, grad_out, grad_mask, B, S, H, C, L, Lq, k, grad_offsets, grad_ref_rows,
-                                   grad_logits, ST_);
+    FwdRoute r;
+    return box_boxes_route(elem_bytes, DIMS, align_from_bytes(elem_bytes, aligned), r) ? 1 : 0;
 }
-int instattn_bwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                            int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
-                            const float *valid_ratios, const float *logits, const uint16_t *grad_out,
-                            const uint16_t *grad_mask, int B, int S, int H, int C, int L, int Lq, int k,
-                            float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
-{
-    return launch_bwd_boxes<bf16_t>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx, valid_ratios,
-                                    logits, grad_out, grad_mask, B, S, H, C, L, Lq, k, grad_offsets, grad_ref_rows,
-                                    grad_logits, ST_);
-}
-int instattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                           int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx,
-                           const float *valid_ratios, const float *logits, const uint16_t *grad_out,
-                           const uint16_t *grad_mask, int B, int S, int H, int C, int L, int Lq, int k,
-                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
-{
-    return launch_bwd_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, kernel_idx,
-                                   valid_ratios, logits, as_f16(grad_out), as_f16(grad_mask), B, S, H, C, L, Lq, k,
-                                   grad_offsets, grad_ref_rows, grad_logits, ST_);
-}
-
 int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P)
 {
     return boxattn_fwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P);   // box_boxes_route: one eligibility
 }
-int boxattn_bwd_boxes_f32(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                          int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
-                          const float *kernel_idx, const float *valid_ratios, const float *logits,
-                          const float *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
-                          float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
-{
-    return launch_bwd_box_boxes<float>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
-                                       kernel_idx, valid_ratios, logits, grad_out, B, S, H, C, L, Lq, P,
-                                       grad_offsets, grad_ref_rows, grad_logits, ST_);
-}
-int boxattn_bwd_boxes_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                           int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
-                           const float *kernel_idx, const float *valid_ratios, const float *logits,
-                           const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
-                           float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
-{
-    return launch_bwd_box_boxes<bf16_t>(value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, V, angle_mode,
-                                        kernel_idx, valid_ratios, logits, grad_out, B, S, H, C, L, Lq, P,
-                                        grad_offsets, grad_ref_rows, grad_logits, ST_);
-}
-int boxattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-                          int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,
-                          const float *kernel_idx, const float *valid_ratios, const float *logits,
-                          const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
-                          float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)
-{
-    return launch_bwd_box_boxes<f16_t>(as_f16(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, V,
-                                       angle_mode, kernel_idx, valid_ratios, logits, as_f16(grad_out), B, S, H, C,
-                                       L, Lq, P, grad_offsets, grad_ref_rows, grad_logits, ST_);
-}
+
+// The storage types of the from-boxes entry points: X(suffix, element type of the C ABI, storage type inside, cast)
+#define BOXES_STORAGE_TYPES(X) X(f32, float, float, ) X(bf16, uint16_t, bf16_t, ) X(f16, uint16_t, f16_t, as_f16)
+// A wrapper's BoxesIn<ST>, from its parameters by their names (the field order of the struct); the instance flavour
+// passes V 4, angle_mode 0 and no P, the box flavour no k
+#define BOXES_IN(ST, CAST, V_, ANGLE_, P_, K_)                                                                 \
+    BoxesIn<ST>{CAST(value), shapes, lsi, ref, ref_dim, ref_per_head, offsets, V_, ANGLE_, kernel_idx,         \
+                valid_ratios, logits, Dims{B, S, H, C, L, Lq, P_}, K_, ST_}
+#define BOXES_GRADS BoxesGrads{grad_offsets, grad_ref_rows, grad_logits}
+
+#define INSTATTN_FWD_BOXES(SUF, CT, ST, CAST)                                                                  \
+    int instattn_fwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \
+                                 int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx, \
+                                 const float *valid_ratios, const float *logits, int B, int S, int H, int C,   \
+                                 int L, int Lq, int k, CT *out, CT *mask_out, void *stream)                    \
+    {                                                                                                          \
+        return launch_fwd_boxes<ST>(BOXES_IN(ST, CAST, 4, 0, 0, k), CAST(out), CAST(mask_out));                \
+    }
+BOXES_STORAGE_TYPES(INSTATTN_FWD_BOXES)
+#undef INSTATTN_FWD_BOXES
+
+#define BOXATTN_FWD_BOXES(SUF, CT, ST, CAST)                                                                   \
+    int boxattn_fwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref,  \
+                                int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,    \
+                                const float *kernel_idx, const float *valid_ratios, const float *logits,       \
+                                int B, int S, int H, int C, int L, int Lq, int P, CT *out, void *stream)       \
+    {                                                                                                          \
+        return launch_fwd_box_boxes<ST>(BOXES_IN(ST, CAST, V, angle_mode, P, 0), CAST(out));                   \
+    }
+BOXES_STORAGE_TYPES(BOXATTN_FWD_BOXES)
+#undef BOXATTN_FWD_BOXES
+
+#define INSTATTN_BWD_BOXES(SUF, CT, ST, CAST)                                                                  \
+    int instattn_bwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \
+                                 int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx, \
+                                 const float *valid_ratios, const float *logits, const CT *grad_out,           \
+                                 const CT *grad_mask, int B, int S, int H, int C, int L, int Lq, int k,        \
+                                 float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)  \
+    {                                                                                                          \
+        return launch_bwd_boxes<ST>(BOXES_IN(ST, CAST, 4, 0, 0, k), CAST(grad_out), CAST(grad_mask),           \
+                                    BOXES_GRADS);                                                              \
+    }
+BOXES_STORAGE_TYPES(INSTATTN_BWD_BOXES)
+#undef INSTATTN_BWD_BOXES
+
+#define BOXATTN_BWD_BOXES(SUF, CT, ST, CAST)                                                                   \
+    int boxattn_bwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref,  \
+                                int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,    \
+                                const float *kernel_idx, const float *valid_ratios, const float *logits,       \
+                                const CT *grad_out, int B, int S, int H, int C, int L, int Lq, int P,          \
+                                float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream)   \
+    {                                                                                                          \
+        return launch_bwd_box_boxes<ST>(BOXES_IN(ST, CAST, V, angle_mode, P, 0), CAST(grad_out), BOXES_GRADS); \
+    }
+BOXES_STORAGE_TYPES(BOXATTN_BWD_BOXES)
+#undef BOXATTN_BWD_BOXES
+#undef BOXES_GRADS
+#undef BOXES_IN
+#undef BOXES_STORAGE_TYPES
 
 int boxattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
                     const float *loc, const float *attn, int B, int S, int H, int C, int L,

@@ -19,6 +19,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import ops
+from .ops import _H16
 
 
 # Whether the Functions' forward already prepares the backward's plan: the count pass and the scans of
@@ -331,7 +332,58 @@ def _ref_grad(ref_windows, rows):
     return grad_ref
 
 
-_H16 = (torch.bfloat16, torch.float16)
+# ---- the two training steps from boxes and logits (``module.fused_boxes_train``): what they share -----------------
+def _boxes_operands(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios,
+                    logits):
+    """-> the operands of ``ops.*_forward_boxes`` (value in its storage type, the rest detached float32), saved for
+    the backward; the caller's types are kept in ``ctx.value_dtype`` / ``ctx.in_dtypes``."""
+    storage = value.dtype if value.dtype in _H16 else torch.float32
+    ctx.value_dtype = value.dtype
+    ctx.in_dtypes = (ref_windows.dtype, offsets.dtype, logits.dtype)
+    f32 = lambda t: t.detach().float().contiguous()
+    value = value.detach().to(storage).contiguous()
+    ref_windows, offsets, kernel_indices, logits = f32(ref_windows), f32(offsets), f32(kernel_indices), f32(logits)
+    if valid_ratios is not None:
+        valid_ratios = f32(valid_ratios)
+    # (the (P, 2) buffer is kept flat: nothing saved here has a point axis)
+    ctx.save_for_backward(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices.view(-1),
+                          valid_ratios, logits)
+    return value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits
+
+
+def _boxes_saved(ctx):
+    """-> the operands again, and whether value / any of ref_windows, offsets and logits needs a gradient."""
+    value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits = ctx.saved_tensors
+    need_v, _, _, need_r, need_o, _, _, need_l = ctx.needs_input_grad[:8]
+    return ((value, shapes, lsi, ref_windows, offsets, kernel_indices.view(-1, 2), valid_ratios, logits),
+            need_v, need_r or need_o or need_l)
+
+
+def _boxes_param_grads(ctx, ref_windows, grads):
+    """(grad_offsets, grad_ref_rows, grad_logits) of ``ops.*_backward_boxes`` -> (grad_ref, grad_offsets, grad_logits)
+    in the inputs' types, None for an input that needs no gradient."""
+    grad_offsets, rows, grad_logits = grads
+    need_r, need_o, need_l = ctx.needs_input_grad[3], ctx.needs_input_grad[4], ctx.needs_input_grad[7]
+    rdt, odt, ldt = ctx.in_dtypes
+    return (_ref_grad(ref_windows, rows).to(rdt) if need_r else None, grad_offsets.to(odt) if need_o else None,
+            grad_logits.to(ldt) if need_l else None)
+
+
+def _boxes_grad_value(ctx, operands, angle_mode, weights, grad_output, grad_mask_output=None):
+    """grad_value from the destination-binned backward, whose records need the per-point tensors: the sampling grid
+    and ``weights()`` -> (weights, level weights or None) are built for this call only.  ``grad_mask_output`` None:
+    the box flavour of the backward."""
+    value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, _ = operands
+    B = offsets.size(0)
+    loc = ops.box_grid_forward(ref_windows, offsets, kernel_indices, valid_ratios, angle_mode)
+    w, level_w = weights()
+    if grad_mask_output is not None:
+        grad_value = ops.instance_attn_backward(value, shapes, lsi, loc, w, level_w, grad_output, grad_mask_output, B,
+                                                plan=None, want=1)[0]
+    else:
+        grad_value = ops.box_attn_backward(value, shapes, lsi, loc, w, grad_output, B, plan=None, want=1)[0]
+    del loc, w, level_w
+    return grad_value.to(ctx.value_dtype)
 
 
 class InstanceAttnBoxesFunction(Function):
@@ -350,58 +402,33 @@ class InstanceAttnBoxesFunction(Function):
     def forward(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios,
                 logits, kernel_size):
         ctx.set_materialize_grads(False)
-        storage = value.dtype if value.dtype in _H16 else torch.float32
-        ctx.value_dtype, ctx.k = value.dtype, int(kernel_size)
-        ctx.in_dtypes = (ref_windows.dtype, offsets.dtype, logits.dtype)
-        f32 = lambda t: t.detach().float().contiguous()
-        value = value.detach().to(storage).contiguous()
-        ref_windows, offsets, kernel_indices, logits = f32(ref_windows), f32(offsets), f32(kernel_indices), f32(logits)
-        if valid_ratios is not None:
-            valid_ratios = f32(valid_ratios)
-        output, mask_output = ops.instance_attn_forward_boxes(
-            value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits,
-            ctx.k, need_mask=True)
-        # (the (k*k, 2) buffer is kept flat: nothing saved here has a point axis)
-        ctx.save_for_backward(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices.view(-1),
-                              valid_ratios, logits)
+        ctx.k = int(kernel_size)
+        operands = _boxes_operands(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                                   valid_ratios, logits)
+        output, mask_output = ops.instance_attn_forward_boxes(*operands, ctx.k, need_mask=True)
         b, l, _, c = mask_output.shape
         return output, mask_output.view(b, l, ctx.k, ctx.k, c)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output, grad_mask_output):
-        none = (None,) * 9
         if grad_output is None and grad_mask_output is None:
-            return none
-        value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits = ctx.saved_tensors
-        kernel_indices = kernel_indices.view(-1, 2)
-        need_v, _, _, need_r, need_o, _, _, need_l = ctx.needs_input_grad[:8]
-        B, Lq, H, L = offsets.shape[:4]
+            return (None,) * 9
+        operands, need_v, need_params = _boxes_saved(ctx)
+        value, ref_windows, offsets, logits = operands[0], operands[3], operands[4], operands[7]
         if grad_output is None:
+            B, Lq, H = offsets.shape[:3]
             grad_output = value.new_zeros((B, Lq, H * value.size(3)))
         grad_output = grad_output.to(value.dtype).contiguous()
         if grad_mask_output is not None:
             grad_mask_output = grad_mask_output.to(value.dtype).contiguous()
         grad_value = grad_ref = grad_offsets = grad_logits = None
-        if need_r or need_o or need_l:
-            grad_offsets, rows, grad_logits = ops.instance_attn_backward_boxes(
-                value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits, ctx.k, grad_output,
-                grad_mask_output, need_ref_grad=need_r)
-            rdt, odt, ldt = ctx.in_dtypes
-            grad_ref = _ref_grad(ref_windows, rows).to(rdt) if need_r else None
-            grad_offsets = grad_offsets.to(odt) if need_o else None
-            grad_logits = grad_logits.to(ldt) if need_l else None
+        if need_params:
+            grad_ref, grad_offsets, grad_logits = _boxes_param_grads(ctx, ref_windows, ops.instance_attn_backward_boxes(
+                *operands, ctx.k, grad_output, grad_mask_output, need_ref_grad=ctx.needs_input_grad[3]))
         if need_v:
-            # the per-point tensors, for this call only
-            loc = ops.box_grid_forward(ref_windows, offsets, kernel_indices, valid_ratios, 0)
-            sw, lw = ops.instance_weights_forward(logits, ctx.k, grad_mask_output is not None)
-            if grad_mask_output is not None:
-                grad_value = ops.instance_attn_backward(value, shapes, lsi, loc, sw, lw, grad_output,
-                                                        grad_mask_output, B, plan=None, want=1)[0]
-            else:
-                grad_value = ops.box_attn_backward(value, shapes, lsi, loc, sw, grad_output, B, plan=None, want=1)[0]
-            del loc, sw, lw
-            grad_value = grad_value.to(ctx.value_dtype)
+            weights = lambda: ops.instance_weights_forward(logits, ctx.k, grad_mask_output is not None)
+            grad_value = _boxes_grad_value(ctx, operands, 0, weights, grad_output, grad_mask_output)
         return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)
 
 
@@ -419,46 +446,26 @@ class BoxAttnBoxesFunction(Function):
     @staticmethod
     def forward(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios,
                 logits, angle_mode):
-        storage = value.dtype if value.dtype in _H16 else torch.float32
-        ctx.value_dtype, ctx.angle_mode = value.dtype, int(angle_mode)
-        ctx.in_dtypes = (ref_windows.dtype, offsets.dtype, logits.dtype)
+        ctx.angle_mode = int(angle_mode)
         ctx.logits_shape = tuple(logits.shape)
-        f32 = lambda t: t.detach().float().contiguous()
-        value = value.detach().to(storage).contiguous()
-        ref_windows, offsets, kernel_indices, logits = f32(ref_windows), f32(offsets), f32(kernel_indices), f32(logits)
         b, lq, h = offsets.shape[:3]
-        logits = logits.view(b, lq, h, -1)
-        if valid_ratios is not None:
-            valid_ratios = f32(valid_ratios)
-        output = ops.box_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets,
-                                            kernel_indices, valid_ratios, logits, ctx.angle_mode)
-        # (the (P, 2) buffer is kept flat: nothing saved here has a point axis)
-        ctx.save_for_backward(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices.view(-1),
-                              valid_ratios, logits)
-        return output
+        operands = _boxes_operands(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                                   valid_ratios, logits.reshape(b, lq, h, -1))
+        return ops.box_attn_forward_boxes(*operands, ctx.angle_mode)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits = ctx.saved_tensors
-        kernel_indices = kernel_indices.view(-1, 2)
-        need_v, _, _, need_r, need_o, _, _, need_l = ctx.needs_input_grad[:8]
-        B, Lq, H, L = offsets.shape[:4]
+        operands, need_v, need_params = _boxes_saved(ctx)
+        value, ref_windows, offsets, logits = operands[0], operands[3], operands[4], operands[7]
         grad_output = grad_output.to(value.dtype).contiguous()
         grad_value = grad_ref = grad_offsets = grad_logits = None
-        if need_r or need_o or need_l:
-            grad_offsets, rows, grad_logits = ops.box_attn_backward_boxes(
-                value, shapes, lsi, ref_windows, offsets, kernel_indices, valid_ratios, logits, ctx.angle_mode,
-                grad_output, need_ref_grad=need_r)
-            rdt, odt, ldt = ctx.in_dtypes
-            grad_ref = _ref_grad(ref_windows, rows).to(rdt) if need_r else None
-            grad_offsets = grad_offsets.to(odt) if need_o else None
-            grad_logits = grad_logits.to(ldt).view(ctx.logits_shape) if need_l else None
+        if need_params:
+            grad_ref, grad_offsets, grad_logits = _boxes_param_grads(ctx, ref_windows, ops.box_attn_backward_boxes(
+                *operands, ctx.angle_mode, grad_output, need_ref_grad=ctx.needs_input_grad[3]))
+            if grad_logits is not None:
+                grad_logits = grad_logits.view(ctx.logits_shape)
         if need_v:
-            # the per-point tensors, for this call only
-            loc = ops.box_grid_forward(ref_windows, offsets, kernel_indices, valid_ratios, ctx.angle_mode)
-            attn = ops.softmax_forward(logits).view(B, Lq, H, L, -1)
-            grad_value = ops.box_attn_backward(value, shapes, lsi, loc, attn, grad_output, B, plan=None, want=1)[0]
-            del loc, attn
-            grad_value = grad_value.to(ctx.value_dtype)
+            weights = lambda: (ops.softmax_forward(logits).view(*offsets.shape[:4], -1), None)
+            grad_value = _boxes_grad_value(ctx, operands, ctx.angle_mode, weights, grad_output)
         return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)

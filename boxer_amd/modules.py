@@ -27,6 +27,10 @@ from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnF16Fun
                         InstanceAttnFunction, InstanceWeightsFunction, LogitSoftmaxFunction, ValueMaskCastFunction)
 
 
+def _f32(t):
+    return t.float().contiguous()
+
+
 def _kernel_offsets(kernel_size, divisor):
     """(k*k, 2) grid of (x, y) offsets in units of the box size, row-major over (y, x).
     Even k: half-pixel centred (-k/2+0.5 .. k/2-0.5); odd k: integer centred."""
@@ -154,10 +158,13 @@ class _BoxAttentionBase(nn.Module):
         ``v_valid_ratios`` None or (B,1,1,L,1,2) (box_transformer.py:118-138)."""
         if not (self.fused_grid and query.is_cuda) or query.dtype == torch.float64:
             return False                      # (the kernel computes in float32)
+        return self._reference_valid_ratios(query, v_valid_ratios)
+
+    def _reference_valid_ratios(self, query, v_valid_ratios):
+        """``v_valid_ratios`` as the reference passes them: None or (B,1,1,L,1,2)."""
         return v_valid_ratios is None or (
-            v_valid_ratios.dim() == 6
-            and tuple(v_valid_ratios.shape[1:]) == (1, 1, self.num_level, 1, 2)
-            and v_valid_ratios.size(0) == query.size(0))
+            v_valid_ratios.dim() == 6 and v_valid_ratios.size(0) == query.size(0)
+            and tuple(v_valid_ratios.shape[1:]) == (1, 1, self.num_level, 1, 2))
 
     def _boxes_operand(self, query, value, v_valid_ratios):
         """``value`` in the type the kernels from boxes take it, or None where they do not run: CPU / float64 tensors,
@@ -166,11 +173,35 @@ class _BoxAttentionBase(nn.Module):
             return None
         if torch.float64 in (query.dtype, value.dtype):
             return None                       # (the kernel computes in float32)
-        if v_valid_ratios is not None and not (
-                v_valid_ratios.dim() == 6 and v_valid_ratios.size(0) == query.size(0)
-                and tuple(v_valid_ratios.shape[1:]) == (1, 1, self.num_level, 1, 2)):
+        if not self._reference_valid_ratios(query, v_valid_ratios):
             return None
         return value.to(self._storage_dtype() or torch.float32).contiguous()
+
+    def _boxes_kernel_ok(self, value, num_query, backward):
+        """Whether the forward / the backward from boxes and logits has its kernel for ``value`` and this module
+        (ops.*_boxes_ok)."""
+        raise NotImplementedError
+
+    def _boxes_value(self, query, value, v_valid_ratios):
+        """The projected ``value`` as the one-launch inference forward takes it (the storage mode's type, float32
+        without one), or None: that path is not taken -- flag off, grad mode, what ``_boxes_operand`` refuses, or no
+        kernel for the shape."""
+        if not self.fused_boxes or torch.is_grad_enabled():
+            return None
+        value = self._boxes_operand(query, value, v_valid_ratios)
+        return value if value is not None and self._boxes_kernel_ok(value, query.size(1), False) else None
+
+    def _boxes_train(self, query, value, v_valid_ratios):
+        """``value`` as the training step from boxes and logits takes it (a differentiable cast), or None: that path
+        is not taken -- ``fused_boxes_train`` off, no grad mode, what ``_boxes_operand`` refuses, or no kernel for the
+        shape one way or the other."""
+        if not self.fused_boxes_train or not torch.is_grad_enabled():
+            return None
+        value = self._boxes_operand(query, value, v_valid_ratios)
+        if value is None:
+            return None
+        n = query.size(1)
+        return value if self._boxes_kernel_ok(value, n, True) and self._boxes_kernel_ok(value, n, False) else None
 
 
 class BoxAttention(_BoxAttentionBase):
@@ -199,41 +230,20 @@ class BoxAttention(_BoxAttentionBase):
     def _angle_mode(self):
         return 0
 
-    def _boxes_value(self, query, value, v_valid_ratios):
-        """The projected ``value`` as the one-launch inference forward takes it (the storage mode's type, float32
-        without one), or None: that path is not taken -- flag off, grad mode, what ``_boxes_operand`` refuses, or no
-        kernel for the shape (ops.box_forward_boxes_ok)."""
-        if not self.fused_boxes or torch.is_grad_enabled():
-            return None
-        value = self._boxes_operand(query, value, v_valid_ratios)
-        return value if value is not None and ops.box_forward_boxes_ok(value, self.num_level, query.size(1),
-                                                                       self.num_point) else None
+    def _boxes_kernel_ok(self, value, num_query, backward):
+        ok = ops.box_backward_boxes_ok if backward else ops.box_forward_boxes_ok
+        return ok(value, self.num_level, num_query, self.num_point)
 
     def _forward_boxes(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows):
         b, l1 = query.shape[:2]
-        f32 = lambda t: t.float().contiguous()
         mode = self._angle_mode()
         logits = dense.linear(query, self.linear_attn_weight, self.linear_attn_bias)
         offsets = self._box_offsets(query, ref_windows, 5 if mode == 1 else 4)
         output = ops.box_attn_forward_boxes(
-            value, v_shape, v_start_index, f32(ref_windows), f32(offsets), f32(self.kernel_indices),
-            None if v_valid_ratios is None else f32(v_valid_ratios).view(b, self.num_level, 2),
-            f32(logits).view(b, l1, self.num_head, -1), mode)
+            value, v_shape, v_start_index, _f32(ref_windows), _f32(offsets), _f32(self.kernel_indices),
+            None if v_valid_ratios is None else _f32(v_valid_ratios).view(b, self.num_level, 2),
+            _f32(logits).view(b, l1, self.num_head, -1), mode)
         return dense.linear(output, self.out_proj.weight, self.out_proj.bias), ()
-
-    def _boxes_train(self, query, value, v_valid_ratios):
-        """``value`` as the training step from boxes and logits takes it (a differentiable cast), or None: that path
-        is not taken -- ``fused_boxes_train`` off, no grad mode, what ``_boxes_operand`` refuses, or no kernel for the
-        shape one way or the other."""
-        if not self.fused_boxes_train or not torch.is_grad_enabled():
-            return None
-        value = self._boxes_operand(query, value, v_valid_ratios)
-        if value is None:
-            return None
-        n = query.size(1)
-        ok = ops.box_backward_boxes_ok(value, self.num_level, n, self.num_point) and \
-            ops.box_forward_boxes_ok(value, self.num_level, n, self.num_point)
-        return value if ok else None
 
     def _forward_boxes_train(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows):
         b, l1 = query.shape[:2]
@@ -309,28 +319,15 @@ class InstanceAttention(_BoxAttentionBase):
 
     _where_to_attend = BoxAttention._where_to_attend
 
-    def _boxes_value(self, query, value, v_valid_ratios):
-        """The projected ``value`` as the one-launch inference forward takes it (the storage mode's type, float32
-        without one), or None: that path is not taken -- flag off, grad mode, CPU / float64 tensors, ``v_valid_ratios``
-        of another shape than the reference's, or no kernel for the shape (ops.forward_boxes_ok)."""
-        if not self.fused_boxes or torch.is_grad_enabled():
-            return None
-        value = self._boxes_operand(query, value, v_valid_ratios)
-        return value if value is not None and ops.forward_boxes_ok(value, self.num_level, query.size(1),
-                                                                   self.kernel_size) else None
+    def _boxes_kernel_ok(self, value, num_query, backward):
+        ok = ops.backward_boxes_ok if backward else ops.forward_boxes_ok
+        return ok(value, self.num_level, num_query, self.kernel_size)
 
     def _boxes_train(self, query, value, v_valid_ratios):
-        """``value`` as the training step from boxes and logits takes it (a differentiable cast), or None: that path
-        is not taken -- ``fused_boxes_train`` off, no grad mode, ``inferencing``, what ``_boxes_operand`` refuses, or
-        no kernel for the shape one way or the other."""
+        """``_BoxAttentionBase._boxes_train``, and not while ``inferencing``."""
         if not self.fused_boxes_train or not torch.is_grad_enabled() or self.inferencing:
             return None
-        value = self._boxes_operand(query, value, v_valid_ratios)
-        if value is None:
-            return None
-        n, k = query.size(1), self.kernel_size
-        ok = ops.backward_boxes_ok(value, self.num_level, n, k) and ops.forward_boxes_ok(value, self.num_level, n, k)
-        return value if ok else None
+        return super()._boxes_train(query, value, v_valid_ratios)
 
     def _forward_boxes_train(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows, logits):
         b, l1 = query.shape[:2]
@@ -351,11 +348,10 @@ class InstanceAttention(_BoxAttentionBase):
     def _forward_boxes(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows, logits):
         b, l1 = query.shape[:2]
         k = self.kernel_size
-        f32 = lambda t: t.float().contiguous()
-        offsets = f32(self._box_offsets(query, ref_windows, 4))
+        offsets = _f32(self._box_offsets(query, ref_windows, 4))
         output, mask_output = ops.instance_attn_forward_boxes(
-            value, v_shape, v_start_index, f32(ref_windows), offsets, f32(self.kernel_indices),
-            None if v_valid_ratios is None else f32(v_valid_ratios).view(b, self.num_level, 2), f32(logits), k,
+            value, v_shape, v_start_index, _f32(ref_windows), offsets, _f32(self.kernel_indices),
+            None if v_valid_ratios is None else _f32(v_valid_ratios).view(b, self.num_level, 2), _f32(logits), k,
             need_mask=not self.inferencing)
         if mask_output is not None:
             mask_output = self.out_proj(mask_output.view(b, l1, k, k, self.d_model))

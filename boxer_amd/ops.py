@@ -20,6 +20,7 @@ from . import _lib
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
 _H16 = (torch.bfloat16, torch.float16)      # 16-bit storage: float32 geometry, same kernels and workspace sizes
+_BOXES_DTYPES = (torch.float32,) + _H16     # the storage types of the calls from boxes
 
 
 def _check(t, name):
@@ -851,31 +852,87 @@ def instance_weights_backward(logits, grad_spatial, grad_level=None):
 # operator: include/boxattn.h, instattn_fwd_boxes_*)
 # ---------------------------------------------------------------------------------------
 def _align_of(*tensors):
-    ptrs = [t.data_ptr() for t in tensors]
-    return 16 if all(p % 16 == 0 for p in ptrs) else 8 if all(p % 8 == 0 for p in ptrs) else 0
+    low = 0
+    for t in tensors:
+        low |= t.data_ptr()             # (the low bits of every address at once)
+    return 16 if low % 16 == 0 else 8 if low % 8 == 0 else 0
 
 
-def _boxes_args(what, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios,
-                logits, kernel_size):
-    """The argument checks the calls from boxes share -> (B, Lq, H, L, P), D, per_head, k."""
-    (B, Lq, H, L, P), (D, per_head, _, _) = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios, 0)
-    _check(value, "value")
-    _check(spatial_shapes, "spatial_shapes")
-    _check(level_start_index, "level_start_index")
-    _check(logits, "logits")
-    k = int(kernel_size)
-    if value.dtype not in (torch.float32,) + _H16:
-        raise RuntimeError("%s: float32, bfloat16 or float16 value expected, got %s" % (what, value.dtype))
+def _boxes_operands(what, exc, kernel_size, operands, angle_mode=0, also=()):
+    """The argument checks the four calls from boxes share.  ``operands``: value, spatial_shapes, level_start_index,
+    ref_windows, offsets, kernel_indices, valid_ratios, logits; ``also``: (tensor, name) pairs checked with them;
+    ``kernel_size``: the instance calls, logits (B,Lq,H,L,2,2) and kernel_size**2 points a level; None: the box calls,
+    B*Lq*H*L*P logits -> (B, S, H, C, L, Lq, P), (D, per_head, V, mode), k (None: the box calls).  Raises ``exc``:
+    RuntimeError with the bare texts (the instance calls), or ValueError with ``what`` in front (the box calls); a
+    non-Tensor is a TypeError for both."""
+    value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits = operands
+    try:
+        (B, Lq, H, L, P), grid = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios, angle_mode)
+        _check(value, "value")
+        _check(spatial_shapes, "spatial_shapes")
+        _check(level_start_index, "level_start_index")
+        _check(logits, "logits")
+        for t, name in also:
+            _check(t, name)
+    except RuntimeError as e:
+        raise _boxes_refusal(what, exc, str(e)) from None
+    k = None if kernel_size is None else int(kernel_size)
+    if value.dtype not in _BOXES_DTYPES:
+        raise exc("%s: float32, bfloat16 or float16 value expected, got %s" % (what, value.dtype))
     if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
-        raise RuntimeError("spatial_shapes / level_start_index must be int64")
-    if logits.dtype != torch.float32 or tuple(logits.shape) != (B, Lq, H, L, 2, 2):
-        raise RuntimeError("expected logits (B,Lq,H,L,2,2) float32 matching offsets")
+        raise _boxes_refusal(what, exc, "spatial_shapes / level_start_index must be int64")
+    if k is not None:
+        if logits.dtype != torch.float32 or tuple(logits.shape) != (B, Lq, H, L, 2, 2):
+            raise _boxes_refusal(what, exc, "expected logits (B,Lq,H,L,2,2) float32 matching offsets")
+    elif logits.dtype != torch.float32 or logits.numel() != B * Lq * H * L * P:
+        raise _boxes_refusal(what, exc, "expected B*Lq*H*L*P float32 logits matching offsets")
     if value.dim() != 4 or value.size(0) != B or value.size(2) != H or spatial_shapes.size(0) != L or \
             level_start_index.numel() != L:
-        raise RuntimeError("offsets / spatial_shapes do not match value (B,S,H,C)")
-    if P != k * k:
-        raise RuntimeError("kernel_indices must have kernel_size**2 rows")
-    return (B, Lq, H, L, P), D, per_head, k
+        raise _boxes_refusal(what, exc, "offsets / spatial_shapes do not match value (B,S,H,C)")
+    if k is not None and P != k * k:
+        raise _boxes_refusal(what, exc, "kernel_indices must have kernel_size**2 rows")
+    return (B, value.size(1), H, value.size(3), L, Lq, P), grid, k
+
+
+def _boxes_refusal(what, exc, text):
+    """The exception of a call from boxes: the box calls' ValueError carries the function's name in front."""
+    return exc("%s: %s" % (what, text) if exc is ValueError else text)
+
+
+def _boxes_upstream(what, exc, value, grads):
+    """The upstream gradients of a backward from boxes, (name, tensor, elements) each: in the type of ``value``."""
+    for name, g, n in grads:
+        try:
+            _check(g, name)
+        except RuntimeError as e:
+            raise _boxes_refusal(what, exc, str(e)) from None
+        if g.dtype != value.dtype or g.numel() != n:
+            raise _boxes_refusal(what, exc, "%s: %d elements of type %s expected" % (name, n, value.dtype))
+
+
+def _boxes_ok(query, value, dims, *points, also=()):
+    """The one body of the four ``*_boxes_ok``: ``query`` of _lib at the element size of ``value`` (B, S, H, C), the
+    alignment of ``value`` and ``also``, and (B, S, H, C) + ``dims`` (+ ``points``)."""
+    if not isinstance(value, torch.Tensor) or value.dim() != 4 or value.dtype not in _BOXES_DTYPES:
+        return False
+    return query(value.element_size(), _align_of(value, *also), (*value.shape, *dims), *points)
+
+
+def _boxes_call(stem, operands, window, angle, upstream, dims, outputs):
+    """``stem`` + the suffix of value's type: the operands with ``window`` = (D, per_head) and ``angle`` = (V, mode) (the
+    box calls) or () in their places, the upstream gradients, the dimensions and the outputs; None: an optional tensor
+    that is absent (ctypes passes it as a NULL pointer)."""
+    value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits = operands
+    _grid_call(stem + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index, ref_windows, *window,
+               offsets, *angle, kernel_indices, valid_ratios, logits, *upstream, *dims, *outputs)
+
+
+def _boxes_grads(value, rows, V, logits_shape, need_ref_grad):
+    """The outputs of a backward from boxes for ``rows`` = (B, Lq, H, L) -> (grad_offsets, grad_ref_rows or None,
+    grad_logits), float32."""
+    f32 = {"dtype": torch.float32, "device": value.device}
+    return (torch.empty((*rows, V), **f32), torch.empty((*rows, 5), **f32) if need_ref_grad else None,
+            torch.empty(logits_shape, **f32))
 
 
 def forward_boxes_ok(value, num_level, num_query, kernel_size):
@@ -883,10 +940,7 @@ def forward_boxes_ok(value, num_level, num_query, kernel_size):
     with the dimensions, element size and alignment of ``value`` (B, S, H, C), ``num_level`` levels, ``num_query``
     queries an image and ``kernel_size`` x ``kernel_size`` points a level.  The outputs are taken as freshly
     allocated (aligned).  Pure host code."""
-    if value.dim() != 4 or value.dtype not in (torch.float32,) + _H16:
-        return False
-    B, S, H, C = value.shape
-    return _lib.fwd_boxes_ok(value.element_size(), _align_of(value), (B, S, H, C, num_level, num_query), kernel_size)
+    return _boxes_ok(_lib.fwd_boxes_ok, value, (num_level, num_query), kernel_size)
 
 
 def instance_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
@@ -899,18 +953,15 @@ def instance_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_wi
     ``box_attn_forward`` on the spatial weights (not ``need_mask``) return, without the per-point tensors in
     between.  No backward here (``instance_attn_backward_boxes``).  Raises where ``forward_boxes_ok`` says no: there
     is no other kernel behind it."""
-    (B, Lq, H, L, P), D, per_head, k = _boxes_args(
-        "instance_attn_forward_boxes", value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
-        valid_ratios, logits, kernel_size)
-    if not forward_boxes_ok(value, L, Lq, k):
+    operands = (value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits)
+    (B, S, H, C, L, Lq, P), (D, per_head, _, _), k = _boxes_operands("instance_attn_forward_boxes", RuntimeError,
+                                                                     kernel_size, operands)
+    if not _boxes_ok(_lib.fwd_boxes_ok, value, (L, Lq), k):
         raise RuntimeError("instance_attn_forward_boxes: no kernel for value %s, %d levels, %d queries, kernel_size %d "
                            "(forward_boxes_ok)" % (tuple(value.shape), L, Lq, k))
-    S, C = value.size(1), value.size(3)
     out = torch.empty((B, Lq, H * C), dtype=value.dtype, device=value.device)
     mask = torch.empty((B, Lq, P, H * C), dtype=value.dtype, device=value.device) if need_mask else None
-    _grid_call("instattn_fwd_boxes_" + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index,
-               ref_windows, D, per_head, offsets, kernel_indices, valid_ratios if valid_ratios is not None else 0,
-               logits, B, S, H, C, L, Lq, k, out, mask if need_mask else 0)
+    _boxes_call("instattn_fwd_boxes_", operands, (D, per_head), (), (), (B, S, H, C, L, Lq, k), (out, mask))
     return out, mask
 
 
@@ -919,10 +970,7 @@ def backward_boxes_ok(value, num_level, num_query, kernel_size):
     (the eligibility of ``forward_boxes_ok``) with the dimensions, element size and alignment of ``value`` (B, S, H,
     C).  The upstream gradients are taken as aligned like ``value``; ``instance_attn_backward_boxes`` asks again with
     their addresses.  Pure host code."""
-    if value.dim() != 4 or value.dtype not in (torch.float32,) + _H16:
-        return False
-    B, S, H, C = value.shape
-    return _lib.bwd_boxes_ok(value.element_size(), _align_of(value), (B, S, H, C, num_level, num_query), kernel_size)
+    return _boxes_ok(_lib.bwd_boxes_ok, value, (num_level, num_query), kernel_size)
 
 
 def instance_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
@@ -934,30 +982,21 @@ def instance_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_w
     ``instance_attn_backward(want=2)`` -> ``box_grid_backward`` + ``instance_weights_backward`` return, without the
     per-point tensors in between.  ``grad_value`` is not computed.  Raises where ``backward_boxes_ok`` says no:
     there is no other kernel behind it."""
-    (B, Lq, H, L, P), D, per_head, k = _boxes_args(
-        "instance_attn_backward_boxes", value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
-        valid_ratios, logits, kernel_size)
-    S, C = value.size(1), value.size(3)
-    grads = [("grad_output", grad_output, B * Lq * H * C)]
+    operands = (value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits)
+    (B, S, H, C, L, Lq, P), (D, per_head, _, _), k = _boxes_operands("instance_attn_backward_boxes", RuntimeError,
+                                                                     kernel_size, operands)
+    upstream = [("grad_output", grad_output, B * Lq * H * C)]
     if grad_mask_output is not None:
-        grads.append(("grad_mask_output", grad_mask_output, B * Lq * P * H * C))
-    for name, g, n in grads:
-        _check(g, name)
-        if g.dtype != value.dtype or g.numel() != n:
-            raise RuntimeError("%s: %d elements of type %s expected" % (name, n, value.dtype))
-    given = [value, grad_output] + ([grad_mask_output] if grad_mask_output is not None else [])
-    if not _lib.bwd_boxes_ok(value.element_size(), _align_of(*given), (B, S, H, C, L, Lq), k):
+        upstream.append(("grad_mask_output", grad_mask_output, B * Lq * P * H * C))
+    _boxes_upstream("instance_attn_backward_boxes", RuntimeError, value, upstream)
+    if not _boxes_ok(_lib.bwd_boxes_ok, value, (L, Lq), k, also=[g for _, g, _ in upstream]):
         raise RuntimeError("instance_attn_backward_boxes: no kernel for value %s, %d levels, %d queries, kernel_size "
                            "%d at the alignment of value and the gradients (backward_boxes_ok)"
                            % (tuple(value.shape), L, Lq, k))
-    grad_offsets = torch.empty((B, Lq, H, L, 4), dtype=torch.float32, device=value.device)
-    grad_rows = torch.empty((B, Lq, H, L, 5), dtype=torch.float32, device=value.device) if need_ref_grad else None
-    grad_logits = torch.empty((B, Lq, H, L, 2, 2), dtype=torch.float32, device=value.device)
-    _grid_call("instattn_bwd_boxes_" + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index,
-               ref_windows, D, per_head, offsets, kernel_indices, valid_ratios if valid_ratios is not None else 0,
-               logits, grad_output, grad_mask_output if grad_mask_output is not None else 0, B, S, H, C, L, Lq, k,
-               grad_offsets, grad_rows if need_ref_grad else 0, grad_logits)
-    return grad_offsets, grad_rows, grad_logits
+    grads = _boxes_grads(value, (B, Lq, H, L), 4, (B, Lq, H, L, 2, 2), need_ref_grad)
+    _boxes_call("instattn_bwd_boxes_", operands, (D, per_head), (), (grad_output, grad_mask_output),
+                (B, S, H, C, L, Lq, k), grads)
+    return grads
 
 
 # ---------------------------------------------------------------------------------------
@@ -968,10 +1007,7 @@ def box_forward_boxes_ok(value, num_level, num_query, num_point):
     """Whether ``box_attn_forward_boxes`` has its kernel under the current switches: ``boxattn_fwd_boxes_ok`` with the
     dimensions, element size and alignment of ``value`` (B, S, H, C), ``num_level`` levels, ``num_query`` queries an
     image and ``num_point`` points a level.  The output is taken as freshly allocated (aligned).  Pure host code."""
-    if not isinstance(value, torch.Tensor) or value.dim() != 4 or value.dtype not in (torch.float32,) + _H16:
-        return False
-    B, S, H, C = value.shape
-    return _lib.box_fwd_boxes_ok(value.element_size(), _align_of(value), (B, S, H, C, num_level, num_query, num_point))
+    return _boxes_ok(_lib.box_fwd_boxes_ok, value, (num_level, num_query, num_point))
 
 
 def box_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
@@ -983,31 +1019,14 @@ def box_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows
     ``box_grid_forward`` -> ``softmax_forward`` -> ``box_attn_forward`` return, without the sampling grid and the
     weights in between.  No backward.  Raises ValueError, before any device call, for arguments that do not fit and
     where ``box_forward_boxes_ok`` says no: there is no other kernel behind it."""
-    try:
-        (B, Lq, H, L, P), (D, per_head, V, mode) = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios,
-                                                              angle_mode)
-        for t, name in ((value, "value"), (spatial_shapes, "spatial_shapes"),
-                        (level_start_index, "level_start_index"), (logits, "logits")):
-            _check(t, name)
-    except RuntimeError as e:
-        raise ValueError("box_attn_forward_boxes: %s" % e) from None
-    if value.dtype not in (torch.float32,) + _H16:
-        raise ValueError("box_attn_forward_boxes: float32, bfloat16 or float16 value expected, got %s" % value.dtype)
-    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
-        raise ValueError("box_attn_forward_boxes: spatial_shapes / level_start_index must be int64")
-    if logits.dtype != torch.float32 or logits.numel() != B * Lq * H * L * P:
-        raise ValueError("box_attn_forward_boxes: expected B*Lq*H*L*P float32 logits matching offsets")
-    if value.dim() != 4 or value.size(0) != B or value.size(2) != H or spatial_shapes.size(0) != L or \
-            level_start_index.numel() != L:
-        raise ValueError("box_attn_forward_boxes: offsets / spatial_shapes do not match value (B,S,H,C)")
-    if not box_forward_boxes_ok(value, L, Lq, P):
+    operands = (value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits)
+    dims, (D, per_head, V, mode), _ = _boxes_operands("box_attn_forward_boxes", ValueError, None, operands, angle_mode)
+    B, _, H, C, L, Lq, P = dims
+    if not _boxes_ok(_lib.box_fwd_boxes_ok, value, (L, Lq, P)):
         raise ValueError("box_attn_forward_boxes: no kernel for value %s, %d levels, %d queries, %d points a level "
                          "(box_forward_boxes_ok)" % (tuple(value.shape), L, Lq, P))
-    S, C = value.size(1), value.size(3)
     out = torch.empty((B, Lq, H * C), dtype=value.dtype, device=value.device)
-    _grid_call("boxattn_fwd_boxes_" + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index,
-               ref_windows, D, per_head, offsets, V, mode, kernel_indices,
-               valid_ratios if valid_ratios is not None else 0, logits, B, S, H, C, L, Lq, P, out)
+    _boxes_call("boxattn_fwd_boxes_", operands, (D, per_head), (V, mode), (), dims, (out,))
     return out
 
 
@@ -1019,10 +1038,7 @@ def box_backward_boxes_ok(value, num_level, num_query, num_point):
     eligibility of ``box_forward_boxes_ok``) with the dimensions, element size and alignment of ``value`` (B, S, H,
     C).  The upstream gradient is taken as aligned like ``value``; ``box_attn_backward_boxes`` asks again with its
     address.  Pure host code."""
-    if not isinstance(value, torch.Tensor) or value.dim() != 4 or value.dtype not in (torch.float32,) + _H16:
-        return False
-    B, S, H, C = value.shape
-    return _lib.box_bwd_boxes_ok(value.element_size(), _align_of(value), (B, S, H, C, num_level, num_query, num_point))
+    return _boxes_ok(_lib.box_bwd_boxes_ok, value, (num_level, num_query, num_point))
 
 
 def box_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
@@ -1035,34 +1051,15 @@ def box_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_window
     device call, for arguments that do not fit and where ``boxattn_bwd_boxes_ok`` says no at the alignment of
     ``value`` and ``grad_output``: there is no other kernel behind it."""
     what = "box_attn_backward_boxes"
-    try:
-        (B, Lq, H, L, P), (D, per_head, V, mode) = _grid_args(ref_windows, offsets, kernel_indices, valid_ratios,
-                                                              angle_mode)
-        for t, name in ((value, "value"), (spatial_shapes, "spatial_shapes"),
-                        (level_start_index, "level_start_index"), (logits, "logits"), (grad_output, "grad_output")):
-            _check(t, name)
-    except RuntimeError as e:
-        raise ValueError("%s: %s" % (what, e)) from None
-    if value.dtype not in (torch.float32,) + _H16:
-        raise ValueError("%s: float32, bfloat16 or float16 value expected, got %s" % (what, value.dtype))
-    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
-        raise ValueError("%s: spatial_shapes / level_start_index must be int64" % what)
-    if logits.dtype != torch.float32 or logits.numel() != B * Lq * H * L * P:
-        raise ValueError("%s: expected B*Lq*H*L*P float32 logits matching offsets" % what)
-    if value.dim() != 4 or value.size(0) != B or value.size(2) != H or spatial_shapes.size(0) != L or \
-            level_start_index.numel() != L:
-        raise ValueError("%s: offsets / spatial_shapes do not match value (B,S,H,C)" % what)
-    S, C = value.size(1), value.size(3)
-    if grad_output.dtype != value.dtype or grad_output.numel() != B * Lq * H * C:
-        raise ValueError("%s: grad_output: %d elements of type %s expected" % (what, B * Lq * H * C, value.dtype))
-    if not _lib.box_bwd_boxes_ok(value.element_size(), _align_of(value, grad_output), (B, S, H, C, L, Lq, P)):
+    operands = (value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits)
+    # (grad_output: checked with the operands, before their types)
+    dims, (D, per_head, V, mode), _ = _boxes_operands(what, ValueError, None, operands, angle_mode,
+                                                      also=[(grad_output, "grad_output")])
+    B, _, H, C, L, Lq, P = dims
+    _boxes_upstream(what, ValueError, value, [("grad_output", grad_output, B * Lq * H * C)])
+    if not _boxes_ok(_lib.box_bwd_boxes_ok, value, (L, Lq, P), also=[grad_output]):
         raise ValueError("%s: no kernel for value %s, %d levels, %d queries, %d points a level at the alignment of "
                          "value and grad_output (box_backward_boxes_ok)" % (what, tuple(value.shape), L, Lq, P))
-    grad_offsets = torch.empty((B, Lq, H, L, V), dtype=torch.float32, device=value.device)
-    grad_rows = torch.empty((B, Lq, H, L, 5), dtype=torch.float32, device=value.device) if need_ref_grad else None
-    grad_logits = torch.empty((B, Lq, H, L * P), dtype=torch.float32, device=value.device)
-    _grid_call("boxattn_bwd_boxes_" + _SUFFIX[value.dtype], value, value, spatial_shapes, level_start_index,
-               ref_windows, D, per_head, offsets, V, mode, kernel_indices,
-               valid_ratios if valid_ratios is not None else 0, logits, grad_output, B, S, H, C, L, Lq, P,
-               grad_offsets, grad_rows if need_ref_grad else 0, grad_logits)
-    return grad_offsets, grad_rows, grad_logits
+    grads = _boxes_grads(value, (B, Lq, H, L), V, (B, Lq, H, L * P), need_ref_grad)
+    _boxes_call("boxattn_bwd_boxes_", operands, (D, per_head), (V, mode), (grad_output,), dims, grads)
+    return grads
