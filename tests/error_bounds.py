@@ -80,6 +80,36 @@ grad_loc jumps at cell edges and a sum cannot leave a point out: a point within 
 an integer coordinate has two legitimate own-axis gradients; want takes the float64 side, J = |the neighbouring
 cell's - that| goes into E of every element the point feeds (times the coefficient).  ``edge_share`` is the share of
 such points (callers assert <= EDGE_CAP), ``edge_dominated`` the share of elements whose bound is more than half J.
+
+The box kind's training step (``boxes_reference(kind="box", grad_out=...)``: grad_offsets (.., L, V), grad_ref_rows
+(.., L, 5), grad_logits (.., L P)) in the three angle modes, V = 4 or 5; g = grad_loc vr, l = kidx relu(size), the sums
+over the P points of a (b, q, h, l) row, sin and cos of the row's theta (1 and 0 in mode 0):
+  a_cx = sum gx,   a_cy = sum gy,   a_w = relu'(w) sum kx (gx cos + gy sin),   a_h = relu'(h) sum ky (gy cos - gx sin),
+  a_t = sum gx (-lx sin - ly cos) + gy (lx cos - ly sin)
+  grad_offsets = [a_cx rw / 8, a_cy rh / 8, a_w rw / 8, a_h rh / 8, a_t 2 pi / 16 (mode 1 only; else 0)]
+  grad_ref_rows = [a_cx, a_cy, a_cx off0 / 8 + a_w (1 + off2 / 8), a_cy off1 / 8 + a_h (1 + off3 / 8),
+                   a_t 2 pi (mode 1) | a_t (mode 2) | 0 (mode 0)]
+  grad_logits = a (Gw - sum_row a Gw)                         (a: the softmax over the row's L P logits, Gw: grad_attn)
+(d grid / d box through the rotation, and the softmax Jacobian, from the definitions of DESIGN.md 1 / 4.4).  A takes every
+factor by its absolute value -- |cos| and |sin| with their own values, every difference as a sum, and in a_t the size
+inside l as |size_ref| + |off / 8 size_ref| where the float32 size may be positive: the size is a difference, and its two
+roundings are then relative to something A holds.  E carries the points' E + W and the edge jumps J times the same
+coefficients, and three more terms: the float32 sine and cosine, each within dtheta + SINCOS_ABS of the float64 one (the
+ALLOWANCE of grid_reference again, not a measurement; test_gpu_boxes_error_bounds measures 0.49 ulp on one device), add
+(dtheta + SINCOS_ABS) sum |kx| (A_gx + A_gy) to a_w, the like to a_h and (dtheta + SINCOS_ABS) sum (|lx| + |ly|)
+(A_gx + A_gy) to a_t; a size whose float32 sign is not certain allows either relu' (the whole A of a_w / a_h into E) and
+either relu(size) in a_t (A covers it).  The weights' allowance enters grad_logits as (da + max da) a (A_Gw + sum a A_Gw).
+n is the points' largest n plus the reduction's roundings, counted from boxattn_grid.h (grid_grad_add, grid_grad_store) and
+the softmax backward of boxattn_pointwise.h:
+  mode 0, the box rows: P + 6 as above (g vr; kx g; the P-term sum; 1 + off / 8, the product, the sum of the row's two);
+  rotated, the box rows: P + 8 (two more: a product with cos or sin, the sum of the two);
+  the angle entries: P + 10 (g vr; the size's two; kx relu(w); the product with sin; the difference; the product with gx;
+    the sum of the two halves; the P-term sum; float32's 2 pi and the product with it; / 16 is exact);
+  grad_logits: L P + 3 (a Gw; the L P-term sum in any order; Gw - sum; the product with a).
+A fused multiply-add only removes roundings from these counts.  ``box_gradients`` redoes the reductions from the kept
+per-point planes with a wrong formula written into ``want`` (``mutation``: the tests of the bound).  The building blocks
+on their own -- ``grid_backward_reference``, ``softmax_backward_reference``, ``cell_logits_backward_reference`` -- are the
+same reductions on exact float32 upstream gradients (want = g, A = |g|, E = 0, n = 0).
 """
 
 import numpy as np
@@ -628,15 +658,22 @@ def _reduce_boxes(r, names, ref, off, kidx, vr, logits, k):
     for d in (goff, rows):
         d["n"][...] = n_out[..., None]
     rows["n"][..., 4] = 0
-    # ---- the 2 x 2 logits
+    glog = _reduce_cells(r[names[0]], r[names[1]] if len(names) > 1 else None, logits, k)
+    return {"grad_offsets": goff, "grad_ref_rows": rows, "grad_logits": glog}
+
+
+def _reduce_cells(sp, lvp, logits, k):
+    """The per-point planes want / A / E / n (B, Lq, H, L, k k) of grad_spatial (``sp``) and grad_level (``lvp``, or
+    None) -> grad_logits (B, Lq, H, L, 2, 2): the Jacobians of the two softmaxes over the 2 x 2 logits (module
+    docstring); a weight off by da adds (da + max da) times the A of its bracket to E; n: the points' largest plus
+    m^2 + 4 L + 8."""
+    lead = f64(logits).shape[:4]
     a, da, t, dt = cell_weights_reference(logits)
     m2 = (k // 2) ** 2
     L = a.shape[3]
     cells = lambda x: x.reshape(lead + (2, k // 2, 2, k // 2)).sum((-1, -3))
     row, lev = (-1, -2, -3), (-3,)
     glog = {}
-    sp = r[names[0]]
-    lvp = r[names[1]] if len(names) > 1 else None
     for m in ("want", "A", "E"):
         Gs = cells(sp[m])
         if m == "want":
@@ -659,13 +696,155 @@ def _reduce_boxes(r, names, ref, off, kidx, vr, logits, k):
     n_pt = sp["n"].max(-1) if lvp is None else np.maximum(sp["n"].max(-1), lvp["n"].max(-1))
     glog["n"] = np.broadcast_to((n_pt + m2 + 4 * L + 8)[..., None, None], glog["want"].shape).copy()
     glog["J"] = np.zeros_like(glog["want"])
-    return {"grad_offsets": goff, "grad_ref_rows": rows, "grad_logits": glog}
+    return glog
+
+
+def _reduce_grid(pl, n_pt, ref, off, kidx, vr, angle_mode, mutation=()):
+    """Per-point planes of grad_loc -- ``pl`` = {want, A, E, J}, each (B, Lq, H, L, P, 2), E with the weights' W and
+    the edge jumps J already in it -- and the points' term counts ``n_pt`` (the same shape, or 0) -> grad_offsets
+    (B, Lq, H, L, V) and grad_ref_rows (B, Lq, H, L, 5) in the three angle modes, V = 4 or 5 (the box terms of the
+    module docstring, "box kind").  ``mutation``: names of wrong formulas written into ``want`` only (the tests of the
+    bound): "no_relu_grad", ("flip_sin_h", level), "no_relu_t", "no_sixteenth"."""
+    ref, off, kidx = f64(ref), f64(off), f64(kidx)
+    lead = off.shape[:4]
+    P, V = kidx.shape[0], off.shape[-1]
+    rr = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]
+    col = lambda j: np.broadcast_to(rr[..., j], lead)
+    mut = {m if isinstance(m, str) else m[0]: m for m in mutation}
+    size = [col(2 + j) + off[..., 2 + j] / 8 * col(2 + j) for j in (0, 1)]
+    asz = [np.abs(col(2 + j)) + np.abs(off[..., 2 + j] / 8 * col(2 + j)) for j in (0, 1)]   # the difference as a sum
+    pos = [s > 0 for s in size]
+    # the sign of a float32 size may differ (two roundings of |asz|): either relu' is legitimate
+    unsure = [(np.abs(s) <= 2 * U32 * a) & (s != 0) for s, a in zip(size, asz)]
+    if angle_mode == 1:
+        theta = (col(4) + off[..., 4] / 16) * 2 * np.pi
+        dsc = 3 * U32 * (np.abs(col(4)) + np.abs(off[..., 4] / 16)) * 2 * np.pi + SINCOS_ABS     # dtheta + the allowance
+    elif angle_mode == 2:
+        theta, dsc = col(4), np.full(lead, SINCOS_ABS)
+    else:
+        theta, dsc = np.zeros(lead), np.zeros(lead)          # cos = 1 and sin = 0 are exact: no allowance
+    cs, sn = np.cos(theta)[..., None], np.sin(theta)[..., None]
+    acs, asn, dsc = np.abs(cs), np.abs(sn), dsc[..., None]
+    kx, ky = kidx[:, 0], kidx[:, 1]
+    akx, aky = np.abs(kx), np.abs(ky)
+    scale = f64(vr) if vr is not None else np.ones(2)                 # d / d (unscaled grid)
+    g = {m: [p[..., j] * (scale if m == "want" else np.abs(scale))[..., j] for j in (0, 1)] for m, p in pl.items()}
+    # local coordinates: l = kidx relu(size); by absolute values with the size's difference as a sum, and where the
+    # float32 size may be positive
+    lx, ly = kx * np.maximum(size[0], 0.0)[..., None], ky * np.maximum(size[1], 0.0)[..., None]
+    alx, aly = akx * (asz[0] * (pos[0] | unsure[0]))[..., None], aky * (asz[1] * (pos[1] | unsure[1]))[..., None]
+    term = {}                                                         # name -> (a_cx, a_cy, a_w, a_h, a_t), (B, Lq, H, L)
+    for m, (gx, gy) in g.items():
+        if m == "want":
+            sh = sn
+            if "flip_sin_h" in mut:
+                sh = np.broadcast_to(sn, lead + (1,)).copy()
+                sh[:, :, :, mut["flip_sin_h"][1]] *= -1.0
+            tx, ty = (kx * size[0][..., None], ky * size[1][..., None]) if "no_relu_t" in mut else (lx, ly)
+            a_w = (kx * (gx * cs + gy * sn)).sum(-1)
+            a_h = (ky * (gy * cs - gx * sh)).sum(-1)
+            if "no_relu_grad" not in mut:
+                a_w, a_h = pos[0] * a_w, pos[1] * a_h
+            a_t = (gx * (-tx * sn - ty * cs) + gy * (tx * cs - ty * sn)).sum(-1)
+        else:
+            a_w = pos[0] * (akx * (gx * acs + gy * asn)).sum(-1)
+            a_h = pos[1] * (aky * (gy * acs + gx * asn)).sum(-1)
+            a_t = (gx * (alx * asn + aly * acs) + gy * (alx * acs + aly * asn)).sum(-1)
+        term[m] = [gx.sum(-1), gy.sum(-1), a_w, a_h, a_t]
+    # E: the float32 sine and cosine (each within dsc), and a relu' that may go either way
+    gxa, gya = g["A"]
+    mag = gxa + gya
+    term["E"][2] = term["E"][2] + pos[0] * (dsc * akx * mag).sum(-1) + unsure[0] * (akx * (gxa * acs + gya * asn)).sum(-1)
+    term["E"][3] = term["E"][3] + pos[1] * (dsc * aky * mag).sum(-1) + unsure[1] * (aky * (gya * acs + gxa * asn)).sum(-1)
+    term["E"][4] = term["E"][4] + (dsc * (alx + aly) * mag).sum(-1)
+    goff = {m: np.zeros(lead + (V,)) for m in ("want", "A", "E", "J", "n")}
+    rows = {m: np.zeros(lead + (5,)) for m in ("want", "A", "E", "J", "n")}
+    two_pi = 2 * np.pi
+    for m, (a_cx, a_cy, a_w, a_h, a_t) in term.items():
+        ab = (lambda x: x) if m == "want" else np.abs
+        rw, rh = ab(col(2)), ab(col(3))
+        goff[m][..., 0], goff[m][..., 1] = a_cx * rw / 8, a_cy * rh / 8
+        goff[m][..., 2], goff[m][..., 3] = a_w * rw / 8, a_h * rh / 8
+        if V == 5 and angle_mode == 1:
+            goff[m][..., 4] = a_t * two_pi if (m == "want" and "no_sixteenth" in mut) else a_t * two_pi / 16
+        rows[m][..., 0], rows[m][..., 1] = a_cx, a_cy
+        rows[m][..., 2] = a_cx * ab(off[..., 0] / 8) + a_w * ab(1 + off[..., 2] / 8)
+        rows[m][..., 3] = a_cy * ab(off[..., 1] / 8) + a_h * ab(1 + off[..., 3] / 8)
+        if angle_mode:
+            rows[m][..., 4] = a_t * two_pi if angle_mode == 1 else a_t
+    n_max = np.max(n_pt, axis=(-1, -2)) if np.ndim(n_pt) else np.full(lead, float(n_pt))
+    for d in (goff, rows):
+        d["n"][...] = (n_max + P + (8 if angle_mode else 6))[..., None]
+        if angle_mode:
+            d["n"][..., 4:] = (n_max + P + 10)[..., None]
+    if not angle_mode:
+        rows["n"][..., 4] = 0
+        goff["n"][..., 4:] = 0
+    return {"grad_offsets": goff, "grad_ref_rows": rows}
+
+
+def _reduce_logits(gp, n_pt, a, da, mutation=()):
+    """Per-point planes want / A / E (..., N) of the weights' gradient Gw, their term counts ``n_pt`` (the same shape,
+    or 0), the row's softmax ``a`` and its relative allowance ``da`` -> grad_logits (..., N) = a (Gw - sum a Gw).
+    ``mutation`` (into ``want`` only): ("dot_first", m): the sum over the first m entries only; "drop_lowest": the
+    lowest-weight point's Gw left out."""
+    mut = {m if isinstance(m, str) else m[0]: m for m in mutation}
+    N = a.shape[-1]
+    Gw = gp["want"]
+    if "drop_lowest" in mut:
+        Gw = Gw.copy()
+        np.put_along_axis(Gw, np.argmin(a, -1)[..., None], 0.0, -1)
+    m = mut["dot_first"][1] if "dot_first" in mut else N
+    res = {"want": a * (Gw - (a * Gw)[..., :m].sum(-1, keepdims=True))}
+    bracket = lambda x: x + (a * x).sum(-1, keepdims=True)
+    res["A"] = a * bracket(gp["A"])
+    res["E"] = a * bracket(gp["E"]) + (da + da.max(-1, keepdims=True)) * a * bracket(gp["A"])
+    n_max = np.max(n_pt, axis=-1, keepdims=True) if np.ndim(n_pt) else float(n_pt)
+    res["n"] = np.broadcast_to(n_max + N + 3, a.shape).astype(np.float64)
+    res["J"] = np.zeros_like(res["want"])
+    return res
+
+
+def box_gradients(points, ref, off, kidx, vr, angle_mode, mutation=()):
+    """The three gradients of the box kind from the per-point planes boxes_reference keeps under "points" (so that a
+    mutation costs the reductions only)."""
+    res = _reduce_grid(points["loc"], points["n_loc"], ref, off, kidx, vr, angle_mode, mutation)
+    res["grad_logits"] = _reduce_logits(points["attn"], points["attn"]["n"], points["a"], points["da"], mutation)
+    return res
+
+
+def grid_backward_reference(ref, off, kidx, vr, angle_mode, grad_grid):
+    """ops.box_grid_backward on its own: ``grad_grid`` (B, Lq, H, L, P, 2) float32 is an exact input (want = g,
+    A = |g|, E = 0, no terms of its own), so what remains is the reduction's roundings and the rotation allowance."""
+    g = f64(grad_grid)
+    zero = np.zeros_like(g)
+    return _reduce_grid({"want": g, "A": np.abs(g), "E": zero, "J": zero}, 0, ref, off, kidx, vr, angle_mode)
+
+
+def softmax_backward_reference(attn, grad_attn):
+    """ops.softmax_backward on its own: float32 ``attn`` and ``grad_attn`` (..., N) are exact inputs."""
+    a, g = f64(attn), f64(grad_attn)
+    zero = np.zeros_like(g)
+    return _reduce_logits({"want": g, "A": np.abs(g), "E": zero}, 0, a, np.zeros_like(a))
+
+
+def cell_logits_backward_reference(logits, k, grad_spatial, grad_level):
+    """ops.instance_weights_backward on its own: float32 upstream gradients (B, Lq, H, L, k k) as exact inputs
+    (either may be None: zeros); the weights are recomputed from the logits, so their da / dt stay."""
+    shape = f64(logits).shape[:4] + (k * k,)
+
+    def planes(g):
+        g = np.zeros(shape) if g is None else f64(g).reshape(shape)
+        return {"want": g, "A": np.abs(g), "E": np.zeros(shape), "n": np.zeros(shape)}
+    return _reduce_cells(planes(grad_spatial), None if grad_level is None else planes(grad_level), logits, k)
 
 
 def boxes_reference(kind, value, shapes, lsi, ref, off, kidx, vr, logits, angle_mode=0, k=None, grad_out=None,
-                    grad_mask=None, loc=None, weights=None):
+                    grad_mask=None, loc=None, weights=None, mutation=()):
     """What the kernels that take boxes and logits must give, from their own inputs (float32 ref, off, kidx, vr,
-    logits; ``value`` and the upstream gradients as stored).  kind "box": logits (B, Lq, H, L P) -> {out}; kind
+    logits; ``value`` and the upstream gradients as stored).  kind "box": logits (B, Lq, H, L P) -> {out} and, with
+    grad_out, {grad_offsets (.., L, V), grad_ref_rows (.., L, 5), grad_logits (.., L P)} in any angle mode (planes want / A
+    / E / n / J), ``edge_share`` and ``points`` (what ``box_gradients`` reduces; ``mutation`` goes to it); kind
     "instance": logits (B, Lq, H, L, 2, 2), k -> {out, mask_out} and, with grad_out (grad_mask None: the mask output took
     no part), {grad_offsets, grad_ref_rows, grad_logits}.  ``loc`` / ``weights`` (a list) replace the model's own in
     ``want``: mutations, for the tests of the bound itself.  Also "grid" and
@@ -688,6 +867,14 @@ def boxes_reference(kind, value, shapes, lsi, ref, off, kidx, vr, logits, angle_
     if kind == "box":
         r = _reference(value, shapes, lsi, loc, ws, [gout], False, slack=dloc, dws=dws)
         res["out"] = r["out"]
+        if grad_out is not None:
+            g = r["grad_loc"]
+            res["points"] = dict(
+                loc={"want": g["want"], "A": g["A"], "E": g["E"] + g["W"], "J": g["J"]}, n_loc=g["n"],
+                attn={m: r["grad_attn"][m].reshape(B, Lq, Hh, L * P) for m in ("want", "A", "E", "n")},
+                a=ws[0].reshape(B, Lq, Hh, L * P), da=dws[0].reshape(B, Lq, Hh, L * P))
+            res.update(box_gradients(res["points"], ref, off, kidx, vr, angle_mode, mutation))
+            res["edge_share"] = g["edge_share"]
         return res
     if grad_out is None or grad_mask is not None:
         gmask = np.zeros((B, Lq, P, Hh, C)) if grad_mask is None else f64(grad_mask).reshape(B, Lq, P, Hh, C)

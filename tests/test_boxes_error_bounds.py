@@ -9,6 +9,17 @@ instance_weights_reference, boxes_reference) and the inputs of tests/test_gpu_bo
   * five mutations fail the bound where today's one-scale ``check`` at today's tolerances passes; a sixth (the softmax
     maximum over the first tile only) fails ``dw`` and, a softmax being shift invariant, stays inside the bound on ``out``;
   * every input keeps the cell-edge condition, and every geometry has elements that must be exactly zero.
+
+The box kind's training step (grad_offsets, grad_ref_rows, grad_logits in the three angle modes):
+  * the model's ``want`` agrees with float64 torch autograd through grid -> softmax -> bilinear sampling for the 16
+    flavours on two geometries, within a tolerance made of float64's unit roundoff and the model's own planes;
+  * the float32 chain on the CPU -- ``reduce_box_f32``: the reduction in the kernels' operation order -- stays within
+    the bound for every case of the GPU matrix, every case keeps the cell-edge condition with the locations' own slack
+    (one case re-seeded: test_gpu_boxes_error_bounds.BWD_RESEED), and every geometry has must-be-zero elements in all
+    three outputs; the backward building blocks restated in float32 numpy stay within theirs;
+  * six wrong formulas (relu' omitted, a sine term's sign, a_t without the relu, the / 16, a partial softmax-Jacobian
+    sum, a dropped gw) are all rejected by the bound; wrong everywhere, today's rule of
+    tests/test_gpu_box_boxes_backward.py rejects them too; wrong in one row, each has rows it accepts.
 """
 import itertools
 import math
@@ -443,3 +454,238 @@ def test_mutation_relu_gradient_omitted_in_grad_offsets():
         if gap(mutant, ref, {"float32": 1e-4}):          # (the gradients are float32 in every storage mode)
             return
     raise AssertionError("relu' omitted is nowhere missed by today's check")
+
+
+# ------------------------------------------------------------------ the box training step from boxes (box kind, gradients)
+BWD_NAMES = gpu_cases.GRAD_NAMES
+POINT_TOL = 1e-4             # today's rule for the three gradients (tests/test_gpu_box_boxes_backward.py: check at POINT_TOL)
+
+
+def reduce_box_f32(g, kidx, gloc, gattn, attn):
+    """The box kind's three gradients from float32 per-point gradients, float32 numpy in the kernels' operation order
+    (boxattn_grid.h grid_grad_add point by point, grid_grad_store; the softmax Jacobian of boxattn_pointwise.h): every
+    operation rounds once, no fused multiply-add."""
+    ref, off, vr, mode = g["ref"], g["off"], g["vr"], g["angle_mode"]
+    lead = off.shape[:4]
+    V = off.shape[-1]
+    r = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]
+    col = lambda j: np.broadcast_to(r[..., j], lead)
+    rw, rh = col(2), col(3)
+    w = rw + off[..., 2] / F(8) * rw
+    h = rh + off[..., 3] / F(8) * rh
+    sn, cs = np.zeros(lead, F), np.ones(lead, F)
+    two_pi = F(2) * F(math.pi)
+    if mode:
+        theta = ((col(4) + off[..., 4] / F(16)) * F(2) * F(math.pi) if mode == 1 else col(4)).astype(F)
+        sn, cs = np.sin(theta), np.cos(theta)
+    vx, vy = (vr[..., 0, 0], vr[..., 0, 1]) if vr is not None else (F(1), F(1))
+    wr, hr = np.maximum(w, F(0)), np.maximum(h, F(0))
+    gloc = gloc.astype(F)
+    a_cx, a_cy, a_w, a_h, a_t = (np.zeros(lead, F) for _ in range(5))
+    for p in range(kidx.shape[0]):
+        gx, gy = gloc[..., p, 0] * vx, gloc[..., p, 1] * vy
+        kx, ky = kidx[p]
+        a_cx = a_cx + gx
+        a_cy = a_cy + gy
+        a_w = a_w + kx * (gx * cs + gy * sn)
+        a_h = a_h + ky * (gy * cs - gx * sn)
+        lx, ly = kx * wr, ky * hr
+        a_t = a_t + (gx * (-lx * sn - ly * cs) + gy * (lx * cs - ly * sn))
+    a_w, a_h = np.where(w > 0, a_w, F(0)), np.where(h > 0, a_h, F(0))
+    go = [a_cx * rw / F(8), a_cy * rh / F(8), a_w * rw / F(8), a_h * rh / F(8)]
+    if V == 5:
+        go.append(a_t * two_pi / F(16) if mode == 1 else np.zeros(lead, F))
+    row_t = a_t * two_pi if mode == 1 else a_t if mode == 2 else np.zeros(lead, F)
+    rows = np.stack([a_cx, a_cy, a_cx * off[..., 0] / F(8) + a_w * (F(1) + off[..., 2] / F(8)),
+                     a_cy * off[..., 1] / F(8) + a_h * (F(1) + off[..., 3] / F(8)), row_t], -1)
+    goff = np.stack(go, -1)
+    attn, gattn = attn.astype(F).reshape(lead[:3] + (-1,)), gattn.astype(F).reshape(lead[:3] + (-1,))
+    glog = attn * (gattn - (attn * gattn).sum(-1, keepdims=True, dtype=F))
+    assert goff.dtype == rows.dtype == glog.dtype == F
+    return goff, rows, glog
+
+
+def box_chain_f32(g):
+    """The training step from boxes in float32 on the CPU: float32 grid and weights, the C oracle's float32 build for
+    the per-point gradients, float32 reductions."""
+    B, S, H, C, L, Lq, P = g["dims"]
+    kidx = gpu_cases.kernel_offsets(int(round(P ** 0.5)))
+    loc = c32(grid_f32(g["ref"], g["off"], kidx, g["vr"], g["angle_mode"]))
+    attn = c32(softmax_f32(g["logits"]).reshape(B, Lq, H, L, P))
+    _, gloc, gattn = oc.box_attn_backward(c32(gpu_cases.every_type(g["value"])), g["shapes"], g["lsi"], loc, attn,
+                                          c32(gpu_cases.bwd_upstream(g)))
+    return reduce_box_f32(g, kidx, np.asarray(gloc).reshape(loc.shape), np.asarray(gattn).reshape(attn.shape), attn)
+
+
+@pytest.mark.parametrize("geometry", gpu_cases.BOX_GEOMETRIES)
+def test_box_backward_chain_in_float32_is_within_the_bound(geometry):
+    """Every case of the GPU matrix: the reference's own arithmetic in float32 meets the bound, the inputs keep the
+    cell-edge condition (with the locations' own slack), and the model has elements that must be exactly zero."""
+    worst, edge, zeros, share = {}, {}, {n: 0 for n in BWD_NAMES}, 0.0
+    for C, flavour in itertools.product(gpu_cases.CHANNELS, gpu_cases.box_cases.FLAVOURS):
+        g = gpu_cases.bwd_problem(geometry, C, flavour)
+        ref = gpu_cases.bwd_reference(geometry, C, flavour)
+        what = "float32 chain, box backward from boxes: %s C=%d angle=%d D=%d per_head=%d vr=%d" % (
+            (geometry, C) + flavour[0] + flavour[1:])
+        share = max(share, ref["edge_share"])
+        assert ref["edge_share"] <= eb.EDGE_CAP, "%s: %.4f %% of the points on a cell edge" % (what,
+                                                                                              100 * ref["edge_share"])
+        for name, got in zip(BWD_NAMES, box_chain_f32(g)):
+            assert got.shape == ref[name]["want"].shape, name
+            worst[name] = max(worst.get(name, 0.0), eb.hold(got, ref[name], "float32", "none", "%s: %s" % (what, name)))
+            edge[name] = max(edge.get(name, 0.0), eb.edge_dominated(ref[name]))
+            zeros[name] += int(((ref[name]["A"] + ref[name]["E"]) == 0).sum())
+    assert all(zeros.values()), "%s: an output without elements that must be exactly zero: %s" % (geometry, zeros)
+    for name, w in worst.items():
+        print("error-bound | float32 chain on the CPU, box backward from boxes: %s (%d must-be-zero elements) | float32 "
+              "| %s | %.3f" % (geometry, zeros[name], name, w))
+    print("%s: worst share of points on a cell edge %.4f %% (cap %.1f %%); share of elements whose bound is more than "
+          "half edge allowance: %s" % (geometry, 100 * share, 100 * eb.EDGE_CAP,
+                                       ", ".join("%s %.4f" % kv for kv in edge.items())))
+
+
+@pytest.mark.parametrize("geometry", ["ragged", "odd_k"])
+def test_box_gradient_model_agrees_with_float64_autograd(geometry):
+    """grid -> softmax -> bilinear sampling in torch float64, differentiated, against the model's ``want``: all 16
+    flavours.  Both sides evaluate the same sums in float64; either is within (n + 8) 2^-53 A of the exact value (the
+    bound's own rounding term with float64's unit), and every float32 allowance in E that is not an edge jump -- the
+    sine and cosine, the weights, the pixel coordinates -- has a float64 counterpart 2^-29 = 2^-53 / 2^-24 times its size
+    or smaller (SINCOS_ABS 2^-22 against one ulp of a double-precision sine, 2^-52).  So
+    |model - autograd| <= 2 (n + 8) 2^-53 A + 2^-29 (E - J) per element; reference-window gradients are compared summed
+    over the levels (and heads) as autograd returns them, with the sums of the planes and that many more terms."""
+    from oracle import torch_fallback
+    worst = 0.0
+    for flavour in gpu_cases.box_cases.FLAVOURS:
+        g = gpu_cases.bwd_problem(geometry, 16, flavour)
+        model = gpu_cases.bwd_reference(geometry, 16, flavour)
+        B, S, H, C, L, Lq, P = g["dims"]
+        leaf = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64)).requires_grad_()
+        ref, off, logits = leaf(g["ref"]), leaf(g["off"]), leaf(g["logits"])
+        vr = None if g["vr"] is None else torch.from_numpy(g["vr"]).double()
+        kidx = torch.from_numpy(gpu_cases.kernel_offsets(int(round(P ** 0.5)))).double()
+        loc = _torch_grid(ref, off, kidx, vr, g["angle_mode"])
+        attn = torch.softmax(logits, -1).view(B, Lq, H, L, P)
+        out = torch_fallback.box_attn(torch.from_numpy(gpu_cases.every_type(g["value"])), g["shapes"], loc, attn)
+        (out * torch.from_numpy(gpu_cases.bwd_upstream(g))).sum().backward()
+        n5 = min(5, g["ref"].shape[-1])
+        axes = (3,) if g["ref"].ndim == 4 else (2, 3)
+        rows = model["grad_ref_rows"]
+        summed = {m: rows[m].sum(axes)[..., :n5] for m in ("want", "A", "E", "J")}
+        summed["n"] = rows["n"].max(axes)[..., :n5] + np.prod([rows["n"].shape[a] for a in axes])
+        assert not ref.grad.numpy()[..., n5:].any()              # (the values past the angle take no part)
+        for name, planes, want in (("offsets", model["grad_offsets"], off.grad.numpy()),
+                                   ("ref_windows", summed, ref.grad.numpy()[..., :n5]),
+                                   ("logits", model["grad_logits"], logits.grad.numpy())):
+            assert planes["want"].shape == want.shape, name
+            tol = 2 * (planes["n"] + 8) * 2.0 ** -53 * planes["A"] + 2.0 ** -29 * (planes["E"] - planes["J"])
+            err = np.abs(planes["want"] - want)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r = np.where(err == 0, 0.0, err / tol)
+            at = np.unravel_index(int(np.argmax(r)), r.shape)
+            worst = max(worst, float(r[at]))
+            assert r[at] <= 1.0, "%s %s: %s at %s: model %.17g, autograd %.17g, allowed %.3e" % (
+                geometry, flavour, name, at, planes["want"][at], want[at], tol[at])
+    print("%s: worst |model - autograd| / float64 tolerance %.3f" % (geometry, worst))
+
+
+def test_backward_building_blocks_in_float32_are_within_the_bound():
+    """ops.box_grid_backward, ops.softmax_backward and ops.instance_weights_backward on their own, restated in float32
+    numpy on the inputs of the GPU tests: exact float32 upstream gradients, so the bound is the reduction's roundings,
+    the rotation allowance and the weights' dw alone."""
+    worst = {}
+    for P, (angle_mode, per_head, with_vr) in itertools.product(gpu_cases.GRID_POINTS, gpu_cases.GRID_FLAVOURS):
+        g = gpu_cases.grid_problem(P, angle_mode, per_head, with_vr)
+        gg = gpu_cases.grid_upstream(P, angle_mode, per_head, with_vr)
+        ref = eb.grid_backward_reference(g["ref"], g["off"], g["kidx"], g["vr"], angle_mode, gg)
+        one = np.ones(g["off"].shape[:3] + (1,), F)
+        goff, rows, _ = reduce_box_f32(g, g["kidx"], gg, one, one)
+        for name, got in (("grad_offsets", goff), ("grad_ref_rows", rows)):
+            what = "box_grid_backward P=%d angle=%d per_head=%d vr=%d: %s" % (P, angle_mode, per_head, with_vr, name)
+            worst[name] = max(worst.get(name, 0.0), eb.hold(got, ref[name], "float32", "none", what))
+    for rows_, n in itertools.product(gpu_cases.SOFTMAX_BWD_ROWS, gpu_cases.SOFTMAX_BWD_LENGTHS):
+        a, gw = gpu_cases.softmax_bwd_problem(rows_, n)
+        got = a * (gw - (a * gw).sum(-1, keepdims=True, dtype=F))
+        ref = eb.softmax_backward_reference(a, gw)
+        for store in eb.STORE:
+            worst["softmax " + store] = max(worst.get("softmax " + store, 0.0),
+                                            eb.hold(eb.round_to(got, store), ref, store, "none",
+                                                    "softmax_backward rows=%d n=%d" % (rows_, n)))
+    for L, k in itertools.product((1, 5, 16), KERNEL_SIZES):
+        z = gpu_cases.cell_rows(L)
+        gs, gl = gpu_cases.cell_upstream(L, k)
+        for which, (s, l) in (("both", (gs, gl)), ("spatial", (gs, None)), ("level", (None, gl))):
+            ref = eb.cell_logits_backward_reference(z, k, s, l)
+            _, _, got = reduce_f32(dict(ref=np.zeros((1, 8, 4), F), off=np.zeros((1, 8, 1, L, 4), F), vr=None, logits=z), k,
+                                   np.zeros((1, 8, 1, L, k * k, 2), F), np.zeros_like(gs) if s is None else s, l)
+            worst["cells " + which] = max(worst.get("cells " + which, 0.0),
+                                          eb.hold(got, ref, "float32", "none", "cells L=%d k=%d %s" % (L, k, which)))
+    print("float32 numpy building blocks, worst err / bound: %s" % ", ".join("%s %.3f" % kv for kv in worst.items()))
+
+
+# ---- mutations of the box kind's gradients: written into ``want``, held against the unmutated reference
+def todays_rule(got, want):
+    """tests/test_gpu_box_boxes_backward.py: |got - want| <= 1e-4 (max(1, rms(want)) + |want|)."""
+    return passes_todays_check(got, want, POINT_TOL)
+
+
+def judge(name, mutant, ref):
+    """The float32 rounding of the mutant's exact value against the unmutated reference -> (the bound rejects the
+    mutant, today's rule accepts it, rows with a gap, rows changed).  Both checks are per element, so a kernel that is
+    wrong in one row only -- one (b, q, h, l) box, one (b, q, h) row of logits: a lane, a level slot -- is judged from
+    the same figures: such a row has a gap if the bound rejects an element of it and today's rule accepts them all."""
+    got = eb.round_to(mutant["want"], "float32")
+    want = ref["want"]
+    r, err, _ = eb.ratio(got, ref, "float32", "none")
+    outside, passes = bool((r > 1).any()), todays_rule(got, want)
+    fine_today = err / (max(1.0, float(np.sqrt(np.mean(want * want)))) + np.abs(want)) <= POINT_TOL      # ``check``
+    assert bool(fine_today.all()) == passes
+    changed = (mutant["want"] != want).any(-1)
+    gaps = (r > 1).any(-1) & fine_today.all(-1)
+    print("mutation | %s | worst err / bound %.3g | everywhere: the bound %s, today's rule %s | in one row: a gap in %d "
+          "of the %d rows it changes" % (name, float(r.max()), "rejects" if outside else "ACCEPTS",
+                                         "accepts" if passes else "rejects", int(gaps.sum()), int(changed.sum())))
+    return outside, passes, int(gaps.sum()), int(changed.sum())
+
+
+def bwd_mutants(geometry, flavour, mutation, C=32):
+    g = gpu_cases.bwd_problem(geometry, C, flavour)
+    ref = gpu_cases.bwd_reference(geometry, C, flavour)
+    a = gpu_cases.bwd_model_args(g)
+    return g, ref, eb.box_gradients(ref["points"], a[4], a[5], a[6], a[7], a[9], mutation)
+
+
+ROTATED = ((1, 5), False, True)
+# name -> (geometry, flavour, the mutation, the outputs it changes): (i) relu' omitted in a rotated case, (ii) the sine
+# term of a_h with its sign flipped on one level, (iii) a_t from kidx size without the relu, (iv) grad_offsets[4] without
+# the / 16, (v) the Jacobian's sum a gw over the first 8 of 16 levels, (vi) the lowest-weight point's gw dropped from its row
+MUTATIONS = {
+    "i_relu_grad_omitted": ("model", ROTATED, ("no_relu_grad",), ("grad_offsets", "grad_ref_rows")),
+    "ii_sine_of_a_h_flipped_on_level_1": ("model", ROTATED, (("flip_sin_h", 1),), ("grad_offsets", "grad_ref_rows")),
+    "iii_a_t_without_the_relu": ("model", ROTATED, ("no_relu_t",), ("grad_offsets", "grad_ref_rows")),
+    "iv_angle_offset_without_the_sixteenth": ("model", ROTATED, ("no_sixteenth",), ("grad_offsets",)),
+    "v_jacobian_sum_over_8_of_16_levels": ("sixteen_levels", ROTATED, (("dot_first", 32),), ("grad_logits",)),
+    "vi_lowest_weight_gw_dropped": ("model", ROTATED, ("drop_lowest",), ("grad_logits",)),
+}
+# The table of DESIGN.md 5.  Wrong everywhere, every one of the six is rejected by the bound AND by today's rule on
+# these inputs (the gradients are of order 0.1 ... 10, far above the rule's floor of 1e-4).  Wrong in one row only, every
+# one has rows that today's rule accepts and the bound rejects (10, 3, 11, 1, 1 and 47 in the first output each changes).
+
+
+@pytest.mark.parametrize("name", sorted(MUTATIONS))
+def test_mutation_of_the_box_gradients(name):
+    """Each wrong formula, in every output it changes: the bound rejects it.  What today's rule says is printed and must
+    be what DESIGN.md 5 records: it rejects the formula that is wrong everywhere, and accepts it in some single row
+    that the bound rejects."""
+    geometry, flavour, mutation, outputs = MUTATIONS[name]
+    g, ref, mutant = bwd_mutants(geometry, flavour, mutation)
+    if mutation == ("no_relu_t",):
+        assert (np.concatenate([1 + g["off"][..., 2] / 8, 1 + g["off"][..., 3] / 8]) < 0).any(), "no size below zero"
+    everywhere, one_row = [], 0
+    for out in outputs:
+        assert (mutant[out]["want"] != ref[out]["want"]).any(), "%s changes nothing in %s" % (name, out)
+        outside, passes, gaps, changed = judge("%s | %s" % (name, out), mutant[out], ref[out])
+        assert outside, "%s in %s is inside the bound" % (name, out)
+        everywhere.append(passes)
+        one_row += gaps
+    assert not any(everywhere), "%s: today's rule accepts it everywhere in %s of %s" % (name, everywhere, outputs)
+    assert one_row, "%s: no single row that today's rule accepts and the bound rejects" % name
