@@ -166,7 +166,7 @@ def needs_build():
 def build(force=False, verbose=False, extra_flags=(), out_path=None):
     """Cross-compile the HIP library for gfx950 in-tree (works without a GPU): one object per
     translation unit (compiled in parallel), then one shared library.  ``extra_flags`` /
-    ``out_path``: tuning builds next to the product (tools/build_variants.sh)."""
+    ``out_path``: a second build next to the product (the step tools' --variant, tools/kernel_diff.py)."""
     variant = out_path is not None
     out_path = out_path or LIB_PATH
     if not (force or variant or needs_build()):
@@ -207,8 +207,8 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    # BOXATTN_HIP_LIB: load another build of the same library (kernel tuning experiments,
-    # tools/build_variants.sh); it must export the same ABI.
+    # BOXATTN_HIP_LIB: load another build of the same library (kernel tuning experiments, built with
+    # `python -m boxer_amd._lib --out PATH`); it must export the same ABI.
     path = os.environ.get("BOXATTN_HIP_LIB") or LIB_PATH
     if not os.path.exists(path):
         raise RuntimeError(

@@ -53,10 +53,7 @@ namespace boxattn {
 // 1 + 3: count / fill as launches of their own (a backward that plans for itself, maps too big for the
 //        riders).  grid = (workgroups, slices), block kBinThreads, dynamic LDS nblk ints.
 // ---------------------------------------------------------------------------------------
-#ifndef BOXATTN_TUNE_BIN_THREADS
-#define BOXATTN_TUNE_BIN_THREADS 512
-#endif
-constexpr int kBinThreads = BOXATTN_TUNE_BIN_THREADS;
+constexpr int kBinThreads = 512;
 template <int BW, int BH, bool FILL, bool WIDE, int PT, bool GRP = false>
 __global__ __launch_bounds__(kBinThreads) void bin_kernel(const float *__restrict__ loc,
                                                   const float *__restrict__ w_sp, BinPlan plan,
@@ -360,14 +357,9 @@ __global__ __launch_bounds__(kScanThreads) void bin_scan_emit_kernel(int *__rest
 //    grid = (waves per slice, slices); waves are persistent and pull items from the slice's
 //    queue.  A block is 8x4 pixels; in the summation phase lane = (pixel, channel half).
 // ---------------------------------------------------------------------------------------
-#ifndef BOXATTN_TUNE_ABLATE
-#define BOXATTN_TUNE_ABLATE 0      // timing experiments only (wrong results): 1 no list walk,
-#endif                             // 2 no ranks / entries, 3 no row fetch + stage, 4 walk without row reads
-#ifndef BOXATTN_TUNE_ACC_WPE
-#define BOXATTN_TUNE_ACC_WPE 1
-#endif
+constexpr int kAccWpe = 1;
 template <typename ST, int C, bool INST, int RPL = 1, bool WIDE = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BOXATTN_TUNE_ACC_WPE)))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kAccWpe)))
 void binned_accumulate_kernel(
     const ST *__restrict__ grad_out, const ST *__restrict__ grad_mask,
     const float *__restrict__ loc, const float *__restrict__ w_sp,
@@ -385,20 +377,14 @@ void binned_accumulate_kernel(
     // two upstream rows of a record are combined while staging, t = a_s * g + a_l * g_mask
     // (reference instance_attn_kernel.cuh:139), as fp32 -- one staged row and one weight per
     // entry, exactly the box flavour's walk, instead of two of each.
-#ifndef BOXATTN_TUNE_STAGE_F32
-#define BOXATTN_TUNE_STAGE_F32 0
-#endif
-    constexpr bool kCvt = INST || (BOXATTN_TUNE_STAGE_F32 && sizeof(ST) == 2);   // staged as fp32
+    constexpr bool kCvt = INST;                        // staged as fp32
     constexpr int SB = kCvt ? 4 : (int)sizeof(ST);     // bytes per staged element
     constexpr int RS = C * SB + 16;                    // LDS row stride: row + pad (banks)
     constexpr int LPR = ROWB / 16;                     // lanes that fetch one row, 16 B each
     constexpr int RPP = 64 / LPR;                      // rows staged per pass
     constexpr int NPASS = R / RPP;                     // staging passes per round
     constexpr int EPL = 16 / (int)sizeof(ST);          // elements per fetched 16-byte piece
-#ifndef BOXATTN_TUNE_UNR
-#define BOXATTN_TUNE_UNR 2
-#endif
-    constexpr int UNR = BOXATTN_TUNE_UNR;              // list entries handled per step
+    constexpr int UNR = 2;                             // list entries handled per step
     typedef float2 Entry;                              // {weight, LDS offset of the staged row}
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));  // plain vector: stays in VGPRs
     constexpr int NQ = CH * SB / 16;                   // 16-byte pieces of a lane's half row
@@ -559,15 +545,15 @@ void binned_accumulate_kernel(
 #pragma unroll
         for (int i = 0; i < RPL; ++i) { xy_n[i] = make_float2(0.f, 0.f); as_n[i] = al_n[i] = 0.f; }
         fetch_point(fetch_ids(item.y), xy_c, as_c, al_c);
-        if (BOXATTN_TUNE_ABLATE != 3) { BOXATTN_FETCH_ROWS() }
+        BOXATTN_FETCH_ROWS()
         Ids rec_n = fetch_ids(item.y + R);
-        if (BOXATTN_TUNE_ABLATE != 3) { BOXATTN_STAGE_ROWS(as_c, al_c) }   // round 0 staged directly
+        BOXATTN_STAGE_ROWS(as_c, al_c)                 // round 0 staged directly
         for (int rr = item.y; rr < item.z; rr += R) {
             const int n = min(R, item.z - rr);
             const bool more = rr + R < item.z;         // wave-uniform
             if (more) {                                // issue everything round r+1 needs
                 fetch_point(rec_n, xy_n, as_n, al_n);
-                if (BOXATTN_TUNE_ABLATE != 3) { BOXATTN_FETCH_ROWS() }
+                BOXATTN_FETCH_ROWS()
                 rec_n = fetch_ids(rr + 2 * R);
             }
             // ---- phase 1: lane = RPL records: geometry, rank inside the destination pixel
@@ -595,7 +581,7 @@ void binned_accumulate_kernel(
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     rank[i][k] = 0;
-                    if (BOXATTN_TUNE_ABLATE != 2 && pixk[i][k] < PB)
+                    if (pixk[i][k] < PB)
                         rank[i][k] = atomicAdd(&pcnt[pixk[i][k]], 1);
                 }
             wave_lds_sync();
@@ -629,7 +615,7 @@ void binned_accumulate_kernel(
             for (int i = 0; i < RPL; ++i)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    if (BOXATTN_TUNE_ABLATE == 2 || pixk[i][k] >= PB) continue;
+                    if (pixk[i][k] >= PB) continue;
                     const float slot = __int_as_float((i * 64 + lane) * RS);   // row's LDS offset
                     // instance attention: both weights are already in the staged row
                     ent[epos[i][k]] = make_float2(INST ? wk[i][k] : wk[i][k] * as_c[i], slot);
@@ -641,7 +627,7 @@ void binned_accumulate_kernel(
             Entry en_n[UNR];                           // entries of the next step (prefetched)
 #pragma unroll
             for (int u = 0; u < UNR; ++u) en_n[u] = ent[e0 + u];
-            for (int e = e0; e < (BOXATTN_TUNE_ABLATE == 1 ? e0 : e1); e += UNR) {
+            for (int e = e0; e < e1; e += UNR) {
                 Entry en[UNR];
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
@@ -663,7 +649,7 @@ void binned_accumulate_kernel(
                         &gstage[jj[u] + half * (CH * SB)]);
 #pragma unroll
                     for (int q = 0; q < NQ; ++q)
-                        rw[u][q] = BOXATTN_TUNE_ABLATE == 4 ? u32x4{(unsigned)jj[u], 1u, 2u, 3u} : gp[q];
+                        rw[u][q] = gp[q];
                 }
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
@@ -675,7 +661,7 @@ void binned_accumulate_kernel(
             }
             wave_lds_sync();
             if (more) {                                // stage round r+1 (rows have arrived)
-                if (BOXATTN_TUNE_ABLATE != 3) { BOXATTN_STAGE_ROWS(as_n, al_n) }
+                BOXATTN_STAGE_ROWS(as_n, al_n)
 #pragma unroll
                 for (int i = 0; i < RPL; ++i) { xy_c[i] = xy_n[i]; as_c[i] = as_n[i]; al_c[i] = al_n[i]; }
             }

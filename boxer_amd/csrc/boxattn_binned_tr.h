@@ -31,28 +31,14 @@
 
 namespace boxattn {
 
-#ifndef BOXATTN_TUNE_TR_WPE
-#define BOXATTN_TUNE_TR_WPE 4
-#endif
-#ifndef BOXATTN_TUNE_REC_AHEAD
-#define BOXATTN_TUNE_REC_AHEAD 1       // float32 kernel: request the next item's first records while the current item is summed
-#endif
-// The group-record round (GRP below), one switch per cut; every one leaves grad_value bitwise what it was
-#ifndef BOXATTN_TUNE_GRP_FOLD
-#define BOXATTN_TUNE_GRP_FOLD 1        // the lane's tile column folded into the column terms and ONE dump offset: 16 adds less
-#endif
-#ifndef BOXATTN_TUNE_GRP_ALIGNED
-#define BOXATTN_TUNE_GRP_ALIGNED 1     // a wave of axis-parallel 2 x 2 grids locates two x and two y, not eight coordinates
-#endif
-#ifndef BOXATTN_TUNE_GRP_TAIL
-#define BOXATTN_TUNE_GRP_TAIL 1        // an item's last round runs ceil(remaining / 16) K-steps, not four
-#endif
-#ifndef BOXATTN_TUNE_GRP_EARLY_EXIT
-#define BOXATTN_TUNE_GRP_EARLY_EXIT 1  // workgroups without an item leave before the tile is cleared; the clear in 16-byte stores
-#endif
-#ifndef BOXATTN_TUNE_GRP_PINGPONG
-#define BOXATTN_TUNE_GRP_PINGPONG 1    // the two point sets swap roles across the round pair instead of a 12-register copy
-#endif
+constexpr int kTrWpe = 4;
+// The group-record round (GRP below) was cut in five steps, each measured with a build switch of its own, since removed;
+// every one leaves grad_value bitwise what it was:
+//   fold        the lane's tile column folded into the column terms and ONE dump offset: 16 adds less
+//   aligned     a wave of axis-parallel 2 x 2 grids locates two x and two y, not eight coordinates
+//   tail        an item's last round runs ceil(remaining / 16) K-steps, not four
+//   early exit  workgroups without an item leave before the tile is cleared; the clear in 16-byte stores
+//   ping-pong   the two point sets swap roles across the round pair instead of a 12-register copy
 
 typedef __bf16 tr_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float tr_f32x16 __attribute__((ext_vector_type(16)));
@@ -98,7 +84,7 @@ struct GroupPts {
 constexpr int kGrpQuadB = 33 * 16;             // bytes of a record quad's row of the float32 tile: 32 pixels + the dump pixel
 constexpr int kGrpTileB = 16 * kGrpQuadB;
 template <typename ST, int C, bool INST = false, bool GRP = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (INST ? 2 : GRP ? 3 : BOXATTN_TUNE_TR_WPE) : 1))) void binned_accumulate_tr_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (INST ? 2 : GRP ? 3 : kTrWpe) : 1))) void binned_accumulate_tr_kernel(
     const ST *__restrict__ grad_out, unsigned grad_out_bytes, BinPlan plan, int S, int H, int Lq,
     const int4 *__restrict__ items, const int *__restrict__ n_items,
     const int *__restrict__ records, ST *__restrict__ grad_value, float *__restrict__ partials, ChunkCombine cc,
@@ -152,12 +138,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
         // The grid is sized by the host's bound on the items (kAccWgCap a slice); at BoxeR-R50 shapes more than half of its
         // workgroups have no item.  Those leave here, before the 33 rounds of the dword clear below, and the others clear
         // the tile sixteen bytes a lane (the surplus waves issued a tenth of the kernel's instructions).
-        if (BOXATTN_TUNE_GRP_EARLY_EXIT && worker >= n_it) return;
-        if (BOXATTN_TUNE_GRP_EARLY_EXIT) {
-            for (int i = lane; i < kGrpTileB / 16; i += 64) reinterpret_cast<u32x4 *>(at)[i] = u32x4{0u, 0u, 0u, 0u};
-        } else {
-            for (int i = lane; i < (int)(sizeof(at) / 4); i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
-        }
+        if (worker >= n_it) return;
+        for (int i = lane; i < kGrpTileB / 16; i += 64) reinterpret_cast<u32x4 *>(at)[i] = u32x4{0u, 0u, 0u, 0u};
     } else {
         for (int i = lane; i < (int)(sizeof(at) / 4); i += 64) reinterpret_cast<unsigned int *>(at)[i] = 0u;
     }
@@ -279,13 +261,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
                 // BoxeR's grid is centre +- size / 4: points 0, 2 share x, 1, 3 share x, 0, 1 share y and 2, 3 share y BIT FOR
                 // BIT (idle lanes: all zeros).  A wave of such groups locates two rows and two columns; the sixteen slots are
                 // row[i] + col[j], the products of the weights those of the per-point code below on the same numbers.
-                bool aligned = false;
-                if (BOXATTN_TUNE_GRP_ALIGNED) {
-                    const bool same = pc.xa.x == pc.xb.x && pc.xa.z == pc.xb.z && pc.xa.y == pc.xa.w && pc.xb.y == pc.xb.w &&
-                                      (kProductMasks >> mask & 1u) != 0u;
-                    aligned = __builtin_amdgcn_ballot_w64(!same) == 0ull;
-                }
-                if (aligned) {
+                const bool same = pc.xa.x == pc.xb.x && pc.xa.z == pc.xb.z && pc.xa.y == pc.xa.w && pc.xb.y == pc.xb.w &&
+                                  (kProductMasks >> mask & 1u) != 0u;
+                if (__builtin_amdgcn_ballot_w64(!same) == 0ull) {
                     const unsigned ys2[2] = {pc.xa.y, pc.xb.y}, xs2[2] = {pc.xa.x, pc.xa.z};
                     float hh[2], lh[2], hw[2], lw[2];
                     int rt[2][2], ct[2][2];
@@ -338,17 +316,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
                         // byte offsets of the corners' pixels (16 bytes each, 8 a block row), kBig when outside the block
                         const int r0 = (unsigned)py < (unsigned)bh ? __mul24(py, BW * 16) : kBig;
                         const int r1 = (unsigned)(py + 1) < (unsigned)bh ? __mul24(py, BW * 16) + BW * 16 : kBig;
-                        if (BOXATTN_TUNE_GRP_FOLD) {       // the lane's column inside the column terms; one dump offset per lane
-                            const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, 16) + lane_at : kBig;
-                            const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, 16) + lane_at + 16 : kBig;
-                            slot[k][0] = min(r0 + c0, dump_lane); slot[k][1] = min(r0 + c1, dump_lane);
-                            slot[k][2] = min(r1 + c0, dump_lane); slot[k][3] = min(r1 + c1, dump_lane);
-                        } else {
-                            const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, 16) : kBig;
-                            const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, 16) + 16 : kBig;
-                            slot[k][0] = lane_at + min(r0 + c0, PB * 16); slot[k][1] = lane_at + min(r0 + c1, PB * 16);
-                            slot[k][2] = lane_at + min(r1 + c0, PB * 16); slot[k][3] = lane_at + min(r1 + c1, PB * 16);
-                        }
+                        // the lane's column inside the column terms; one dump offset per lane
+                        const int c0 = (unsigned)px < (unsigned)bw ? __mul24(px, 16) + lane_at : kBig;
+                        const int c1 = (unsigned)(px + 1) < (unsigned)bw ? __mul24(px, 16) + lane_at + 16 : kBig;
+                        slot[k][0] = min(r0 + c0, dump_lane); slot[k][1] = min(r0 + c1, dump_lane);
+                        slot[k][2] = min(r1 + c0, dump_lane); slot[k][3] = min(r1 + c1, dump_lane);
                     }
                 }
                 // The four corners of ONE point are four pixels (or the dump pixel, whose content nobody reads): point 0 is
@@ -393,7 +365,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
                 // idle lanes only -- to the dump pixel -- and their rows are zeros: no tile read, split, clear, operand
                 // read or product for them (a product of zeros leaves the sums what they are).
                 const int n_k = more ? R / 16 : (item.z - rr + 15) >> 4;      // wave-uniform
-                if (BOXATTN_TUNE_GRP_TAIL && n_k < R / 16) {
+                if (n_k < R / 16) {
                     for (int t = 0; t < n_k; ++t) {
                         char *fp = reinterpret_cast<char *>(at) + f_off + 4 * t * kGrpQuadB;
                         const float4 f0 = *reinterpret_cast<const float4 *>(fp);
@@ -440,7 +412,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
                 }
                 if (more) {          // the next round's rows and points have arrived
                     stage_rows(next);
-                    if (!BOXATTN_TUNE_GRP_PINGPONG) pc = pn;
                     rec_c = rec_n; rec_n = rec_n2; rec_n2 = rec_n3;
                 }
                 wave_lds_sync();
@@ -448,8 +419,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
             for (int rr = item.y; rr < item.z; rr += 2 * R) {
                 round(rr, grow_a, grow_b, pts_a, pts_b);
                 if (rr + R >= item.z) break;
-                if (BOXATTN_TUNE_GRP_PINGPONG) round(rr + R, grow_b, grow_a, pts_b, pts_a);
-                else round(rr + R, grow_b, grow_a, pts_a, pts_b);
+                round(rr + R, grow_b, grow_a, pts_b, pts_a);
             }
         } else {
             // software pipeline over rounds of 64 records: the records are read three rounds ahead, their
@@ -675,16 +645,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C <= 32 ? (I
                     piece_hi = u32x4{s2[0], s3[0], s2[1], s3[1]};
                 }
                 const int c_lo = cb * 32 + 8 * kb, c_hi = cb * 32 + 16 + 8 * kb;
-#ifndef BOXATTN_TUNE_GV_NT
-#define BOXATTN_TUNE_GV_NT 0       // grad_value rows with non-temporal stores (nobody on the GPU reads them soon)
-#endif
-                if (BOXATTN_TUNE_GV_NT) {
-                    if (live && c_lo < C) __builtin_nontemporal_store(piece_lo, reinterpret_cast<u32x4 *>(dst + c_lo));
-                    if (live && c_hi < C) __builtin_nontemporal_store(piece_hi, reinterpret_cast<u32x4 *>(dst + c_hi));
-                } else {
-                    if (live && c_lo < C) *reinterpret_cast<u32x4 *>(dst + c_lo) = piece_lo;
-                    if (live && c_hi < C) *reinterpret_cast<u32x4 *>(dst + c_hi) = piece_hi;
-                }
+                // (plain stores: grad_value rows with non-temporal stores -- nobody on the GPU reads them soon -- were
+                // measured with a build switch, since removed, and not adopted)
+                if (live && c_lo < C) *reinterpret_cast<u32x4 *>(dst + c_lo) = piece_lo;
+                if (live && c_hi < C) *reinterpret_cast<u32x4 *>(dst + c_hi) = piece_hi;
             }
         } else {
             // a chunk: fp32 partial tile; the block's last chunk to finish sums them (chunk_finish)
@@ -798,7 +762,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INST ? 2 : 3
     // round trips -- its records, then the rows they name -- in front of its first product; C2 float32 step -1 %)
     const int4 *rec_s = reinterpret_cast<const int4 *>(records) + (size_t)s * plan.rec_cap;
     int4 rec_first = make_int4(-1, 0, 0, 0);
-    if (BOXATTN_TUNE_REC_AHEAD && worker < n_it && item_n.y + lane < item_n.z) rec_first = rec_s[item_n.y + lane];
+    if (worker < n_it && item_n.y + lane < item_n.z) rec_first = rec_s[item_n.y + lane];
     for (int it = worker; it < n_it; it += workers) {
         const int4 item = item_n;
         item_n = my_items[min(it + workers, plan.item_cap - 1)];
@@ -850,13 +814,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INST ? 2 : 3
             x1 -= __uint_as_float(pk & 0xffff0000u);
             return pk;
         };
-        int4 rec_c = BOXATTN_TUNE_REC_AHEAD ? rec_first : fetch_rec(item.y);
+        int4 rec_c = rec_first;
         int4 rec_n = fetch_rec(item.y + R), rec_n2 = fetch_rec(item.y + 2 * R);
         fetch_rows(rec_c);
-        if (BOXATTN_TUNE_REC_AHEAD) {
-            rec_first = make_int4(-1, 0, 0, 0);
-            if (it + workers < n_it && item_n.y + lane < item_n.z) rec_first = rec_s[item_n.y + lane];
-        }
+        rec_first = make_int4(-1, 0, 0, 0);
+        if (it + workers < n_it && item_n.y + lane < item_n.z) rec_first = rec_s[item_n.y + lane];
         for (int rr = item.y; rr < item.z; rr += R) {
             const bool more = rr + R < item.z;         // wave-uniform
             int4 rec_n3 = make_int4(-1, 0, 0, 0);

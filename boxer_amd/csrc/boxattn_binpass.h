@@ -48,10 +48,8 @@ __device__ __forceinline__ void bin_pass_body(int *hist, BinLevel *s_lv, const f
     const float2 *loc2 = reinterpret_cast<const float2 *>(loc);
     static_assert(PT == 1 || PT == 4, "points per thread and step");
     static_assert(!GRP || (PT == 4 && !WIDE), "a group is the four points of one (query, level)");
-#ifndef BOXATTN_TUNE_BIN_U
-#define BOXATTN_TUNE_BIN_U 2
-#endif
-    constexpr int U = PT == 4 ? BOXATTN_TUNE_BIN_U : 4;     // groups of PT points per thread per step (loads in flight)
+    constexpr int kBinU = 2;
+    constexpr int U = PT == 4 ? kBinU : 4;    // groups of PT points per thread per step (loads in flight)
     const size_t pid0 = (((size_t)b * Lq + q0) * H + h) * LP;     // first point of query q0
     const size_t qstride = (size_t)H * LP * qstep;           // points between this WG's queries
     const int LPG = LP / PT, n_grp = n_q * LPG;               // groups per query, groups of this WG
@@ -197,18 +195,7 @@ struct BinRide {
     int flavour;             // kRideWide | kRideInterleave | kRidePt4
     RideGrid grid;           // grid.n_riders == 0: no riders in this launch
     SpecRide spec;           // flavour & kRideSpec
-    unsigned long long *trace;   // builds with BOXATTN_RIDE_TRACE: 8 s_memrealtime stamps per rider (tools/gpu_ride_trace.py)
 };
-#ifndef BOXATTN_RIDE_TRACE
-#define BOXATTN_RIDE_TRACE 0
-#endif
-#define RIDE_STAMP(k_)                                                                              \
-    do {                                                                                            \
-        if (BOXATTN_RIDE_TRACE && r.trace && threadIdx.x == 0) {                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                      \
-            r.trace[(size_t)id * 8 + (k_)] = __builtin_amdgcn_s_memrealtime();                      \
-        }                                                                                           \
-    } while (0)
 
 // LDS of a rider: [histogram: kRideMaxBlocks ints][level table][4 x 4 wave sums][flag]
 struct RideLds {
@@ -229,11 +216,6 @@ __device__ __forceinline__ void bin_count_ride(const BinRide r, unsigned id, int
 {
     static_assert(THREADS == 256, "4 wave sums per scan quantity");
     if (id >= r.grid.n_riders) return;
-#ifndef BOXATTN_TUNE_RIDE_PRIO
-#define BOXATTN_TUNE_RIDE_PRIO 0
-#endif
-    if (BOXATTN_TUNE_RIDE_PRIO) __builtin_amdgcn_s_setprio(BOXATTN_TUNE_RIDE_PRIO);
-    RIDE_STAMP(0);
     const RideLds m(lds);
     const BinPlan plan = r.plan;
     unsigned s_u, wg_u;
@@ -246,7 +228,6 @@ __device__ __forceinline__ void bin_count_ride(const BinRide r, unsigned id, int
     else
         bin_pass_body<THREADS, 8, 4, false, false, 1>(m.hist, m.lv, r.loc, r.w_sp, plan, r.H, r.Lq, r.P, r.q_per_wg,
                                                      r.n_wg, inter, r.part, r.subtot, r.offsets, r.records, s, wg);
-    RIDE_STAMP(1);
     // publish my row of counts, then the chain of last arrivers
     int *mypart = r.part + ((size_t)s * r.n_wg + wg) * plan.nblk;
     for (int k = threadIdx.x; k < plan.nblk; k += THREADS) agent_store(mypart + k, m.hist[k]);
@@ -255,22 +236,18 @@ __device__ __forceinline__ void bin_count_ride(const BinRide r, unsigned id, int
     const int n_in_sub = min(r.n_wg, (u + 1) * wps) - u * wps, n_sub = (r.n_wg + wps - 1) / wps;
     int *tk = r.tickets + (size_t)s * kRideTickets;
     const bool last = last_arriver<THREADS>(tk + u, n_in_sub, m.flag);
-    RIDE_STAMP(2);
     if (!last) return;       // workgroup-uniform
     const ScanOut o{r.subtot, r.offsets, r.items, r.combos, r.n_items};
     if (n_sub == 1) {        // one sub-range: its last arriver is the slice's, and does both scan stages in one pass
-        RIDE_STAMP(3);
         if (plan.nblk <= kScanThreads) scan_blocks_body<THREADS>(o, plan, m.lv, 1, s, m.wsum, r.part, r.n_wg);
         else scan_blocks_big_body<THREADS>(o, plan, m.lv, 1, s, m.wsum, m.hist, r.part, r.n_wg);
     } else {
         scan_sub_body<THREADS>(r.part, r.subtot, plan, r.n_wg, s, u);
         stores_left();
-        RIDE_STAMP(3);
         if (!last_arriver<THREADS>(tk + kScanSub, n_sub, m.flag)) return;
         if (plan.nblk <= kScanThreads) scan_blocks_body<THREADS>(o, plan, m.lv, n_sub, s, m.wsum);
         else scan_blocks_big_body<THREADS>(o, plan, m.lv, n_sub, s, m.wsum, m.hist);
     }
-    RIDE_STAMP(4);
 }
 
 template <int THREADS, bool GRP = false>
@@ -282,12 +259,10 @@ template <int THREADS, bool GRP = false>
 __device__ __forceinline__ void bin_fill_ride(const BinRide r, unsigned id, int *lds)
 {
     if (id >= r.grid.n_riders) return;
-    if (BOXATTN_TUNE_RIDE_PRIO) __builtin_amdgcn_s_setprio(BOXATTN_TUNE_RIDE_PRIO);
     if (r.flavour & kRideSpec) {        // one pass into guessed ranges, then the chain of the slice's last rider
         bin_fill_spec_ride<THREADS, GRP>(r, id, lds);
         return;
     }
-    RIDE_STAMP(5);
     const RideLds m(lds);
     const BinPlan plan = r.plan;
     unsigned s_u, wg_u;
@@ -308,8 +283,6 @@ __device__ __forceinline__ void bin_fill_ride(const BinRide r, unsigned id, int 
     else      // 4-byte records: one point per thread keeps neighbouring lanes on neighbouring slots (18.9 against 23.0 us)
         bin_pass_body<THREADS, 8, 4, true, false, 1>(m.hist, m.lv, r.loc, r.w_sp, plan, r.H, r.Lq, r.P, r.q_per_wg,
                                                     r.n_wg, inter, r.part, r.subtot, r.offsets, r.records, s, wg);
-    if (BOXATTN_RIDE_TRACE) { stores_left(); __syncthreads(); }
-    RIDE_STAMP(6);
 }
 
 }  // namespace boxattn

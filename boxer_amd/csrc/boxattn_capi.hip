@@ -69,42 +69,33 @@ inline bool opt_live(int k)
     return k == kOptBinChunk || k == kOptDense || k == kOptRiders || k == kOptAccF32 || k == kOptRideShift ||
            k == kOptWideBox || k == kOptInstAcc16 || k == kOptGroupRecords;
 }
-#ifndef BOXATTN_RIDE_SHIFT_COUNT
-#define BOXATTN_RIDE_SHIFT_COUNT 0     // count riders: all in front of the forward kernel's grid (measured: interleaving
-                                       // them with the tiles only stretches the count pass -- riders and tiles want the same
-                                       // wave slots, profiles/r04_rider_sweep.log)
-#endif
-#ifndef BOXATTN_RIDE_SHIFT_FILL
-#define BOXATTN_RIDE_SHIFT_FILL 0      // fill riders: in front of the point-gradient kernel's grid
-#endif
-#ifndef BOXATTN_BIN_WG_TARGET
-#define BOXATTN_BIN_WG_TARGET 256      // bin workgroups (= riders) in all, of 256 threads' worth: one per CU.  FEW, FAT riders
+// (The riders' default place: count riders all in front of the forward kernel's grid -- measured: interleaving them with
+// the tiles only stretches the count pass, riders and tiles want the same wave slots, profiles/r04_rider_sweep.log -- and
+// fill riders in front of the point-gradient kernel's grid: shift 0 for both, ride_shift.)
+constexpr int kBinWgTarget = 256;      // bin workgroups (= riders) in all, of 256 threads' worth: one per CU.  FEW, FAT riders
                                        // with the next step's locations always in flight cost a quarter of the chip's
                                        // wave slots; 1024 thin ones cost all of them for as long (C2 bf16 step
                                        // 146 / 139 / 135 / 154 us with 1024 / 512 / 256 / 128 riders)
-#endif
-#ifndef BOXATTN_SPEC_Q_PER_RIDER
-#define BOXATTN_SPEC_Q_PER_RIDER 600   // ... of the one-pass fill (boxattn_spec.h) at encoder-sized problems: one rider per ~600
+constexpr int kSpecQPerRider = 600;    // ... of the one-pass fill (boxattn_spec.h) at encoder-sized problems: one rider per ~600
                                        // (query, slice) pairs, 256 ... 768 of them.  Its riders are bound by latency (two
                                        // barriers and an atomic round trip a step), not by instruction issue, so somewhat more,
                                        // shorter riders than the two-pass fill wants.  C2 bf16 (213 k pairs), one box, resident /
                                        // cache-cold inputs, us a step: 256 riders 126.3 / 140.2, 384: 122.5 / 132.9, 512: 119.8 /
                                        // 135.0, 768: 119.3 / 135.0, 1024: 122.8 / 136.2 (two-pass, 256: 124.0 / 133.2); C2' (354 k):
                                        // 512: 209.8 / 219.4, 1024: 218.5 / 225.1 (two-pass: 211.3 / 221.5) -- profiles/r06_onepass_ab.log
-#endif
 // one_pass: the shape's box-attention backward fills its bins in one pass (a property of the map, plan_layout)
 inline long long bin_wg_target(bool one_pass, long long queries)
 {
     const int v = (opt(kOptRideShift) >> 8) & 31;       // 64 v riders
     if (v > 0) return 64ll * v;
-    if (!one_pass || queries < 65536) return BOXATTN_BIN_WG_TARGET;
-    const long long r = (queries / BOXATTN_SPEC_Q_PER_RIDER + 32) / 64 * 64;
+    if (!one_pass || queries < 65536) return kBinWgTarget;
+    const long long r = (queries / kSpecQPerRider + 32) / 64 * 64;
     return std::min(768ll, std::max(256ll, r));
 }
 inline unsigned ride_shift(bool fill)
 {
     const int o = opt(kOptRideShift), v = fill ? (o >> 4) & 15 : o & 15;
-    return v > 0 ? (unsigned)(v - 1) : (unsigned)(fill ? BOXATTN_RIDE_SHIFT_FILL : BOXATTN_RIDE_SHIFT_COUNT);
+    return v > 0 ? (unsigned)(v - 1) : 0u;
 }
 
 inline int ceil_div_sz(size_t a, size_t b) { return (int)((a + b - 1) / b); }
@@ -168,28 +159,14 @@ struct FwdAlign { bool fast, rows16, staged; };
 
 // Lanes per (query, head) pair and channels per lane of the gather kernels (boxattn_gather2.h):
 // 8 channels per lane when C allows and the rows can be fetched 16 bytes at a time.
-#ifndef BOXATTN_TUNE_VEC_F32
-#define BOXATTN_TUNE_VEC_F32 4      // measured: 128-byte fp32 rows gain nothing from 8 channels per lane
-#endif
-#ifndef BOXATTN_TUNE_VEC_BF16
-#define BOXATTN_TUNE_VEC_BF16 8
-#endif
-#ifndef BOXATTN_TUNE_U8_F32
-#define BOXATTN_TUNE_U8_F32 2
-#endif
-#ifndef BOXATTN_TUNE_U8_BF16
-#define BOXATTN_TUNE_U8_BF16 4
-#endif
-#ifndef BOXATTN_TUNE_U4_F32
-#define BOXATTN_TUNE_U4_F32 4      // 0: all G points of a tile
-#endif
-#ifndef BOXATTN_TUNE_U4_BF16
-#define BOXATTN_TUNE_U4_BF16 4
-#endif
+constexpr int kGatherVecF32 = 4;    // measured: 128-byte fp32 rows gain nothing from 8 channels per lane
+constexpr int kGatherVecBf16 = 8;
+constexpr int kGatherU8F32 = 2, kGatherU8Bf16 = 4;      // points in flight of the 8-channel kernels
+constexpr int kGatherU4F32 = 4, kGatherU4Bf16 = 4;      // ... of the 4-channel kernels
 struct GatherCfg { int G, VEC; };
 inline GatherCfg gather_cfg(int elem_bytes, const Dims &d, bool rows_16b_aligned)
 {
-    const int want = elem_bytes == 2 ? BOXATTN_TUNE_VEC_BF16 : BOXATTN_TUNE_VEC_F32;
+    const int want = elem_bytes == 2 ? kGatherVecBf16 : kGatherVecF32;
     if (want == 8 && rows_16b_aligned && (d.C == 32 || d.C == 64)) return {d.C / 8, 8};
     return {fast_group(d), 4};
 }
@@ -199,10 +176,10 @@ template <typename ST> inline GatherCfg gather_cfg(const Dims &d, bool rows_16b_
 }
 // points of a pair in flight per lane (loads issued before the first use)
 template <typename ST, int G, int VEC> struct GatherUnroll {
-    static constexpr int u8 = sizeof(ST) == 2 ? BOXATTN_TUNE_U8_BF16 : BOXATTN_TUNE_U8_F32;
-    static constexpr int u4 = sizeof(ST) == 2 ? BOXATTN_TUNE_U4_BF16 : BOXATTN_TUNE_U4_F32;
+    static constexpr int u8 = sizeof(ST) == 2 ? kGatherU8Bf16 : kGatherU8F32;
+    static constexpr int u4 = sizeof(ST) == 2 ? kGatherU4Bf16 : kGatherU4F32;
     static constexpr int want = VEC == 8 ? u8 : u4;
-    static constexpr int value = (want <= 0 || want > G) ? G : want;
+    static constexpr int value = want > G ? G : want;
 };
 inline unsigned div_magic(unsigned d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / d); }
 // index constants of the gather kernels; false if the problem is outside their 32-bit arithmetic
@@ -239,7 +216,7 @@ inline GatherIdx with_grid(GatherIdx ix, int grid_x, int grid_y, int tiles)
 }
 // (the 8-channel kernels are only instantiated for the storage types that select them)
 template <typename ST> struct GatherVec8 {
-    static constexpr bool value = (sizeof(ST) == 2 ? BOXATTN_TUNE_VEC_BF16 : BOXATTN_TUNE_VEC_F32) == 8;
+    static constexpr bool value = (sizeof(ST) == 2 ? kGatherVecBf16 : kGatherVecF32) == 8;
 };
 #define BOXATTN_GATHER_DISPATCH(cfg, X)                                                       \
     do {                                                                                      \
@@ -861,7 +838,6 @@ inline BinRide make_ride(const float *loc, const float *w_sp, const Dims &d, con
     r.flavour = flavour;
     r.grid.n_riders = (unsigned)(pl.n_wg * d.B * d.H);
     r.grid.shift = ride_shift(fill);
-    r.trace = (unsigned long long *)g_dense_dbg.load();      // (read only by builds with BOXATTN_RIDE_TRACE)
     return r;
 }
 
@@ -892,12 +868,10 @@ inline void launch_binning(int flavour, const float *loc, const float *w_sp, con
             hipLaunchKernelGGL(zero_geo_kernel, dim3((plan.nblk + 255) / 256), dim3(256), 0, st, plan,
                                (int2 *)(pbuf + w.zgeo));
     }
-#ifndef BOXATTN_TUNE_SCAN_FUSE_WG
-#define BOXATTN_TUNE_SCAN_FUSE_WG 48   // up to this many bin workgroups per slice the block scan does kernel A's work too
-                                       // (38 workgroups, the 300-query decoders: C3'' fp32 68 -> 61 us; 64, C2: binning 49 -> 61 us)
-#endif
+    constexpr int kScanFuseWg = 48;        // up to this many bin workgroups per slice the block scan does kernel A's work too
+                                           // (38 workgroups, the 300-query decoders: C3'' fp32 68 -> 61 us; 64, C2: binning 49 -> 61 us)
     // (big maps, multi-workgroup block scan: fused up to 8 bin workgroups per slice -- the 1 000-query BEV decoder has 1)
-    const bool fuse_a = plan.nblk <= kScanThreads ? w.n_wg <= BOXATTN_TUNE_SCAN_FUSE_WG : w.n_wg <= 8;
+    const bool fuse_a = plan.nblk <= kScanThreads ? w.n_wg <= kScanFuseWg : w.n_wg <= 8;
     if (stages & kBinScan) {
         if (!fuse_a)
             hipLaunchKernelGGL(bin_scan_a_kernel,
@@ -1007,9 +981,7 @@ hipLaunchKernelGGL((pointgrad2_kernel<ST, GG, INST, GatherUnroll<ST, GG, VV>::va
 // worker) themselves (XCD affinity), hence the 8-aligned grid.
 constexpr int kAccWgCap = 1024;   // accumulate workgroups per slice; beyond that a workgroup takes several items (its next one in
                                   // flight); 256 / 512 / 1024 / 3072 / 6144: C5 99 / 85 / 83 / 93 / 111 us, C2 67 / 54 / 54 / 55 / 54
-#ifndef BOXATTN_TUNE_GRP_WG_CAP
-#define BOXATTN_TUNE_GRP_WG_CAP kAccWgCap      // the same bound for the group-record flavour (sweep: DESIGN.md 4.2.3)
-#endif
+                                  // (the same bound for the group-record flavour; sweep: DESIGN.md 4.2.3)
 template <typename ST, int G, bool INST>
 int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, const float *loc, const float *w_sp,
                       const float *w_lv, const Dims &d, const BinPlan &plan, const int *offsets, const int4 *items,
@@ -1018,7 +990,7 @@ int launch_accumulate(AccKind acc, const ST *grad_out, const ST *grad_mask, cons
 {
     constexpr int C = 4 * G;
     const int ns = d.B * d.H, ns8 = (ns + 7) / 8 * 8;
-    const int wg_per_slice = std::min(rec == kRecGroup ? (int)(BOXATTN_TUNE_GRP_WG_CAP) : kAccWgCap, std::max(1, plan.item_cap));
+    const int wg_per_slice = std::min(kAccWgCap, std::max(1, plan.item_cap));
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdAccum], st);
     if constexpr (IsHalf16<ST>::value && !INST) {
         if (acc == kAccTr && rec == kRecGroup) {
@@ -1641,9 +1613,8 @@ int boxattn_set_variant(int variant)
     return g_variant.exchange(variant);
 }
 
-// debugging aid, not part of the documented ABI: a device buffer the window-staged point-gradient kernel fills
-// with per-wave time stamps in builds with BOXATTN_DENSE_DEBUG (nullptr: off)
-void boxattn_set_debug_buffer(float *p) { g_dense_dbg.store(p); }
+// no effect: the time-stamp builds that read the buffer are gone; kept exported for ABI 8
+void boxattn_set_debug_buffer(float *) {}
 
 int boxattn_set_option(int key, int value)
 {

@@ -34,15 +34,7 @@
 
 namespace boxattn {
 
-#ifndef BOXATTN_DENSE_DEBUG
-#define BOXATTN_DENSE_DEBUG 0     // 2: s_memtime stamps of every wave (tools/gpu_dense_trace.py, DensePlan::dbg)
-#endif
-#ifndef BOXATTN_TUNE_PG_ROWS
-#define BOXATTN_TUNE_PG_ROWS 2    // corner rows a lane has in flight from LDS (2: 8 reads, 32 registers)
-#endif
-#ifndef BOXATTN_DENSE_WPE
-#define BOXATTN_DENSE_WPE 5       // waves per SIMD the register allocation aims at (96 registers; 26 / 30 KB of LDS: 5 workgroups per CU)
-#endif
+constexpr int kDenseWpe = 5;      // waves per SIMD the register allocation aims at (96 registers; 26 / 30 KB of LDS: 5 workgroups per CU)
 typedef unsigned int dense_u32x4 __attribute__((ext_vector_type(4)));
 
 // one 64-byte row (32 bf16 / f16 channels) as 16 words.  (The words go through a plain array: a bit_cast
@@ -154,14 +146,6 @@ struct DenseWinPos {
 };
 
 typedef __attribute__((address_space(3))) void dense_lds_void;
-// timing experiments only (phase split of the tile kernels): the windows are not fetched (the arithmetic
-// runs on whatever the LDS holds) / the arithmetic is skipped (windows fetched, locations loaded, zeros stored)
-#ifndef BOXATTN_DEBUG_NO_STAGE
-#define BOXATTN_DEBUG_NO_STAGE 0
-#endif
-#ifndef BOXATTN_DEBUG_NO_MATH
-#define BOXATTN_DEBUG_NO_MATH 0
-#endif
 
 template <int L>
 __device__ __forceinline__ void dense_stage_issue(const DenseHot<L> &hot, const DenseWin (&wrow)[L],
@@ -193,7 +177,7 @@ __device__ __forceinline__ void dense_stage_issue(const DenseHot<L> &hot, const 
         if (j < o.cols()) {
 #pragma unroll
             for (int k = 0; k < RPW; ++k) {
-                if (wv + 4 * k < rows && !BOXATTN_DEBUG_NO_STAGE)      // wave-uniform
+                if (wv + 4 * k < rows)                                  // wave-uniform
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (dense_lds_void *)(lds + dst), 16, voff, soff, 0, 0);
                 soff += 4u * row_bytes;
                 dst += step;
@@ -283,7 +267,7 @@ __device__ __forceinline__ void dense_corner_sums(const DensePoint &s, const Den
         // that do not count are read from a clamped slot and masked out bitwise -- a select on the
         // finished sum lets the compiler put every corner under its own branch (reads, wait, dots, four
         // times in a row), a multiplication by 0 would let a non-finite value of an unrelated pixel through
-#if BOXATTN_TUNE_PG_ROWS == 2
+        // (2 corner rows a lane has in flight from LDS: 8 reads, 32 registers)
 #pragma unroll
         for (int k0 = 0; k0 < 4; k0 += 2) {
             unsigned va[16], vb[16];
@@ -293,14 +277,6 @@ __device__ __forceinline__ void dense_corner_sums(const DensePoint &s, const Den
             sk[k0] = __uint_as_float(__float_as_uint(da) & m[k0]);
             sk[k0 + 1] = __uint_as_float(__float_as_uint(db) & m[k0 + 1]);
         }
-#else
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            unsigned va[16];
-            dense_load_row(lds + slot[k], va);
-            sk[k] = __uint_as_float(__float_as_uint(dense_dot_row<ST>(gw, va)) & m[k]);
-        }
-#endif
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) sk[k] = 0.f;
@@ -359,16 +335,14 @@ __device__ __forceinline__ void dense_corner_sums(const DensePoint &s, const Den
 constexpr int kDenseResFloats = 16 * 16 * 3;       // per wave: the results of 16 queries x 16 points
 
 template <typename ST, int L>
-__global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel(
+__global__ __launch_bounds__(256, kDenseWpe) void pointgrad_dense_kernel(
     const ST *__restrict__ value, const float *__restrict__ loc, const float *__restrict__ attn,
     const ST *__restrict__ grad_out, float *__restrict__ grad_loc, float *__restrict__ grad_attn,
     DensePlan pl, unsigned value_bytes, BinRide ride)
 {
     constexpr int C = 32, P = 4, LP = L * P;
-#ifndef BOXATTN_TUNE_PG_STASH
-#define BOXATTN_TUNE_PG_STASH 1    // a lane parks its L attention weights in LDS until it needs them (4 registers)
-#endif
-    __shared__ __attribute__((aligned(16))) unsigned char win_lds[kDenseLdsBytes + (BOXATTN_TUNE_PG_STASH ? 256 * 16 : 0)];
+    // (+ 256 * 16: a lane parks its L attention weights in LDS until it needs them (4 registers))
+    __shared__ __attribute__((aligned(16))) unsigned char win_lds[kDenseLdsBytes + 256 * 16];
     static_assert(4 * kDenseResFloats * sizeof(float) <= sizeof(win_lds), "the result tiles reuse the window buffer");
     static_assert(kRideLdsInts * sizeof(int) <= sizeof(win_lds), "so do the riders");
     // (the wave index as a scalar: everything per window row -- row index, clamps, byte offsets, the
@@ -382,19 +356,6 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
         bin_fill_ride<256, true>(ride, role.id, reinterpret_cast<int *>(win_lds));
         return;
     }
-#ifdef BOXATTN_DEBUG_NO_TILES          // timing experiments only: the riders alone
-    return;
-#endif
-#if BOXATTN_DENSE_DEBUG == 2
-    unsigned long long ts[12];
-    int ts_n = 0;
-    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();     // 100 MHz, the same on every XCD
-#define DENSE_STAMP() do { __builtin_amdgcn_sched_barrier(0); ts[ts_n++] = __builtin_amdgcn_s_memtime(); \
-                           __builtin_amdgcn_sched_barrier(0); } while (0)
-    DENSE_STAMP();
-#else
-#define DENSE_STAMP() do { } while (0)
-#endif
     DenseHot<L> hot;
     DenseMap Q;
     DenseWin wrow[L];
@@ -416,9 +377,7 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
     // the window rows first: they are what the workgroup's barrier waits for; the lane's own inputs
     // (locations, weights, grad_out row) are requested behind them and land while the rows are staged
     DenseWinPos win[L];
-    DENSE_STAMP();                                                 // tile decoded
     dense_stage_issue<L>(hot, wrow, t, lane, wv, rs, win_lds, win);
-    DENSE_STAMP();                                                 // window rows requested
     float2 xy[L];
     float a[L];
 #pragma unroll
@@ -430,11 +389,6 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
     }
     unsigned gw[16];                                               // the query's grad_out row
     dense_load_row(grad_out + (size_t)qh * C, gw);
-    DENSE_STAMP();                                                 // own inputs requested
-#if BOXATTN_DENSE_DEBUG == 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    DENSE_STAMP();                                                 // everything has arrived
-#endif
     // (the attention weights are needed last, for the location gradients: parked in a lane-private piece of LDS
     // meanwhile -- held in registers the kernel does not fit five waves per SIMD, and the compiler's own spill
     // goes to scratch with a full memory wait per value)
@@ -443,28 +397,20 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
     // front of the barrier, with every window row and operand load of the wave still in flight)
     typedef __attribute__((address_space(3))) float dense_lds_float;
     volatile dense_lds_float *a_stash = (volatile dense_lds_float *)(win_lds + kDenseLdsBytes) + 4 * threadIdx.x;
-    if (BOXATTN_TUNE_PG_STASH) {
 #pragma unroll
-        for (int l = 0; l < L; ++l) a_stash[l] = a[l];
-    }
+    for (int l = 0; l < L; ++l) a_stash[l] = a[l];
     dense_stage_wait();                    // windows complete
-    DENSE_STAMP();
 
     float ga[L], gx[L], gy[L];
 #pragma unroll
     for (int l = 0; l < L; ++l) {
-        if (BOXATTN_DEBUG_NO_MATH) {                               // (timing experiments: loads kept, arithmetic gone)
-            asm volatile("" ::"v"(xy[l].x), "v"(xy[l].y), "v"(a[l]), "v"(gw[0]), "v"(gw[15]));
-            ga[l] = gx[l] = gy[l] = 0.f;
-            continue;
-        }
         const DenseMap T = hot.lv[l];
         const DensePoint s = dense_locate(xy[l].x, xy[l].y, T.H, T.W);
         float sk[4];
         dense_corner_sums<ST>(s, T, win[l], win_lds, gw, value, t.b * (unsigned)hot.S + (unsigned)T.start, H, h, vq, p, sk);
         const float w1 = s.hh * s.hw, w2 = s.hh * s.lw, w3 = s.lh * s.hw, w4 = s.lh * s.lw;
         const float gs_ = w1 * sk[0] + w2 * sk[1] + w3 * sk[2] + w4 * sk[3];
-        const float al = BOXATTN_TUNE_PG_STASH ? a_stash[l] : a[l];
+        const float al = a_stash[l];
         const float gx_ = (float)T.W * al * (s.hh * (sk[1] - sk[0]) + s.lh * (sk[3] - sk[2]));
         const float gy_ = (float)T.H * al * (s.hw * (sk[2] - sk[0]) + s.lw * (sk[3] - sk[1]));
         ga[l] = s.inside ? gs_ : 0.f;
@@ -474,7 +420,6 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
         // values per level -- corner sums and weights -- instead of three)
         asm volatile("" : "+v"(ga[l]), "+v"(gx[l]), "+v"(gy[l]));
     }
-    DENSE_STAMP();
     // ---- results: lane (q, p) holds its point on every level; memory wants, per (query, head),
     //      [level][point] runs -- transposed through (wave-private) LDS so that lane (q, j) writes
     //      level j's 4 points as 16 + 32 contiguous bytes (whole 64- / 128-byte runs per query)
@@ -491,35 +436,15 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void pointgrad_dense_kernel
         const float4 o_a = *reinterpret_cast<const float4 *>(res_a + p * P);
         const float4 o_0 = *reinterpret_cast<const float4 *>(res_xy + p * P * 2);
         const float4 o_1 = *reinterpret_cast<const float4 *>(res_xy + p * P * 2 + 4);
-#ifndef BOXATTN_TUNE_PG_NT
-#define BOXATTN_TUNE_PG_NT 1       // the point gradients leave with non-temporal stores: nobody on the GPU reads them soon, and
-#endif                             // the bin records the fill riders of this launch write should stay in the Infinity Cache
-        float4 *ga4 = reinterpret_cast<float4 *>(grad_attn + pt0 + p * P);
-        float4 *gl = reinterpret_cast<float4 *>(grad_loc + 2 * (size_t)(pt0 + p * P));
-        if (BOXATTN_TUNE_PG_NT) {
-            typedef float pg_f32x4 __attribute__((ext_vector_type(4)));
-            __builtin_nontemporal_store(pg_f32x4{o_a.x, o_a.y, o_a.z, o_a.w}, reinterpret_cast<pg_f32x4 *>(ga4));
-            __builtin_nontemporal_store(pg_f32x4{o_0.x, o_0.y, o_0.z, o_0.w}, reinterpret_cast<pg_f32x4 *>(gl));
-            __builtin_nontemporal_store(pg_f32x4{o_1.x, o_1.y, o_1.z, o_1.w}, reinterpret_cast<pg_f32x4 *>(gl + 1));
-        } else {
-            *ga4 = o_a;
-            gl[0] = o_0;
-            gl[1] = o_1;
-        }
+        // the point gradients leave with non-temporal stores: nobody on the GPU reads them soon, and
+        // the bin records the fill riders of this launch write should stay in the Infinity Cache
+        typedef float pg_f32x4 __attribute__((ext_vector_type(4)));
+        pg_f32x4 *ga4 = reinterpret_cast<pg_f32x4 *>(grad_attn + pt0 + p * P);
+        pg_f32x4 *gl = reinterpret_cast<pg_f32x4 *>(grad_loc + 2 * (size_t)(pt0 + p * P));
+        __builtin_nontemporal_store(pg_f32x4{o_a.x, o_a.y, o_a.z, o_a.w}, ga4);
+        __builtin_nontemporal_store(pg_f32x4{o_0.x, o_0.y, o_0.z, o_0.w}, gl);
+        __builtin_nontemporal_store(pg_f32x4{o_1.x, o_1.y, o_1.z, o_1.w}, gl + 1);
     }
-#if BOXATTN_DENSE_DEBUG == 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    DENSE_STAMP();
-    if (pl.dbg && lane == 0) {
-        float *o = pl.dbg + ((size_t)role.id * 4 + wv) * 20;
-        o[0] = (float)t.lq;
-        o[1] = (float)(unsigned)(ts[0] & 0xffffffu);
-        for (int i = 1; i < ts_n; ++i) o[1 + i] = (float)(unsigned)(ts[i] - ts[0]);
-        o[19] = (float)ts_n;
-        o[17] = (float)(unsigned)(rt0 & 0xffffffu);
-        o[18] = (float)(unsigned)(__builtin_amdgcn_s_memrealtime() & 0xffffffu);
-    }
-#endif
 }
 
 }  // namespace boxattn

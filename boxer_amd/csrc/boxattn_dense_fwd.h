@@ -53,7 +53,7 @@ typedef short fwd_i16x4 __attribute__((ext_vector_type(4)));
 typedef float fwd_f32x4 __attribute__((ext_vector_type(4)));
 
 template <typename ST, int L>
-__global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
+__global__ __launch_bounds__(256, kDenseWpe) void fwd_dense_kernel(
     const ST *__restrict__ value, const float *__restrict__ loc, const float *__restrict__ attn,
     ST *__restrict__ out, DensePlan pl, unsigned value_bytes, BinRide ride,
     unsigned long long *__restrict__ stats)
@@ -70,9 +70,6 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
         bin_count_ride<256>(ride, role.id, reinterpret_cast<int *>(win_lds));
         return;
     }
-#ifdef BOXATTN_DEBUG_NO_TILES          // timing experiments only: the riders alone
-    return;
-#endif
     DenseHot<L> hot;
     DenseMap Q;
     DenseWin wrow[L];
@@ -114,10 +111,6 @@ __global__ __launch_bounds__(256, BOXATTN_DENSE_WPE) void fwd_dense_kernel(
     for (int m = 0; m < 8; ++m) { acc[m] = fwd_f32x4{0.f, 0.f, 0.f, 0.f}; accv[m] = 0.f; }
 #pragma unroll
     for (int l = 0; l < L; ++l) {
-        if (BOXATTN_DEBUG_NO_MATH) {                               // (timing experiments: loads kept, arithmetic gone)
-            asm volatile("" ::"v"(xy[l].x), "v"(xy[l].y), "v"(a[l]));
-            continue;
-        }
         const DenseMap T = hot.lv[l];
         const DenseWinPos &o = win[l];
         const DensePoint s = dense_locate(xy[l].x, xy[l].y, T.H, T.W);

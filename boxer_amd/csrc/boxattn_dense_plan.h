@@ -22,10 +22,7 @@ constexpr int kDenseWinMax = 16;           // window rows / columns at most (one
 // lanes spread over the 16 groups as well as a padded slot would, at 4/5 of the bytes.
 constexpr int kDenseSlotBytes = 64;        // one staged pixel: 32 bf16 channels
 constexpr int kDenseRowSkew = 16;          // bytes between the end of a window row and the start of the next
-#ifndef BOXATTN_DENSE_LDS
-#define BOXATTN_DENSE_LDS 28160
-#endif
-constexpr int kDenseLdsBytes = BOXATTN_DENSE_LDS;  // per workgroup: 27.5 KB -- five workgroups per CU also with the point-gradient
+constexpr int kDenseLdsBytes = 28160;              // per workgroup: 27.5 KB -- five workgroups per CU also with the point-gradient
                                                    // kernel's 4 KB stash (157.5 of 160 KB); BoxeR-R50 tiles need 25.4 KB,
                                                    // odd map sizes (10 x 10 instead of 9 x 9 on the next level) 26.7
 constexpr int kDenseZeroOff = kDenseLdsBytes - kDenseSlotBytes;    // the forward's row of zeros (make_dense_plan leaves it free)
@@ -54,7 +51,7 @@ struct DensePlan {
     unsigned mag_h;          // floor(2^32 / H)
     DenseLevel lv[kDenseMaxLevels];
     DenseWin win[kDenseMaxLevels][kDenseMaxLevels];      // [query level][sampled level]
-    float *dbg;              // debugging aid (builds with BOXATTN_DENSE_DEBUG; boxattn_set_debug_buffer)
+    float *dbg;              // unused; keeps the kernel-argument layout
 };
 
 // workgroups of the kernels: 8 XCD queues x heads x the longest queue (dense_tile_of_block)
@@ -93,9 +90,9 @@ void launch_pointgrad_dense_f32(const float *value, const float *loc, const floa
                                 hipStream_t st, const BinRide &ride);
 void launch_fwd_dense_f32(const float *value, const float *loc, const float *attn, float *out, const DensePlan &dp,
                           unsigned value_bytes, const BinRide &ride, unsigned long long *stats, hipStream_t st);
-#ifndef BOXATTN_DENSE_F32_LDS
-#define BOXATTN_DENSE_F32_LDS 53248
-#endif
+// their LDS per workgroup -- 52 KB: three workgroups per CU, BoxeR-R50 tiles need 50.8 KB -- defined ONCE, here, next to
+// the host's window budget that must agree with it (make_dense_plan)
+constexpr int kDenseF32LdsBytes = 53248;
 
 // The matrix-core accumulate of 16-bit box attention (boxattn_binned_tr.h; lives in this translation unit
 // because it mixes float32 VALU work with MFMAs, see boxattn_dense.hip).  C = 16, 32 or 64 channels per

@@ -41,7 +41,7 @@ __device__ __forceinline__ void load_levels(LevelTable &t, const int64_t *shapes
 // The same in two steps, so that a kernel can put its own first loads BETWEEN the request of the
 // level table and the barrier that publishes it: one global round trip at the start of a wave
 // instead of two in a row (s_memtime stamps in the point-gradient kernel: 6 600 of a wave's
-// 21 000 cycles passed before its loop started, tools/gpu_pg_trace.py).
+// 21 000 cycles passed before its loop started; measured with a build switch, since removed).
 struct LevelRegs { int h, w, start; };
 __device__ __forceinline__ LevelRegs levels_request(const int64_t *shapes, const int64_t *lsi, int L)
 {

@@ -42,25 +42,16 @@ constexpr unsigned kOobOffset = 0x80000000u;     // >= any valid byte offset (te
 // useful load could be issued (s_memtime stamps: 6 200 of a wave's 21 000 cycles).
 constexpr unsigned kGatherWaves = 4;
 
-// Tuning switches (tools/build_variants.sh builds the alternatives side by side).
-#ifndef BOXATTN_TUNE_SCHED
-#define BOXATTN_TUNE_SCHED 1      // all row loads of a step are issued before the first FMA
-#endif
-#ifndef BOXATTN_TUNE_PREFETCH
-#define BOXATTN_TUNE_PREFETCH 1   // locations / weights of tile t+1 are requested during tile t
-#endif
-#ifndef BOXATTN_TUNE_PRELOAD
-#define BOXATTN_TUNE_PRELOAD 1    // L P == 4 G: the locations / weights of all tiles up front
-#endif
-constexpr bool kGatherPreload = BOXATTN_TUNE_PRELOAD != 0;
+// Three schedules, each measured against its alternative with a build switch, since removed:
+//   all row loads of a step are issued before the first FMA (loads_issued)
+//   locations / weights of tile t+1 are requested during tile t
+//   L P == 4 G: the locations / weights of all tiles up front
 constexpr int kPreTiles = 4;
-constexpr bool kGatherSched = BOXATTN_TUNE_SCHED != 0;
-constexpr bool kGatherPrefetch = BOXATTN_TUNE_PREFETCH != 0;
 __device__ __forceinline__ void loads_issued()
 {
     // keep the compiler from sinking loads below the math to save registers: the point of the
     // step is to have them all in flight at once
-    if constexpr (kGatherSched) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 // The VEC channels a lane owns, as raw 32-bit words (fp32: VEC words, bf16 / f16: VEC / 2 words).
@@ -128,21 +119,9 @@ __device__ __forceinline__ f32x2 row_pair(const Row<ST, VEC> &v, int i)
 }
 
 // acc (VEC / 2 channel pairs) += w * row
-#ifndef BOXATTN_TUNE_FWD_ABLATE
-#define BOXATTN_TUNE_FWD_ABLATE 0   // timing experiments only (wrong results): 1 = the rows are
-#endif                              // consumed by one XOR per word instead of unpack + FMA,
-                                    // 2 = every row load hits the first 4 KiB of value (L1 hits),
-                                    // 3 = no row loads
 template <typename ST, int VEC>
 __device__ __forceinline__ void row_axpy(f32x2 (&acc)[VEC / 2], float w, const Row<ST, VEC> &v)
 {
-    if constexpr (BOXATTN_TUNE_FWD_ABLATE == 1 && sizeof(ST) == 2) {
-#pragma unroll
-        for (int i = 0; i < VEC / 2; ++i)
-            acc[i].x = __uint_as_float(__float_as_uint(acc[i].x) ^ v.w[i]);
-        acc[0].y = __uint_as_float(__float_as_uint(acc[0].y) ^ __float_as_uint(w));
-        return;
-    }
     const f32x2 w2 = {w, w};
 #pragma unroll
     for (int i = 0; i < VEC / 2; ++i)
@@ -190,10 +169,6 @@ __device__ __forceinline__ void row_store(ST *p, const f32x2 (&acc)[VEC / 2])
 // G == 4: a pair is one DPP quad, so lane (j, t)'s step-A registers reach the other lanes of the
 // pair with quad_perm broadcasts (VALU moves the compiler folds into the consuming add where it
 // can) -- no LDS tile, no LDS round trip between the two steps.
-#ifndef BOXATTN_TUNE_QUAD_DPP
-#define BOXATTN_TUNE_QUAD_DPP 1
-#endif
-template <int G> struct UseQuadDpp { static constexpr bool value = G == 4 && BOXATTN_TUNE_QUAD_DPP; };
 template <int CTRL> __device__ __forceinline__ unsigned dpp_mov(unsigned v)
 {
     return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
@@ -351,7 +326,7 @@ __global__ __launch_bounds__(256) void fwd2_kernel(
                     corner_offsets<ST>(s, b * (unsigned)S + (unsigned)lv.start[l], H, h, C, have);
                 const u32x4_t wt = as_u32x4(s.hh * s.hw * a, s.hh * s.lw * a, s.lh * s.hw * a,
                                             s.lh * s.lw * a);
-                if constexpr (UseQuadDpp<G>::value) {
+                if constexpr (G == 4) {
                     my_off = off;
                     my_wt = wt;
                 } else {
@@ -368,22 +343,12 @@ __global__ __launch_bounds__(256) void fwd2_kernel(
                 RowT v[U][4];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    if constexpr (UseQuadDpp<G>::value) {
+                    if constexpr (G == 4) {
                         off[u] = quad_bcast(my_off, tb + u);
                         wt[u] = quad_bcast(my_wt, tb + u);
                     } else {
                         off[u] = geo[(tb + u) * NH];
                         wt[u] = geo[(tb + u) * NH + 1];
-                    }
-                    if constexpr (BOXATTN_TUNE_FWD_ABLATE == 2) {
-                        off[u].x &= 0xfc0u; off[u].y &= 0xfc0u; off[u].z &= 0xfc0u; off[u].w &= 0xfc0u;
-                    }
-                    if constexpr (BOXATTN_TUNE_FWD_ABLATE == 3) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-#pragma unroll
-                            for (int i = 0; i < RowT::NW; ++i) v[u][k].w[i] = off[u][k] + i;
-                        continue;
                     }
                     row_load<ST, VEC, PSB>(rs, off[u].x + lane_off, v[u][0]);
                     row_load<ST, VEC, PSB>(rs, off[u].y + lane_off, v[u][1]);
@@ -405,7 +370,7 @@ __global__ __launch_bounds__(256) void fwd2_kernel(
         // look-ahead the kernel ran at the HBM LATENCY of that stream (4 dependent round trips
         // per wave, 1.6 TB/s on 54 MB).  BoxeR's shape (L P = 4 G: 4 levels x 2 x 2 points, 4
         // lanes per pair) requests all four tiles up front -- one round trip per wave.
-        if (kGatherPreload && G == 4 && LP == kPreTiles * G) {
+        if (G == 4 && LP == kPreTiles * G) {
             float2 xy4[kPreTiles];
             float a4[kPreTiles];
 #pragma unroll
@@ -430,18 +395,11 @@ __global__ __launch_bounds__(256) void fwd2_kernel(
             float a_n = w_sp[pt0 + min(slot, LP - 1)];
             levels_commit(lv, lv_regs, L);
             for (int t0 = 0; t0 < LP; t0 += G) {
-                float2 xy = xy_n;
-                float a = a_n;
-                const int lp = t0 + slot;
-                if constexpr (kGatherPrefetch) {
-                    const int nq = min(lp + G, LP - 1);           // same point again past the end
-                    xy_n = loc2[pt0 + nq];
-                    a_n = w_sp[pt0 + nq];
-                } else {
-                    const int lq = min(lp, LP - 1);
-                    xy = loc2[pt0 + lq];
-                    a = w_sp[pt0 + lq];
-                }
+                const float2 xy = xy_n;
+                const float a = a_n;
+                const int nq = min(t0 + slot + G, LP - 1);        // same point again past the end
+                xy_n = loc2[pt0 + nq];
+                a_n = w_sp[pt0 + nq];
                 tile(t0, xy, a);
             }
         }
@@ -762,18 +720,6 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
     // per-point results are collected per pair in LDS and written once, 16 / 32 contiguous bytes
     // per lane.  (Written tile by tile -- 4-byte and 8-byte pieces per lane, 16 points of a pair
     // in four separate instructions -- the kernel's HBM write traffic was twice its output.)
-#ifndef BOXATTN_TUNE_PG_TRACE
-#define BOXATTN_TUNE_PG_TRACE 0     // experiments only (overwrites grad_weight): s_memtime stamps of wave 0 of
-#endif                              // every workgroup: start, loop entry, each tile, end (tools/gpu_pg_trace.py)
-    unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int ts_n = 0;
-    if constexpr (BOXATTN_TUNE_PG_TRACE) {
-        ts[ts_n++] = __builtin_amdgcn_s_memtime();
-        if (BOXATTN_TUNE_PG_TRACE == 2) {                     // finer stamps of the prologue instead of the tiles
-            asm volatile("" ::"s"(S), "s"(Lq));               // explicit kernel arguments have arrived
-            ts[2] = __builtin_amdgcn_s_memtime();
-        }
-    }
     constexpr int kBufLP = 16;
     constexpr bool kCanBuffer = !INST && (G == 4 || G == 8);
     __shared__ float res_all[kCanBuffer ? 4 * PAIRS * kBufLP * 3 : 1];
@@ -793,10 +739,6 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
         qh = pair_of_lane<PAIRS>(ix, blk, H, lane / G, wv, active);
     }
     const int slot = lane % G;
-    if constexpr (BOXATTN_TUNE_PG_TRACE == 2) {
-        asm volatile("" ::"v"(qh));                           // the pair index exists (grid size read)
-        ts[3] = __builtin_amdgcn_s_memtime();
-    }
     unsigned bq, hu, b, qu;
     divmod_magic(qh, (unsigned)H, ix.magic_h, bq, hu);
     divmod_magic(bq, (unsigned)Lq, ix.magic_lq, b, qu);
@@ -824,7 +766,7 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
     float al_n = INST ? w_lv[pt0 + min(t_begin + slot, LP - 1)] : 0.f;
     // BoxeR's shape (L P = 4 G): all four tiles' locations / weights are requested up front,
     // one HBM round trip per wave instead of one per tile (see fwd2_kernel)
-    constexpr bool kCanPre = kGatherPreload && !INST && !WP && G == 4;
+    constexpr bool kCanPre = !INST && !WP && G == 4;
     const bool pre = kCanPre && ix.grid_y == 1 && LP == kPreTiles * G;
     float2 xyq[kCanPre ? kPreTiles - 1 : 1];
     float asq[kCanPre ? kPreTiles - 1 : 1];
@@ -841,16 +783,10 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
             asq[k] = w_sp[pt0 + pq];
         }
     }
-    if constexpr (BOXATTN_TUNE_PG_TRACE) {
-        __builtin_amdgcn_sched_barrier(0);
-        ts[6] = __builtin_amdgcn_s_memtime();                 // first loads issued, before the barrier
-        __builtin_amdgcn_sched_barrier(0);
-    }
     levels_commit(lv, lv_regs, L);
     const bool buffered = kCanBuffer && !WP && ix.grid_y == 1 && (LP == 16 || LP == 8) &&
                           ((reinterpret_cast<uintptr_t>(grad_sp) | reinterpret_cast<uintptr_t>(grad_loc)) & 15) == 0;
     float *res = res_all + (kCanBuffer ? (wv * PAIRS + lane / G) * (kBufLP * 3) : 0);
-    if constexpr (BOXATTN_TUNE_PG_TRACE) ts[ts_n++] = __builtin_amdgcn_s_memtime();
     // (wave-uniform trip count: with WP the groups whose tile lies past the end idle)
     for (int tu = t_first, t0 = t_begin; tu < t_end; tu += t_step, t0 += t_step) {
         // ---- step A (the lane keeps its point's geometry in registers for the finish)
@@ -858,33 +794,27 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
         const bool have = lp < t_end;
         const int lq = have ? lp : LP - 1;
         const int l = (int)(((float)lq + 0.5f) * rcp_p);           // lq / P (exact, see rcp_p)
-        float2 xy;
-        float as, al;
-        if constexpr (kGatherPrefetch) {
-            xy = xy_n; as = as_n; al = al_n;
-            if (kCanPre && pre) {
-                xy_n = xyq[0];
-                as_n = asq[0];
+        // (the locations / weights of the next tile are requested during this one)
+        const float2 xy = xy_n;
+        const float as = as_n, al = al_n;
+        if (kCanPre && pre) {
+            xy_n = xyq[0];
+            as_n = asq[0];
 #pragma unroll
-                for (int k = 0; k + 1 < (kCanPre ? kPreTiles - 1 : 1); ++k) {
-                    xyq[k] = xyq[k + 1];
-                    asq[k] = asq[k + 1];
-                }
-            } else {
-                const int nq = min(lp + t_step, LP - 1);
-                xy_n = loc2[pt0 + nq];
-                as_n = w_sp[pt0 + nq];
-                al_n = INST ? w_lv[pt0 + nq] : 0.f;
+            for (int k = 0; k + 1 < (kCanPre ? kPreTiles - 1 : 1); ++k) {
+                xyq[k] = xyq[k + 1];
+                asq[k] = asq[k + 1];
             }
         } else {
-            xy = loc2[pt0 + lq];
-            as = w_sp[pt0 + lq];
-            al = INST ? w_lv[pt0 + lq] : 0.f;
+            const int nq = min(lp + t_step, LP - 1);
+            xy_n = loc2[pt0 + nq];
+            as_n = w_sp[pt0 + nq];
+            al_n = INST ? w_lv[pt0 + nq] : 0.f;
         }
         const Sample<float> s = locate<float>(xy.x, xy.y, lv.h[l], lv.w[l]);
         const u32x4_t myoff =
             corner_offsets<ST>(s, b * (unsigned)S + (unsigned)lv.start[l], H, h, C, have);
-        if constexpr (!UseQuadDpp<G>::value) {
+        if constexpr (G != 4) {
             wave_lds_sync();
             geo[slot] = myoff;
             wave_lds_sync();
@@ -899,21 +829,8 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 u32x4_t off;
-                if constexpr (UseQuadDpp<G>::value) off = quad_bcast(myoff, tb + u);
+                if constexpr (G == 4) off = quad_bcast(myoff, tb + u);
                 else off = geo[tb + u];
-#ifndef BOXATTN_TUNE_PG_ABLATE
-#define BOXATTN_TUNE_PG_ABLATE 0    // timing experiments only (wrong results): 2 = every row load hits
-#endif                              // the first 4 KiB of value (L1 hits), 3 = no row loads
-                if constexpr (BOXATTN_TUNE_PG_ABLATE == 2) {
-                    off.x &= 0xfc0u; off.y &= 0xfc0u; off.z &= 0xfc0u; off.w &= 0xfc0u;
-                }
-                if constexpr (BOXATTN_TUNE_PG_ABLATE == 3 && !INST) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-#pragma unroll
-                        for (int i = 0; i < RowT::NW; ++i) v[u][k].w[i] = off[k] + i;
-                    continue;
-                }
                 row_load<ST, VEC, PSB>(rs, off.x + lane_off, v[u][0]);
                 row_load<ST, VEC, PSB>(rs, off.y + lane_off, v[u][1]);
                 row_load<ST, VEC, PSB>(rs, off.z + lane_off, v[u][2]);
@@ -943,10 +860,6 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
                     m1 = mine ? b1 : m1; m2 = mine ? b2 : m2; m3 = mine ? b3 : m3; m4 = mine ? b4 : m4;
                 }
             }
-        }
-        if constexpr (BOXATTN_TUNE_PG_TRACE) {
-            asm volatile("" ::"v"(s1), "v"(s4));              // after the tile's sums exist
-            if (BOXATTN_TUNE_PG_TRACE == 1 && ts_n < 7) ts[ts_n++] = __builtin_amdgcn_s_memtime();
         }
         // ---- finish: lane (pair, slot) owns point t0 + slot
         if (active && have) {
@@ -995,15 +908,6 @@ __global__ __launch_bounds__(256) void pointgrad2_kernel(
                 *gsp = res[p0];
                 *reinterpret_cast<float2 *>(gl) = make_float2(r[0], r[1]);
             }
-        }
-    }
-    if constexpr (BOXATTN_TUNE_PG_TRACE) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores have left
-        ts[7] = __builtin_amdgcn_s_memtime();
-        if (lane == 0 && wv == 0 && active) {
-#pragma unroll
-            for (int k = 1; k < 8; ++k) grad_sp[pt0 + k] = (float)(unsigned)(ts[k] - ts[0]);
-            grad_sp[pt0] = (float)(unsigned)(ts[0] & 0xffffffu);      // start time (low bits): launch order
         }
     }
 }

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void fwd2_boxes_kernel(
                 corner_offsets<ST>(s, b * (unsigned)S + (unsigned)lv.start[l], H, h, C, have);
             const u32x4_t wt = as_u32x4(s.hh * s.hw * a, s.hh * s.lw * a, s.lh * s.hw * a,
                                         s.lh * s.lw * a);
-            if constexpr (UseQuadDpp<G>::value) {
+            if constexpr (G == 4) {
                 my_off = off;
                 my_wt = wt;
             } else {
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void fwd2_boxes_kernel(
             RowT v[U][4];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if constexpr (UseQuadDpp<G>::value) {
+                if constexpr (G == 4) {
                     off[u] = quad_bcast(my_off, tb + u);
                     wt[u] = quad_bcast(my_wt, tb + u);
                 } else {

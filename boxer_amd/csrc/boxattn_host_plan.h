@@ -235,8 +235,6 @@ inline bool make_plan(const Dims &d, const int64_t *sh, const int64_t *ls, BinPl
     return make_plan_blocks(d, sh, ls, p, rec);
 }
 
-std::atomic<float *> g_dense_dbg{nullptr};      // debugging aid: time stamps (boxattn_set_debug_buffer)
-
 // The PLAN of a backward -- everything the binning knows before the records are written: per bin workgroup
 // and block the first slot, per block the first record, the work-item list -- is what a training forward
 // hands to its backward (a few hundred KB: 1.4 MB at BoxeR-R50 shapes).  The SCRATCH -- the records
@@ -418,9 +416,8 @@ inline bool make_dense_plan(const Dims &d, const int64_t *sh, const int64_t *ls,
     if ((size_t)d.B * d.Lq * d.H * d.L * d.P >= (1ull << 31)) return false;       // 32-bit point ids
     if (d.n_value() * (size_t)elem >= kOobOffset) return false;
     const int unit = 8 * elem;                                  // bytes per unit of a window's pitch / offset
-    const int budget = elem == 2 ? kDenseZeroOff : BOXATTN_DENSE_F32_LDS - 128;      // (minus the forwards' row of zeros)
+    const int budget = elem == 2 ? kDenseZeroOff : kDenseF32LdsBytes - 128;     // (minus the forwards' row of zeros)
     p = DensePlan{};
-    p.dbg = g_dense_dbg.load();
     p.L = d.L; p.B = d.B; p.Lq = d.Lq; p.S = d.S; p.H = d.H;
     const auto magic = [](int dd) { return dd == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned)dd); };
     p.mag_h = magic(d.H);

@@ -62,18 +62,15 @@ __device__ __forceinline__ int spec_want(int c, int cap_old)
 // ---------------------------------------------------------------------------------------------------------------
 // fill: one pass of bin workgroup `wg` of slice `s` over its (contiguous) queries; wide records only
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef BOXATTN_TUNE_SPEC_U
-#define BOXATTN_TUNE_SPEC_U 1
-#endif
+constexpr int kSpecU = 1;
 template <int THREADS, int PT>
 __device__ __forceinline__ void spec_fill_body(int *hist, int *base, BinLevel *s_lv, const float *__restrict__ loc,
                                                const float *__restrict__ w_sp, const BinPlan &plan, int H, int Lq,
                                                int P, int q_per_wg, int *__restrict__ cursor_s,
-                                               const int *__restrict__ cbase_s, int *__restrict__ records, int s, int wg,
-                                               unsigned long long *trace = nullptr)
+                                               const int *__restrict__ cbase_s, int *__restrict__ records, int s, int wg)
 {
     static_assert(PT == 1 || PT == 4, "points per thread and group");
-    constexpr int U = PT == 4 ? BOXATTN_TUNE_SPEC_U : 4;          // groups of PT points per thread and step
+    constexpr int U = PT == 4 ? kSpecU : 4;         // groups of PT points per thread and step
     constexpr int STRIDE = THREADS * U;
     static_assert(STRIDE * PT * 4 < (1 << kSpecRankBits), "ranks of a step");
     const int b = s / H, h = s % H;
@@ -117,20 +114,9 @@ __device__ __forceinline__ void spec_fill_body(int *hist, int *base, BinLevel *s
     // column << 13 | crosses a block row << 14, and its <= 4 ranks, 16 bits each.  The footprint's blocks are b, b + 1
     // (next block column), b + nbx (next block row), b + nbx + 1: block indices step by at most one per pixel.
     constexpr unsigned kIn = 1u << 12, kCc = 1u << 13, kCr = 1u << 14;
-    unsigned long long ph[4] = {0, 0, 0, 0};      // trace builds: time in rank / wait + claim / wait / store (thread 0)
-#define SPEC_PHASE(i_, t0_)                                                                            \
-    do {                                                                                             \
-        if (BOXATTN_RIDE_TRACE) {                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                       \
-            const unsigned long long now_ = __builtin_amdgcn_s_memrealtime();                        \
-            ph[i_] += now_ - t0_;                                                                    \
-            t0_ = now_;                                                                              \
-        }                                                                                            \
-    } while (0)
     auto work_step = [&](const Step &t, int g0) {
         unsigned meta[U][PT], rk01[U][PT], rk23[U][PT];
         int nbx_u[U];
-        unsigned long long tph = BOXATTN_RIDE_TRACE ? __builtin_amdgcn_s_memrealtime() : 0ull;
         // ---- rank.  Three loops, so that the <= 4 PT LDS atomics of a group are all IN FLIGHT before the first rank is
         // used: one returned LDS atomic is ~100 cycles, and waited for one at a time (16 of them a step) they were a
         // third of the phase (rider trace: 1.75 us a step for ~300 instructions).
@@ -180,7 +166,6 @@ __device__ __forceinline__ void spec_fill_body(int *hist, int *base, BinLevel *s
                 rk23[u][k] = (r[k][2] & 0xFFFFu) | (r[k][3] << 16);
             }
         }
-        SPEC_PHASE(0, tph);
         lds_barrier();
         // ---- claim: thread t speaks for the blocks t, t + THREADS, ...: ONE returned global atomic per touched block and
         // step, all of a thread's claims of a batch in flight at once (the rank-0 thread of a block claiming it saved this
@@ -211,9 +196,7 @@ __device__ __forceinline__ void spec_fill_body(int *hist, int *base, BinLevel *s
                     base[bk] = old[i] + c[i] <= end[i] ? old[i] : -1;         // -1: the range is full, the block will be redone
                 }
         }
-        SPEC_PHASE(1, tph);
         lds_barrier();
-        SPEC_PHASE(2, tph);
         // ---- store (the slice's records are < 4 GB, spec_ok: 32-bit byte offsets from a uniform base).  The bases of a
         // group's points are all read before the first is used (as the ranks above).
 #pragma unroll
@@ -244,11 +227,7 @@ __device__ __forceinline__ void spec_fill_body(int *hist, int *base, BinLevel *s
                     *reinterpret_cast<int4 *>(rb8 + ((unsigned)(sb[k][3] + (int)(rk23[u][k] >> 16)) << 4)) = r;
             }
         }
-        SPEC_PHASE(3, tph);
     };
-#ifndef BOXATTN_TUNE_SPEC_PREFETCH
-#define BOXATTN_TUNE_SPEC_PREFETCH 1      // the next step's locations in flight while a step is worked (a second Step of registers)
-#endif
     Step sa;
     if (n_grp > 0) load_step(sa, (int)threadIdx.x);
     if (threadIdx.x == 0) {
@@ -257,26 +236,16 @@ __device__ __forceinline__ void spec_fill_body(int *hist, int *base, BinLevel *s
     }
     for (int k = threadIdx.x; k < plan.nblk; k += THREADS) hist[k] = 0;
     __syncthreads();
-    if constexpr (BOXATTN_TUNE_SPEC_PREFETCH != 0) {
-        Step sb;
-        for (int start = 0; start < n_grp; start += 2 * STRIDE) {           // workgroup-uniform trip count
-            const int g0 = start + (int)threadIdx.x;
-            if (start + STRIDE < n_grp) load_step(sb, g0 + STRIDE);
-            work_step(sa, g0);
-            if (start + STRIDE >= n_grp) break;
-            if (start + 2 * STRIDE < n_grp) load_step(sa, g0 + 2 * STRIDE);
-            work_step(sb, g0 + STRIDE);
-        }
-    } else {
-        for (int start = 0; start < n_grp; start += STRIDE) {
-            const int g0 = start + (int)threadIdx.x;
-            work_step(sa, g0);
-            if (start + STRIDE < n_grp) load_step(sa, g0 + STRIDE);
-        }
+    // the next step's locations in flight while a step is worked (a second Step of registers)
+    Step sb;
+    for (int start = 0; start < n_grp; start += 2 * STRIDE) {           // workgroup-uniform trip count
+        const int g0 = start + (int)threadIdx.x;
+        if (start + STRIDE < n_grp) load_step(sb, g0 + STRIDE);
+        work_step(sa, g0);
+        if (start + STRIDE >= n_grp) break;
+        if (start + 2 * STRIDE < n_grp) load_step(sa, g0 + 2 * STRIDE);
+        work_step(sb, g0 + STRIDE);
     }
-#undef SPEC_PHASE
-    if (BOXATTN_RIDE_TRACE && trace && threadIdx.x == 0)
-        for (int i = 0; i < 4; ++i) trace[i] = ph[i];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -585,23 +554,19 @@ __device__ __forceinline__ void bin_fill_spec_ride(const BinRide r, unsigned id,
         for (int k = threadIdx.x; k < plan.nblk; k += THREADS) r.ctickets[(size_t)s * plan.nblk + k] = 0;
     int *cursor_s = r.spec.cursor + (size_t)s * plan.nblk;
     int *cbase_s = r.spec.cbase + (size_t)s * (plan.nblk + 1);
-    RIDE_STAMP(5);
-    unsigned long long *tr = BOXATTN_RIDE_TRACE && r.trace ? r.trace + (size_t)id * 8 : nullptr;     // [0..3]: phase times
     if (GRP && (r.flavour & kRideGroup))
         spec_fill_group_body<THREADS>(hist, base, m.lv, r.loc, plan, r.H, r.Lq, r.q_per_wg, cursor_s, cbase_s, r.records, s, wg);
     else if (r.flavour & kRidePt4)
         spec_fill_body<THREADS, 4>(hist, base, m.lv, r.loc, r.w_sp, plan, r.H, r.Lq, r.P, r.q_per_wg, cursor_s, cbase_s,
-                                   r.records, s, wg, tr);
+                                   r.records, s, wg);
     else
         spec_fill_body<THREADS, 1>(hist, base, m.lv, r.loc, r.w_sp, plan, r.H, r.Lq, r.P, r.q_per_wg, cursor_s, cbase_s,
-                                   r.records, s, wg, tr);
-    RIDE_STAMP(6);
+                                   r.records, s, wg);
     // every claim of this workgroup has returned (its value was used); the ticket orders the riders of the slice
     if (!last_arriver<THREADS>(r.tickets + (size_t)s * kRideTickets + kScanSub, r.n_wg, m.flag)) return;
     const ScanOut o{r.subtot, r.offsets, r.items, r.combos, r.n_items};
     spec_chain_body<THREADS>(o, plan, m.lv, s, m.wsum, hist, base, cursor_s, cbase_s,
                              r.spec.redo + (size_t)s * (plan.nblk + 1), r.spec.stats);
-    RIDE_STAMP(7);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

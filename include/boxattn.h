@@ -167,7 +167,7 @@ int instattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t
  *   hints : 0, or BOXATTN_HINT_* bits (see *_fwd_train_*); speed only, never results.
  *   state / state_bytes : NULL / 0, or the caller's state buffer of this (stream, dimensions, level shapes) -- see
  *       *_fwd_train_* below.  With it, box attention whose accumulate runs on the matrix cores (16-bit storage at 16 /
- *       32 / 64 channels per head, float32 at 32) on maps of up to 1 535 blocks of 8x4 pixels per (image, head) fills
+ *       32 / 64 channels per head, float32 at 32) on maps of up to 1 279 blocks of 8x4 pixels per (image, head) fills
  *       its bins in ONE pass: the state keeps, per block, the record range the previous call planned
  *       from its own counts; the fill riders claim slots in those ranges with one returned atomic per block and step;
  *       a block that outgrows its range is recomputed from the sampling locations by a redo worker of the accumulate
@@ -728,8 +728,8 @@ int boxattn_bwd_record_kind(int elem_bytes, int instance, int B, int S, int H, i
 int boxattn_options_epoch(void);
 
 /*
- * Debugging aid of the window-staged kernels: builds with -DBOXATTN_DENSE_DEBUG=2 write per-wave time
- * stamps to this device buffer (tools/gpu_dense_trace.py).  Ignored by regular builds.
+ * Has no effect; kept for ABI 8.  (It named the device buffer of time-stamp builds of the kernels, which no
+ * longer exist.)
  */
 void boxattn_set_debug_buffer(float *device_buffer);
 
