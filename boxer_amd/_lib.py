@@ -32,94 +32,88 @@ BUILD_DIR = os.path.join(_PKG, "_build")
 
 _lib = None
 
-_vp, _i = ctypes.c_void_p, ctypes.c_int
-_DIMS = [_i] * 7                      # B, S, H, C, L, Lq, P
-_SIGNATURES = {
-    # name: argtypes  (see include/boxattn.h)
-    "boxattn_fwd": [_vp] * 5 + _DIMS + [_vp, _vp],
-    "boxattn_bwd": [_vp] * 6 + _DIMS + [_vp] * 3 + [_vp],
-    "instattn_fwd": [_vp] * 6 + _DIMS + [_vp] * 2 + [_vp],
-    "instattn_bwd": [_vp] * 8 + _DIMS + [_vp] * 4 + [_vp],
-}
-_WS_SIGNATURES = {
-    # plain backward args + shapes_host, lsi_host, workspace, workspace_bytes, plan, plan_bytes, state, state_bytes,
-    # hints, stream
-    "boxattn_bwd_ws": [_vp] * 6 + _DIMS + [_vp] * 3 + [_vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
-                                                       _vp, ctypes.c_size_t, _i, _vp],
-    "instattn_bwd_ws": [_vp] * 8 + _DIMS + [_vp] * 4 + [_vp, _vp, _vp, ctypes.c_size_t, _vp,
-                                                        ctypes.c_size_t, _vp, ctypes.c_size_t, _i, _vp],
-    # forward args + shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, int *plan_built, stream
-    "boxattn_fwd_train": [_vp] * 5 + _DIMS + [_vp] + [_vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
-                                                      _i, _vp, _vp],
-    "instattn_fwd_train": [_vp] * 6 + _DIMS + [_vp] * 2 + [_vp, _vp, _vp, ctypes.c_size_t, _vp,
-                                                          ctypes.c_size_t, _i, _vp, _vp],
-}
-WANT_VALUE, WANT_POINTS, WANT_ALL = 1, 2, 3      # BOXATTN_WANT_*: the gradient groups of a partial backward
-# *_bwd_part_*: the arguments of *_bwd_ws_* (float64: of the plain backward) + int want
-_PART_SIGNATURES = {stem.replace("_bwd_ws", "_bwd_part"): args + [_i] for stem, args in _WS_SIGNATURES.items()
-                    if "_bwd_ws" in stem}
-_PART_F64_SIGNATURES = {stem + "_part_f64": _SIGNATURES[stem] + [_i] for stem in ("boxattn_bwd", "instattn_bwd")}
-_HL_SIGNATURES = {
-    # forward args + shapes_host, lsi_host, stream
-    "boxattn_fwd_hl": [_vp] * 5 + _DIMS + [_vp] + [_vp, _vp, _vp],
-}
-HINT_NOT_LOCAL = 1          # BOXATTN_HINT_NOT_LOCAL
-HINT_FRESH_STATE = 2        # BOXATTN_HINT_FRESH_STATE
-_ll = ctypes.c_longlong
-_POINTWISE_SIGNATURES = {
-    "boxattn_softmax_fwd_f32": [_vp, _ll, _i, _vp, _vp],
-    "boxattn_softmax_fwd_bf16": [_vp, _ll, _i, _vp, _vp],
-    "boxattn_softmax_fwd_f16": [_vp, _ll, _i, _vp, _vp],
-    "boxattn_softmax_bwd_f32": [_vp, _vp, _ll, _i, _vp, _vp],
-    "boxattn_softmax_bwd_bf16": [_vp, _vp, _ll, _i, _vp, _vp],
-    "boxattn_softmax_bwd_f16": [_vp, _vp, _ll, _i, _vp, _vp],
-    "boxattn_value_prep_f32": [_vp, _vp, _ll, _i, _vp, _vp],
-    "boxattn_value_prep_bf16": [_vp, _vp, _ll, _i, _vp, _vp],
-    "boxattn_value_prep_f32_f16": [_vp, _vp, _ll, _i, _vp, _vp],     # float32 -> f16
-    "boxattn_value_prep_f16": [_vp, _vp, _ll, _i, _vp, _vp],
-    # logits, rows, L, k, spatial_w, level_w | NULL, stream
-    **{"instattn_weights_fwd_" + suf: [_vp, _ll, _i, _i, _vp, _vp, _vp] for suf in ("f32", "bf16", "f16")},
-    # logits, grad_spatial_w | NULL, grad_level_w | NULL, rows, L, k, grad_logits, stream
-    **{"instattn_weights_bwd_" + suf: [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp] for suf in ("f32", "bf16", "f16")},
-}
-_GRID_SIGNATURES = {
-    # ref, ref_dim, ref_per_head, offsets, V, angle_mode, kernel_idx, valid_ratios, [grad_grid,]
-    # B, Lq, H, L, P, outputs..., stream
-    "boxattn_grid_fwd_f32": [_vp, _i, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp],
-    "boxattn_grid_bwd_f32": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp, _vp],
-}
-# The calls from boxes and logits: value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, [V, angle_mode: the box
-# flavour,] kernel_idx, valid_ratios | NULL, logits, <upstream gradients>, B, S, H, C, L, Lq, k | P, <outputs>, stream
-def _boxes_signatures(stem, box, upstream, outputs):
-    args = ([_vp] * 4 + [_i, _i] + [_vp] + ([_i, _i] if box else []) + [_vp] * 3 + [_vp] * upstream + _DIMS +
-            [_vp] * outputs + [_vp])
-    return {stem + suf: args for suf in ("f32", "bf16", "f16")}
-
-
-# out, mask_out | NULL
-_BOXES_SIGNATURES = _boxes_signatures("instattn_fwd_boxes_", False, 0, 2)
-# grad_out, grad_mask | NULL; grad_offsets, grad_ref_rows | NULL, grad_logits
-_BOXES_BWD_SIGNATURES = _boxes_signatures("instattn_bwd_boxes_", False, 2, 3)
-# out
-_BOX_BOXES_SIGNATURES = _boxes_signatures("boxattn_fwd_boxes_", True, 0, 1)
-# grad_out; grad_offsets, grad_ref_rows | NULL, grad_logits
-_BOX_BOXES_BWD_SIGNATURES = _boxes_signatures("boxattn_bwd_boxes_", True, 1, 3)
-EXPORTS = ["boxattn_abi_version", "boxattn_build_info", "boxattn_set_variant", "boxattn_set_option",
-           "boxattn_options_epoch", "boxattn_fwd_route", "boxattn_bwd_accumulate_kind", "boxattn_bwd_record_kind",
-           "boxattn_set_debug_buffer",
-           "boxattn_fwd_hl_f32", "boxattn_fwd_hl_bf16", "boxattn_fwd_hl_f16", *sorted(_POINTWISE_SIGNATURES),
-           "boxattn_profile_begin", "boxattn_profile_end", "boxattn_bwd_workspace_bytes",
-           "boxattn_plan_bytes", "boxattn_state_bytes",
-           "boxattn_grid_fwd_f32", "boxattn_grid_bwd_f32", "instattn_fwd_boxes_ok", *sorted(_BOXES_SIGNATURES),
-           "instattn_bwd_boxes_ok", *sorted(_BOXES_BWD_SIGNATURES),
-           "boxattn_fwd_boxes_ok", *sorted(_BOX_BOXES_SIGNATURES),
-           "boxattn_bwd_boxes_ok", *sorted(_BOX_BOXES_BWD_SIGNATURES)] + [
-    "%s_%s" % (stem, suf) for stem in _SIGNATURES for suf in ("f32", "f64", "bf16", "f16")] + [
-    "%s_%s" % (stem, suf) for stem in _WS_SIGNATURES for suf in ("f32", "bf16", "f16")] + [
-    "%s_%s" % (stem, suf) for stem in _PART_SIGNATURES for suf in ("f32", "bf16", "f16")] + sorted(_PART_F64_SIGNATURES)
+_vp, _i, _ll, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t
+_S3, _S4 = ("f32", "bf16", "f16"), ("f32", "f64", "bf16", "f16")
 # 16-bit storage types: the suffix of their entry points, which share signatures (uint16_t storage)
 H16_SUFFIXES = ("bf16", "f16")
 ABI_VERSION = 8
+WANT_VALUE, WANT_POINTS, WANT_ALL = 1, 2, 3      # BOXATTN_WANT_*: the gradient groups of a partial backward
+HINT_NOT_LOCAL = 1          # BOXATTN_HINT_NOT_LOCAL
+HINT_FRESH_STATE = 2        # BOXATTN_HINT_FRESH_STATE
+
+# The argument lists of include/boxattn.h, in pieces
+_DIMS = [_i] * 7                      # B, S, H, C, L, Lq, P
+_STREAM = [_vp]
+# a flavour's forward / backward up to its last output: value, shapes, lsi, loc, weights, [grad_out, [grad_mask]],
+# dims, outputs
+_FWD = {"boxattn": [_vp] * 5 + _DIMS + [_vp], "instattn": [_vp] * 6 + _DIMS + [_vp] * 2}
+_BWD = {"boxattn": [_vp] * 6 + _DIMS + [_vp] * 3, "instattn": [_vp] * 8 + _DIMS + [_vp] * 4}
+_HOST = [_vp, _vp]                    # shapes_host, lsi_host
+_TRAIN = _HOST + [_vp, _sz, _vp, _sz, _i, _vp]         # + plan, plan_bytes, state, state_bytes, hints, int *plan_built
+# + workspace, workspace_bytes, plan, plan_bytes, state, state_bytes, hints
+_WS = _HOST + [_vp, _sz, _vp, _sz, _vp, _sz, _i]
+_QUERY = [_i] * 9                     # elem_bytes, instance | aligned, dims
+_SIZES = [_i] * 8 + _HOST             # is_16bit, dims, shapes_host, lsi_host
+
+
+def _boxes(box, upstream, outputs):
+    """The calls from boxes and logits: value, shapes, lsi, ref, ref_dim, ref_per_head, offsets, [V, angle_mode: the
+    box flavour,] kernel_idx, valid_ratios | NULL, logits, <upstream gradients>, B, S, H, C, L, Lq, k | P, <outputs>,
+    stream"""
+    return ([_vp] * 4 + [_i, _i, _vp] + ([_i, _i] if box else []) + [_vp] * 3 + [_vp] * upstream + _DIMS +
+            [_vp] * outputs + _STREAM)
+
+
+def _family(stem, suffixes, argtypes, restype=_i):
+    return {"%s_%s" % (stem, suf): (restype, argtypes) for suf in suffixes}
+
+
+# name -> (restype, argtypes): every function include/boxattn.h declares (tests/test_capi_symbols.py holds it to that)
+_SIGNATURES = {
+    "boxattn_abi_version": (_i, []),
+    "boxattn_build_info": (ctypes.c_char_p, []),
+    "boxattn_set_variant": (_i, [_i]),
+    "boxattn_set_option": (_i, [_i, _i]),
+    "boxattn_options_epoch": (_i, []),
+    "boxattn_set_debug_buffer": (None, [_vp]),
+    "boxattn_profile_begin": (_i, []),
+    "boxattn_profile_end": (_i, [_vp, _vp]),              # double *ms_sum, int *launches
+    "boxattn_fwd_route": (_i, [_i] + _QUERY + _HOST),     # elem_bytes, instance, aligned, dims, shapes_host, lsi_host
+    "boxattn_bwd_accumulate_kind": (_i, _QUERY),
+    "boxattn_bwd_record_kind": (_i, _QUERY),
+    "boxattn_state_bytes": (_sz, _DIMS + _HOST),
+    "boxattn_bwd_workspace_bytes": (_sz, _SIZES),
+    "boxattn_plan_bytes": (_sz, _SIZES),
+    **_family("boxattn_fwd_hl", _S3, _FWD["boxattn"] + _HOST + _STREAM),
+    # ref, ref_dim, ref_per_head, offsets, V, angle_mode, kernel_idx, valid_ratios, [grad_grid,] B, Lq, H, L, P, outputs,
+    # stream
+    "boxattn_grid_fwd_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp] + _STREAM),
+    "boxattn_grid_bwd_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp] + _STREAM),
+    **_family("boxattn_softmax_fwd", _S3, [_vp, _ll, _i, _vp] + _STREAM),
+    **_family("boxattn_softmax_bwd", _S3, [_vp, _vp, _ll, _i, _vp] + _STREAM),
+    **_family("boxattn_value_prep", _S3 + ("f32_f16",), [_vp, _vp, _ll, _i, _vp] + _STREAM),     # f32_f16: float32 -> f16
+    # logits, rows, L, k, spatial_w, level_w | NULL, stream
+    **_family("instattn_weights_fwd", _S3, [_vp, _ll, _i, _i, _vp, _vp] + _STREAM),
+    # logits, grad_spatial_w | NULL, grad_level_w | NULL, rows, L, k, grad_logits, stream
+    **_family("instattn_weights_bwd", _S3, [_vp, _vp, _vp, _ll, _i, _i, _vp] + _STREAM),
+    **_family("instattn_fwd_boxes", _S3, _boxes(False, 0, 2)),          # out, mask_out | NULL
+    # grad_out, grad_mask | NULL; grad_offsets, grad_ref_rows | NULL, grad_logits
+    **_family("instattn_bwd_boxes", _S3, _boxes(False, 2, 3)),
+    **_family("boxattn_fwd_boxes", _S3, _boxes(True, 0, 1)),            # out
+    **_family("boxattn_bwd_boxes", _S3, _boxes(True, 1, 3)),            # grad_out; the three gradients
+    **{"%s_%s_boxes_ok" % (op, way): (_i, _QUERY) for op in _FWD for way in ("fwd", "bwd")},
+}
+for _op in _FWD:
+    for _stem, _suffixes, _args in (
+            ("fwd", _S4, _FWD[_op] + _STREAM),
+            ("fwd_train", _S3, _FWD[_op] + _TRAIN + _STREAM),
+            ("bwd", ("f32", "f64"), _BWD[_op] + _STREAM),
+            ("bwd", H16_SUFFIXES, _BWD[_op] + [_vp] + _STREAM),         # + float *grad_value_ws
+            ("bwd_ws", _S3, _BWD[_op] + _WS + _STREAM),
+            ("bwd_part", _S3, _BWD[_op] + _WS + _STREAM + [_i]),        # *_bwd_ws_* + int want
+            ("bwd_part", ("f64",), _BWD[_op] + _STREAM + [_i])):        # *_bwd_f64 + int want
+        _SIGNATURES.update(_family("%s_%s" % (_op, _stem), _suffixes, _args))
+EXPORTS = list(_SIGNATURES)
 
 
 def hipcc_path():
@@ -216,56 +210,9 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'`). boxer_amd has no CPU "
             "fallback by design." % path)
     lib = ctypes.CDLL(path)
-    lib.boxattn_abi_version.restype = _i
-    lib.boxattn_build_info.restype = ctypes.c_char_p
-    lib.boxattn_set_variant.argtypes = [_i]
-    lib.boxattn_set_variant.restype = _i
-    for stem, args in _SIGNATURES.items():
-        for suf in ("f32", "f64") + H16_SUFFIXES:
-            fn = getattr(lib, "%s_%s" % (stem, suf))
-            extra = [_vp] if (suf in H16_SUFFIXES and stem.endswith("bwd")) else []
-            fn.argtypes = args[:-1] + extra + args[-1:]        # ..., [grad_value_ws], stream
-            fn.restype = _i
-    for stem, args in _WS_SIGNATURES.items():
-        for suf in ("f32",) + H16_SUFFIXES:
-            fn = getattr(lib, "%s_%s" % (stem, suf))
-            fn.argtypes = args
-            fn.restype = _i
-    for stem, args in _PART_SIGNATURES.items():
-        for suf in ("f32",) + H16_SUFFIXES:
-            fn = getattr(lib, "%s_%s" % (stem, suf))
-            fn.argtypes = args
-            fn.restype = _i
-    for name, args in _PART_F64_SIGNATURES.items():
-        getattr(lib, name).argtypes = args
-        getattr(lib, name).restype = _i
-    for stem, args in _HL_SIGNATURES.items():
-        for suf in ("f32",) + H16_SUFFIXES:
-            fn = getattr(lib, "%s_%s" % (stem, suf))
-            fn.argtypes = args
-            fn.restype = _i
-    lib.boxattn_set_option.argtypes = [_i, _i]
-    lib.boxattn_set_option.restype = _i
-    lib.boxattn_options_epoch.restype = _i
-    lib.boxattn_fwd_route.argtypes = [_i] * 10 + [_vp, _vp]
-    lib.boxattn_fwd_route.restype = _i
-    lib.boxattn_bwd_accumulate_kind.argtypes = [_i] * 9
-    lib.boxattn_bwd_accumulate_kind.restype = _i
-    lib.boxattn_bwd_record_kind.argtypes = [_i] * 9
-    lib.boxattn_bwd_record_kind.restype = _i
-    for name, args in (list(_GRID_SIGNATURES.items()) + list(_POINTWISE_SIGNATURES.items()) +
-                       list(_BOXES_SIGNATURES.items()) + list(_BOXES_BWD_SIGNATURES.items()) +
-                       list(_BOX_BOXES_SIGNATURES.items()) + list(_BOX_BOXES_BWD_SIGNATURES.items())):
-        getattr(lib, name).argtypes = args
-        getattr(lib, name).restype = _i
-    for name in ("instattn_fwd_boxes_ok", "instattn_bwd_boxes_ok", "boxattn_fwd_boxes_ok", "boxattn_bwd_boxes_ok"):
-        getattr(lib, name).argtypes = [_i] * 9
-        getattr(lib, name).restype = _i
-    lib.boxattn_state_bytes.argtypes = [_i] * 7 + [_vp, _vp]
-    lib.boxattn_state_bytes.restype = ctypes.c_size_t
-    for name in ("boxattn_bwd_workspace_bytes", "boxattn_plan_bytes"):
-        getattr(lib, name).argtypes = [_i] * 8 + [_vp, _vp]
-        getattr(lib, name).restype = ctypes.c_size_t
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.boxattn_abi_version() != ABI_VERSION:
         raise RuntimeError("ABI version mismatch in %s" % path)
     _lib = lib

@@ -304,10 +304,22 @@ inline BinRide place_riders(const BinRide *ride_in, unsigned own_blocks, unsigne
 // ------------------------------------------------------------------------------ forward
 inline bool make_dense_plan(const Dims &d, const int64_t *sh, const int64_t *ls, DensePlan &p, int elem);
 
-// What only some forward entry points pass.  count_ride: the backward's count pass + scans to run as rider workgroups
-// of the forward kernel (training forward); *ride_taken says whether the kernel that was launched carried them
+// A forward call's operands and its outputs, filled by the extern "C" wrappers (T: float; double for float64 storage).
+// w_lv / mask: instance attention only; shapes_host / lsi_host: the host copies of the level tables (NULL in the entry
+// points that take none).
+template <typename ST> struct FwdIn {
+    typedef typename Storage<ST>::compute T;
+    const ST *value;
+    const int64_t *shapes, *lsi;
+    const T *loc, *w_sp, *w_lv;
+    Dims d;
+    const int64_t *shapes_host, *lsi_host;
+    hipStream_t st;
+};
+template <typename ST> struct FwdOut { ST *out, *mask; };
+// What only the training forward passes.  count_ride: the backward's count pass + scans to run as rider workgroups
+// of the forward kernel; *ride_taken says whether the kernel that was launched carried them
 struct FwdExtras {
-    const int64_t *shapes_host = nullptr, *lsi_host = nullptr;
     const BinRide *count_ride = nullptr;
     bool *ride_taken = nullptr;
     bool allow_dense = true;
@@ -367,35 +379,33 @@ inline int fwd_route(int elem_bytes, bool inst, const Dims &d, const FwdAlign &a
 }
 
 template <typename ST, bool INST>
-int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
-               const typename Storage<ST>::compute *loc,
-               const typename Storage<ST>::compute *w_sp,
-               const typename Storage<ST>::compute *w_lv, const Dims &d, ST *out, ST *mask,
-               const FwdExtras &x, hipStream_t st)
+int launch_fwd(const FwdIn<ST> &in, const FwdOut<ST> &o, const FwdExtras &x)
 {
+    const Dims &d = in.d;
+    const hipStream_t st = in.st;
     const BinRide *const count_ride = x.count_ride;
     bool *const ride_taken = x.ride_taken;
     if (ride_taken) *ride_taken = false;
     if (!d.valid()) return (int)hipErrorInvalidValue;
     if (d.empty()) return 0;                                   // no queries: nothing to write
-    if (!shapes || !lsi || !loc || !w_sp || !out || (INST && (!w_lv || !mask)))
+    if (!in.shapes || !in.lsi || !in.loc || !in.w_sp || !o.out || (INST && (!in.w_lv || !o.mask)))
         return (int)hipErrorInvalidValue;
     const size_t n_qh = d.n_qh();
     if (d.n_value() == 0) {                                    // no pixels: every sample is 0
-        hipError_t e = zero_async(out, n_qh * d.C * sizeof(ST), st);
+        hipError_t e = zero_async(o.out, n_qh * d.C * sizeof(ST), st);
         if (e == hipSuccess && INST)
-            e = zero_async(mask, n_qh * d.C * d.P * sizeof(ST), st);
+            e = zero_async(o.mask, n_qh * d.C * d.P * sizeof(ST), st);
         return (int)e;
     }
-    if (!value) return (int)hipErrorInvalidValue;
+    if (!in.value) return (int)hipErrorInvalidValue;
     const size_t va = 4 * sizeof(ST);
     FwdAlign al;
-    al.fast = aligned(value, va) && aligned(loc, 8) && aligned(out, va) && (!INST || aligned(mask, va));
-    al.rows16 = aligned(value, 16) && aligned(out, 16) && (!INST || aligned(mask, 16));
-    al.staged = aligned(value, 16) && aligned(out, 16) && aligned(loc, 8);
+    al.fast = aligned(in.value, va) && aligned(in.loc, 8) && aligned(o.out, va) && (!INST || aligned(o.mask, va));
+    al.rows16 = aligned(in.value, 16) && aligned(o.out, 16) && (!INST || aligned(o.mask, 16));
+    al.staged = aligned(in.value, 16) && aligned(o.out, 16) && aligned(in.loc, 8);
     FwdRoute r;
     DensePlan dp;
-    const int family = fwd_route((int)sizeof(ST), INST, d, al, x.shapes_host, x.lsi_host, x.allow_dense, r, dp);
+    const int family = fwd_route((int)sizeof(ST), INST, d, al, in.shapes_host, in.lsi_host, x.allow_dense, r, dp);
     if (family < 0) return (int)hipErrorInvalidValue;
     if constexpr (!std::is_same<ST, double>::value) {
         if (family != kFwdGeneric) {
@@ -407,8 +417,8 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                 if (family == kFwdStaged) {
                     const BinRide ride = count_ride ? *count_ride : BinRide{};
                     if constexpr (IsHalf16<ST>::value)
-                        launch_fwd_dense<ST>(value, loc, w_sp, out, dp, (unsigned)vbytes, ride, x.stats, st);
-                    else launch_fwd_dense_f32(value, loc, w_sp, out, dp, (unsigned)vbytes, ride, x.stats, st);
+                        launch_fwd_dense<ST>(in.value, in.loc, in.w_sp, o.out, dp, (unsigned)vbytes, ride, x.stats, st);
+                    else launch_fwd_dense_f32(in.value, in.loc, in.w_sp, o.out, dp, (unsigned)vbytes, ride, x.stats, st);
                     if (count_ride && ride_taken) *ride_taken = true;
                     return finish();
                 }
@@ -422,15 +432,17 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                 if constexpr (INST) {
 #define BOXATTN_LAUNCH_WIDE(GG, VV)                                                           \
     hipLaunchKernelGGL((fwd_wide_kernel<ST, GG, VV, true>), dim3(total), dim3(256), 0, st,    \
-                       value, shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.L, d.Lq, d.P, out,    \
-                       mask, with_grid(ix, r.wblocks, 1, 1), (unsigned)vbytes, ride, ws);
+                       in.value, in.shapes, in.lsi, in.loc, in.w_sp, in.w_lv, d.S, d.H, d.L,  \
+                       d.Lq, d.P, o.out, o.mask, with_grid(ix, r.wblocks, 1, 1),              \
+                       (unsigned)vbytes, ride, ws);
                     BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_WIDE);
 #undef BOXATTN_LAUNCH_WIDE
                 } else {
 #define BOXATTN_LAUNCH_WIDE(GG, VV)                                                           \
     hipLaunchKernelGGL((fwd_wide_kernel<ST, GG, VV, false>), dim3(total), dim3(256), 0, st,   \
-                       value, shapes, lsi, loc, w_sp, NoArg{}, d.S, d.H, d.L, d.Lq, d.P, out, \
-                       NoArg{}, with_grid(ix, r.wblocks, 1, 1), (unsigned)vbytes, ride, ws);
+                       in.value, in.shapes, in.lsi, in.loc, in.w_sp, NoArg{}, d.S, d.H, d.L,  \
+                       d.Lq, d.P, o.out, NoArg{}, with_grid(ix, r.wblocks, 1, 1),             \
+                       (unsigned)vbytes, ride, ws);
                     BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_LAUNCH_WIDE);
 #undef BOXATTN_LAUNCH_WIDE
                 }
@@ -443,8 +455,8 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
                 const BinRide ride = place_riders(count_ride, (unsigned)blocks, &total);
 #define BOXATTN_FWD2(GG, VV)                                                                  \
     hipLaunchKernelGGL((fwd2_kernel<ST, GG, INST, GatherUnroll<ST, GG, VV>::value, VV>),      \
-                       dim3(total, 1), dim3(256), 0, st, value, shapes, lsi, loc, w_sp,       \
-                       w_lv, d.S, d.H, d.L, d.Lq, d.P, out, mask,                             \
+                       dim3(total, 1), dim3(256), 0, st, in.value, in.shapes, in.lsi, in.loc, \
+                       in.w_sp, in.w_lv, d.S, d.H, d.L, d.Lq, d.P, o.out, o.mask,             \
                        with_grid(ix, blocks, 1, (d.P + GG - 1) / GG), (unsigned)vbytes, ride);
                 BOXATTN_GATHER_DISPATCH(cfg, BOXATTN_FWD2);
 #undef BOXATTN_FWD2
@@ -452,7 +464,8 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
             } else {
                 for_group(cfg.G, [&](auto g) {
                     hipLaunchKernelGGL((fwd_fast_kernel<ST, 4, decltype(g)::value, INST>), dim3(blocks), dim3(256), 0, st,
-                                       value, shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.L, d.Lq, d.P, out, mask, n_qh);
+                                       in.value, in.shapes, in.lsi, in.loc, in.w_sp, in.w_lv, d.S, d.H, d.L, d.Lq, d.P,
+                                       o.out, o.mask, n_qh);
                 });
             }
             return finish();
@@ -461,8 +474,8 @@ int launch_fwd(const ST *value, const int64_t *shapes, const int64_t *lsi,
     const size_t n = n_qh * d.C;
     const int blocks = (int)std::min<size_t>((n + 255) / 256, (size_t)1 << 20);
     ScopedKernelTimer timer(g_prof.ev[kSlotFwd], st);
-    hipLaunchKernelGGL((fwd_generic_kernel<ST, INST>), dim3(blocks), dim3(256), 0, st, value,
-                       shapes, lsi, loc, w_sp, w_lv, d.S, d.H, d.C, d.L, d.Lq, d.P, out, mask,
+    hipLaunchKernelGGL((fwd_generic_kernel<ST, INST>), dim3(blocks), dim3(256), 0, st, in.value,
+                       in.shapes, in.lsi, in.loc, in.w_sp, in.w_lv, d.S, d.H, d.C, d.L, d.Lq, d.P, o.out, o.mask,
                        n);
     return finish();
 }
@@ -1227,60 +1240,55 @@ int launch_bwd_routed(const BwdIn<ST> &in, BwdOut<ST> out, void *workspace, size
 // Training forward: the forward kernel with the backward's count pass and scans riding in its launch (they only
 // depend on the sampling locations); `plan_buf` then carries the plan to the *_bwd_ws_* call.
 template <typename ST, bool INST>
-int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
-                     const float *w_sp, const float *w_lv, const Dims &d, ST *out, ST *mask,
-                     const int64_t *shapes_host, const int64_t *lsi_host, void *plan_buf,
-                     size_t plan_bytes, void *state, size_t state_bytes, int hints, int *plan_built,
-                     hipStream_t st)
+int launch_fwd_train(const FwdIn<ST> &in, const FwdOut<ST> &o, void *plan_buf, size_t plan_bytes, void *state,
+                     size_t state_bytes, int hints, int *plan_built)
 {
+    const Dims &d = in.d;
+    const hipStream_t st = in.st;
     if (plan_built) *plan_built = 0;
     // the locality counters of the window-staged forward, then the riders' tickets, then the one-pass fill's ranges
     const size_t tbytes = (size_t)std::max(0, d.B) * (size_t)std::max(0, d.H) * kRideTickets * sizeof(int);
     BinPlan plan;
-    const bool planned = d.valid() && make_plan(d, shapes_host, lsi_host, plan);
+    const bool planned = d.valid() && make_plan(d, in.shapes_host, in.lsi_host, plan);
     const StateLayout sy = state_layout(d, planned ? &plan : nullptr);
     // (a state buffer that is too small or misaligned is an error, not "no state": the caller would silently lose the
     // locality counters and pay a zero-fill launch in front of every forward)
-    if (state_check(state, state_bytes, sy, d, shapes_host, st, (hints & BOXATTN_HINT_FRESH_STATE) != 0) < 0)
+    if (state_check(state, state_bytes, sy, d, in.shapes_host, st, (hints & BOXATTN_HINT_FRESH_STATE) != 0) < 0)
         return (int)hipErrorInvalidValue;
     const bool have_state = state != nullptr;
     FwdExtras x;                  // of every launch_fwd below; the one that carries the count riders adds them
-    x.shapes_host = shapes_host;
-    x.lsi_host = lsi_host;
     x.allow_dense = !(hints & BOXATTN_HINT_NOT_LOCAL);
     x.stats = have_state ? (unsigned long long *)state : nullptr;
+    // what the backward will check and the forward can already see (its other operands, grad_out / grad_value, are
+    // re-checked there; an ineligible backward ignores the plan)
+    const auto bwd_fast_ok = [&] {
+        return fast_ok<ST>(d, in.value, in.loc, o.out, INST ? (const void *)o.mask : (const void *)o.out, o.out);
+    };
     // The backward of this shape fills its bins in one pass, from ranges it keeps in the state buffer: nothing of the
     // backward rides in the forward, and there is no plan to hand over (*plan_built stays 0)
-    if (have_state && planned && d.n_value() && d.n_qh() && (g_variant == 0 || g_variant == 3) &&
-        fast_ok<ST>(d, value, loc, out, INST ? (const void *)mask : (const void *)out, out) &&
+    if (have_state && planned && d.n_value() && d.n_qh() && (g_variant == 0 || g_variant == 3) && bwd_fast_ok() &&
         spec_ok<ST, INST>(d, plan, plan_layout(d, plan)))
-        return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
-    bool ok = (g_variant == 0 || g_variant == 3) && plan_buf && planned &&
-              d.n_value() && d.n_qh() &&
-              aligned(plan_buf, 256) &&
-              // what the backward will check and the forward can already see (its other operands,
-              // grad_out / grad_value, are re-checked there; an ineligible backward ignores the plan)
-              fast_ok<ST>(d, value, loc, out, INST ? (const void *)mask : (const void *)out, out);
+        return launch_fwd<ST, INST>(in, o, x);
+    bool ok = (g_variant == 0 || g_variant == 3) && plan_buf && planned && d.n_value() && d.n_qh() &&
+              aligned(plan_buf, 256) && bwd_fast_ok();
     PlanLayout pl{};
     if (ok) {
         pl = plan_layout(d, plan);
         ok = plan_bytes >= pl.total;
     }
-    if (!ok)
-        return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
     // (a shape that may take group records: its backward counts groups, and plans for itself)
-    if (record_kind<ST, INST>(d) == kRecGroup)
-        return launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
+    if (!ok || record_kind<ST, INST>(d) == kRecGroup) return launch_fwd<ST, INST>(in, o, x);
     char *pbuf = (char *)plan_buf;
+    const float *loc = in.loc, *w_sp = in.w_sp;
     const int flavour = bin_flavour(acc_kind<ST, INST>(d), d, loc, w_sp);
     bool taken = false;
-    int rc = 0;
+    BinRide ride;
     if (riders_ok(plan, pl)) {
         // The riders' tickets start at zero and are left zero by the call.  `state`: the caller's zeroed,
         // persistent ticket buffer (one per stream: calls on a stream never overlap); without it the tickets live
         // in the -- possibly fresh -- plan buffer and are cleared by a launch of their own (~5 us in front of
         // the forward kernel).
-        BinRide ride = make_ride(loc, w_sp, d, plan, pl, pbuf, nullptr, nullptr, flavour, false);
+        ride = make_ride(loc, w_sp, d, plan, pl, pbuf, nullptr, nullptr, flavour, false);
         if (have_state) {
             ride.tickets = (int *)((char *)state + sy.tickets);
         } else {
@@ -1289,10 +1297,8 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
         }
         x.count_ride = &ride;
         x.ride_taken = &taken;
-        rc = launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
-    } else {
-        rc = launch_fwd<ST, INST>(value, shapes, lsi, loc, w_sp, w_lv, d, out, mask, x, st);
     }
+    int rc = launch_fwd<ST, INST>(in, o, x);
     if (rc) return rc;
     if (!taken)
         launch_binning(flavour, loc, w_sp, d, plan, pl, pbuf, nullptr, st, kBinCount | kBinScan, nullptr);
@@ -1301,13 +1307,10 @@ int launch_fwd_train(const ST *value, const int64_t *shapes, const int64_t *lsi,
     return rc;
 }
 
-}  // namespace
-
-
-namespace {
 // the C ABI passes 16-bit storage as uint16_t; f16 storage is f16_t inside
 inline const f16_t *as_f16(const uint16_t *p) { return reinterpret_cast<const f16_t *>(p); }
 inline f16_t *as_f16(uint16_t *p) { return reinterpret_cast<f16_t *>(p); }
+
 }  // namespace
 
 extern "C" {
@@ -1315,62 +1318,59 @@ extern "C" {
 #define DIMS Dims{B, S, H, C, L, Lq, P}
 #define ST_ (hipStream_t) stream
 
-int boxattn_fwd_train_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                          const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                          int Lq, int P, float *out, const int64_t *shapes_host,
-                          const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
-                          size_t state_bytes, int hints, int *plan_built, void *stream)
-{
-    return launch_fwd_train<float, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
-                                          shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
-}
-int boxattn_fwd_train_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                           const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                           int Lq, int P, uint16_t *out, const int64_t *shapes_host,
-                           const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
-                           size_t state_bytes, int hints, int *plan_built, void *stream)
-{
-    return launch_fwd_train<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
-                                           shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
-}
-int boxattn_fwd_train_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                          const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                          int Lq, int P, uint16_t *out, const int64_t *shapes_host,
-                          const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
-                          size_t state_bytes, int hints, int *plan_built, void *stream)
-{
-    return launch_fwd_train<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, DIMS, as_f16(out), nullptr,
-                                           shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
-}
-int instattn_fwd_train_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                           const float *loc, const float *spatial_w, const float *level_w, int B,
-                           int S, int H, int C, int L, int Lq, int P, float *out, float *mask_out,
-                           const int64_t *shapes_host, const int64_t *lsi_host, void *plan,
-                           size_t plan_bytes, void *state, size_t state_bytes, int hints, int *plan_built, void *stream)
-{
-    return launch_fwd_train<float, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out, mask_out,
-                                         shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
-}
-int instattn_fwd_train_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                            const float *loc, const float *spatial_w, const float *level_w, int B,
-                            int S, int H, int C, int L, int Lq, int P, uint16_t *out,
-                            uint16_t *mask_out, const int64_t *shapes_host,
-                            const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
-                            size_t state_bytes, int hints, int *plan_built, void *stream)
-{
-    return launch_fwd_train<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out, mask_out,
-                                          shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
-}
-int instattn_fwd_train_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                           const float *loc, const float *spatial_w, const float *level_w, int B,
-                           int S, int H, int C, int L, int Lq, int P, uint16_t *out,
-                           uint16_t *mask_out, const int64_t *shapes_host,
-                           const int64_t *lsi_host, void *plan, size_t plan_bytes, void *state,
-                           size_t state_bytes, int hints, int *plan_built, void *stream)
-{
-    return launch_fwd_train<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, DIMS, as_f16(out), as_f16(mask_out),
-                                          shapes_host, lsi_host, plan, plan_bytes, state, state_bytes, hints, plan_built, ST_);
-}
+// The storage types of the entry points: X(suffix, element type of the C ABI, storage type inside, cast, geometry
+// type: double for float64, [FL]).  A family of entry points is one macro X, expanded over the three types
+// (STORAGE_TYPES), the four with float64 in the header's order (STORAGE_TYPES_F64) or a part of them.  FL is what the
+// expansion passes on to X: the flavour, BOX or INST, of the families that have both (the from-boxes ones take none)
+#define STORAGE_F32(X, ...) X(f32, float, float, , float, __VA_ARGS__)
+#define STORAGE_F64(X, ...) X(f64, double, double, , double, __VA_ARGS__)
+#define STORAGE_H16(X, ...) \
+    X(bf16, uint16_t, bf16_t, , float, __VA_ARGS__) X(f16, uint16_t, f16_t, as_f16, float, __VA_ARGS__)
+#define STORAGE_TYPES(X, ...) STORAGE_F32(X, __VA_ARGS__) STORAGE_H16(X, __VA_ARGS__)
+#define STORAGE_TYPES_F64(X, ...) STORAGE_F32(X, __VA_ARGS__) STORAGE_F64(X, __VA_ARGS__) STORAGE_H16(X, __VA_ARGS__)
+
+// The two flavours FL of a family, BOX and INST: the prefix of the name, launch_*'s INST, a forward's / a backward's
+// parameters up to its last output (include/boxattn.h documents them), and the FwdIn / FwdOut / BwdIn / BwdOut of the
+// call, from those parameters by their names (the field order of the structs; SH, LH: the host tables or nullptr)
+#define HEAD_PARAMS(CT, GT) const CT *value, const int64_t *shapes, const int64_t *lsi, const GT *loc
+#define DIMS_PARAMS int B, int S, int H, int C, int L, int Lq, int P
+#define HOST_TABLES const int64_t *shapes_host, const int64_t *lsi_host
+#define BOX_NAME(fn) boxattn_##fn
+#define BOX_INST false
+#define BOX_FWD_PARAMS(CT, GT) HEAD_PARAMS(CT, GT), const GT *attn, DIMS_PARAMS, CT *out
+#define BOX_FWD_IN(ST, CAST, SH, LH) FwdIn<ST>{CAST(value), shapes, lsi, loc, attn, nullptr, DIMS, SH, LH, ST_}
+#define BOX_FWD_OUT(ST, CAST) FwdOut<ST>{CAST(out), nullptr}
+#define BOX_BWD_PARAMS(CT, GT)                                                                                 \
+    HEAD_PARAMS(CT, GT), const GT *attn, const CT *grad_out, DIMS_PARAMS, CT *grad_value, GT *grad_loc, GT *grad_attn
+#define BOX_BWD_IN(ST, CAST, SH, LH) \
+    BwdIn<ST>{CAST(value), shapes, lsi, loc, attn, nullptr, CAST(grad_out), nullptr, DIMS, SH, LH, ST_}
+#define BOX_BWD_OUT(ST, CAST) BwdOut<ST>{CAST(grad_value), grad_loc, grad_attn, nullptr}
+#define INST_NAME(fn) instattn_##fn
+#define INST_INST true
+#define INST_FWD_PARAMS(CT, GT) \
+    HEAD_PARAMS(CT, GT), const GT *spatial_w, const GT *level_w, DIMS_PARAMS, CT *out, CT *mask_out
+#define INST_FWD_IN(ST, CAST, SH, LH) \
+    FwdIn<ST>{CAST(value), shapes, lsi, loc, spatial_w, level_w, DIMS, SH, LH, ST_}
+#define INST_FWD_OUT(ST, CAST) FwdOut<ST>{CAST(out), CAST(mask_out)}
+#define INST_BWD_PARAMS(CT, GT)                                                                                \
+    HEAD_PARAMS(CT, GT), const GT *spatial_w, const GT *level_w, const CT *grad_out, const CT *grad_mask,      \
+        DIMS_PARAMS, CT *grad_value, GT *grad_loc, GT *grad_spatial_w, GT *grad_level_w
+#define INST_BWD_IN(ST, CAST, SH, LH)                                                                          \
+    BwdIn<ST>{CAST(value), shapes, lsi, loc, spatial_w, level_w, CAST(grad_out), CAST(grad_mask), DIMS, SH, LH, ST_}
+#define INST_BWD_OUT(ST, CAST) BwdOut<ST>{CAST(grad_value), grad_loc, grad_spatial_w, grad_level_w}
+
+// *_fwd_train_*: the forward with the host tables, the plan and state buffers, hints and *plan_built
+#define FWD_TRAIN(SUF, CT, ST, CAST, GT, FL)                                                                   \
+    int FL##_NAME(fwd_train_##SUF)(FL##_FWD_PARAMS(CT, GT), HOST_TABLES, void *plan, size_t plan_bytes,        \
+                                   void *state, size_t state_bytes, int hints, int *plan_built, void *stream)  \
+    {                                                                                                          \
+        return launch_fwd_train<ST, FL##_INST>(FL##_FWD_IN(ST, CAST, shapes_host, lsi_host),                   \
+                                               FL##_FWD_OUT(ST, CAST), plan, plan_bytes, state, state_bytes,   \
+                                               hints, plan_built);                                             \
+    }
+STORAGE_TYPES(FWD_TRAIN, BOX)
+STORAGE_TYPES(FWD_TRAIN, INST)
+#undef FWD_TRAIN
 
 size_t boxattn_plan_bytes(int is_16bit, int B, int S, int H, int C, int L, int Lq, int P,
                           const int64_t *shapes_host, const int64_t *lsi_host)
@@ -1417,166 +1417,46 @@ size_t boxattn_bwd_workspace_bytes(int is_16bit, int B, int S, int H, int C, int
     return std::max(fallback, need);
 }
 
-int boxattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                       const float *loc, const float *attn, const float *grad_out, int B, int S,
-                       int H, int C, int L, int Lq, int P, float *grad_value, float *grad_loc,
-                       float *grad_attn, const int64_t *shapes_host, const int64_t *lsi_host,
-                       void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state,
-        size_t state_bytes, int hints, void *stream)
-{
-    return launch_bwd_routed<float, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
-        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, workspace, workspace_bytes, plan,
-        plan_bytes, state, state_bytes, hints, kWantAll);
-}
-int boxattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                        const float *loc, const float *attn, const uint16_t *grad_out, int B,
-                        int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
-                        float *grad_loc, float *grad_attn, const int64_t *shapes_host,
-                        const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
-                        const void *plan, size_t plan_bytes, void *state,
-        size_t state_bytes, int hints, void *stream)
-{
-    return launch_bwd_routed<bf16_t, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
-        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, workspace, workspace_bytes, plan,
-        plan_bytes, state, state_bytes, hints, kWantAll);
-}
-int boxattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                       const float *loc, const float *attn, const uint16_t *grad_out, int B,
-                       int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
-                       float *grad_loc, float *grad_attn, const int64_t *shapes_host,
-                       const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
-                       const void *plan, size_t plan_bytes, void *state,
-       size_t state_bytes, int hints, void *stream)
-{
-    return launch_bwd_routed<f16_t, false>({as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr,
-        DIMS, shapes_host, lsi_host, ST_}, {as_f16(grad_value), grad_loc, grad_attn, nullptr}, workspace,
-        workspace_bytes, plan, plan_bytes, state, state_bytes, hints, kWantAll);
-}
-int instattn_bwd_ws_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                        const float *loc, const float *spatial_w, const float *level_w,
-                        const float *grad_out, const float *grad_mask, int B, int S, int H, int C,
-                        int L, int Lq, int P, float *grad_value, float *grad_loc,
-                        float *grad_spatial_w, float *grad_level_w, const int64_t *shapes_host,
-                        const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
-                        const void *plan, size_t plan_bytes, void *state,
-        size_t state_bytes, int hints, void *stream)
-{
-    return launch_bwd_routed<float, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, workspace, workspace_bytes,
-        plan, plan_bytes, state, state_bytes, hints, kWantAll);
-}
-int instattn_bwd_ws_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                         const float *loc, const float *spatial_w, const float *level_w,
-                         const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
-                         int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
-                         float *grad_spatial_w, float *grad_level_w, const int64_t *shapes_host,
-                         const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
-                         const void *plan, size_t plan_bytes, void *state,
-        size_t state_bytes, int hints, void *stream)
-{
-    return launch_bwd_routed<bf16_t, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, workspace, workspace_bytes,
-        plan, plan_bytes, state, state_bytes, hints, kWantAll);
-}
-int instattn_bwd_ws_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                        const float *loc, const float *spatial_w, const float *level_w,
-                        const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
-                        int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
-                        float *grad_spatial_w, float *grad_level_w, const int64_t *shapes_host,
-                        const int64_t *lsi_host, void *workspace, size_t workspace_bytes,
-                        const void *plan, size_t plan_bytes, void *state,
-       size_t state_bytes, int hints, void *stream)
-{
-    return launch_bwd_routed<f16_t, true>({as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out),
-        as_f16(grad_mask), DIMS, shapes_host, lsi_host, ST_}, {as_f16(grad_value), grad_loc, grad_spatial_w,
-        grad_level_w}, workspace, workspace_bytes, plan, plan_bytes, state, state_bytes, hints, kWantAll);
-}
+// *_bwd_ws_* and the partial backward *_bwd_part_* (BOXATTN_WANT_*): one body, the first with kWantAll
+#define WS_PARAMS                                                                                              \
+    void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, \
+        int hints
+#define BWD_ROUTED(ST, CAST, FL, WANT)                                                                         \
+    launch_bwd_routed<ST, FL##_INST>(FL##_BWD_IN(ST, CAST, shapes_host, lsi_host), FL##_BWD_OUT(ST, CAST),     \
+                                     workspace, workspace_bytes, plan, plan_bytes, state, state_bytes, hints, WANT)
+#define BWD_WS_PART(SUF, CT, ST, CAST, GT, FL)                                                                 \
+    int FL##_NAME(bwd_ws_##SUF)(FL##_BWD_PARAMS(CT, GT), HOST_TABLES, WS_PARAMS, void *stream)                 \
+    {                                                                                                          \
+        return BWD_ROUTED(ST, CAST, FL, kWantAll);                                                             \
+    }                                                                                                          \
+    int FL##_NAME(bwd_part_##SUF)(FL##_BWD_PARAMS(CT, GT), HOST_TABLES, WS_PARAMS, void *stream, int want)     \
+    {                                                                                                          \
+        return BWD_ROUTED(ST, CAST, FL, want);                                                                 \
+    }
+STORAGE_TYPES(BWD_WS_PART, BOX)
+STORAGE_TYPES(BWD_WS_PART, INST)
+#undef BWD_WS_PART
+#undef BWD_ROUTED
+#undef WS_PARAMS
 
-
-// Partial backward (BOXATTN_WANT_*): the arguments of *_bwd_ws_* (f64: of *_bwd_f64) + want
-int boxattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-        const float *loc, const float *attn, const float *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
-        float *grad_value, float *grad_loc, float *grad_attn, const int64_t *shapes_host, const int64_t *lsi_host,
-        void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
-        int hints, void *stream, int want)
-{
-    return launch_bwd_routed<float, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
-        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, workspace, workspace_bytes, plan,
-        plan_bytes, state, state_bytes, hints, want);
-}
-int boxattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-        const float *loc, const float *attn, const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
-        uint16_t *grad_value, float *grad_loc, float *grad_attn, const int64_t *shapes_host, const int64_t *lsi_host,
-        void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
-        int hints, void *stream, int want)
-{
-    return launch_bwd_routed<bf16_t, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS,
-        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, workspace, workspace_bytes, plan,
-        plan_bytes, state, state_bytes, hints, want);
-}
-int boxattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-        const float *loc, const float *attn, const uint16_t *grad_out, int B, int S, int H, int C, int L, int Lq, int P,
-        uint16_t *grad_value, float *grad_loc, float *grad_attn, const int64_t *shapes_host, const int64_t *lsi_host,
-        void *workspace, size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes,
-        int hints, void *stream, int want)
-{
-    return launch_bwd_routed<f16_t, false>({as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr,
-        DIMS, shapes_host, lsi_host, ST_}, {as_f16(grad_value), grad_loc, grad_attn, nullptr}, workspace,
-        workspace_bytes, plan, plan_bytes, state, state_bytes, hints, want);
-}
-int instattn_bwd_part_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-        const float *loc, const float *spatial_w, const float *level_w, const float *grad_out, const float *grad_mask,
-        int B, int S, int H, int C, int L, int Lq, int P, float *grad_value, float *grad_loc, float *grad_spatial_w,
-        float *grad_level_w, const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
-        size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
-        void *stream, int want)
-{
-    return launch_bwd_routed<float, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, workspace, workspace_bytes,
-        plan, plan_bytes, state, state_bytes, hints, want);
-}
-int instattn_bwd_part_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-        const float *loc, const float *spatial_w, const float *level_w, const uint16_t *grad_out, const uint16_t *grad_mask,
-        int B, int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc, float *grad_spatial_w,
-        float *grad_level_w, const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
-        size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
-        void *stream, int want)
-{
-    return launch_bwd_routed<bf16_t, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS,
-        shapes_host, lsi_host, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, workspace, workspace_bytes,
-        plan, plan_bytes, state, state_bytes, hints, want);
-}
-int instattn_bwd_part_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-        const float *loc, const float *spatial_w, const float *level_w, const uint16_t *grad_out, const uint16_t *grad_mask,
-        int B, int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc, float *grad_spatial_w,
-        float *grad_level_w, const int64_t *shapes_host, const int64_t *lsi_host, void *workspace,
-        size_t workspace_bytes, const void *plan, size_t plan_bytes, void *state, size_t state_bytes, int hints,
-        void *stream, int want)
-{
-    return launch_bwd_routed<f16_t, true>({as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out),
-        as_f16(grad_mask), DIMS, shapes_host, lsi_host, ST_}, {as_f16(grad_value), grad_loc, grad_spatial_w,
-        grad_level_w}, workspace, workspace_bytes, plan, plan_bytes, state, state_bytes, hints, want);
-}
-int boxattn_bwd_part_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
-        const double *loc, const double *attn, const double *grad_out, int B, int S, int H, int C, int L, int Lq,
-        int P, double *grad_value, double *grad_loc, double *grad_attn, void *stream, int want)
-{
-    if (want != kWantValue && want != kWantPoints && want != kWantAll) return (int)hipErrorInvalidValue;
-    return launch_bwd<double, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, nullptr,
-        nullptr, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, grad_value, want);
-}
-int instattn_bwd_part_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
-        const double *loc, const double *spatial_w, const double *level_w, const double *grad_out,
-        const double *grad_mask, int B, int S, int H, int C, int L, int Lq, int P, double *grad_value,
-        double *grad_loc, double *grad_spatial_w, double *grad_level_w, void *stream, int want)
-{
-    if (want != kWantValue && want != kWantPoints && want != kWantAll) return (int)hipErrorInvalidValue;
-    return launch_bwd<double, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS, nullptr,
-        nullptr, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, grad_value, want);
-}
+// The atomic kernels behind *_bwd_* (ACC: where grad_value is accumulated) and *_bwd_part_f64
+#define BWD_ATOMIC(ST, CAST, FL, ACC, WANT)                                                                    \
+    launch_bwd<ST, FL##_INST>(FL##_BWD_IN(ST, CAST, nullptr, nullptr), FL##_BWD_OUT(ST, CAST), ACC, WANT)
+// float64: the arguments of *_bwd_f64 + want
+#define BWD_PART_F64(SUF, CT, ST, CAST, GT, FL)                                                                \
+    int FL##_NAME(bwd_part_##SUF)(FL##_BWD_PARAMS(CT, GT), void *stream, int want)                             \
+    {                                                                                                          \
+        if (want != kWantValue && want != kWantPoints && want != kWantAll) return (int)hipErrorInvalidValue;   \
+        return BWD_ATOMIC(ST, CAST, FL, grad_value, want);                                                     \
+    }
+STORAGE_F64(BWD_PART_F64, BOX)
+STORAGE_F64(BWD_PART_F64, INST)
+#undef BWD_PART_F64
 
 int boxattn_abi_version(void) { return BOXATTN_ABI_VERSION; }
 
+#define STR_(x) #x
+#define STR(x) STR_(x)
 const char *boxattn_build_info(void)
 {
     return "boxattn gfx950 (CDNA4, wave64) | hipcc " __VERSION__
@@ -1584,8 +1464,10 @@ const char *boxattn_build_info(void)
            "window-staged encoder forward + point gradients{bf16/f16 on MFMA 4x4x4, f32 on VALU}, "
            "binned-bwd{bf16/f16 on MFMA 32x32x16, f32 on the bf16 MFMA over exact three-term bf16 splits} "
            "with fill / combine riding in the point-gradient and accumulate launches, "
-           "one-pass fill into guessed bin ranges (caller-owned state), box-grid{f32} | abi 8";
+           "one-pass fill into guessed bin ranges (caller-owned state), box-grid{f32} | abi " STR(BOXATTN_ABI_VERSION);
 }
+#undef STR
+#undef STR_
 
 int boxattn_profile_begin(void)
 {
@@ -1677,8 +1559,6 @@ int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C
     return boxattn_fwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P);   // box_boxes_route: one eligibility
 }
 
-// The storage types of the from-boxes entry points: X(suffix, element type of the C ABI, storage type inside, cast)
-#define BOXES_STORAGE_TYPES(X) X(f32, float, float, ) X(bf16, uint16_t, bf16_t, ) X(f16, uint16_t, f16_t, as_f16)
 // A wrapper's BoxesIn<ST>, from its parameters by their names (the field order of the struct); the instance flavour
 // passes V 4, angle_mode 0 and no P, the box flavour no k
 #define BOXES_IN(ST, CAST, V_, ANGLE_, P_, K_)                                                                 \
@@ -1686,7 +1566,7 @@ int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C
                 valid_ratios, logits, Dims{B, S, H, C, L, Lq, P_}, K_, ST_}
 #define BOXES_GRADS BoxesGrads{grad_offsets, grad_ref_rows, grad_logits}
 
-#define INSTATTN_FWD_BOXES(SUF, CT, ST, CAST)                                                                  \
+#define INSTATTN_FWD_BOXES(SUF, CT, ST, CAST, ...)                                                             \
     int instattn_fwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \
                                  int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx, \
                                  const float *valid_ratios, const float *logits, int B, int S, int H, int C,   \
@@ -1694,10 +1574,10 @@ int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C
     {                                                                                                          \
         return launch_fwd_boxes<ST>(BOXES_IN(ST, CAST, 4, 0, 0, k), CAST(out), CAST(mask_out));                \
     }
-BOXES_STORAGE_TYPES(INSTATTN_FWD_BOXES)
+STORAGE_TYPES(INSTATTN_FWD_BOXES)
 #undef INSTATTN_FWD_BOXES
 
-#define BOXATTN_FWD_BOXES(SUF, CT, ST, CAST)                                                                   \
+#define BOXATTN_FWD_BOXES(SUF, CT, ST, CAST, ...)                                                              \
     int boxattn_fwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref,  \
                                 int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,    \
                                 const float *kernel_idx, const float *valid_ratios, const float *logits,       \
@@ -1705,10 +1585,10 @@ BOXES_STORAGE_TYPES(INSTATTN_FWD_BOXES)
     {                                                                                                          \
         return launch_fwd_box_boxes<ST>(BOXES_IN(ST, CAST, V, angle_mode, P, 0), CAST(out));                   \
     }
-BOXES_STORAGE_TYPES(BOXATTN_FWD_BOXES)
+STORAGE_TYPES(BOXATTN_FWD_BOXES)
 #undef BOXATTN_FWD_BOXES
 
-#define INSTATTN_BWD_BOXES(SUF, CT, ST, CAST)                                                                  \
+#define INSTATTN_BWD_BOXES(SUF, CT, ST, CAST, ...)                                                             \
     int instattn_bwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \
                                  int ref_dim, int ref_per_head, const float *offsets, const float *kernel_idx, \
                                  const float *valid_ratios, const float *logits, const CT *grad_out,           \
@@ -1718,10 +1598,10 @@ BOXES_STORAGE_TYPES(BOXATTN_FWD_BOXES)
         return launch_bwd_boxes<ST>(BOXES_IN(ST, CAST, 4, 0, 0, k), CAST(grad_out), CAST(grad_mask),           \
                                     BOXES_GRADS);                                                              \
     }
-BOXES_STORAGE_TYPES(INSTATTN_BWD_BOXES)
+STORAGE_TYPES(INSTATTN_BWD_BOXES)
 #undef INSTATTN_BWD_BOXES
 
-#define BOXATTN_BWD_BOXES(SUF, CT, ST, CAST)                                                                   \
+#define BOXATTN_BWD_BOXES(SUF, CT, ST, CAST, ...)                                                              \
     int boxattn_bwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref,  \
                                 int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode,    \
                                 const float *kernel_idx, const float *valid_ratios, const float *logits,       \
@@ -1730,171 +1610,70 @@ BOXES_STORAGE_TYPES(INSTATTN_BWD_BOXES)
     {                                                                                                          \
         return launch_bwd_box_boxes<ST>(BOXES_IN(ST, CAST, V, angle_mode, P, 0), CAST(grad_out), BOXES_GRADS); \
     }
-BOXES_STORAGE_TYPES(BOXATTN_BWD_BOXES)
+STORAGE_TYPES(BOXATTN_BWD_BOXES)
 #undef BOXATTN_BWD_BOXES
 #undef BOXES_GRADS
 #undef BOXES_IN
-#undef BOXES_STORAGE_TYPES
 
-int boxattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                    const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                    int Lq, int P, float *out, void *stream)
-{
-    return launch_fwd<float, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
-                                    {}, ST_);
-}
-int boxattn_fwd_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
-                    const double *loc, const double *attn, int B, int S, int H, int C, int L,
-                    int Lq, int P, double *out, void *stream)
-{
-    return launch_fwd<double, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out,
-                                     nullptr, {}, ST_);
-}
-int boxattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                     const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                     int Lq, int P, uint16_t *out, void *stream)
-{
-    return launch_fwd<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out,
-                                     nullptr, {}, ST_);
-}
-int boxattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                    const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                    int Lq, int P, uint16_t *out, void *stream)
-{
-    return launch_fwd<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, DIMS, as_f16(out),
-                                     nullptr, {}, ST_);
-}
+// *_fwd_*, and boxattn_fwd_hl_* with the host copies of the level tables (the window-staged kernels' plan)
+#define FWD(SUF, CT, ST, CAST, GT, FL)                                                                         \
+    int FL##_NAME(fwd_##SUF)(FL##_FWD_PARAMS(CT, GT), void *stream)                                            \
+    {                                                                                                          \
+        return launch_fwd<ST, FL##_INST>(FL##_FWD_IN(ST, CAST, nullptr, nullptr), FL##_FWD_OUT(ST, CAST), {}); \
+    }
+#define FWD_HL(SUF, CT, ST, CAST, GT, FL)                                                                      \
+    int FL##_NAME(fwd_hl_##SUF)(FL##_FWD_PARAMS(CT, GT), HOST_TABLES, void *stream)                            \
+    {                                                                                                          \
+        return launch_fwd<ST, FL##_INST>(FL##_FWD_IN(ST, CAST, shapes_host, lsi_host), FL##_FWD_OUT(ST, CAST), \
+                                         {});                                                                  \
+    }
+// *_bwd_*: float32 and float64 accumulate into grad_value itself, the 16-bit types into the float32 grad_value_ws
+#define BWD(SUF, CT, ST, CAST, GT, FL)                                                                         \
+    int FL##_NAME(bwd_##SUF)(FL##_BWD_PARAMS(CT, GT), void *stream)                                            \
+    {                                                                                                          \
+        return BWD_ATOMIC(ST, CAST, FL, grad_value, kWantAll);                                                 \
+    }
+#define BWD_H16(SUF, CT, ST, CAST, GT, FL)                                                                     \
+    int FL##_NAME(bwd_##SUF)(FL##_BWD_PARAMS(CT, GT), float *grad_value_ws, void *stream)                      \
+    {                                                                                                          \
+        return BWD_ATOMIC(ST, CAST, FL, grad_value_ws, kWantAll);                                              \
+    }
+STORAGE_TYPES_F64(FWD, BOX)
+STORAGE_TYPES(FWD_HL, BOX)
+STORAGE_F32(BWD, BOX) STORAGE_F64(BWD, BOX) STORAGE_H16(BWD_H16, BOX)
+STORAGE_TYPES_F64(FWD, INST)
+STORAGE_F32(BWD, INST) STORAGE_F64(BWD, INST) STORAGE_H16(BWD_H16, INST)
+#undef BWD_H16
+#undef BWD
+#undef FWD_HL
+#undef FWD
+#undef BWD_ATOMIC
 
-int boxattn_fwd_hl_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                       const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                       int Lq, int P, float *out, const int64_t *shapes_host,
-                       const int64_t *lsi_host, void *stream)
-{
-    return launch_fwd<float, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
-                                    {shapes_host, lsi_host}, ST_);
-}
-int boxattn_fwd_hl_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                        const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                        int Lq, int P, uint16_t *out, const int64_t *shapes_host,
-                        const int64_t *lsi_host, void *stream)
-{
-    return launch_fwd<bf16_t, false>(value, shapes, lsi, loc, attn, nullptr, DIMS, out, nullptr,
-                                     {shapes_host, lsi_host}, ST_);
-}
-int boxattn_fwd_hl_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                       const float *loc, const float *attn, int B, int S, int H, int C, int L,
-                       int Lq, int P, uint16_t *out, const int64_t *shapes_host,
-                       const int64_t *lsi_host, void *stream)
-{
-    return launch_fwd<f16_t, false>(as_f16(value), shapes, lsi, loc, attn, nullptr, DIMS, as_f16(out), nullptr,
-                                     {shapes_host, lsi_host}, ST_);
-}
-
-int boxattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                    const float *loc, const float *attn, const float *grad_out, int B, int S,
-                    int H, int C, int L, int Lq, int P, float *grad_value, float *grad_loc,
-                    float *grad_attn, void *stream)
-{
-    return launch_bwd<float, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, nullptr,
-        nullptr, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, grad_value, kWantAll);
-}
-int boxattn_bwd_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
-                    const double *loc, const double *attn, const double *grad_out, int B,
-                    int S, int H, int C, int L, int Lq, int P, double *grad_value,
-                    double *grad_loc, double *grad_attn, void *stream)
-{
-    return launch_bwd<double, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, nullptr,
-        nullptr, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, grad_value, kWantAll);
-}
-int boxattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                     const float *loc, const float *attn, const uint16_t *grad_out, int B,
-                     int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
-                     float *grad_loc, float *grad_attn, float *grad_value_ws, void *stream)
-{
-    return launch_bwd<bf16_t, false>({value, shapes, lsi, loc, attn, nullptr, grad_out, nullptr, DIMS, nullptr,
-        nullptr, ST_}, {grad_value, grad_loc, grad_attn, nullptr}, grad_value_ws, kWantAll);
-}
-int boxattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                    const float *loc, const float *attn, const uint16_t *grad_out, int B,
-                    int S, int H, int C, int L, int Lq, int P, uint16_t *grad_value,
-                    float *grad_loc, float *grad_attn, float *grad_value_ws, void *stream)
-{
-    return launch_bwd<f16_t, false>({as_f16(value), shapes, lsi, loc, attn, nullptr, as_f16(grad_out), nullptr, DIMS,
-        nullptr, nullptr, ST_}, {as_f16(grad_value), grad_loc, grad_attn, nullptr}, grad_value_ws, kWantAll);
-}
-
-int instattn_fwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                     const float *loc, const float *spatial_w, const float *level_w, int B,
-                     int S, int H, int C, int L, int Lq, int P, float *out, float *mask_out,
-                     void *stream)
-{
-    return launch_fwd<float, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out,
-                                   mask_out, {}, ST_);
-}
-int instattn_fwd_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
-                     const double *loc, const double *spatial_w, const double *level_w, int B,
-                     int S, int H, int C, int L, int Lq, int P, double *out, double *mask_out,
-                     void *stream)
-{
-    return launch_fwd<double, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out,
-                                    mask_out, {}, ST_);
-}
-int instattn_fwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                      const float *loc, const float *spatial_w, const float *level_w, int B,
-                      int S, int H, int C, int L, int Lq, int P, uint16_t *out,
-                      uint16_t *mask_out, void *stream)
-{
-    return launch_fwd<bf16_t, true>(value, shapes, lsi, loc, spatial_w, level_w, DIMS, out,
-                                    mask_out, {}, ST_);
-}
-int instattn_fwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                     const float *loc, const float *spatial_w, const float *level_w, int B,
-                     int S, int H, int C, int L, int Lq, int P, uint16_t *out,
-                     uint16_t *mask_out, void *stream)
-{
-    return launch_fwd<f16_t, true>(as_f16(value), shapes, lsi, loc, spatial_w, level_w, DIMS, as_f16(out),
-                                    as_f16(mask_out), {}, ST_);
-}
-
-int instattn_bwd_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                     const float *loc, const float *spatial_w, const float *level_w,
-                     const float *grad_out, const float *grad_mask, int B, int S, int H, int C,
-                     int L, int Lq, int P, float *grad_value, float *grad_loc,
-                     float *grad_spatial_w, float *grad_level_w, void *stream)
-{
-    return launch_bwd<float, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS, nullptr,
-        nullptr, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, grad_value, kWantAll);
-}
-int instattn_bwd_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
-                     const double *loc, const double *spatial_w, const double *level_w,
-                     const double *grad_out, const double *grad_mask, int B, int S, int H,
-                     int C, int L, int Lq, int P, double *grad_value, double *grad_loc,
-                     double *grad_spatial_w, double *grad_level_w, void *stream)
-{
-    return launch_bwd<double, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS, nullptr,
-        nullptr, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, grad_value, kWantAll);
-}
-int instattn_bwd_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                      const float *loc, const float *spatial_w, const float *level_w,
-                      const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
-                      int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
-                      float *grad_spatial_w, float *grad_level_w, float *grad_value_ws,
-                      void *stream)
-{
-    return launch_bwd<bf16_t, true>({value, shapes, lsi, loc, spatial_w, level_w, grad_out, grad_mask, DIMS, nullptr,
-        nullptr, ST_}, {grad_value, grad_loc, grad_spatial_w, grad_level_w}, grad_value_ws, kWantAll);
-}
-int instattn_bwd_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
-                     const float *loc, const float *spatial_w, const float *level_w,
-                     const uint16_t *grad_out, const uint16_t *grad_mask, int B, int S, int H,
-                     int C, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc,
-                     float *grad_spatial_w, float *grad_level_w, float *grad_value_ws,
-                     void *stream)
-{
-    return launch_bwd<f16_t, true>({as_f16(value), shapes, lsi, loc, spatial_w, level_w, as_f16(grad_out),
-        as_f16(grad_mask), DIMS, nullptr, nullptr, ST_}, {as_f16(grad_value), grad_loc, grad_spatial_w, grad_level_w},
-        grad_value_ws, kWantAll);
-}
-
+#undef INST_BWD_OUT
+#undef INST_BWD_IN
+#undef INST_BWD_PARAMS
+#undef INST_FWD_OUT
+#undef INST_FWD_IN
+#undef INST_FWD_PARAMS
+#undef INST_INST
+#undef INST_NAME
+#undef BOX_BWD_OUT
+#undef BOX_BWD_IN
+#undef BOX_BWD_PARAMS
+#undef BOX_FWD_OUT
+#undef BOX_FWD_IN
+#undef BOX_FWD_PARAMS
+#undef BOX_INST
+#undef BOX_NAME
+#undef HOST_TABLES
+#undef DIMS_PARAMS
+#undef HEAD_PARAMS
+#undef STORAGE_TYPES_F64
+#undef STORAGE_TYPES
+#undef STORAGE_H16
+#undef STORAGE_F64
+#undef STORAGE_F32
+#undef ST_
+#undef DIMS
 
 }  // extern "C"

@@ -14,6 +14,9 @@ using namespace boxattn;
 namespace {
 inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 inline int finish() { return (int)hipGetLastError(); }
+// the C ABI passes 16-bit storage as uint16_t; f16 storage is f16_t inside
+inline const f16_t *as_f16(const uint16_t *p) { return reinterpret_cast<const f16_t *>(p); }
+inline f16_t *as_f16(uint16_t *p) { return reinterpret_cast<f16_t *>(p); }
 
 int grid_dims(int ref_dim, int ref_per_head, int V, int angle_mode, int B, int Lq, int H,
               int L, int P, GridDims &d)
@@ -213,90 +216,59 @@ static int inst_weights_bwd(const T *logits, const float *grad_spatial_w, const 
 
 extern "C" {
 
-int boxattn_softmax_fwd_f32(const float *logits, long long rows, int n, float *attn, void *stream)
-{
-    return softmax_fwd<float>(logits, rows, n, attn, (hipStream_t)stream);
-}
-int boxattn_softmax_fwd_bf16(const uint16_t *logits, long long rows, int n, float *attn, void *stream)
-{
-    return softmax_fwd<bf16_t>(logits, rows, n, attn, (hipStream_t)stream);
-}
-int boxattn_softmax_fwd_f16(const uint16_t *logits, long long rows, int n, float *attn, void *stream)
-{
-    return softmax_fwd<f16_t>(reinterpret_cast<const f16_t *>(logits), rows, n, attn, (hipStream_t)stream);
-}
-int boxattn_softmax_bwd_f32(const float *attn, const float *grad_attn, long long rows, int n,
-                            float *grad_logits, void *stream)
-{
-    return softmax_bwd<float>(attn, grad_attn, rows, n, grad_logits, (hipStream_t)stream);
-}
-int boxattn_softmax_bwd_bf16(const float *attn, const float *grad_attn, long long rows, int n,
-                             uint16_t *grad_logits, void *stream)
-{
-    return softmax_bwd<bf16_t>(attn, grad_attn, rows, n, grad_logits, (hipStream_t)stream);
-}
+// The storage types of the entry points below: X(suffix, element type of the C ABI, type inside, cast)
+#define STORAGE_TYPES(X) X(f32, float, float, ) X(bf16, uint16_t, bf16_t, ) X(f16, uint16_t, f16_t, as_f16)
+#define ST_ (hipStream_t) stream
 
-int boxattn_softmax_bwd_f16(const float *attn, const float *grad_attn, long long rows, int n,
-                            uint16_t *grad_logits, void *stream)
-{
-    return softmax_bwd<f16_t>(attn, grad_attn, rows, n, reinterpret_cast<f16_t *>(grad_logits), (hipStream_t)stream);
-}
+#define SOFTMAX_FWD(SUF, CT, T, CAST)                                                                          \
+    int boxattn_softmax_fwd_##SUF(const CT *logits, long long rows, int n, float *attn, void *stream)          \
+    {                                                                                                          \
+        return softmax_fwd<T>(CAST(logits), rows, n, attn, ST_);                                               \
+    }
+STORAGE_TYPES(SOFTMAX_FWD)
+#undef SOFTMAX_FWD
 
-int boxattn_value_prep_f32(const float *value, const unsigned char *mask, long long rows, int d,
-                           uint16_t *out, void *stream)
-{
-    return value_prep<float>(value, mask, rows, d, out, (hipStream_t)stream);
-}
-int boxattn_value_prep_bf16(const uint16_t *value, const unsigned char *mask, long long rows, int d,
-                            uint16_t *out, void *stream)
-{
-    return value_prep<bf16_t>(value, mask, rows, d, out, (hipStream_t)stream);
-}
-int boxattn_value_prep_f32_f16(const float *value, const unsigned char *mask, long long rows, int d,
-                               uint16_t *out, void *stream)
-{
-    return value_prep<float, f16_t>(value, mask, rows, d, reinterpret_cast<f16_t *>(out), (hipStream_t)stream);
-}
-int boxattn_value_prep_f16(const uint16_t *value, const unsigned char *mask, long long rows, int d,
-                           uint16_t *out, void *stream)
-{
-    return value_prep<f16_t, f16_t>(reinterpret_cast<const f16_t *>(value), mask, rows, d,
-                                    reinterpret_cast<f16_t *>(out), (hipStream_t)stream);
-}
+#define SOFTMAX_BWD(SUF, CT, T, CAST)                                                                          \
+    int boxattn_softmax_bwd_##SUF(const float *attn, const float *grad_attn, long long rows, int n,            \
+                                  CT *grad_logits, void *stream)                                               \
+    {                                                                                                          \
+        return softmax_bwd<T>(attn, grad_attn, rows, n, CAST(grad_logits), ST_);                               \
+    }
+STORAGE_TYPES(SOFTMAX_BWD)
+#undef SOFTMAX_BWD
 
-int instattn_weights_fwd_f32(const float *logits, long long rows, int L, int k, float *spatial_w, float *level_w,
-                             void *stream)
-{
-    return inst_weights_fwd<float>(logits, rows, L, k, spatial_w, level_w, (hipStream_t)stream);
-}
-int instattn_weights_fwd_bf16(const uint16_t *logits, long long rows, int L, int k, float *spatial_w,
-                              float *level_w, void *stream)
-{
-    return inst_weights_fwd<bf16_t>(logits, rows, L, k, spatial_w, level_w, (hipStream_t)stream);
-}
-int instattn_weights_fwd_f16(const uint16_t *logits, long long rows, int L, int k, float *spatial_w,
-                             float *level_w, void *stream)
-{
-    return inst_weights_fwd<f16_t>(reinterpret_cast<const f16_t *>(logits), rows, L, k, spatial_w, level_w,
-                                   (hipStream_t)stream);
-}
-int instattn_weights_bwd_f32(const float *logits, const float *grad_spatial_w, const float *grad_level_w,
-                             long long rows, int L, int k, float *grad_logits, void *stream)
-{
-    return inst_weights_bwd<float>(logits, grad_spatial_w, grad_level_w, rows, L, k, grad_logits,
-                                   (hipStream_t)stream);
-}
-int instattn_weights_bwd_bf16(const uint16_t *logits, const float *grad_spatial_w, const float *grad_level_w,
-                              long long rows, int L, int k, uint16_t *grad_logits, void *stream)
-{
-    return inst_weights_bwd<bf16_t>(logits, grad_spatial_w, grad_level_w, rows, L, k, grad_logits,
-                                    (hipStream_t)stream);
-}
-int instattn_weights_bwd_f16(const uint16_t *logits, const float *grad_spatial_w, const float *grad_level_w,
-                             long long rows, int L, int k, uint16_t *grad_logits, void *stream)
-{
-    return inst_weights_bwd<f16_t>(reinterpret_cast<const f16_t *>(logits), grad_spatial_w, grad_level_w, rows, L,
-                                   k, reinterpret_cast<f16_t *>(grad_logits), (hipStream_t)stream);
-}
+// value_prep: its own table, (suffix, input element type, type inside, cast) and (output type inside, cast)
+#define VALUE_PREP(SUF, CT, T, CAST, OT, OCAST)                                                                \
+    int boxattn_value_prep_##SUF(const CT *value, const unsigned char *mask, long long rows, int d,            \
+                                 uint16_t *out, void *stream)                                                  \
+    {                                                                                                          \
+        return value_prep<T, OT>(CAST(value), mask, rows, d, OCAST(out), ST_);                                 \
+    }
+VALUE_PREP(f32, float, float, , bf16_t, )
+VALUE_PREP(bf16, uint16_t, bf16_t, , bf16_t, )
+VALUE_PREP(f32_f16, float, float, , f16_t, as_f16)
+VALUE_PREP(f16, uint16_t, f16_t, as_f16, f16_t, as_f16)
+#undef VALUE_PREP
+
+#define INSTATTN_WEIGHTS_FWD(SUF, CT, T, CAST)                                                                 \
+    int instattn_weights_fwd_##SUF(const CT *logits, long long rows, int L, int k, float *spatial_w,           \
+                                   float *level_w, void *stream)                                               \
+    {                                                                                                          \
+        return inst_weights_fwd<T>(CAST(logits), rows, L, k, spatial_w, level_w, ST_);                         \
+    }
+STORAGE_TYPES(INSTATTN_WEIGHTS_FWD)
+#undef INSTATTN_WEIGHTS_FWD
+
+#define INSTATTN_WEIGHTS_BWD(SUF, CT, T, CAST)                                                                 \
+    int instattn_weights_bwd_##SUF(const CT *logits, const float *grad_spatial_w, const float *grad_level_w,   \
+                                   long long rows, int L, int k, CT *grad_logits, void *stream)                \
+    {                                                                                                          \
+        return inst_weights_bwd<T>(CAST(logits), grad_spatial_w, grad_level_w, rows, L, k, CAST(grad_logits),  \
+                                   ST_);                                                                       \
+    }
+STORAGE_TYPES(INSTATTN_WEIGHTS_BWD)
+#undef INSTATTN_WEIGHTS_BWD
+#undef ST_
+#undef STORAGE_TYPES
 
 }  // extern "C"

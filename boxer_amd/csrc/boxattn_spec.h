@@ -157,7 +157,7 @@ __device__ __forceinline__ void spec_fill_body(int *hist, int *base, BinLevel *s
                 r[k][0] = (unsigned)atomicAdd(&hist[in[k] ? b0[k] : dump], 1);                      // LDS
                 r[k][1] = (unsigned)atomicAdd(&hist[cc[k] ? b0[k] + 1 : dump], 1);
                 r[k][2] = (unsigned)atomicAdd(&hist[cr[k] ? b0[k] + lv.nbx : dump], 1);
-                r[k][3] = (unsigned)atomicAdd(&hist[cc[k] & cr[k] ? b0[k] + lv.nbx + 1 : dump], 1);
+                r[k][3] = (unsigned)atomicAdd(&hist[(cc[k] & cr[k]) ? b0[k] + lv.nbx + 1 : dump], 1);
             }
 #pragma unroll
             for (int k = 0; k < PT; ++k) {
@@ -297,7 +297,7 @@ __device__ __forceinline__ void spec_fill_group_body(int *hist, int *base, BinLe
             const unsigned r0 = (unsigned)atomicAdd(&hist[in ? b0 : dump], 1);
             const unsigned r1 = (unsigned)atomicAdd(&hist[cc ? b0 + 1 : dump], 1);
             const unsigned r2 = (unsigned)atomicAdd(&hist[cr ? b0 + lv.nbx : dump], 1);
-            const unsigned r3 = (unsigned)atomicAdd(&hist[cc & cr ? b0 + lv.nbx + 1 : dump], 1);
+            const unsigned r3 = (unsigned)atomicAdd(&hist[(cc & cr) ? b0 + lv.nbx + 1 : dump], 1);
             rk[j][0] = (r0 & 0xFFFFu) | (r1 << 16);
             rk[j][1] = (r2 & 0xFFFFu) | (r3 << 16);
         };

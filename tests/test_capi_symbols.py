@@ -38,6 +38,32 @@ def test_library_exports_every_declared_symbol(lib):
     assert sorted(_lib.EXPORTS) == declared_functions()
 
 
+def declared_parameter_counts():
+    """name -> number of parameters of every function the header declares ((void): 0)."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    counts = {}
+    for name, params in re.findall(r"\b((?:boxattn|instattn)_\w+)\s*\(([^()]*)\)\s*;", text):
+        params = " ".join(params.split())
+        counts[name] = 0 if params in ("", "void") else params.count(",") + 1
+    return counts
+
+
+def test_every_declared_function_is_bound_with_the_header_s_parameter_count(lib):
+    """_lib.load() sets argtypes on every function of the header (none is called through ctypes' guesses), as many as
+    the declaration has parameters: the signature table of _lib.py cannot drift from include/boxattn.h unnoticed."""
+    from boxer_amd import _lib
+    counts = declared_parameter_counts()
+    assert sorted(counts) == declared_functions() and len(counts) > 60
+    assert counts["boxattn_abi_version"] == 0 and counts["boxattn_profile_end"] == 2       # the parser's own check
+    assert counts["boxattn_set_debug_buffer"] == 1 and counts["boxattn_fwd_f32"] == 14
+    loaded = _lib.load()
+    for name, n in sorted(counts.items()):
+        argtypes = getattr(loaded, name).argtypes
+        assert argtypes is not None, "no argtypes: " + name
+        assert len(argtypes) == n, (name, len(argtypes), n)
+
+
 def test_library_metadata(lib):
     from boxer_amd import _lib
     declared = int(re.search(r"#define BOXATTN_ABI_VERSION (\d+)", open(HEADER).read()).group(1))
