@@ -11,8 +11,8 @@ The compute lives in a C-ABI HIP library (``include/boxattn.h``, ``boxer_amd/csr
 DESIGN.md and INTEGRATION.md.  There is no CPU fallback: ops raise if the library is missing.
 """
 from . import _lib, ops
-from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnF16Function, BoxAttnFunction,
-                        BoxGridFunction, InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
+from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnBoxesValueFunction, BoxAttnF16Function,
+                        BoxAttnFunction, BoxGridFunction, InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
                         InstanceAttnBoxesFunction, InstanceWeightsFunction, LogitSoftmaxFunction,
                         ValueMaskCastFunction)
 from .modules import Box3dAttention, BoxAttention, InstanceAttention
@@ -21,6 +21,7 @@ __all__ = [
     "ops", "BoxAttnFunction", "InstanceAttnFunction", "BoxAttnBF16Function",
     "InstanceAttnBF16Function", "BoxAttnF16Function", "InstanceAttnF16Function", "BoxGridFunction", "LogitSoftmaxFunction", "ValueMaskCastFunction",
     "InstanceWeightsFunction", "InstanceAttnBoxesFunction", "BoxAttnBoxesFunction",
+    "BoxAttnBoxesValueFunction",
     "BoxAttention", "InstanceAttention", "Box3dAttention",
     "build", "build_info",
 ]

@@ -101,7 +101,11 @@ _SIGNATURES = {
     **_family("instattn_bwd_boxes", _S3, _boxes(False, 2, 3)),
     **_family("boxattn_fwd_boxes", _S3, _boxes(True, 0, 1)),            # out
     **_family("boxattn_bwd_boxes", _S3, _boxes(True, 1, 3)),            # grad_out; the three gradients
+    # boxattn_bwd_boxes_* up to P, then want, grad_value, workspace, workspace_bytes, the three gradients, stream
+    **_family("boxattn_bwd_boxes_value", _S3, _boxes(True, 1, 0)[:-1] + [_i, _vp, _vp, _sz] + [_vp] * 3 + _STREAM),
     **{"%s_%s_boxes_ok" % (op, way): (_i, _QUERY) for op in _FWD for way in ("fwd", "bwd")},
+    "boxattn_bwd_boxes_value_ok": (_i, _QUERY),
+    "boxattn_bwd_boxes_value_workspace_bytes": (_sz, [_i] * 5),      # elem_bytes, B, S, H, C
 }
 for _op in _FWD:
     for _stem, _suffixes, _args in (
@@ -271,6 +275,18 @@ def box_bwd_boxes_ok(elem_bytes, aligned, dims):
     """boxattn_bwd_boxes_ok(): whether the boxattn_bwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
     C, L, Lq, P) under the current switches.  Pure host code (no GPU needed)."""
     return _boxes_ok("boxattn_bwd_boxes_ok", elem_bytes, aligned, dims)
+
+
+def box_bwd_boxes_value_ok(elem_bytes, aligned, dims):
+    """boxattn_bwd_boxes_value_ok(): whether the boxattn_bwd_boxes_value_* entry points have their kernel for ``dims`` =
+    (B, S, H, C, L, Lq, P) under the current switches.  Pure host code (no GPU needed)."""
+    return _boxes_ok("boxattn_bwd_boxes_value_ok", elem_bytes, aligned, dims)
+
+
+def box_bwd_boxes_value_workspace_bytes(elem_bytes, dims):
+    """boxattn_bwd_boxes_value_workspace_bytes(): the bytes of float32 accumulator a boxattn_bwd_boxes_value_* call
+    takes for ``dims`` = (B, S, H, C, ...): 0 for 4-byte storage.  Pure host code (no GPU needed)."""
+    return int(load().boxattn_bwd_boxes_value_workspace_bytes(int(elem_bytes), *[int(v) for v in dims[:4]]))
 
 
 def bwd_boxes_ok(elem_bytes, aligned, dims, k):

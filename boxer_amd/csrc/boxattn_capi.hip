@@ -672,28 +672,95 @@ int launch_bwd_boxes(const BoxesIn<ST> &in, const ST *grad_out, const ST *grad_m
     return finish();
 }
 
+// The two gradient groups of a backward (BOXATTN_WANT_*): VALUE = grad_value, POINTS = grad_loc + the weight gradients
+// (from boxes: the box and logit gradients).
+enum { kWantValue = BOXATTN_WANT_VALUE, kWantPoints = BOXATTN_WANT_POINTS, kWantAll = kWantValue | kWantPoints };
+
+// One launch of bwd2_boxes_kernel for a prepared call.  SCATTER / POINTS: the kernel's flavour; acc: the float32
+// accumulator of grad_value (SCATTER), zero-filled by the caller
+template <typename ST, bool SCATTER, bool POINTS>
+void launch_bwd2_boxes(const BoxesIn<ST> &in, const BoxesLaunch &l, const ST *grad_out, const BoxesGrads &g, float *acc)
+{
+    const Dims &d = l.d;
+    const unsigned stride = bwd2_boxes_pair_stride(d.L * d.P);
+#define BOXATTN_BWD2_BOXES(GG, VV)                                                                          \
+    hipLaunchKernelGGL((bwd2_boxes_kernel<ST, GG, GatherUnroll<ST, GG, VV>::value, VV, SCATTER, POINTS>),   \
+                       dim3(l.r.blocks), dim3(256),                                                         \
+                       (size_t)kGatherWaves * (kWave / GG) * stride * sizeof(float), in.st,                 \
+                       in.value, in.shapes, in.lsi, in.ref, in.offsets, in.kernel_idx, in.valid_ratios,     \
+                       in.logits, grad_out, d.S, d.H, d.L, d.Lq, d.P, g.offsets, g.ref_rows, g.logits,      \
+                       l.gd, with_grid(l.r.ix, l.r.blocks, 1, (d.L * d.P + GG - 1) / GG), l.vbytes, stride, \
+                       acc);
+    BOXATTN_GATHER_DISPATCH(l.r.cfg, BOXATTN_BWD2_BOXES);
+#undef BOXATTN_BWD2_BOXES
+}
+
 template <typename ST> int launch_bwd_box_boxes(const BoxesIn<ST> &in, const ST *grad_out, const BoxesGrads &g)
 {
     BoxesLaunch l;
     int rc;
     if (!boxes_prepare_bwd<ST, false>(in, grad_out, nullptr, g, l, rc)) return rc;
-    const Dims &d = l.d;
-    const unsigned stride = bwd2_boxes_pair_stride(d.L * d.P);
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], in.st);
-#define BOXATTN_BWD2_BOXES(GG, VV)                                                                          \
-    hipLaunchKernelGGL((bwd2_boxes_kernel<ST, GG, GatherUnroll<ST, GG, VV>::value, VV>), dim3(l.r.blocks),  \
-                       dim3(256), (size_t)kGatherWaves * (kWave / GG) * stride * sizeof(float), in.st,      \
-                       in.value, in.shapes, in.lsi, in.ref, in.offsets, in.kernel_idx, in.valid_ratios,     \
-                       in.logits, grad_out, d.S, d.H, d.L, d.Lq, d.P, g.offsets, g.ref_rows, g.logits,      \
-                       l.gd, with_grid(l.r.ix, l.r.blocks, 1, (d.L * d.P + GG - 1) / GG), l.vbytes, stride);
-    BOXATTN_GATHER_DISPATCH(l.r.cfg, BOXATTN_BWD2_BOXES);
-#undef BOXATTN_BWD2_BOXES
+    launch_bwd2_boxes<ST, false, true>(in, l, grad_out, g, nullptr);
+    return finish();
+}
+
+// Bytes of the float32 accumulator a 16-bit boxattn_bwd_boxes_value_* call takes as its workspace
+inline size_t bwd_boxes_value_ws_bytes(int elem_bytes, const Dims &d)
+{
+    return elem_bytes == 2 ? d.n_value() * sizeof(float) : 0;
+}
+
+// The same step with grad_value in the launch (want: BOXATTN_WANT_*; POINTS alone is launch_bwd_box_boxes).  float32
+// accumulates into grad_value itself, the 16-bit types into `ws` (float32, 16-byte aligned), cast by launch_bwd's pass.
+// Every refusal comes before the first launch; no queries: grad_value is zero-filled, no pixels: the other gradients.
+template <typename ST>
+int launch_bwd_box_boxes_value(const BoxesIn<ST> &in, const ST *grad_out, const BoxesGrads &g, int want,
+                               ST *grad_value, float *ws, size_t ws_bytes)
+{
+    if (want == kWantPoints) return launch_bwd_box_boxes<ST>(in, grad_out, g);
+    if ((want != kWantValue && want != kWantAll) || !in.d.valid()) return (int)hipErrorInvalidValue;
+    const bool wp = want == kWantAll;
+    const size_t nv = in.d.n_value();
+    float *acc = nullptr;
+    if (nv) {
+        if (!grad_value) return (int)hipErrorInvalidValue;
+        if constexpr (IsHalf16<ST>::value) {
+            if (!ws || !aligned(ws, 16) || ws_bytes < bwd_boxes_value_ws_bytes(2, in.d) ||
+                !aligned(grad_value, 4 * sizeof(ST)))
+                return (int)hipErrorInvalidValue;
+            acc = ws;
+        } else {
+            acc = grad_value;
+        }
+    }
+    BoxesLaunch l;
+    int rc;
+    const BoxesGrads none{nullptr, nullptr, nullptr};
+    const bool ready = wp ? boxes_prepare_bwd<ST, false>(in, grad_out, nullptr, g, l, rc)
+                          : boxes_prepare<ST, false>(in, grad_out, nullptr, grad_out != nullptr, {}, l, rc);
+    if (!ready) {
+        if (rc == 0 && nv) rc = (int)zero_async(grad_value, nv * sizeof(ST), in.st);   // no queries
+        return rc;
+    }
+    ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], in.st);
+    hipError_t e = zero_async(acc, nv * sizeof(float), in.st);
+    if (e != hipSuccess) return (int)e;
+    if (wp) launch_bwd2_boxes<ST, true, true>(in, l, grad_out, g, acc);
+    else launch_bwd2_boxes<ST, true, false>(in, l, grad_out, none, acc);
+    if constexpr (IsHalf16<ST>::value) {
+        rc = finish();
+        if (rc) return rc;
+        const int blocks = (int)std::min<size_t>((nv / 4 + 255) / 256 + 1, 256 * 16);
+        if constexpr (std::is_same<ST, bf16_t>::value)
+            hipLaunchKernelGGL(cvt_f32_to_bf16_kernel, dim3(blocks), dim3(256), 0, in.st, acc, grad_value, nv);
+        else
+            hipLaunchKernelGGL(cvt_f32_to_f16_kernel, dim3(blocks), dim3(256), 0, in.st, acc, grad_value, nv);
+    }
     return finish();
 }
 
 // ----------------------------------------------------------------------------- backward
-// The two gradient groups of a backward (BOXATTN_WANT_*): VALUE = grad_value, POINTS = grad_loc + the weight gradients.
-enum { kWantValue = BOXATTN_WANT_VALUE, kWantPoints = BOXATTN_WANT_POINTS, kWantAll = kWantValue | kWantPoints };
 
 // A backward call's operands and its outputs, filled by the extern "C" wrappers (T: float; double for float64 storage).
 // shapes_host / lsi_host: the host copies of the level tables (NULL in the entry points that take none).
@@ -1558,6 +1625,15 @@ int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C
 {
     return boxattn_fwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P);   // box_boxes_route: one eligibility
 }
+int boxattn_bwd_boxes_value_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P)
+{
+    return boxattn_bwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P);   // the same kernel family
+}
+size_t boxattn_bwd_boxes_value_workspace_bytes(int elem_bytes, int B, int S, int H, int C)
+{
+    if (B < 0 || S < 0 || H < 0 || C < 0) return 0;
+    return bwd_boxes_value_ws_bytes(elem_bytes, Dims{B, S, H, C, 1, 0, 1});
+}
 
 // A wrapper's BoxesIn<ST>, from its parameters by their names (the field order of the struct); the instance flavour
 // passes V 4, angle_mode 0 and no P, the box flavour no k
@@ -1612,6 +1688,22 @@ STORAGE_TYPES(INSTATTN_BWD_BOXES)
     }
 STORAGE_TYPES(BOXATTN_BWD_BOXES)
 #undef BOXATTN_BWD_BOXES
+
+#define BOXATTN_BWD_BOXES_VALUE(SUF, CT, ST, CAST, ...)                                                           \
+    int boxattn_bwd_boxes_value_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \
+                                      int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode, \
+                                      const float *kernel_idx, const float *valid_ratios, const float *logits,    \
+                                      const CT *grad_out, int B, int S, int H, int C, int L, int Lq, int P,       \
+                                      int want, CT *grad_value, void *workspace, size_t workspace_bytes,          \
+                                      float *grad_offsets, float *grad_ref_rows, float *grad_logits,              \
+                                      void *stream)                                                               \
+    {                                                                                                             \
+        return launch_bwd_box_boxes_value<ST>(BOXES_IN(ST, CAST, V, angle_mode, P, 0), CAST(grad_out),            \
+                                              BOXES_GRADS, want, CAST(grad_value), (float *)workspace,            \
+                                              workspace_bytes);                                                   \
+    }
+STORAGE_TYPES(BOXATTN_BWD_BOXES_VALUE)
+#undef BOXATTN_BWD_BOXES_VALUE
 #undef BOXES_GRADS
 #undef BOXES_IN
 

@@ -469,3 +469,35 @@ class BoxAttnBoxesFunction(Function):
             weights = lambda: (ops.softmax_forward(logits).view(*offsets.shape[:4], -1), None)
             grad_value = _boxes_grad_value(ctx, operands, ctx.angle_mode, weights, grad_output)
         return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)
+
+
+class BoxAttnBoxesValueFunction(Function):
+    """``BoxAttnBoxesFunction`` -- its signature, its forward, what it saves -- with the whole backward as ONE
+    ``ops.box_attn_backward_boxes_value`` call (``module.fused_boxes_value``): ``grad_value`` is scattered with
+    float32 atomics by the kernel that computes the gradients of ``offsets``, ``ref_windows`` and ``logits``, so no
+    sampling grid, no weights and no plan exist in the backward either.  ``want`` follows ``needs_input_grad``: a
+    frozen ``value`` runs the box and logit gradients alone, frozen heads ``grad_value`` alone.  ``grad_value`` is NOT
+    bitwise reproducible here (the adds' order is the hardware's); the other three are, and equal
+    ``BoxAttnBoxesFunction``'s bit for bit.  For few queries against the map (decoder cross-attention)."""
+
+    forward = staticmethod(BoxAttnBoxesFunction.forward)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        operands, need_v, need_params = _boxes_saved(ctx)
+        value, ref_windows = operands[0], operands[3]
+        grad_ref = grad_offsets = grad_logits = None
+        if not (need_v or need_params):
+            return (None,) * 9
+        grad_output = grad_output.to(value.dtype).contiguous()
+        grad_value, *grads = ops.box_attn_backward_boxes_value(
+            *operands, ctx.angle_mode, grad_output, want=(1 if need_v else 0) | (2 if need_params else 0),
+            need_ref_grad=ctx.needs_input_grad[3])
+        if need_params:
+            grad_ref, grad_offsets, grad_logits = _boxes_param_grads(ctx, ref_windows, grads)
+            if grad_logits is not None:
+                grad_logits = grad_logits.view(ctx.logits_shape)
+        if need_v:
+            grad_value = grad_value.to(ctx.value_dtype)
+        return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)

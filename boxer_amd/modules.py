@@ -22,9 +22,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import dense, ops
-from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnF16Function, BoxAttnFunction,
-                        BoxGridFunction, InstanceAttnBF16Function, InstanceAttnBoxesFunction, InstanceAttnF16Function,
-                        InstanceAttnFunction, InstanceWeightsFunction, LogitSoftmaxFunction, ValueMaskCastFunction)
+from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnBoxesValueFunction, BoxAttnF16Function,
+                        BoxAttnFunction, BoxGridFunction, InstanceAttnBF16Function, InstanceAttnBoxesFunction,
+                        InstanceAttnF16Function, InstanceAttnFunction, InstanceWeightsFunction, LogitSoftmaxFunction,
+                        ValueMaskCastFunction)
 
 
 def _f32(t):
@@ -76,6 +77,11 @@ class _BoxAttentionBase(nn.Module):
         # BoxAttnBoxesFunction, the second element of the return is then the empty tuple.  `fused_boxes` does not
         # imply it.
         self.fused_boxes_train = False
+        # opt-in, only together with `fused_boxes_train` (BoxAttention / Box3dAttention; InstanceAttention ignores it):
+        # where that step is taken with fewer queries than pixels (cross-attention) and ops.box_backward_boxes_value_ok
+        # says yes, BoxAttnBoxesValueFunction -- grad_value from float32 atomics inside the backward's one launch, NOT
+        # bitwise reproducible -- instead of BoxAttnBoxesFunction
+        self.fused_boxes_value = False
 
         self.linear_box_weight = nn.Parameter(torch.zeros(num_level * num_head * box_vars, d_model))
         self.linear_box_bias = nn.Parameter(torch.zeros(num_head * num_level * box_vars))
@@ -245,12 +251,21 @@ class BoxAttention(_BoxAttentionBase):
             _f32(logits).view(b, l1, self.num_head, -1), mode)
         return dense.linear(output, self.out_proj.weight, self.out_proj.bias), ()
 
+    def _boxes_train_function(self, value, num_query):
+        """The Function of the training step from boxes for ``value`` (B,S,H,C) as ``_boxes_train`` returned it:
+        ``fused_boxes_value`` with fewer queries than pixels and a kernel for the shape -> the one with grad_value in
+        the backward's own launch."""
+        if (self.fused_boxes_value and num_query < value.size(1) and
+                ops.box_backward_boxes_value_ok(value, self.num_level, num_query, self.num_point)):
+            return BoxAttnBoxesValueFunction
+        return BoxAttnBoxesFunction
+
     def _forward_boxes_train(self, query, value, v_shape, v_start_index, v_valid_ratios, ref_windows):
         b, l1 = query.shape[:2]
         mode = self._angle_mode()
         logits = dense.linear(query, self.linear_attn_weight, self.linear_attn_bias)
         # (differentiable casts: the gradients flow on to the projections, the query and the reference windows)
-        output = BoxAttnBoxesFunction.apply(
+        output = self._boxes_train_function(value, l1).apply(
             value, v_shape, v_start_index, ref_windows.float(),
             self._box_offsets(query, ref_windows, 5 if mode == 1 else 4).float(), self.kernel_indices,
             None if v_valid_ratios is None else v_valid_ratios.view(b, self.num_level, 2),

@@ -1063,3 +1063,52 @@ def box_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_window
     grads = _boxes_grads(value, (B, Lq, H, L), V, (B, Lq, H, L * P), need_ref_grad)
     _boxes_call("boxattn_bwd_boxes_", operands, (D, per_head), (V, mode), (grad_output,), dims, grads)
     return grads
+
+
+# ---------------------------------------------------------------------------------------
+# the same step with grad_value in the backward's own launch (opt-in; include/boxattn.h, boxattn_bwd_boxes_value_*)
+# ---------------------------------------------------------------------------------------
+def box_backward_boxes_value_ok(value, num_level, num_query, num_point):
+    """Whether ``box_attn_backward_boxes_value`` has its kernel under the current switches:
+    ``boxattn_bwd_boxes_value_ok`` (the eligibility of ``box_backward_boxes_ok``) with the dimensions, element size
+    and alignment of ``value`` (B, S, H, C).  The upstream gradient is taken as aligned like ``value``;
+    ``box_attn_backward_boxes_value`` asks again with its address.  Pure host code."""
+    return _boxes_ok(_lib.box_bwd_boxes_value_ok, value, (num_level, num_query, num_point))
+
+
+def box_attn_backward_boxes_value(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                                  valid_ratios, logits, angle_mode, grad_output, want=3, need_ref_grad=False):
+    """BoxAttention's / Box3dAttention's whole backward in one call, from the operands of ``box_attn_forward_boxes`` and
+    the upstream gradient ``grad_output`` (B,Lq,H*C) in the type of ``value`` -> ``(grad_value (B,S,H,C) in the type of
+    value, grad_offsets (B,Lq,H,L,V), grad_ref_rows (B,Lq,H,L,5) or None, grad_logits (B,Lq,H,L*P))``, the last three
+    float32.  ``want``: 1 grad_value only, 2 the three others only (``box_attn_backward_boxes`` exactly), 3 all; a group
+    not wanted comes back as None.  ``grad_value`` is scattered with float32 atomics by the kernel that computes the
+    other three -- no sampling grid, no weights, no plan -- into itself (float32) or into a float32 scratch from the
+    caching allocator that one pass casts (16-bit): it is NOT bitwise reproducible from call to call; the other three
+    are, and are bit for bit those of ``box_attn_backward_boxes``.  Raises ValueError, before any device call, for
+    arguments that do not fit and where ``boxattn_bwd_boxes_value_ok`` says no at the alignment of ``value`` and
+    ``grad_output``: there is no other kernel behind it."""
+    what = "box_attn_backward_boxes_value"
+    operands = (value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits)
+    dims, (D, per_head, V, mode), _ = _boxes_operands(what, ValueError, None, operands, angle_mode,
+                                                      also=[(grad_output, "grad_output")])
+    B, _, H, C, L, Lq, P = dims
+    _boxes_upstream(what, ValueError, value, [("grad_output", grad_output, B * Lq * H * C)])
+    if isinstance(want, bool) or want not in (_lib.WANT_VALUE, _lib.WANT_POINTS, _lib.WANT_ALL):
+        raise ValueError("%s: want must be 1 (grad_value), 2 (the box and logit gradients) or 3, got %r" % (what, want))
+    if not _boxes_ok(_lib.box_bwd_boxes_value_ok, value, (L, Lq, P), also=[grad_output]):
+        raise ValueError("%s: no kernel for value %s, %d levels, %d queries, %d points a level at the alignment of "
+                         "value and grad_output (box_backward_boxes_value_ok)" % (what, tuple(value.shape), L, Lq, P))
+    grad_value = scratch = None
+    scratch_bytes = 0
+    if want & _lib.WANT_VALUE:
+        grad_value = torch.empty(value.shape, dtype=value.dtype, device=value.device)
+        scratch_bytes = _lib.box_bwd_boxes_value_workspace_bytes(value.element_size(), dims)
+        if scratch_bytes:
+            scratch = torch.empty(scratch_bytes // 4, dtype=torch.float32, device=value.device)
+    grads = (None, None, None)
+    if want & _lib.WANT_POINTS:
+        grads = _boxes_grads(value, (B, Lq, H, L), V, (B, Lq, H, L * P), need_ref_grad)
+    _boxes_call("boxattn_bwd_boxes_value_", operands, (D, per_head), (V, mode), (grad_output,), dims,
+                (int(want), grad_value, scratch, scratch_bytes) + grads)
+    return (grad_value,) + grads

@@ -642,6 +642,52 @@ int boxattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const in
 int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P);
 
 /*
+ * The same step with grad_value in the SAME launch: the operands of boxattn_bwd_boxes_*, then
+ *   want         BOXATTN_WANT_VALUE (1), BOXATTN_WANT_POINTS (2) or both (3); anything else is hipErrorInvalidValue.
+ *                POINTS alone is boxattn_bwd_boxes_* exactly: grad_value, workspace and workspace_bytes are not read.
+ *                VALUE alone: grad_offsets, grad_ref_rows and grad_logits are neither checked nor written.
+ *   grad_value   (B,S,H,C) in the storage type, every element written (needed with VALUE)
+ *   workspace    16-bit storage: boxattn_bwd_boxes_value_workspace_bytes() bytes, 16-byte aligned -- the float32
+ *                accumulator, cast into grad_value by one pass behind the kernel (grad_value 8-byte aligned then);
+ *                float32 storage accumulates into grad_value itself and reads neither workspace argument
+ * The kernel of boxattn_bwd_boxes_* in a flavour that, where it walks a level's four corner rows, also adds
+ * weight * corner weight * grad_out row into the accumulator with one hardware float32 atomic an element -- only at
+ * corners inside the map, so a non-finite grad_out row reaches no row its points do not touch.  The entry zero-fills
+ * the accumulator itself.  The order of the adds is not fixed: grad_value from this entry is NOT bitwise reproducible;
+ * grad_offsets, grad_ref_rows and grad_logits are bit for bit those of boxattn_bwd_boxes_* and still are.  Meant for
+ * few queries against the map (decoder cross-attention); DESIGN.md 4.1 has the measurements.
+ * Refusals as boxattn_bwd_boxes_* (hipErrorInvalidValue, nothing launched), and with VALUE: a NULL grad_value, and for
+ * 16-bit storage a workspace that is NULL, smaller than the query says or not 16-byte aligned.  No queries: grad_value
+ * is zero-filled; no pixels: the three other gradients are.  No host reads, no allocation: capturable, on the one
+ * stream.  Profile slot 1 (the zero-fill and the cast included).
+ */
+int boxattn_bwd_boxes_value_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                                const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                                int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                                const float *logits, const float *grad_out,
+                                int B, int S, int H, int C, int L, int Lq, int P,
+                                int want, float *grad_value, void *workspace, size_t workspace_bytes,
+                                float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+int boxattn_bwd_boxes_value_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                                 const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                                 int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                                 const float *logits, const uint16_t *grad_out,
+                                 int B, int S, int H, int C, int L, int Lq, int P,
+                                 int want, uint16_t *grad_value, void *workspace, size_t workspace_bytes,
+                                 float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+int boxattn_bwd_boxes_value_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                                const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                                int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                                const float *logits, const uint16_t *grad_out,
+                                int B, int S, int H, int C, int L, int Lq, int P,
+                                int want, uint16_t *grad_value, void *workspace, size_t workspace_bytes,
+                                float *grad_offsets, float *grad_ref_rows, float *grad_logits, void *stream);
+/* 1 where the entry points above have their kernel: boxattn_bwd_boxes_ok's function. */
+int boxattn_bwd_boxes_value_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P);
+/* Bytes of `workspace`: 0 for 4-byte storage, 4 * B * S * H * C for 2-byte storage.  Pure host code. */
+size_t boxattn_bwd_boxes_value_workspace_bytes(int elem_bytes, int B, int S, int H, int C);
+
+/*
  * Tuning options for A/B runs (process-wide, relaxed atomics; 0 = default).  Returns the
  * previous value, -1 for an unknown key.  (The key numbers of earlier ABI versions are kept; the keys
  * of kernels that were removed are gone.)

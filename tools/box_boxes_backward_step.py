@@ -4,8 +4,10 @@ level, float32 / bf16 / f16, gradients for value, reference windows, box offsets
   encoder shapes   C2 (Lq = S) at B 1 and 2; C5' (234 x 234, 117 x 117, Lq = S, fixed angle) at B 1.
   points  today's fastest configuration: ``BoxGridFunction`` -> ``LogitSoftmaxFunction`` ->
           ``BoxAttn{,BF16,F16}Function`` (the module with ``fused_grid`` and ``fused_pointwise``);
-  boxes   ``BoxAttnBoxesFunction`` (the module with ``fused_boxes_train``).
-Both legs are built from the same sources; the "points" leg is code the "boxes" leg did not touch.
+  boxes   ``BoxAttnBoxesFunction`` (the module with ``fused_boxes_train``);
+  value   ``BoxAttnBoxesValueFunction`` called directly (the module takes it with ``fused_boxes_value`` where Lq < S
+          only: the encoder cells are measured here although the module would not route them).
+The legs are built from the same sources; the "points" leg is code the other two did not touch.
 
     python tools/box_boxes_backward_step.py [--steps K] [--warmup W] [--repeats R] [--out FILE] [--only LEG]
                                             [--dtype f32|bf16|f16] [--cell NAME] [--batch B]
@@ -17,7 +19,7 @@ After the timing, one step per leg alone with the caching allocator's peak count
 ``torch.cuda.max_memory_allocated`` of that step, what it adds to the bytes allocated before it (the inputs of all sets;
 the library's cached workspaces are released first, so each leg's figure holds its own), and the bytes the forward
 saved for the backward beyond the inputs' own storages.  ``--table`` prints, per cell, the points leg's FASTEST repeat
-and the boxes leg's SLOWEST.  ``--only points|boxes`` runs one leg alone, K steps per cell once: the process to put
+and the boxes and value legs' SLOWEST.  ``--only points|boxes|value`` runs one leg alone, K steps per cell once: the process to put
 under a kernel trace."""
 import argparse
 import json
@@ -109,7 +111,10 @@ def measure(args):
             for nxt, _ in node.next_functions:
                 saved_bytes(nxt, seen, tensors)
 
-        legs = {"points": points, "boxes": boxes}
+        def value(fn, value, ref, off, logits):
+            return ba.BoxAttnBoxesValueFunction.apply(value, shapes, lsi, ref, off, kidx, None, logits, mode)
+
+        legs = {"points": points, "boxes": boxes, "value": value}
         if args.only:
             legs = {args.only: legs[args.only]}
         for name, dtype, fn in (("f32", torch.float32, ba.BoxAttnFunction), ("bf16", torch.bfloat16, ba.BoxAttnBF16Function),
@@ -118,6 +123,7 @@ def measure(args):
                 continue
             sets = [inputs(dtype, seed) for seed in range(SETS)]
             assert ops.box_forward_boxes_ok(sets[0][0][0], L, Lq, P) and ops.box_backward_boxes_ok(sets[0][0][0], L, Lq, P)
+            assert "value" not in legs or ops.box_backward_boxes_value_ok(sets[0][0][0], L, Lq, P)
             runs = {leg: [] for leg in legs}
             for _ in range(1 if args.only else args.repeats):
                 for leg, body in legs.items():                                 # the legs alternate
@@ -174,16 +180,18 @@ def table(paths):
                     for leg, n in r["saved_for_backward_bytes"].items():
                         kept.setdefault(key, {}).setdefault(leg, []).append(n)
     print("| shape | B | type | Lq | points, us a step (fastest .. slowest) | boxes, us a step (fastest .. slowest) | "
-          "slowest boxes / fastest points | peak MB over start, points | boxes | saved for backward MB, points | boxes |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|")
+          "value, us a step (fastest .. slowest) | slowest boxes / fastest points | slowest value / slowest boxes | "
+          "peak MB over start, points | boxes | value | saved for backward MB, points | boxes | value |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     nan = [float("nan")]
     for key in sorted(rows):
-        p, b = rows[key].get("points", nan), rows[key].get("boxes", nan)
-        mp, mb = mem[key].get("points", nan), mem[key].get("boxes", nan)
-        kp, kb = kept[key].get("points", nan), kept[key].get("boxes", nan)
-        print("| %s | %d | %s | %d | %.1f .. %.1f | %.1f .. %.1f | %.2f | %.1f | %.1f | %.1f | %.1f |" % (
-            key[0], key[1], key[2], key[3], min(p), max(p), min(b), max(b), max(b) / min(p), max(mp) / 1e6,
-            max(mb) / 1e6, max(kp) / 1e6, max(kb) / 1e6))
+        p, b, v = (rows[key].get(leg, nan) for leg in ("points", "boxes", "value"))
+        mp, mb, mv = (mem[key].get(leg, nan) for leg in ("points", "boxes", "value"))
+        kp, kb, kv = (kept[key].get(leg, nan) for leg in ("points", "boxes", "value"))
+        print("| %s | %d | %s | %d | %.1f .. %.1f | %.1f .. %.1f | %.1f .. %.1f | %.2f | %.2f | %.1f | %.1f | %.1f | %.1f "
+              "| %.1f | %.1f |" % (key[0], key[1], key[2], key[3], min(p), max(p), min(b), max(b), min(v), max(v),
+                                   max(b) / min(p), max(v) / max(b), max(mp) / 1e6, max(mb) / 1e6, max(mv) / 1e6,
+                                   max(kp) / 1e6, max(kb) / 1e6, max(kv) / 1e6))
     return 0
 
 
@@ -192,7 +200,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--only", choices=("points", "boxes"), help="one leg alone, once per cell (for a kernel trace)")
+    ap.add_argument("--only", choices=("points", "boxes", "value"), help="one leg alone, once per cell (for a kernel trace)")
     ap.add_argument("--dtype", choices=("f32", "bf16", "f16"), help="this storage type only")
     ap.add_argument("--cell", help="this shape only (e.g. 'C2 dec')")
     ap.add_argument("--batch", type=int, help="this batch size only")
