@@ -100,6 +100,9 @@ _SIGNATURES = {
     # grad_out, grad_mask | NULL; grad_offsets, grad_ref_rows | NULL, grad_logits
     **_family("instattn_bwd_boxes", _S3, _boxes(False, 2, 3)),
     **_family("boxattn_fwd_boxes", _S3, _boxes(True, 0, 1)),            # out
+    # boxattn_fwd_boxes_* up to out, then shapes_host, lsi_host, stream: the window-staged forward from boxes
+    **_family("boxattn_fwd_boxes_hl", _S3, _boxes(True, 0, 1)[:-1] + _HOST + _STREAM),
+    "boxattn_fwd_boxes_hl_ok": (_i, _QUERY + _HOST),      # elem_bytes, aligned, dims, shapes_host, lsi_host
     **_family("boxattn_bwd_boxes", _S3, _boxes(True, 1, 3)),            # grad_out; the three gradients
     # boxattn_bwd_boxes_* up to P, then want, grad_value, workspace, workspace_bytes, the three gradients, stream
     **_family("boxattn_bwd_boxes_value", _S3, _boxes(True, 1, 0)[:-1] + [_i, _vp, _vp, _sz] + [_vp] * 3 + _STREAM),
@@ -269,6 +272,15 @@ def box_fwd_boxes_ok(elem_bytes, aligned, dims):
     """boxattn_fwd_boxes_ok(): whether the boxattn_fwd_boxes_* entry points have their kernel for ``dims`` = (B, S, H,
     C, L, Lq, P) under the current switches.  Pure host code (no GPU needed)."""
     return _boxes_ok("boxattn_fwd_boxes_ok", elem_bytes, aligned, dims)
+
+
+def box_fwd_boxes_hl_ok(elem_bytes, aligned, dims, shapes_host=None, lsi_host=None):
+    """boxattn_fwd_boxes_hl_ok(): whether the boxattn_fwd_boxes_hl_* entry points have their kernel for ``dims`` = (B, S,
+    H, C, L, Lq, P) and the level tables ``shapes_host`` / ``lsi_host`` (int64 numpy arrays; None: no) under the current
+    switches -- where ``fwd_route`` with them answers FWD_STAGED.  Pure host code (no GPU needed)."""
+    ptr = lambda a: None if a is None else a.ctypes.data
+    return bool(load().boxattn_fwd_boxes_hl_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims],
+                                               ptr(shapes_host), ptr(lsi_host)))
 
 
 def box_bwd_boxes_ok(elem_bytes, aligned, dims):

@@ -483,7 +483,9 @@ int launch_fwd(const FwdIn<ST> &in, const FwdOut<ST> &o, const FwdExtras &x)
 // ---- attention from boxes and logits: the four routes and the host path they share --------------------------
 // instance flavour (k x k points a level, 2x2 logits): fwd_wide_boxes_kernel (boxattn_boxes.h) and
 // pointgrad_boxes_kernel (boxattn_boxes_bwd.h); box flavour (P points a level, L P logits): fwd2_boxes_kernel
-// (boxattn_gather2_boxes.h) and bwd2_boxes_kernel (boxattn_gather2_boxes_bwd.h).  No other kernel behind these entries.
+// (boxattn_gather2_boxes.h) and bwd2_boxes_kernel (boxattn_gather2_boxes_bwd.h); the box flavour's window-staged
+// forward with the host tables: fwd_dense_boxes_kernel / fwd_dense_f32_boxes_kernel (boxattn_dense_fwd.h,
+// boxattn_dense_f32.h).  No other kernel behind these entries.
 
 // What the eligibility queries know of the tensors' addresses.  aligned: 0 nothing beyond the elements' own alignment,
 // 8 every tensor to 8 bytes, else to 16 bytes (staged: left false, boxattn_fwd_route sets it)
@@ -516,6 +518,18 @@ inline bool box_boxes_route(int elem_bytes, const Dims &d, const FwdAlign &al, F
     return fwd_route(elem_bytes, false, d, al, nullptr, nullptr, false, r, dp) == kFwdGather;
 }
 
+// Whether the window-staged forward from boxes runs these dimensions: where the box flavour of fwd_route WITH these
+// host tables takes the window-staged family (make_dense_plan's conditions and switches; the tensors' alignment to 16
+// bytes).  The ONE function behind boxattn_fwd_boxes_hl_ok and the boxattn_fwd_boxes_hl_* entry points; dp: the plan.
+inline bool box_boxes_staged_route(int elem_bytes, const Dims &d, FwdAlign al, const int64_t *shapes_host,
+                                   const int64_t *lsi_host, DensePlan &dp)
+{
+    if ((elem_bytes != 2 && elem_bytes != 4) || !d.valid()) return false;
+    al.staged = al.rows16;
+    FwdRoute r;
+    return fwd_route(elem_bytes, false, d, al, shapes_host, lsi_host, true, r, dp) == kFwdStaged;
+}
+
 // A from-boxes call's operands, filled by the extern "C" wrappers.  Instance flavour: k x k points a level (d.P is
 // not read: boxes_prepare sets it), V 4, angle_mode 0; box flavour: d.P points a level (k is not read).
 template <typename ST> struct BoxesIn {
@@ -529,6 +543,7 @@ template <typename ST> struct BoxesIn {
     Dims d;
     int k;
     hipStream_t st;
+    const int64_t *shapes_host = nullptr, *lsi_host = nullptr;     // the window-staged forward only
 };
 // An output of a from-boxes call (p NULL: an optional one that is absent) and its bytes a (query, head) pair
 struct BoxesOutput { void *p; size_t pair_bytes; };
@@ -539,13 +554,15 @@ struct BoxesLaunch {
     GridDims gd;
     BoxesDims bd;           // instance flavour
     unsigned vbytes;
+    DensePlan dp;           // window-staged forward (STAGED)
 };
 
 // Everything a from-boxes launcher does before its launch; false: the call ends here with rc.  The order shows in
 // the return codes: the dimensions and the flavour's limit, no queries -> 0 before any pointer is looked at, the
 // required pointers (have_required: those of the launcher's own), no pixels -> the outputs zero-filled, value, the
 // route (rows / rows_opt: the row-sized tensors next to value, out / mask_out or grad_out / grad_mask; NULL: aligned).
-template <typename ST, bool INST>
+// STAGED: the box flavour's window-staged forward -- the route is box_boxes_staged_route with in's host tables.
+template <typename ST, bool INST, bool STAGED = false>
 bool boxes_prepare(const BoxesIn<ST> &in, const ST *rows, const ST *rows_opt, bool have_required,
                    std::initializer_list<BoxesOutput> outputs, BoxesLaunch &l, int &rc)
 {
@@ -578,8 +595,12 @@ bool boxes_prepare(const BoxesIn<ST> &in, const ST *rows, const ST *rows_opt, bo
     const size_t va = 4 * sizeof(ST);
     const FwdAlign al{aligned(in.value, va) && aligned(rows, va) && aligned(rows_opt, va),
                       aligned(in.value, 16) && aligned(rows, 16) && aligned(rows_opt, 16), false};
-    if (!(INST ? boxes_route((int)sizeof(ST), d, in.k, al, l.r) : box_boxes_route((int)sizeof(ST), d, al, l.r)))
+    if constexpr (STAGED) {
+        static_assert(!INST, "box flavour");
+        if (!box_boxes_staged_route((int)sizeof(ST), d, al, in.shapes_host, in.lsi_host, l.dp)) return false;
+    } else if (!(INST ? boxes_route((int)sizeof(ST), d, in.k, al, l.r) : box_boxes_route((int)sizeof(ST), d, al, l.r))) {
         return false;
+    }
     l.gd = GridDims{d.Lq, d.H, d.L, d.P, in.V, in.ref_dim, in.ref_per_head ? 1 : 0, in.angle_mode};
     if constexpr (INST) {
         const float m = (float)(in.k / 2);
@@ -645,6 +666,20 @@ template <typename ST> int launch_fwd_box_boxes(const BoxesIn<ST> &in, ST *out)
                        with_grid(l.r.ix, l.r.blocks, 1, (d.L * d.P + GG - 1) / GG), l.vbytes, stride);
     BOXATTN_GATHER_DISPATCH(l.r.cfg, BOXATTN_FWD2_BOXES);
 #undef BOXATTN_FWD2_BOXES
+    return finish();
+}
+
+// ... on the window-staged forward (in.shapes_host / in.lsi_host: the host copies of the level tables)
+template <typename ST> int launch_fwd_box_boxes_staged(const BoxesIn<ST> &in, ST *out)
+{
+    BoxesLaunch l;
+    int rc;
+    if (!boxes_prepare<ST, false, true>(in, out, nullptr, out != nullptr, {{out, (size_t)in.d.C * sizeof(ST)}}, l, rc))
+        return rc;
+    ScopedKernelTimer timer(g_prof.ev[kSlotFwd], in.st);
+    const DenseBoxes bx{in.ref, in.offsets, in.kernel_idx, in.valid_ratios, in.logits,
+                        l.gd.ref_dim, l.gd.ref_per_head, l.gd.V, l.gd.angle_mode};
+    launch_fwd_dense_boxes<ST>(in.value, bx, out, l.dp, l.vbytes, in.st);
     return finish();
 }
 
@@ -1621,6 +1656,13 @@ int boxattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C
     FwdRoute r;
     return box_boxes_route(elem_bytes, DIMS, align_from_bytes(elem_bytes, aligned), r) ? 1 : 0;
 }
+int boxattn_fwd_boxes_hl_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P,
+                            const int64_t *shapes_host, const int64_t *lsi_host)
+{
+    DensePlan dp;
+    const FwdAlign al = align_from_bytes(elem_bytes, aligned);
+    return box_boxes_staged_route(elem_bytes, DIMS, al, shapes_host, lsi_host, dp) ? 1 : 0;
+}
 int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P)
 {
     return boxattn_fwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P);   // box_boxes_route: one eligibility
@@ -1663,6 +1705,21 @@ STORAGE_TYPES(INSTATTN_FWD_BOXES)
     }
 STORAGE_TYPES(BOXATTN_FWD_BOXES)
 #undef BOXATTN_FWD_BOXES
+
+#define BOXATTN_FWD_BOXES_HL(SUF, CT, ST, CAST, ...)                                                           \
+    int boxattn_fwd_boxes_hl_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \
+                                   int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode, \
+                                   const float *kernel_idx, const float *valid_ratios, const float *logits,    \
+                                   int B, int S, int H, int C, int L, int Lq, int P, CT *out, HOST_TABLES,     \
+                                   void *stream)                                                               \
+    {                                                                                                          \
+        BoxesIn<ST> in = BOXES_IN(ST, CAST, V, angle_mode, P, 0);                                              \
+        in.shapes_host = shapes_host;                                                                          \
+        in.lsi_host = lsi_host;                                                                                \
+        return launch_fwd_box_boxes_staged<ST>(in, CAST(out));                                                 \
+    }
+STORAGE_TYPES(BOXATTN_FWD_BOXES_HL)
+#undef BOXATTN_FWD_BOXES_HL
 
 #define INSTATTN_BWD_BOXES(SUF, CT, ST, CAST, ...)                                                             \
     int instattn_bwd_boxes_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \

@@ -86,6 +86,29 @@ void launch_fwd_dense_f32(const float *value, const float *loc, const float *att
 #undef BOXATTN_DENSE_FWD32
 }
 
+// the forwards from boxes and logits: no riders, one workgroup a (tile, head)
+template <typename ST>
+void launch_fwd_dense_boxes(const ST *value, const DenseBoxes &bx, ST *out, const DensePlan &dp, unsigned value_bytes,
+                            hipStream_t st)
+{
+    const GridDims gd{dp.Lq, dp.H, dp.L, 4, bx.V, bx.ref_dim, bx.ref_per_head, bx.angle_mode};
+#define BOXATTN_DENSE_FWD_BOXES(LV_)                                                                       \
+    case LV_:                                                                                              \
+        if constexpr (sizeof(ST) == 2)                                                                     \
+            hipLaunchKernelGGL((fwd_dense_boxes_kernel<ST, LV_>), dim3(dense_blocks(dp)), dim3(256), 0, st, value, \
+                               bx.ref, bx.offsets, bx.kernel_idx, bx.valid_ratios, bx.logits, out, dp, value_bytes, gd); \
+        else                                                                                               \
+            hipLaunchKernelGGL((fwd_dense_f32_boxes_kernel<LV_>), dim3(dense_blocks(dp)), dim3(256), 0, st, value, \
+                               bx.ref, bx.offsets, bx.kernel_idx, bx.valid_ratios, bx.logits, out, dp, value_bytes, gd); \
+        break;
+    switch (dp.L) {
+        BOXATTN_DENSE_FWD_BOXES(1) BOXATTN_DENSE_FWD_BOXES(2) BOXATTN_DENSE_FWD_BOXES(3) BOXATTN_DENSE_FWD_BOXES(4)
+    }
+#undef BOXATTN_DENSE_FWD_BOXES
+}
+template void launch_fwd_dense_boxes<float>(const float *, const DenseBoxes &, float *, const DensePlan &, unsigned,
+                                            hipStream_t);
+
 template <typename ST>
 void launch_accumulate_tr(int C, const ST *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
                           int H, int Lq, const int4 *items, const int *n_items, const int *records,
@@ -152,6 +175,8 @@ void launch_accumulate_tr_inst(int C, const ST *grad_out, size_t grad_out_bytes,
                                               const BinRide &);                                             \
     template void launch_fwd_dense<ST_>(const ST_ *, const float *, const float *, ST_ *, const DensePlan &, \
                                         unsigned, const BinRide &, unsigned long long *, hipStream_t);      \
+    template void launch_fwd_dense_boxes<ST_>(const ST_ *, const DenseBoxes &, ST_ *, const DensePlan &,   \
+                                              unsigned, hipStream_t);                                       \
     template void launch_accumulate_tr<ST_>(int, const ST_ *, size_t, const BinPlan &, int, int, int,       \
                                             const int4 *, const int *, const int *, ST_ *, float *, int, int, \
                                             const ChunkCombine &, const ZeroRole &, hipStream_t);              \

@@ -84,6 +84,18 @@ void launch_fwd_dense(const ST *value, const float *loc, const float *attn, ST *
                       const DensePlan &dp, unsigned value_bytes, const BinRide &ride,
                       unsigned long long *stats, hipStream_t st);
 
+// out of box attention on a query grid at inference, from the boxes and logits instead of loc and attn
+// (fwd_dense_boxes_kernel, fwd_dense_f32_boxes_kernel; ST = bf16_t, f16_t or float, the plan made for its element size):
+// ref (B, Lq, ref_dim) or (B, Lq, H, ref_dim), offsets (B, Lq, H, L, V), kernel_idx (4, 2), valid_ratios (B, L, 2) or
+// null, logits (B, Lq, H, 4 L).  No riders, no statistics.
+struct DenseBoxes {
+    const float *ref, *offsets, *kernel_idx, *valid_ratios, *logits;
+    int ref_dim, ref_per_head, V, angle_mode;
+};
+template <typename ST>
+void launch_fwd_dense_boxes(const ST *value, const DenseBoxes &bx, ST *out, const DensePlan &dp, unsigned value_bytes,
+                            hipStream_t st);
+
 // float32 storage (boxattn_dense_f32.h): the plan's window geometry in 32-byte units (make_dense_plan with 4-byte elements)
 void launch_pointgrad_dense_f32(const float *value, const float *loc, const float *attn, const float *grad_out,
                                 const DensePlan &dp, float *grad_loc, float *grad_attn, unsigned value_bytes,

@@ -20,25 +20,6 @@
 
 namespace boxattn {
 
-// max over aligned groups of G <= 16 consecutive lanes, in every lane of the group (the DPP steps of group_sum)
-template <int G> __device__ __forceinline__ float group_fmax(float v)
-{
-    static_assert(G <= 16, "one DPP row");
-    if constexpr (G >= 2)
-        v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                         0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));    // quad_perm [1,0,3,2]
-    if constexpr (G >= 4)
-        v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                         0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)));    // quad_perm [2,3,0,1]
-    if constexpr (G >= 8)
-        v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                         0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)));   // row_half_mirror
-    if constexpr (G >= 16)
-        v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-                         0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true)));   // row_ror:8
-    return v;
-}
-
 constexpr int kBoxesMaxLP = 64;          // L P logits a pair: the limit of the softmax kernels
 
 // 16-byte pieces of wave-private LDS a pair takes: two a level {cx, cy, w, h}{sin, cos, vx, vy}, then its L P weights

@@ -71,6 +71,12 @@ class _BoxAttentionBase(nn.Module):
         # ops.instance_attn_forward_boxes, the third element of the return is then the empty tuple; BoxAttention /
         # Box3dAttention: ops.box_attn_forward_boxes, the second element of the return is then the empty tuple
         self.fused_boxes = False
+        # opt-in, only together with `fused_boxes` and where that path is taken (BoxAttention / Box3dAttention;
+        # InstanceAttention ignores it, and so does grad mode): where ops.box_forward_boxes_staged_ok says yes -- the
+        # encoder's self-attention: one query per pixel, 32 channels a head, at most 4 levels --
+        # ops.box_attn_forward_boxes_staged, the window-staged forward from the same operands; elsewhere
+        # ops.box_attn_forward_boxes as without it
+        self.fused_boxes_staged = False
         # opt-in, in training (grad mode): forward and backward from the boxes and logits -- no per-point tensor is built
         # in the forward or kept for the backward.  InstanceAttention (`inferencing` false): InstanceAttnBoxesFunction,
         # the third element of the return is then the empty tuple; BoxAttention / Box3dAttention:
@@ -245,7 +251,9 @@ class BoxAttention(_BoxAttentionBase):
         mode = self._angle_mode()
         logits = dense.linear(query, self.linear_attn_weight, self.linear_attn_bias)
         offsets = self._box_offsets(query, ref_windows, 5 if mode == 1 else 4)
-        output = ops.box_attn_forward_boxes(
+        staged = self.fused_boxes_staged and ops.box_forward_boxes_staged_ok(value, v_shape, v_start_index, l1,
+                                                                             self.num_point)
+        output = (ops.box_attn_forward_boxes_staged if staged else ops.box_attn_forward_boxes)(
             value, v_shape, v_start_index, _f32(ref_windows), _f32(offsets), _f32(self.kernel_indices),
             None if v_valid_ratios is None else _f32(v_valid_ratios).view(b, self.num_level, 2),
             _f32(logits).view(b, l1, self.num_head, -1), mode)

@@ -1031,6 +1031,46 @@ def box_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows
 
 
 # ---------------------------------------------------------------------------------------
+# ... for the encoder case on the window-staged forward (opt-in; include/boxattn.h, boxattn_fwd_boxes_hl_*)
+# ---------------------------------------------------------------------------------------
+def box_forward_boxes_staged_ok(value, spatial_shapes, level_start_index, num_query, num_point):
+    """Whether ``box_attn_forward_boxes_staged`` has its kernel under the current switches: ``boxattn_fwd_boxes_hl_ok``
+    with the dimensions, element size and alignment of ``value`` (B, S, H, C), the host copies of the level tables
+    ``spatial_shapes`` (L, 2) / ``level_start_index`` (L) (``_host_table``: the first call with a tensor synchronises),
+    ``num_query`` queries an image and ``num_point`` points a level -- the encoder case: one query per pixel, C = 32,
+    2x2 points, at most 4 levels.  The output is taken as freshly allocated (aligned).  Otherwise pure host code."""
+    if not isinstance(spatial_shapes, torch.Tensor) or not isinstance(level_start_index, torch.Tensor) or \
+            spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64 or \
+            spatial_shapes.dim() != 2 or spatial_shapes.size(1) != 2 or level_start_index.numel() != spatial_shapes.size(0):
+        return False
+    sh, ls = _host_table(spatial_shapes), _host_table(level_start_index)
+    return _boxes_ok(lambda elem, aligned, dims: _lib.box_fwd_boxes_hl_ok(elem, aligned, dims, sh, ls), value,
+                     (spatial_shapes.size(0), num_query, num_point))
+
+
+def box_attn_forward_boxes_staged(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                                  valid_ratios, logits, angle_mode=0):
+    """``box_attn_forward_boxes`` -- the same operands, the same result up to the order of the float32 sums -- for the
+    encoder case (one query per pixel, C = 32, 2x2 points, at most 4 levels) on the window-staged forward: the kernels
+    of ``box_attn_forward``'s encoder route, the locations and weights made inside them from the boxes and logits.  The
+    level tables are also read on the host (``_host_table``).  No backward.  Raises ValueError, before any device
+    call, for arguments that do not fit and where ``box_forward_boxes_staged_ok`` says no: there is no other kernel
+    behind it."""
+    operands = (value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits)
+    dims, (D, per_head, V, mode), _ = _boxes_operands("box_attn_forward_boxes_staged", ValueError, None, operands,
+                                                      angle_mode)
+    B, _, H, C, L, Lq, P = dims
+    if not box_forward_boxes_staged_ok(value, spatial_shapes, level_start_index, Lq, P):
+        raise ValueError("box_attn_forward_boxes_staged: no kernel for value %s, %d levels, %d queries, %d points a "
+                         "level (box_forward_boxes_staged_ok)" % (tuple(value.shape), L, Lq, P))
+    sh, ls = _host_table(spatial_shapes), _host_table(level_start_index)
+    out = torch.empty((B, Lq, H * C), dtype=value.dtype, device=value.device)
+    _boxes_call("boxattn_fwd_boxes_hl_", operands, (D, per_head), (V, mode), (), dims,
+                (out, sh.ctypes.data, ls.ctypes.data))
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # box attention's training step from the same operands (opt-in; include/boxattn.h, boxattn_bwd_boxes_*)
 # ---------------------------------------------------------------------------------------
 def box_backward_boxes_ok(value, num_level, num_query, num_point):

@@ -561,6 +561,41 @@ int boxattn_fwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const in
 int boxattn_fwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P);
 
 /*
+ * The same call for the ENCODER case (one query per pixel, C = 32, P = 4, L <= 4) on the WINDOW-STAGED forward
+ * (boxattn_fwd_hl_*'s kernels: an 8x8 query tile's value windows in LDS; 16-bit storage on the matrix cores), with the
+ * host copies of the level tables (shapes_host / lsi_host as boxattn_fwd_hl_*; read during the call, never the device
+ * copies).  Each quad of lanes makes its query's 4 L locations and weights in registers while the windows are fetched:
+ * locations as above (the grid kernel's, bit for bit); weights exp(z - max) * (1 / sum) in float32 -- maximum and sum
+ * over the lane's own L values in level order, then over the quad.  One window-staged kernel per storage type and
+ * no other behind these entries: dimensions for which boxattn_fwd_boxes_hl_ok answers 0 (NULL host tables among
+ * them), and everything boxattn_fwd_boxes_* refuses, are hipErrorInvalidValue; nothing is launched then.  The checks
+ * run in that entry's order.  No riders, no state, no atomics (bitwise reproducible), no host reads beyond the two
+ * tables, no allocation: capturable, on the one stream.  Profile slot 0.
+ */
+int boxattn_fwd_boxes_hl_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                             const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                             int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                             const float *logits, int B, int S, int H, int C, int L, int Lq, int P, float *out,
+                             const int64_t *shapes_host, const int64_t *lsi_host, void *stream);
+int boxattn_fwd_boxes_hl_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                              const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                              int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                              const float *logits, int B, int S, int H, int C, int L, int Lq, int P, uint16_t *out,
+                              const int64_t *shapes_host, const int64_t *lsi_host, void *stream);
+int boxattn_fwd_boxes_hl_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                             const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                             int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                             const float *logits, int B, int S, int H, int C, int L, int Lq, int P, uint16_t *out,
+                             const int64_t *shapes_host, const int64_t *lsi_host, void *stream);
+/* 1 where the entry points above have their kernel: exactly where boxattn_fwd_route answers BOXATTN_FWD_STAGED for the
+ * box flavour of these dimensions WITH these host tables (Lq = S, C = 32, P = 4, L <= 4, the tables consistent with S,
+ * value and out aligned to 16 bytes, value < 2 GiB, boxattn_set_variant 0 / 3 and option key 11 not 1); else 0, also
+ * without host tables.  elem_bytes 2 / 4; aligned as boxattn_fwd_route.  Pure host code: no device call; the entry
+ * points call the same function. */
+int boxattn_fwd_boxes_hl_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P,
+                            const int64_t *shapes_host, const int64_t *lsi_host);
+
+/*
  * Instance attention's TRAINING step from the same operands: the gradients the module needs per (batch, query, head,
  * level) -- of the box offsets, of the reference window (rows, summed by the caller as after boxattn_grid_bwd_f32) and
  * of the 2x2 logits -- in one launch: what instattn_bwd_part_* (want = BOXATTN_WANT_POINTS), boxattn_grid_bwd_f32
