@@ -11,7 +11,8 @@ The compute lives in a C-ABI HIP library (``include/boxattn.h``, ``boxer_amd/csr
 DESIGN.md and INTEGRATION.md.  There is no CPU fallback: ops raise if the library is missing.
 """
 from . import _lib, ops
-from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnBoxesValueFunction, BoxAttnF16Function,
+from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnBoxesStagedFunction,
+                        BoxAttnBoxesValueFunction, BoxAttnF16Function,
                         BoxAttnFunction, BoxGridFunction, InstanceAttnBF16Function, InstanceAttnF16Function, InstanceAttnFunction,
                         InstanceAttnBoxesFunction, InstanceWeightsFunction, LogitSoftmaxFunction,
                         ValueMaskCastFunction)
@@ -21,7 +22,7 @@ __all__ = [
     "ops", "BoxAttnFunction", "InstanceAttnFunction", "BoxAttnBF16Function",
     "InstanceAttnBF16Function", "BoxAttnF16Function", "InstanceAttnF16Function", "BoxGridFunction", "LogitSoftmaxFunction", "ValueMaskCastFunction",
     "InstanceWeightsFunction", "InstanceAttnBoxesFunction", "BoxAttnBoxesFunction",
-    "BoxAttnBoxesValueFunction",
+    "BoxAttnBoxesValueFunction", "BoxAttnBoxesStagedFunction",
     "BoxAttention", "InstanceAttention", "Box3dAttention",
     "build", "build_info",
 ]

@@ -104,6 +104,9 @@ _SIGNATURES = {
     **_family("boxattn_fwd_boxes_hl", _S3, _boxes(True, 0, 1)[:-1] + _HOST + _STREAM),
     "boxattn_fwd_boxes_hl_ok": (_i, _QUERY + _HOST),      # elem_bytes, aligned, dims, shapes_host, lsi_host
     **_family("boxattn_bwd_boxes", _S3, _boxes(True, 1, 3)),            # grad_out; the three gradients
+    # boxattn_bwd_boxes_* up to grad_logits, then shapes_host, lsi_host, stream: the window-staged backward from boxes
+    **_family("boxattn_bwd_boxes_hl", _S3, _boxes(True, 1, 3)[:-1] + _HOST + _STREAM),
+    "boxattn_bwd_boxes_hl_ok": (_i, _QUERY + _HOST),      # elem_bytes, aligned, dims, shapes_host, lsi_host
     # boxattn_bwd_boxes_* up to P, then want, grad_value, workspace, workspace_bytes, the three gradients, stream
     **_family("boxattn_bwd_boxes_value", _S3, _boxes(True, 1, 0)[:-1] + [_i, _vp, _vp, _sz] + [_vp] * 3 + _STREAM),
     **{"%s_%s_boxes_ok" % (op, way): (_i, _QUERY) for op in _FWD for way in ("fwd", "bwd")},
@@ -280,6 +283,15 @@ def box_fwd_boxes_hl_ok(elem_bytes, aligned, dims, shapes_host=None, lsi_host=No
     switches -- where ``fwd_route`` with them answers FWD_STAGED.  Pure host code (no GPU needed)."""
     ptr = lambda a: None if a is None else a.ctypes.data
     return bool(load().boxattn_fwd_boxes_hl_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims],
+                                               ptr(shapes_host), ptr(lsi_host)))
+
+
+def box_bwd_boxes_hl_ok(elem_bytes, aligned, dims, shapes_host=None, lsi_host=None):
+    """boxattn_bwd_boxes_hl_ok(): whether the boxattn_bwd_boxes_hl_* entry points have their kernel for ``dims`` = (B, S,
+    H, C, L, Lq, P) with the host copies of the level tables (int64 numpy arrays or None) under the current switches:
+    ``box_fwd_boxes_hl_ok``'s function, ``aligned`` speaking of value and grad_out.  Pure host code."""
+    ptr = lambda a: None if a is None else a.ctypes.data
+    return bool(load().boxattn_bwd_boxes_hl_ok(int(elem_bytes), int(aligned), *[int(v) for v in dims],
                                                ptr(shapes_host), ptr(lsi_host)))
 
 

@@ -613,12 +613,12 @@ bool boxes_prepare(const BoxesIn<ST> &in, const ST *rows, const ST *rows_opt, bo
 // The gradients of a from-boxes backward: per (query, head, level) row V offsets, 5 window terms (optional) and the
 // row's logits (instance flavour: 2x2; box flavour: P)
 struct BoxesGrads { float *offsets, *ref_rows, *logits; };
-template <typename ST, bool INST>
+template <typename ST, bool INST, bool STAGED = false>
 bool boxes_prepare_bwd(const BoxesIn<ST> &in, const ST *grad_out, const ST *grad_mask, const BoxesGrads &g,
                        BoxesLaunch &l, int &rc)
 {
     const size_t row = (size_t)in.d.L * sizeof(float);
-    return boxes_prepare<ST, INST>(
+    return boxes_prepare<ST, INST, STAGED>(
         in, grad_out, grad_mask, grad_out && g.offsets && g.logits,
         {{g.offsets, row * in.V}, {g.ref_rows, row * 5}, {g.logits, row * (INST ? 4 : in.d.P)}}, l, rc);
 }
@@ -737,6 +737,23 @@ template <typename ST> int launch_bwd_box_boxes(const BoxesIn<ST> &in, const ST 
     if (!boxes_prepare_bwd<ST, false>(in, grad_out, nullptr, g, l, rc)) return rc;
     ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], in.st);
     launch_bwd2_boxes<ST, false, true>(in, l, grad_out, g, nullptr);
+    return finish();
+}
+
+// ... on the window-staged point-gradient kernels from boxes (in.shapes_host / in.lsi_host: the host copies of the
+// level tables; the route of launch_fwd_box_boxes_staged, the alignment now value's and grad_out's).  A pair's 4 L
+// logit gradients leave as 16-byte stores: grad_logits aligned to 16 bytes, checked last.
+template <typename ST> int launch_bwd_box_boxes_staged(const BoxesIn<ST> &in, const ST *grad_out, const BoxesGrads &g)
+{
+    BoxesLaunch l;
+    int rc;
+    if (!boxes_prepare_bwd<ST, false, true>(in, grad_out, nullptr, g, l, rc)) return rc;
+    if (!aligned(g.logits, 16)) return (int)hipErrorInvalidValue;
+    ScopedKernelTimer timer(g_prof.ev[kSlotBwdPoints], in.st);
+    const DenseBoxes bx{in.ref, in.offsets, in.kernel_idx, in.valid_ratios, in.logits,
+                        l.gd.ref_dim, l.gd.ref_per_head, l.gd.V, l.gd.angle_mode};
+    launch_pointgrad_dense_boxes<ST>(in.value, bx, grad_out, DenseBoxesGrads{g.offsets, g.ref_rows, g.logits}, l.dp,
+                                     l.vbytes, in.st);
     return finish();
 }
 
@@ -1667,6 +1684,12 @@ int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C
 {
     return boxattn_fwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P);   // box_boxes_route: one eligibility
 }
+int boxattn_bwd_boxes_hl_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P,
+                            const int64_t *shapes_host, const int64_t *lsi_host)
+{
+    // box_boxes_staged_route: one eligibility
+    return boxattn_fwd_boxes_hl_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P, shapes_host, lsi_host);
+}
 int boxattn_bwd_boxes_value_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P)
 {
     return boxattn_bwd_boxes_ok(elem_bytes, aligned, B, S, H, C, L, Lq, P);   // the same kernel family
@@ -1745,6 +1768,22 @@ STORAGE_TYPES(INSTATTN_BWD_BOXES)
     }
 STORAGE_TYPES(BOXATTN_BWD_BOXES)
 #undef BOXATTN_BWD_BOXES
+
+#define BOXATTN_BWD_BOXES_HL(SUF, CT, ST, CAST, ...)                                                           \
+    int boxattn_bwd_boxes_hl_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \
+                                   int ref_dim, int ref_per_head, const float *offsets, int V, int angle_mode, \
+                                   const float *kernel_idx, const float *valid_ratios, const float *logits,    \
+                                   const CT *grad_out, int B, int S, int H, int C, int L, int Lq, int P,       \
+                                   float *grad_offsets, float *grad_ref_rows, float *grad_logits, HOST_TABLES, \
+                                   void *stream)                                                               \
+    {                                                                                                          \
+        BoxesIn<ST> in = BOXES_IN(ST, CAST, V, angle_mode, P, 0);                                              \
+        in.shapes_host = shapes_host;                                                                          \
+        in.lsi_host = lsi_host;                                                                                \
+        return launch_bwd_box_boxes_staged<ST>(in, CAST(grad_out), BOXES_GRADS);                               \
+    }
+STORAGE_TYPES(BOXATTN_BWD_BOXES_HL)
+#undef BOXATTN_BWD_BOXES_HL
 
 #define BOXATTN_BWD_BOXES_VALUE(SUF, CT, ST, CAST, ...)                                                           \
     int boxattn_bwd_boxes_value_##SUF(const CT *value, const int64_t *shapes, const int64_t *lsi, const float *ref, \

@@ -7,6 +7,7 @@
 #include "boxattn_binned_tr.h"
 #include "boxattn_dense_fwd.h"
 #include "boxattn_dense_f32.h"
+#include "boxattn_dense_boxes_bwd.h"
 
 namespace boxattn {
 
@@ -109,6 +110,31 @@ void launch_fwd_dense_boxes(const ST *value, const DenseBoxes &bx, ST *out, cons
 template void launch_fwd_dense_boxes<float>(const float *, const DenseBoxes &, float *, const DensePlan &, unsigned,
                                             hipStream_t);
 
+// the box and logit gradients from boxes and logits (boxattn_dense_boxes_bwd.h): no riders, one workgroup a (tile, head)
+template <typename ST>
+void launch_pointgrad_dense_boxes(const ST *value, const DenseBoxes &bx, const ST *grad_out, const DenseBoxesGrads &g,
+                                  const DensePlan &dp, unsigned value_bytes, hipStream_t st)
+{
+    const GridDims gd{dp.Lq, dp.H, dp.L, 4, bx.V, bx.ref_dim, bx.ref_per_head, bx.angle_mode};
+#define BOXATTN_DENSE_PG_BOXES(LV_)                                                                        \
+    case LV_:                                                                                              \
+        if constexpr (sizeof(ST) == 2)                                                                     \
+            hipLaunchKernelGGL((pointgrad_dense_boxes_kernel<ST, LV_>), dim3(dense_blocks(dp)), dim3(256), 0, st, value, \
+                               bx.ref, bx.offsets, bx.kernel_idx, bx.valid_ratios, bx.logits, grad_out, g.offsets, \
+                               g.ref_rows, g.logits, dp, value_bytes, gd);                                 \
+        else                                                                                               \
+            hipLaunchKernelGGL((pointgrad_dense_f32_boxes_kernel<LV_>), dim3(dense_blocks(dp)), dim3(256), 0, st, value, \
+                               bx.ref, bx.offsets, bx.kernel_idx, bx.valid_ratios, bx.logits, grad_out, g.offsets, \
+                               g.ref_rows, g.logits, dp, value_bytes, gd);                                 \
+        break;
+    switch (dp.L) {
+        BOXATTN_DENSE_PG_BOXES(1) BOXATTN_DENSE_PG_BOXES(2) BOXATTN_DENSE_PG_BOXES(3) BOXATTN_DENSE_PG_BOXES(4)
+    }
+#undef BOXATTN_DENSE_PG_BOXES
+}
+template void launch_pointgrad_dense_boxes<float>(const float *, const DenseBoxes &, const float *,
+                                                  const DenseBoxesGrads &, const DensePlan &, unsigned, hipStream_t);
+
 template <typename ST>
 void launch_accumulate_tr(int C, const ST *grad_out, size_t grad_out_bytes, const BinPlan &plan, int S,
                           int H, int Lq, const int4 *items, const int *n_items, const int *records,
@@ -177,6 +203,9 @@ void launch_accumulate_tr_inst(int C, const ST *grad_out, size_t grad_out_bytes,
                                         unsigned, const BinRide &, unsigned long long *, hipStream_t);      \
     template void launch_fwd_dense_boxes<ST_>(const ST_ *, const DenseBoxes &, ST_ *, const DensePlan &,   \
                                               unsigned, hipStream_t);                                       \
+    template void launch_pointgrad_dense_boxes<ST_>(const ST_ *, const DenseBoxes &, const ST_ *,           \
+                                                    const DenseBoxesGrads &, const DensePlan &, unsigned,   \
+                                                    hipStream_t);                                           \
     template void launch_accumulate_tr<ST_>(int, const ST_ *, size_t, const BinPlan &, int, int, int,       \
                                             const int4 *, const int *, const int *, ST_ *, float *, int, int, \
                                             const ChunkCombine &, const ZeroRole &, hipStream_t);              \

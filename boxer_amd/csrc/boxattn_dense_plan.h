@@ -96,6 +96,15 @@ template <typename ST>
 void launch_fwd_dense_boxes(const ST *value, const DenseBoxes &bx, ST *out, const DensePlan &dp, unsigned value_bytes,
                             hipStream_t st);
 
+// ... and the training step's box and logit gradients from the same operands and grad_out (B, Lq, H, 32) in the storage
+// type (pointgrad_dense_boxes_kernel, pointgrad_dense_f32_boxes_kernel: boxattn_dense_boxes_bwd.h): grad_offsets
+// (B, Lq, H, L, V), grad_ref_rows (B, Lq, H, L, 5) or null, grad_logits (B, Lq, H, 4 L; 16-byte aligned), float32.
+// No riders, no state.
+struct DenseBoxesGrads { float *offsets, *ref_rows, *logits; };
+template <typename ST>
+void launch_pointgrad_dense_boxes(const ST *value, const DenseBoxes &bx, const ST *grad_out, const DenseBoxesGrads &g,
+                                  const DensePlan &dp, unsigned value_bytes, hipStream_t st);
+
 // float32 storage (boxattn_dense_f32.h): the plan's window geometry in 32-byte units (make_dense_plan with 4-byte elements)
 void launch_pointgrad_dense_f32(const float *value, const float *loc, const float *attn, const float *grad_out,
                                 const DensePlan &dp, float *grad_loc, float *grad_attn, unsigned value_bytes,

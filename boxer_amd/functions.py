@@ -471,6 +471,43 @@ class BoxAttnBoxesFunction(Function):
         return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)
 
 
+class BoxAttnBoxesStagedFunction(Function):
+    """``BoxAttnBoxesFunction`` -- its signature, what it saves -- for the encoder's self-attention (one query per
+    pixel, 32 channels a head, 2x2 points, at most 4 levels; ``module.fused_boxes_train_staged``) on the window-staged
+    kernels: the forward is ``ops.box_attn_forward_boxes_staged``, the gradients of ``offsets``, ``ref_windows`` and
+    ``logits`` come from one ``ops.box_attn_backward_boxes_staged`` call (bitwise reproducible).  ``grad_value`` comes
+    from the destination-binned backward on rebuilt per-point tensors, as in ``BoxAttnBoxesFunction``.  Both calls raise
+    where their ``ops.*_staged_ok`` says no: the caller asks first."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios,
+                logits, angle_mode):
+        ctx.angle_mode = int(angle_mode)
+        ctx.logits_shape = tuple(logits.shape)
+        b, lq, h = offsets.shape[:3]
+        operands = _boxes_operands(ctx, value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                                   valid_ratios, logits.reshape(b, lq, h, -1))
+        return ops.box_attn_forward_boxes_staged(*operands, ctx.angle_mode)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        operands, need_v, need_params = _boxes_saved(ctx)
+        value, ref_windows, offsets, logits = operands[0], operands[3], operands[4], operands[7]
+        grad_output = grad_output.to(value.dtype).contiguous()
+        grad_value = grad_ref = grad_offsets = grad_logits = None
+        if need_params:
+            grad_ref, grad_offsets, grad_logits = _boxes_param_grads(
+                ctx, ref_windows, ops.box_attn_backward_boxes_staged(*operands, ctx.angle_mode, grad_output,
+                                                                     need_ref_grad=ctx.needs_input_grad[3]))
+            if grad_logits is not None:
+                grad_logits = grad_logits.view(ctx.logits_shape)
+        if need_v:
+            weights = lambda: (ops.softmax_forward(logits).view(*offsets.shape[:4], -1), None)
+            grad_value = _boxes_grad_value(ctx, operands, ctx.angle_mode, weights, grad_output)
+        return (grad_value, None, None, grad_ref, grad_offsets, None, None, grad_logits, None)
+
+
 class BoxAttnBoxesValueFunction(Function):
     """``BoxAttnBoxesFunction`` -- its signature, its forward, what it saves -- with the whole backward as ONE
     ``ops.box_attn_backward_boxes_value`` call (``module.fused_boxes_value``): ``grad_value`` is scattered with

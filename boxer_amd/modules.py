@@ -22,7 +22,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import dense, ops
-from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnBoxesValueFunction, BoxAttnF16Function,
+from .functions import (BoxAttnBF16Function, BoxAttnBoxesFunction, BoxAttnBoxesStagedFunction,
+                        BoxAttnBoxesValueFunction, BoxAttnF16Function,
                         BoxAttnFunction, BoxGridFunction, InstanceAttnBF16Function, InstanceAttnBoxesFunction,
                         InstanceAttnF16Function, InstanceAttnFunction, InstanceWeightsFunction, LogitSoftmaxFunction,
                         ValueMaskCastFunction)
@@ -88,6 +89,13 @@ class _BoxAttentionBase(nn.Module):
         # says yes, BoxAttnBoxesValueFunction -- grad_value from float32 atomics inside the backward's one launch, NOT
         # bitwise reproducible -- instead of BoxAttnBoxesFunction
         self.fused_boxes_value = False
+        # opt-in, only together with `fused_boxes_train` (BoxAttention / Box3dAttention; InstanceAttention ignores it):
+        # where that step is taken and both ops.box_forward_boxes_staged_ok and ops.box_backward_boxes_staged_ok say
+        # yes -- the encoder's self-attention: one query per pixel, 32 channels a head, at most 4 levels --
+        # BoxAttnBoxesStagedFunction, forward and parameter gradients on the window-staged kernels from the same
+        # operands, instead of BoxAttnBoxesFunction; elsewhere as without it.  (`fused_boxes_staged` stays an
+        # inference switch: grad mode ignores it.)
+        self.fused_boxes_train_staged = False
 
         self.linear_box_weight = nn.Parameter(torch.zeros(num_level * num_head * box_vars, d_model))
         self.linear_box_bias = nn.Parameter(torch.zeros(num_head * num_level * box_vars))
@@ -259,10 +267,15 @@ class BoxAttention(_BoxAttentionBase):
             _f32(logits).view(b, l1, self.num_head, -1), mode)
         return dense.linear(output, self.out_proj.weight, self.out_proj.bias), ()
 
-    def _boxes_train_function(self, value, num_query):
+    def _boxes_train_function(self, value, num_query, v_shape=None, v_start_index=None):
         """The Function of the training step from boxes for ``value`` (B,S,H,C) as ``_boxes_train`` returned it:
-        ``fused_boxes_value`` with fewer queries than pixels and a kernel for the shape -> the one with grad_value in
-        the backward's own launch."""
+        ``fused_boxes_train_staged`` where both staged calls have their kernel (the encoder: one query per pixel) ->
+        the window-staged one; ``fused_boxes_value`` with fewer queries than pixels and a kernel for the shape -> the
+        one with grad_value in the backward's own launch."""
+        if (self.fused_boxes_train_staged and v_shape is not None and
+                ops.box_forward_boxes_staged_ok(value, v_shape, v_start_index, num_query, self.num_point) and
+                ops.box_backward_boxes_staged_ok(value, v_shape, v_start_index, num_query, self.num_point)):
+            return BoxAttnBoxesStagedFunction
         if (self.fused_boxes_value and num_query < value.size(1) and
                 ops.box_backward_boxes_value_ok(value, self.num_level, num_query, self.num_point)):
             return BoxAttnBoxesValueFunction
@@ -273,7 +286,7 @@ class BoxAttention(_BoxAttentionBase):
         mode = self._angle_mode()
         logits = dense.linear(query, self.linear_attn_weight, self.linear_attn_bias)
         # (differentiable casts: the gradients flow on to the projections, the query and the reference windows)
-        output = self._boxes_train_function(value, l1).apply(
+        output = self._boxes_train_function(value, l1, v_shape, v_start_index).apply(
             value, v_shape, v_start_index, ref_windows.float(),
             self._box_offsets(query, ref_windows, 5 if mode == 1 else 4).float(), self.kernel_indices,
             None if v_valid_ratios is None else v_valid_ratios.view(b, self.num_level, 2),

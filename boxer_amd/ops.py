@@ -1033,15 +1033,21 @@ def box_attn_forward_boxes(value, spatial_shapes, level_start_index, ref_windows
 # ---------------------------------------------------------------------------------------
 # ... for the encoder case on the window-staged forward (opt-in; include/boxattn.h, boxattn_fwd_boxes_hl_*)
 # ---------------------------------------------------------------------------------------
+def _host_tables_ok(spatial_shapes, level_start_index):
+    """Whether the two level tables are what ``_host_table`` copies for the staged calls from boxes."""
+    return (isinstance(spatial_shapes, torch.Tensor) and isinstance(level_start_index, torch.Tensor) and
+            spatial_shapes.dtype == torch.int64 and level_start_index.dtype == torch.int64 and
+            spatial_shapes.dim() == 2 and spatial_shapes.size(1) == 2 and
+            level_start_index.numel() == spatial_shapes.size(0))
+
+
 def box_forward_boxes_staged_ok(value, spatial_shapes, level_start_index, num_query, num_point):
     """Whether ``box_attn_forward_boxes_staged`` has its kernel under the current switches: ``boxattn_fwd_boxes_hl_ok``
     with the dimensions, element size and alignment of ``value`` (B, S, H, C), the host copies of the level tables
     ``spatial_shapes`` (L, 2) / ``level_start_index`` (L) (``_host_table``: the first call with a tensor synchronises),
     ``num_query`` queries an image and ``num_point`` points a level -- the encoder case: one query per pixel, C = 32,
     2x2 points, at most 4 levels.  The output is taken as freshly allocated (aligned).  Otherwise pure host code."""
-    if not isinstance(spatial_shapes, torch.Tensor) or not isinstance(level_start_index, torch.Tensor) or \
-            spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64 or \
-            spatial_shapes.dim() != 2 or spatial_shapes.size(1) != 2 or level_start_index.numel() != spatial_shapes.size(0):
+    if not _host_tables_ok(spatial_shapes, level_start_index):
         return False
     sh, ls = _host_table(spatial_shapes), _host_table(level_start_index)
     return _boxes_ok(lambda elem, aligned, dims: _lib.box_fwd_boxes_hl_ok(elem, aligned, dims, sh, ls), value,
@@ -1102,6 +1108,47 @@ def box_attn_backward_boxes(value, spatial_shapes, level_start_index, ref_window
                          "value and grad_output (box_backward_boxes_ok)" % (what, tuple(value.shape), L, Lq, P))
     grads = _boxes_grads(value, (B, Lq, H, L), V, (B, Lq, H, L * P), need_ref_grad)
     _boxes_call("boxattn_bwd_boxes_", operands, (D, per_head), (V, mode), (grad_output,), dims, grads)
+    return grads
+
+
+# ---------------------------------------------------------------------------------------
+# ... for the encoder case on the window-staged point-gradient kernels (opt-in; include/boxattn.h, boxattn_bwd_boxes_hl_*)
+# ---------------------------------------------------------------------------------------
+def box_backward_boxes_staged_ok(value, spatial_shapes, level_start_index, num_query, num_point, also=()):
+    """Whether ``box_attn_backward_boxes_staged`` has its kernel under the current switches: ``boxattn_bwd_boxes_hl_ok``
+    (the eligibility of ``box_forward_boxes_staged_ok``) with the dimensions, element size and alignment of ``value``
+    (B, S, H, C) and the host copies of the level tables (``_host_table``: the first call with a tensor synchronises).
+    The upstream gradient is taken as aligned like ``value``; ``box_attn_backward_boxes_staged`` asks again with its
+    address (``also``).  Otherwise pure host code."""
+    if not _host_tables_ok(spatial_shapes, level_start_index):
+        return False
+    sh, ls = _host_table(spatial_shapes), _host_table(level_start_index)
+    return _boxes_ok(lambda elem, aligned, dims: _lib.box_bwd_boxes_hl_ok(elem, aligned, dims, sh, ls), value,
+                     (spatial_shapes.size(0), num_query, num_point), also=also)
+
+
+def box_attn_backward_boxes_staged(value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices,
+                                   valid_ratios, logits, angle_mode, grad_output, need_ref_grad=False):
+    """``box_attn_backward_boxes`` -- the same operands, the same three results up to the order of the float32 sums --
+    for the encoder case (one query per pixel, C = 32, 2x2 points, at most 4 levels) on the window-staged kernels of
+    ``box_attn_backward``'s encoder route: the locations and weights are made inside them from the boxes and logits
+    (bit for bit ``box_attn_forward_boxes_staged``'s), the per-point gradients never leave the chip.  Bitwise
+    reproducible.  The level tables are also read on the host (``_host_table``).  ``grad_value`` is not computed.
+    Raises ValueError, before any device call, for arguments that do not fit and where ``boxattn_bwd_boxes_hl_ok`` says
+    no at the alignment of ``value`` and ``grad_output``: there is no other kernel behind it."""
+    what = "box_attn_backward_boxes_staged"
+    operands = (value, spatial_shapes, level_start_index, ref_windows, offsets, kernel_indices, valid_ratios, logits)
+    dims, (D, per_head, V, mode), _ = _boxes_operands(what, ValueError, None, operands, angle_mode,
+                                                      also=[(grad_output, "grad_output")])
+    B, _, H, C, L, Lq, P = dims
+    _boxes_upstream(what, ValueError, value, [("grad_output", grad_output, B * Lq * H * C)])
+    if not box_backward_boxes_staged_ok(value, spatial_shapes, level_start_index, Lq, P, also=[grad_output]):
+        raise ValueError("%s: no kernel for value %s, %d levels, %d queries, %d points a level at the alignment of "
+                         "value and grad_output (box_backward_boxes_staged_ok)" % (what, tuple(value.shape), L, Lq, P))
+    sh, ls = _host_table(spatial_shapes), _host_table(level_start_index)
+    grads = _boxes_grads(value, (B, Lq, H, L), V, (B, Lq, H, L * P), need_ref_grad)
+    _boxes_call("boxattn_bwd_boxes_hl_", operands, (D, per_head), (V, mode), (grad_output,), dims,
+                grads + (sh.ctypes.data, ls.ctypes.data))
     return grads
 
 

@@ -677,6 +677,49 @@ int boxattn_bwd_boxes_f16(const uint16_t *value, const int64_t *shapes, const in
 int boxattn_bwd_boxes_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P);
 
 /*
+ * The same step for the ENCODER case (one query per pixel, C = 32, P = 4, L <= 4) on the WINDOW-STAGED point-gradient
+ * kernels (boxattn_bwd_part_*'s encoder route: an 8x8 query tile's value windows in LDS once, a quad of lanes per
+ * (query, head) pair), with the host copies of the level tables (shapes_host / lsi_host as boxattn_fwd_boxes_hl_*; read
+ * during the call, never the device copies): the operands and outputs of boxattn_bwd_boxes_*, then the two tables.
+ * Locations are the grid kernel's and weights boxattn_fwd_boxes_hl_*'s, bit for bit; grad_loc and grad_attn stay on
+ * the chip: grad_logits = a (g - sum a g), the sum over the lane's L levels in level order, then over the quad; a
+ * level's box gradient from its four points in point order, as boxattn_grid_bwd_f32 (all three angle modes, valid
+ * ratios).  The results agree with boxattn_bwd_boxes_* up to the order of the float32 sums.
+ *   grad_logits additionally aligned to 16 bytes (a level's four values leave as one store).
+ * One window-staged kernel per storage type and no other behind these entries: dimensions for which
+ * boxattn_bwd_boxes_hl_ok answers 0 (NULL host tables among them) -- with `aligned` what value and grad_out are aligned
+ * to --, and everything boxattn_bwd_boxes_* refuses, are hipErrorInvalidValue; nothing is launched then.  The checks
+ * run in that entry's order.  No queries: nothing is written.  No riders, no state, no atomics and a fixed summation
+ * order (bitwise reproducible), no host reads beyond the two tables, no allocation: capturable, on the one stream.
+ * Profile slot 1.
+ */
+int boxattn_bwd_boxes_hl_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                             const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                             int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                             const float *logits, const float *grad_out,
+                             int B, int S, int H, int C, int L, int Lq, int P,
+                             float *grad_offsets, float *grad_ref_rows, float *grad_logits,
+                             const int64_t *shapes_host, const int64_t *lsi_host, void *stream);
+int boxattn_bwd_boxes_hl_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                              const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                              int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                              const float *logits, const uint16_t *grad_out,
+                              int B, int S, int H, int C, int L, int Lq, int P,
+                              float *grad_offsets, float *grad_ref_rows, float *grad_logits,
+                              const int64_t *shapes_host, const int64_t *lsi_host, void *stream);
+int boxattn_bwd_boxes_hl_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                             const float *ref, int ref_dim, int ref_per_head, const float *offsets, int V,
+                             int angle_mode, const float *kernel_idx, const float *valid_ratios,
+                             const float *logits, const uint16_t *grad_out,
+                             int B, int S, int H, int C, int L, int Lq, int P,
+                             float *grad_offsets, float *grad_ref_rows, float *grad_logits,
+                             const int64_t *shapes_host, const int64_t *lsi_host, void *stream);
+/* 1 where the entry points above have their kernel: exactly where boxattn_fwd_boxes_hl_ok answers 1 (the same host
+ * function), `aligned` now speaking of value and grad_out.  Pure host code: no device call. */
+int boxattn_bwd_boxes_hl_ok(int elem_bytes, int aligned, int B, int S, int H, int C, int L, int Lq, int P,
+                            const int64_t *shapes_host, const int64_t *lsi_host);
+
+/*
  * The same step with grad_value in the SAME launch: the operands of boxattn_bwd_boxes_*, then
  *   want         BOXATTN_WANT_VALUE (1), BOXATTN_WANT_POINTS (2) or both (3); anything else is hipErrorInvalidValue.
  *                POINTS alone is boxattn_bwd_boxes_* exactly: grad_value, workspace and workspace_bytes are not read.
