@@ -14,9 +14,14 @@ the rounded inputs (``reference``).
 The rules that choose the exponents of the f16 families are here too: they read the inputs and the float64 model, never
 a kernel's output.  ``wrong_box`` is box attention in numpy with three deliberate faults, the tests of these tests.
 """
+import functools
+
 import numpy as np
 
 import error_bounds as eb
+from boxes_cases import (bwd_problem, bwd_upstream, every_type, inst_problem, inst_upstream, kernel_offsets, model_of,
+                         staged_bwd_case, staged_upstream)
+from point_cases import decoder_input, encoder_input, k14_input, shape_a_input, wide_input
 
 F16_MAX = 65504.0
 F16_TIE = 65520.0            # round-to-nearest: the tie between 65504 and 2^16, the first magnitude that becomes inf
@@ -237,3 +242,111 @@ def wrong_box(inp, store, fault=None):
         res = {k: np.clip(v, -F16_MAX, F16_MAX) for k, v in res.items()}
     with np.errstate(over="ignore"):
         return {k: eb.round_to(v, store) for k, v in res.items()}
+
+
+def base_input(group, dtype):
+    if group == "encoder":
+        return encoder_input("model", dtype, 1)
+    if group == "decoder":
+        return decoder_input("model", dtype)
+    if group == "wide":
+        return wide_input(36)
+    if group == "shape_a":
+        return shape_a_input("bf16" if dtype == "f32" else dtype)
+    if group == "k14":
+        return k14_input(dtype)
+    return boxes_input(group)                  # (numbers every storage type holds: one input for the three)
+
+
+GROUPS = ("encoder", "decoder", "wide", "shape_a", "k14")
+
+
+# from boxes: the smallest geometry of each file; angle mode 0 and one rotated flavour (turns, valid ratios given)
+PLAIN, TURNS = ((0, 4), False, True), ((1, 5), False, True)
+BOXES_GROUPS = ("instance from boxes", "box from boxes, plain", "box from boxes, turns", "staged from boxes, plain",
+                "staged from boxes, turns")
+INST_CASE = ("one_level", 32, 4, False, True)               # geometry, C, k, per_head, with_vr
+BOX_GEOMETRY, STAGED_GEOMETRY = "one_level", "tiny_levels"
+
+
+def boxes_problem(group):
+    """-> (the problem of the file the group comes from, its float64 upstream gradients)."""
+    flavour = TURNS if group.endswith("turns") else PLAIN
+    if group.startswith("instance"):
+        p = inst_problem(*INST_CASE)
+        return p, inst_upstream(p, INST_CASE[2])
+    if group.startswith("box"):
+        p = bwd_problem(BOX_GEOMETRY, 32, flavour)
+        return p, (bwd_upstream(p),)
+    p = staged_bwd_case(STAGED_GEOMETRY, "local", *flavour[0], *flavour[1:])
+    return p, (staged_upstream(p),)
+
+
+@functools.lru_cache(maxsize=None)
+def boxes_input(group):
+    p, ups = boxes_problem(group)
+    return dict(zip(UPSTREAM, ups), kind="boxes", group=group, value=every_type(p["value"]))
+
+
+def boxes_model(inp):
+    """The float64 model of a from-boxes input (the files' own: error_bounds.boxes_reference; grad_value of the box
+    step by boxes_cases.model_of), once per input."""
+    if "_ref" not in inp:
+        p, _ = boxes_problem(inp["group"])
+        P = p["dims"][6] if len(p["dims"]) > 6 else INST_CASE[2] ** 2
+        common = (inp["value"], p["shapes"], p["lsi"], p["ref"], p["off"], kernel_offsets(int(round(P ** 0.5))),
+                  p["vr"], p["logits"])
+        if inp["group"].startswith("instance"):
+            ref = eb.boxes_reference("instance", *common, 0, INST_CASE[2], inp["grad_out"], inp["grad_mask"])
+        else:
+            ref = eb.boxes_reference("box", *common, p["angle_mode"], grad_out=inp["grad_out"])
+            if inp["group"].startswith("box"):
+                ref["grad_value"] = model_of(p, inp["grad_out"])         # (grad_value does not read ``value``)
+        inp["_ref"] = {k: v for k, v in ref.items() if k not in ("points", "grid", "weights")}
+    return inp["_ref"]
+
+
+def reference_of(inp):
+    return boxes_model(inp) if inp["kind"] == "boxes" else eb.reference_of(inp)
+
+
+@functools.lru_cache(maxsize=None)
+def f16_exponents(group):
+    """-> ((a, b) of f16 high, (a, b) of f16 low)."""
+    inp = base_input(group, "f16")
+    return high_exponents(inp, reference_of), low_exponents(inp)
+
+
+@functools.lru_cache(maxsize=None)
+def f16_reference(group, a, b):
+    """-> (the inputs at (a, b) rounded to f16, their reference)."""
+    return reference(base_input(group, "f16"), a, b, "f16", reference_of)
+
+
+@functools.lru_cache(maxsize=None)
+def overflow_problem():
+    """-> (b, the one-pixel encoder input with |grad_out| 2^b, its reference)."""
+    inp = overflow_input(scaled(encoder_input("model", "f16", 1), 0, 0, "f16"))
+    b = overflow_exponent(inp)
+    s, ref = reference(inp, 0, b, "f16")
+    return b, s, ref
+
+
+VALUE_OVERFLOW = ("encoder", 32, PLAIN)          # geometry, C, flavour of boxes_cases.bwd_problem
+
+
+@functools.lru_cache(maxsize=None)
+def value_overflow_problem():
+    """-> (b, the problem, |upstream| 2^b, grad_value's reference): the box step from boxes with every reference window
+    shrunk onto one spot (centre 0.02 + 0.4, size 0.02: the construction of dynamic_range.overflow_input, on the windows)
+    and an upstream gradient of one sign -- the weights are a softmax, so every term of grad_value is positive and the 80
+    queries add into the same four pixels a level.  (The files' own problems never get there: their largest sums stay
+    finite at every exponent the upstream gradient itself survives.)"""
+    p = dict(bwd_problem(*VALUE_OVERFLOW))
+    ref = p["ref"].copy()
+    ref[..., :4] = ref[..., :4] * np.float32(0.02) + np.asarray([0.4, 0.4, 0.0, 0.0], dtype=np.float32)
+    p["ref"] = ref
+    gout = np.abs(bwd_upstream(p))
+    base = model_of(p, gout)
+    b = overflow_exponent(dict(grad_out=gout), ref=dict(grad_value=base), split="none")
+    return b, p, np.ldexp(gout, b), scaled_reference(dict(grad_value=base), 0, b)["grad_value"]

@@ -115,8 +115,8 @@ same reductions on exact float32 upstream gradients (want = g, A = |g|, E = 0, n
 import numpy as np
 import torch
 
-EDGE_PX = 1e-4          # grad_loc: points this close to a bilinear cell edge are left out (tests/test_gpu_parity.on_cell_edge)
-EDGE_CAP = 2e-3         # ... and may be at most this share of a case's points (tests/test_gpu_boxes_backward.EDGE_CAP)
+EDGE_PX = 1e-4          # grad_loc: points this close to a bilinear cell edge are left out (tests/point_cases.on_cell_edge)
+EDGE_CAP = 2e-3         # ... and may be at most this share of a case's points (tests/boxes_cases.EDGE_CAP)
 
 # stored type -> (u, t): one round-to-nearest-even; f16's t is half the subnormal spacing 2^-24
 STORE = {"float32": (2.0 ** -24, 0.0), "bf16": (2.0 ** -8, 0.0), "f16": (2.0 ** -11, 2.0 ** -25)}
@@ -492,8 +492,8 @@ def hold_all(got, refs, dtype, split="none", what="", splits=None, table=None):
 
 # ------------------------------------------------------------------ inputs, generated on the CPU (the same on every machine)
 def make(levels, lq, family="model", dtype=torch.bfloat16, B=2, H=2, C=32, seed=0, kind="box", P=4):
-    """bench.make_inputs for an ad-hoc shape on the CPU (tests/test_gpu_group_records.make); family "border": uniform
-    locations in [-0.2, 1.2] (tests/test_gpu_dense.make_case)."""
+    """bench.make_inputs for an ad-hoc shape on the CPU (tests/point_cases.make); family "border": uniform
+    locations in [-0.2, 1.2] (tests/point_cases.make_dense_case)."""
     import bench
     name = "_error_bounds_test"
     bench.WORKLOADS[name] = (list(levels), lq, P, kind)

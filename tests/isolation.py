@@ -468,3 +468,15 @@ def input_arena(t, align=16):
 def guards_intact(a):
     """Every guard byte of the arena still holds what it was filled with."""
     return all(bool((g == a.byte).all().item()) for g in a.guards())
+
+
+ENCODER = [(13, 13), (7, 5)]
+DECODER = [(20, 30), (10, 15), (5, 8), (3, 4)]
+WIDE_LEVELS = [(11, 9), (6, 5), (3, 2)]
+
+STAGED_LEVELS = [(37, 23), (19, 12), (10, 6), (5, 3)]
+
+
+BOX_FLAVOURS = [(0, 4), (1, 5), (1, 7), (2, 5)]                  # angle mode, values a reference window
+STAGED_GEOMETRY = {"four_levels": (STAGED_LEVELS, 2, 3), "one_level": ([(9, 13)], 2, 1),
+                   "tiny_levels": ([(4, 5), (2, 3), (1, 1)], 1, 2)}

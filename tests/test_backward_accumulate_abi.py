@@ -3,14 +3,12 @@ include/boxattn.h, exported by the built library and bound by the ctypes loader;
 exists; the route table: box attention (both storage widths, the float32 switch 19), instance attention in float32
 and -- the new route -- in 16-bit storage under key 23.  The query is pure host code: there is no GPU here."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
+from capi_cases import C2, C2P, HEADER
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
 
 VALU, TR, F32, SPLIT = range(4)
 # What the measurement decided for 16-bit instance attention under key 23 = 0 (profiles/instance_accumulate16_step.log,
@@ -20,8 +18,6 @@ DEFAULT_INST16 = {"C3": VALU, "C3p": TR}
 OPT_INST_ACC16, OPT_ACC_F32 = 23, 19
 INST16_VALU, INST16_TR = 1, 2
 
-C2P = [(100, 167), (50, 84), (25, 42), (13, 21)]
-C2 = [(100, 100), (50, 50), (25, 25), (13, 13)]
 # instance workloads: levels, Lq, P
 INST = {"C3": (C2, 300, 16), "C3p": (C2P, 300, 196)}
 

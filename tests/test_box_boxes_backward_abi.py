@@ -5,23 +5,12 @@ reference window or offsets that do not fit the angle mode, and NULL required po
 before any device call, and ``BoxAttnBoxesFunction`` is part of the package.  No compute calls: there is no GPU here."""
 import ctypes
 import itertools
-import os
 import re
 
 import pytest
+from capi_cases import BOX_GEOMETRIES as GEOMETRIES, HEADER, INVALID_VALUE, declarations
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
 ENTRY_POINTS = ["boxattn_bwd_boxes_" + suf for suf in ("f32", "bf16", "f16")]
-INVALID_VALUE = 1                        # hipErrorInvalidValue
-# (levels, B, Lq, H): a decoder-like and an encoder-like (one query a pixel) geometry
-GEOMETRIES = [([(9, 11), (4, 5), (3, 3), (2, 2)], 2, 5, 8), ([(6, 5)], 1, 30, 2)]
-
-
-def declarations():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return {m.group(1): " ".join(m.group(2).split())
-            for m in re.finditer(r"\b((?:boxattn|instattn)_\w+)\s*\(([^;{]*?)\)\s*;", text, re.S)}
 
 
 @pytest.fixture(scope="module")

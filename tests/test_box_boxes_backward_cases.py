@@ -7,7 +7,7 @@
     float64 against float64.
 (b) The inputs of the GPU matrix keep the cell-edge condition: at most 0.2 % of a case's sample points lie within
     1e-4 px of a bilinear cell edge, where grad_loc is ambiguous and the expectation has to take the chain's value.
-    18 of the 336 cases from the seeds of test_gpu_box_boxes_forward.problem break it (by 1-4 points of 384-1 280: a box
+    18 of the 336 cases from the seeds of boxes_cases.box_boxes_problem break it (by 1-4 points of 384-1 280: a box
     of size <= 0 puts a whole row of points on one line; the worst, k4 C = 64 mode 0 per head without valid ratios, has
     1.04 %); they take another seed (RESEED).  The grid is evaluated in float32 numpy, operation by operation as the
     kernels do."""
@@ -17,9 +17,10 @@ import torch
 
 from oracle import boxattn_oracle as oc
 from oracle import torch_fallback
-from test_gpu_box_boxes_backward import (CHANNELS, EDGE_CAP, FLAVOURS, RESEED, SMALL, case, edge_share, problem,
-                                         reduce_grid, reduce_logits)
-from test_gpu_parity import _torch_grid
+from boxes_cases import (BOX_BWD_CHANNELS as CHANNELS, BOX_BWD_RESEED as RESEED, EDGE_CAP, FLAVOURS, SMALL,
+                         box_boxes_problem as problem, box_bwd_case as case, box_edge_share as edge_share,
+                         box_reduce_grid as reduce_grid, box_reduce_logits as reduce_logits)
+from point_cases import _torch_grid
 
 
 def autograd_and_reductions(g):

@@ -8,16 +8,13 @@ import ctypes
 import itertools
 import re
 
-import numpy as np
 import pytest
 
-from test_box_boxes_forward_abi import HEADER, INVALID_VALUE, declarations
+from capi_cases import HEADER, INVALID_VALUE, STAGED_GEOMETRIES as GEOMETRIES, declarations, host_tables
 
 ENTRY_POINTS = ["boxattn_fwd_boxes_hl_" + suf for suf in ("f32", "bf16", "f16")]
 QUERY = "boxattn_fwd_boxes_hl_ok"
 STAGED = 4
-# (levels, B, H): one query a pixel in all of them (Lq is varied below)
-GEOMETRIES = list(itertools.product([[(9, 11), (4, 5), (3, 3), (2, 2)], [(6, 5)], [(37, 23), (19, 12)]], (1, 2), (1, 3, 8)))
 
 
 @pytest.fixture(scope="module")
@@ -27,15 +24,6 @@ def lib():
     _lib.set_variant(0)
     yield _lib
     _lib.set_variant(0)
-
-
-def host_tables(levels, L=None, broken=False):
-    """int64 (L, 2) shapes and (L) start indices of the first L levels (cycled if there are fewer), and S; broken: an S
-    one above the sum of the tables' sizes."""
-    L = len(levels) if L is None else L
-    shapes = np.asarray([levels[i % len(levels)] for i in range(L)], dtype=np.int64)
-    sizes = shapes.prod(1)
-    return shapes, np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64), int(sizes.sum()) + (1 if broken else 0)
 
 
 def test_header_declares_the_four_names_and_the_bindings_know_them(lib):

@@ -1,6 +1,6 @@
 """CPU: the window-staged backward from boxes and L*P logits at the C ABI -- boxattn_bwd_boxes_hl_{f32, bf16, f16} and
 the eligibility query boxattn_bwd_boxes_hl_ok are declared in include/boxattn.h, exported and bound with the header's
-parameter counts, the query equals boxattn_fwd_boxes_hl_ok over the dimension table of test_box_boxes_staged_abi.py, and
+parameter counts, the query equals boxattn_fwd_boxes_hl_ok over the dimension table capi_cases.STAGED_GEOMETRIES, and
 the entry points refuse, with hipErrorInvalidValue before any device call, NULL host tables, Lq != S, C = 64, P = 9,
 L = 5, an unaligned grad_out, a NULL among the required pointers and V / ref_dim that do not fit the angle mode.  No
 compute calls: there is no GPU here."""
@@ -11,8 +11,7 @@ import re
 
 import pytest
 
-from test_box_boxes_forward_abi import HEADER, INVALID_VALUE, declarations
-from test_box_boxes_staged_abi import GEOMETRIES, host_tables
+from capi_cases import HEADER, INVALID_VALUE, STAGED_GEOMETRIES as GEOMETRIES, declarations, host_tables
 
 ENTRY_POINTS = ["boxattn_bwd_boxes_hl_" + suf for suf in ("f32", "bf16", "f16")]
 QUERY = "boxattn_bwd_boxes_hl_ok"

@@ -2,42 +2,18 @@
 point crosses a bilinear cell edge, so a box gradient that sums such a point cannot be held to a bound; the GPU matrix
 therefore asks of its INPUTS that the share of sample points within 1e-4 px of a cell edge is at most
 error_bounds.EDGE_CAP (0.2 %) -- a condition on inputs, not a tolerance.  The inputs are
-test_gpu_box_boxes_staged_forward.problem's; four of them are over the cap (two points each) and are built from another
+boxes_cases.staged_problem's; four of them are over the cap (two points each) and are built from another
 seed (RESEED, as tests/test_gpu_box_boxes_backward.py does).  This file proves the cap for every case the GPU file
-uses, with the float32 grid of test_boxes_error_bounds.grid_f32 and test_gpu_parity.on_cell_edge, and that the four
+uses, with the float32 grid of boxes_cases.grid_f32 and point_cases.on_cell_edge, and that the four
 are the only ones that needed it."""
-import functools
 
 import numpy as np
 import pytest
 
 import error_bounds as eb
-from test_boxes_error_bounds import grid_f32
-from test_gpu_box_boxes_staged_forward import FAMILIES, flavours_of, problem
-from test_gpu_boxes_error_bounds import kernel_offsets
-from test_gpu_parity import on_cell_edge
-
-MATRIX = ["two_levels", "four_levels", "three_levels", "one_level", "tiny_levels"]
-# (geometry, family, angle_mode, ref_dim, per_head, with_vr) -> what is added to problem's seed
-RESEED = {("one_level", "local", 1, 5, True, False): 1000003,        # 0.214 % from problem's own seed
-          ("one_level", "scattered", 1, 7, False, False): 1000003,   # 0.214 %
-          ("tiny_levels", "local", 0, 4, True, True): 1000003,       # 0.309 %
-          ("tiny_levels", "scattered", 1, 5, True, True): 1000003}   # 0.309 %
-
-
-@functools.lru_cache(maxsize=None)
-def case(geometry, family, angle_mode, ref_dim, per_head, with_vr):
-    """test_gpu_box_boxes_staged_forward.problem, from another seed for the keys of RESEED."""
-    key = (geometry, family, angle_mode, ref_dim, per_head, with_vr)
-    bump = RESEED.get(key)
-    if bump is None:
-        return problem(*key)
-    make = np.random.default_rng
-    np.random.default_rng = lambda seed: make(seed + bump)           # (problem() seeds its generator from its arguments)
-    try:
-        return problem.__wrapped__(*key)
-    finally:
-        np.random.default_rng = make
+from boxes_cases import (FAMILIES, MATRIX, STAGED_BWD_RESEED as RESEED, flavours_of, grid_f32, kernel_offsets,
+                         staged_bwd_case as case, staged_problem as problem)
+from point_cases import on_cell_edge
 
 
 def edge_share(g):

@@ -12,7 +12,7 @@ import re
 
 import pytest
 
-from test_box_boxes_backward_abi import GEOMETRIES, HEADER, INVALID_VALUE, declarations
+from capi_cases import BOX_GEOMETRIES as GEOMETRIES, HEADER, INVALID_VALUE, call_value as call, declarations
 
 SUFFIXES = ("f32", "bf16", "f16")
 ENTRY_POINTS = ["boxattn_bwd_boxes_value_" + suf for suf in SUFFIXES]
@@ -88,14 +88,6 @@ def test_workspace_query(lib):
         assert lib.box_bwd_boxes_value_workspace_bytes(2, dims) == 4 * B * S * H * C
         assert getattr(lib.load(), WS)(2, B, S, H, C) == 4 * B * S * H * C
     assert getattr(lib.load(), WS)(2, 16, 1 << 20, 8, 64) == 4 * 16 * (1 << 20) * 8 * 64      # beyond 32 bits
-
-
-def call(lib, name, ptrs, dims, want, gv, ws, ws_bytes, ref_dim=4, V=4, angle_mode=0):
-    """An entry call with fake (never dereferenced) pointers; ptrs: value, shapes, lsi, ref, offsets, kernel_idx,
-    valid_ratios, logits, grad_out, grad_offsets, grad_ref_rows, grad_logits."""
-    v, sh, ls, ref, off, kid, vr, lg, go, goff, grow, glog = ptrs
-    return getattr(lib.load(), name)(v, sh, ls, ref, ref_dim, 0, off, V, angle_mode, kid, vr, lg, go, *dims, want, gv,
-                                     ws, ws_bytes, goff, grow, glog, None)
 
 
 @pytest.mark.parametrize("want", [1, 2, 3])

@@ -3,63 +3,37 @@
 ``value_reference`` is grad_value's float64 model from boxes and logits: ``error_bounds.grid_reference``,
 ``softmax_reference`` and ``_reference(..., slack=dloc, dws=[dw])["grad_value"]`` -- exactly the arguments
 ``boxes_reference(kind="box")`` passes; it computes this plane too and discards it.  The problems are those of
-``test_gpu_boxes_error_bounds.bwd_problem`` with upstream ``bwd_upstream`` and value ``every_type(value)`` (imported, not
-copied).  tests/test_gpu_box_boxes_value.py holds the kernel to the same planes.
+``boxes_cases.bwd_problem`` with upstream ``bwd_upstream`` and value ``every_type(value)`` (the GPU file's
+own).  tests/test_gpu_box_boxes_value.py holds the kernel to the same planes.
 
-Here: a float32 evaluation on the CPU -- ``test_boxes_error_bounds.grid_f32``, a float32 torch softmax, the C oracle's
+Here: a float32 evaluation on the CPU -- ``boxes_cases.grid_f32``, a float32 torch softmax, the C oracle's
 float32 ``box_attn_backward`` -- holds the bound (``error_bounds.hold``, split "none") in float32 and rounded to bf16 and
 f16, over all 16 flavours of seven cases; the same result scaled by 1 + 2^-12 does not hold it in float32.  grad_value
 has no cell-edge ambiguity: no exclusion and no cap.  Elements whose bound is 0 (pixels no point touches) must be
 exactly zero; their share is printed per case."""
-import functools
 
 import numpy as np
 import pytest
 import torch
 
 import error_bounds as eb
-import test_gpu_boxes_error_bounds as gpu_cases
+import boxes_cases
+from boxes_cases import c32, grid_f32, value_reference
+from compare_rules import must_be_zero_share
 from oracle import boxattn_oracle as oc
-from test_boxes_error_bounds import c32, grid_f32
 
 CASES = [("model", 32), ("ragged", 16), ("k4", 32), ("sixteen_levels", 64), ("encoder", 32), ("odd_k", 32),
          ("one_level", 16)]
 
 
-def model_of(g, gout):
-    """grad_value's planes (want / A / E / n / G / W, (B, S, H, C)) for the problem ``g`` (keys of
-    test_gpu_box_boxes_forward.problem) and the upstream gradient ``gout`` (B, Lq, H * C)."""
-    value = eb.f64(gpu_cases.every_type(g["value"]))
-    B, S, H, C = value.shape
-    P = g["dims"][6]
-    loc, dloc = eb.grid_reference(g["ref"], g["off"], gpu_cases.kernel_offsets(int(round(P ** 0.5))), g["vr"],
-                                  g["angle_mode"])
-    Lq, L = loc.shape[1], loc.shape[3]
-    w, dw = eb.softmax_reference(g["logits"])
-    r = eb._reference(value, eb.f64(g["shapes"]).astype(np.int64), eb.f64(g["lsi"]).astype(np.int64), loc,
-                      [w.reshape(B, Lq, H, L, P)], [eb.f64(gout).reshape(B, Lq, H, C)], False, slack=dloc,
-                      dws=[dw.reshape(B, Lq, H, L, P)])
-    return r["grad_value"]
-
-
-@functools.lru_cache(maxsize=16)
-def value_reference(geometry, C, flavour):
-    g = gpu_cases.bwd_problem(geometry, C, flavour)
-    return model_of(g, gpu_cases.bwd_upstream(g))
-
-
-def must_be_zero_share(ref):
-    return float(((ref["A"] + ref["E"]) == 0).mean())
-
-
 def value_f32(g, gout):
     """grad_value in float32 on the CPU: float32 grid, float32 torch softmax, the C oracle's float32 build."""
     B, S, H, C, L, Lq, P = g["dims"]
-    kidx = gpu_cases.kernel_offsets(int(round(P ** 0.5)))
+    kidx = boxes_cases.kernel_offsets(int(round(P ** 0.5)))
     loc = c32(grid_f32(g["ref"], g["off"], kidx, g["vr"], g["angle_mode"]))
     logits = torch.from_numpy(c32(g["logits"])).reshape(B, Lq, H, L * P)
     attn = c32(torch.softmax(logits, -1).numpy().reshape(B, Lq, H, L, P))
-    gval, _, _ = oc.box_attn_backward(c32(gpu_cases.every_type(g["value"])), g["shapes"], g["lsi"], loc, attn, c32(gout))
+    gval, _, _ = oc.box_attn_backward(c32(boxes_cases.every_type(g["value"])), g["shapes"], g["lsi"], loc, attn, c32(gout))
     gval = np.asarray(gval).reshape(B, S, H, C)
     assert gval.dtype == np.float32
     return gval
@@ -69,10 +43,10 @@ def value_f32(g, gout):
 def test_float32_evaluation_holds_the_bound_and_a_scaled_one_does_not(geometry, C):
     worst = {"float32": 0.0, "bf16": 0.0, "f16": 0.0}
     shares, outside = [], []
-    for flavour in gpu_cases.box_cases.FLAVOURS:
-        g = gpu_cases.bwd_problem(geometry, C, flavour)
+    for flavour in boxes_cases.FLAVOURS:
+        g = boxes_cases.bwd_problem(geometry, C, flavour)
         ref = value_reference(geometry, C, flavour)
-        got = value_f32(g, gpu_cases.bwd_upstream(g))
+        got = value_f32(g, boxes_cases.bwd_upstream(g))
         what = "float32 grad_value on the CPU: %s C=%d angle=%d D=%d per_head=%d vr=%d" % ((geometry, C) + flavour[0]
                                                                                          + flavour[1:])
         assert got.shape == ref["want"].shape

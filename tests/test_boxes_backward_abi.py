@@ -9,7 +9,7 @@ import re
 
 import pytest
 
-from test_boxes_forward_abi import GEOMETRIES, HEADER, INVALID_VALUE, declarations
+from capi_cases import HEADER, INST_GEOMETRIES as GEOMETRIES, INVALID_VALUE, declarations
 
 ENTRY_POINTS = ["instattn_bwd_boxes_" + suf for suf in ("f32", "bf16", "f16")]
 OK = "instattn_bwd_boxes_ok"

@@ -7,7 +7,8 @@ import itertools
 
 import pytest
 
-from test_gpu_boxes_backward import EDGE_CAP, GEOMETRY, KERNEL_SIZES, case, edge_share
+from boxes_cases import (EDGE_CAP, INST_GEOMETRY as GEOMETRY, KERNEL_SIZES, inst_bwd_case as case,
+                         inst_edge_share as edge_share)
 
 
 @pytest.mark.parametrize("geometry", sorted(GEOMETRY))

@@ -15,7 +15,7 @@ The box kind's training step (grad_offsets, grad_ref_rows, grad_logits in the th
     flavours on two geometries, within a tolerance made of float64's unit roundoff and the model's own planes;
   * the float32 chain on the CPU -- ``reduce_box_f32``: the reduction in the kernels' operation order -- stays within
     the bound for every case of the GPU matrix, every case keeps the cell-edge condition with the locations' own slack
-    (one case re-seeded: test_gpu_boxes_error_bounds.BWD_RESEED), and every geometry has must-be-zero elements in all
+    (one case re-seeded: boxes_cases.BWD_RESEED), and every geometry has must-be-zero elements in all
     three outputs; the backward building blocks restated in float32 numpy stay within theirs;
   * six wrong formulas (relu' omitted, a sine term's sign, a_t without the relu, the / 16, a partial softmax-Jacobian
     sum, a dropped gw) are all rejected by the bound; wrong everywhere, today's rule of
@@ -29,40 +29,19 @@ import pytest
 import torch
 
 import error_bounds as eb
-import test_gpu_boxes_error_bounds as gpu_cases
+import boxes_cases
+import compare_rules
+from boxes_cases import F, c32, grid_f32
+from compare_rules import POINT_TOL, check_scaled as check
+from point_cases import _torch_grid
 from oracle import boxattn_oracle as oc
-from test_gpu_parity import _torch_grid
-from test_gpu_wide_box_forward import check
 
-F = np.float32
-BOX_CASES = list(itertools.product(gpu_cases.BOX_GEOMETRIES, gpu_cases.CHANNELS, gpu_cases.box_cases.FLAVOURS))
-INST_GEOMETRIES = sorted(gpu_cases.inst_cases.GEOMETRY)
-KERNEL_SIZES = gpu_cases.inst_cases.KERNEL_SIZES
+BOX_CASES = list(itertools.product(boxes_cases.BOX_GEOMETRIES, boxes_cases.CHANNELS, boxes_cases.FLAVOURS))
+INST_GEOMETRIES = sorted(boxes_cases.INST_GEOMETRY)
+KERNEL_SIZES = boxes_cases.KERNEL_SIZES
 
 
 # ------------------------------------------------------------------ float32 numpy, operation by operation
-def grid_f32(ref, off, kidx, vr, angle_mode):
-    """_where_to_attend in float32 numpy in the documented order: every operation rounds once, no
-    fused multiply-add."""
-    r = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]
-    lead = off.shape[:4]
-    col = lambda j: np.broadcast_to(r[..., j], lead)
-    cx = col(0) + off[..., 0] / F(8) * col(2)
-    cy = col(1) + off[..., 1] / F(8) * col(3)
-    w = col(2) + off[..., 2] / F(8) * col(2)
-    h = col(3) + off[..., 3] / F(8) * col(3)
-    lx = kidx[:, 0] * np.maximum(w, F(0))[..., None]
-    ly = kidx[:, 1] * np.maximum(h, F(0))[..., None]
-    if angle_mode:
-        theta = (col(4) + off[..., 4] / F(16)) * F(2) * F(math.pi) if angle_mode == 1 else col(4)
-        sn, cs = np.sin(theta.astype(F))[..., None], np.cos(theta.astype(F))[..., None]
-        gx = cx[..., None] + (lx * cs - ly * sn)
-        gy = cy[..., None] + (lx * sn + ly * cs)
-    else:
-        gx, gy = cx[..., None] + lx, cy[..., None] + ly
-    grid = np.stack([gx, gy], -1)
-    assert grid.dtype == F
-    return grid * vr if vr is not None else grid
 
 
 def softmax_f32(z, axes=(-1,), first=None):
@@ -86,7 +65,7 @@ def instance_weights_f32(logits, k):
 def reduce_f32(g, k, gloc, gs, gl):
     """The three gradients from float32 per-point gradients, float32 numpy: d grid / d box with relu' and the softmax
     Jacobians of the 2 x 2 logits, from their definitions."""
-    ref, off, kidx, vr = g["ref"], g["off"], gpu_cases.kernel_offsets(k), g["vr"]
+    ref, off, kidx, vr = g["ref"], g["off"], boxes_cases.kernel_offsets(k), g["vr"]
     lead = off.shape[:4]
     r = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]
     col = lambda j: np.broadcast_to(r[..., j], lead)
@@ -114,14 +93,11 @@ def reduce_f32(g, k, gloc, gs, gl):
     return goff, rows, glog
 
 
-c32 = lambda a: np.ascontiguousarray(a, dtype=F)
-
-
 # ------------------------------------------------------------------ the grid
-@pytest.mark.parametrize("P", gpu_cases.GRID_POINTS)
+@pytest.mark.parametrize("P", boxes_cases.GRID_POINTS)
 def test_float64_grid_agrees_with_the_reference_module_in_double(P):
-    for angle_mode, per_head, with_vr in gpu_cases.GRID_FLAVOURS:
-        g = gpu_cases.grid_problem(P, angle_mode, per_head, with_vr)
+    for angle_mode, per_head, with_vr in boxes_cases.GRID_FLAVOURS:
+        g = boxes_cases.grid_problem(P, angle_mode, per_head, with_vr)
         t = lambda a: None if a is None else torch.from_numpy(a).double()
         want = _torch_grid(t(g["ref"]), t(g["off"]), t(g["kidx"]), t(g["vr"]), angle_mode).numpy()
         loc, dloc = eb.grid_reference(g["ref"], g["off"], g["kidx"], g["vr"], angle_mode)
@@ -131,19 +107,19 @@ def test_float64_grid_agrees_with_the_reference_module_in_double(P):
 
 def grid_inputs():
     """(name, ref, off, kidx, vr, angle_mode) of every input of the GPU file."""
-    for P, (angle_mode, per_head, with_vr) in itertools.product(gpu_cases.GRID_POINTS, gpu_cases.GRID_FLAVOURS):
-        g = gpu_cases.grid_problem(P, angle_mode, per_head, with_vr)
+    for P, (angle_mode, per_head, with_vr) in itertools.product(boxes_cases.GRID_POINTS, boxes_cases.GRID_FLAVOURS):
+        g = boxes_cases.grid_problem(P, angle_mode, per_head, with_vr)
         yield ("grid P=%d %s" % (P, (angle_mode, per_head, with_vr)), g["ref"], g["off"], g["kidx"], g["vr"], angle_mode)
     for geometry, C, flavour in BOX_CASES:
-        g = gpu_cases.box_problem(geometry, C, flavour)
+        g = boxes_cases.box_problem(geometry, C, flavour)
         k = int(round(g["dims"][6] ** 0.5))
-        yield ("box %s C=%d %s" % (geometry, C, flavour), g["ref"], g["off"], gpu_cases.kernel_offsets(k), g["vr"],
+        yield ("box %s C=%d %s" % (geometry, C, flavour), g["ref"], g["off"], boxes_cases.kernel_offsets(k), g["vr"],
                g["angle_mode"])
-    for geometry, C, k, (per_head, with_vr) in itertools.product(INST_GEOMETRIES, gpu_cases.CHANNELS, KERNEL_SIZES,
-                                                                 gpu_cases.INST_FLAVOURS):
-        g = gpu_cases.inst_problem(geometry, C, k, per_head, with_vr)
+    for geometry, C, k, (per_head, with_vr) in itertools.product(INST_GEOMETRIES, boxes_cases.CHANNELS, KERNEL_SIZES,
+                                                                 boxes_cases.INST_FLAVOURS):
+        g = boxes_cases.inst_problem(geometry, C, k, per_head, with_vr)
         yield ("instance %s C=%d k=%d %s" % (geometry, C, k, (per_head, with_vr)), g["ref"], g["off"],
-               gpu_cases.kernel_offsets(k), g["vr"], 0)
+               boxes_cases.kernel_offsets(k), g["vr"], 0)
 
 
 def test_float32_grid_stays_within_dloc_at_every_point_of_every_case():
@@ -152,7 +128,7 @@ def test_float32_grid_stays_within_dloc_at_every_point_of_every_case():
     for name, ref, off, kidx, vr, angle_mode in grid_inputs():
         loc, dloc = eb.grid_reference(ref, off, kidx, vr, angle_mode)
         got = grid_f32(ref, off, kidx, vr, angle_mode)
-        worst[angle_mode] = max(worst[angle_mode], gpu_cases.within(got, loc, dloc, name))
+        worst[angle_mode] = max(worst[angle_mode], compare_rules.within(got, loc, dloc, name))
         if angle_mode:
             turns = max(turns, float(np.abs(ref[..., 4]).max()) / (1.0 if angle_mode == 1 else 2 * math.pi))
     assert turns >= 3.0, "no angle of several turns among the cases"
@@ -161,24 +137,24 @@ def test_float32_grid_stays_within_dloc_at_every_point_of_every_case():
 
 def test_float32_weights_stay_within_dw():
     worst = {"softmax": 0.0, "spatial": 0.0, "level": 0.0}
-    rows = [gpu_cases.softmax_rows(n) for n in (1, 4, 12, 18, 64)]
-    rows += [gpu_cases.box_problem(*c)["logits"] for c in BOX_CASES]
+    rows = [boxes_cases.softmax_rows(n) for n in (1, 4, 12, 18, 64)]
+    rows += [boxes_cases.box_problem(*c)["logits"] for c in BOX_CASES]
     for z in rows:
         want, dw = eb.softmax_reference(z)
-        worst["softmax"] = max(worst["softmax"], gpu_cases.within(softmax_f32(z), want, dw * want, "softmax"))
-    cells = [(gpu_cases.cell_rows(L), k) for L in (1, 5, 16) for k in KERNEL_SIZES]
-    cells += [(gpu_cases.inst_problem(geo, C, k, ph, vr)["logits"], k) for geo, C, k, (ph, vr) in
-              itertools.product(INST_GEOMETRIES, gpu_cases.CHANNELS, KERNEL_SIZES, gpu_cases.INST_FLAVOURS)]
+        worst["softmax"] = max(worst["softmax"], compare_rules.within(softmax_f32(z), want, dw * want, "softmax"))
+    cells = [(boxes_cases.cell_rows(L), k) for L in (1, 5, 16) for k in KERNEL_SIZES]
+    cells += [(boxes_cases.inst_problem(geo, C, k, ph, vr)["logits"], k) for geo, C, k, (ph, vr) in
+              itertools.product(INST_GEOMETRIES, boxes_cases.CHANNELS, KERNEL_SIZES, boxes_cases.INST_FLAVOURS)]
     for z, k in cells:
         sw, lw, dsw, dlw = eb.instance_weights_reference(z, k, True)
         got_s, got_l = instance_weights_f32(z, k)
-        worst["spatial"] = max(worst["spatial"], gpu_cases.within(got_s, sw, dsw * sw, "spatial weights"))
-        worst["level"] = max(worst["level"], gpu_cases.within(got_l, lw, dlw * lw, "level weights"))
+        worst["spatial"] = max(worst["spatial"], compare_rules.within(got_s, sw, dsw * sw, "spatial weights"))
+        worst["level"] = max(worst["level"], compare_rules.within(got_l, lw, dlw * lw, "level weights"))
     print("float32 numpy weights, worst err / dw: %s" % ", ".join("%s %.3f" % kv for kv in worst.items()))
 
 
 def test_weights_of_a_row_sum_to_one_and_expand_row_major():
-    z = gpu_cases.cell_rows(5)
+    z = boxes_cases.cell_rows(5)
     sw, lw, _, _ = eb.instance_weights_reference(z, 6, True)
     assert np.abs(sw.sum((-1, -2)) - 1).max() < 1e-14 and np.abs(lw.sum(-2) - 1).max() < 1e-14
     # point (y, x) of a 6 x 6 kernel lies in cell (y >= 3, x >= 3); the reference module repeats along both axes
@@ -190,17 +166,17 @@ def test_weights_of_a_row_sum_to_one_and_expand_row_major():
 
 
 # ------------------------------------------------------------------ the whole chain in float32 on the CPU
-@pytest.mark.parametrize("geometry", gpu_cases.BOX_GEOMETRIES)
+@pytest.mark.parametrize("geometry", boxes_cases.BOX_GEOMETRIES)
 def test_box_chain_in_float32_is_within_the_bound(geometry):
     worst, zeros = 0.0, 0
-    for C, flavour in itertools.product(gpu_cases.CHANNELS, gpu_cases.box_cases.FLAVOURS):
-        g = gpu_cases.box_problem(geometry, C, flavour)
+    for C, flavour in itertools.product(boxes_cases.CHANNELS, boxes_cases.FLAVOURS):
+        g = boxes_cases.box_problem(geometry, C, flavour)
         B, S, H, _, L, Lq, P = g["dims"]
-        ref = gpu_cases.box_reference(geometry, C, flavour)["out"]
-        kidx = gpu_cases.kernel_offsets(int(round(P ** 0.5)))
+        ref = boxes_cases.box_reference(geometry, C, flavour)["out"]
+        kidx = boxes_cases.kernel_offsets(int(round(P ** 0.5)))
         loc = grid_f32(g["ref"], g["off"], kidx, g["vr"], g["angle_mode"])
         attn = softmax_f32(g["logits"]).reshape(B, Lq, H, L, P)
-        out = oc.box_attn_forward(c32(gpu_cases.every_type(g["value"])), g["shapes"], g["lsi"], c32(loc), c32(attn))
+        out = oc.box_attn_forward(c32(boxes_cases.every_type(g["value"])), g["shapes"], g["lsi"], c32(loc), c32(attn))
         worst = max(worst, eb.hold(out, ref, "float32", "none", "float32 chain: %s C=%d %s" % (geometry, C, flavour)))
         must = ((ref["A"] + ref["E"]) == 0).reshape(-1, C)          # a row: the C channels of a (query, head) pair
         zeros += int(must.all(-1).sum())
@@ -212,10 +188,10 @@ def test_box_chain_in_float32_is_within_the_bound(geometry):
 def inst_chain_f32(g, k, with_mask):
     B, S, H, C, L, Lq = g["dims"]
     P = k * k
-    gout, gmask = gpu_cases.inst_upstream(g, k)
-    loc = c32(grid_f32(g["ref"], g["off"], gpu_cases.kernel_offsets(k), g["vr"], 0))
+    gout, gmask = boxes_cases.inst_upstream(g, k)
+    loc = c32(grid_f32(g["ref"], g["off"], boxes_cases.kernel_offsets(k), g["vr"], 0))
     sw, lw = (c32(a) for a in instance_weights_f32(g["logits"], k))
-    value = c32(gpu_cases.every_type(g["value"]))
+    value = c32(boxes_cases.every_type(g["value"]))
     if with_mask:
         a = (value, g["shapes"], g["lsi"], loc, sw, lw)
         out, mask = oc.instance_attn_forward(*a)
@@ -226,7 +202,7 @@ def inst_chain_f32(g, k, with_mask):
         out, mask, gl = oc.box_attn_forward(*a), None, None
         _, gloc, gs = oc.box_attn_backward(*a, c32(gout))
     grads = reduce_f32(g, k, np.asarray(gloc).reshape(loc.shape), np.asarray(gs).reshape(B, Lq, H, L, P), gl)
-    res = dict(zip(gpu_cases.GRAD_NAMES, grads), out=out)
+    res = dict(zip(boxes_cases.GRAD_NAMES, grads), out=out)
     if with_mask:
         res["mask_out"] = mask
     return res
@@ -238,17 +214,17 @@ def test_instance_chain_in_float32_is_within_the_bound(geometry, k):
     """Also: every input keeps the cell-edge condition, and every case has an all-zero row of ``out`` and a
     ``grad_offsets`` size component that must be exactly zero."""
     worst, edge, zero_rows, zero_sizes = {}, {}, 0, 0
-    for C, (per_head, with_vr), with_mask in itertools.product(gpu_cases.CHANNELS, gpu_cases.INST_FLAVOURS,
+    for C, (per_head, with_vr), with_mask in itertools.product(boxes_cases.CHANNELS, boxes_cases.INST_FLAVOURS,
                                                               (True, False)):
-        g = gpu_cases.inst_problem(geometry, C, k, per_head, with_vr)
-        ref = gpu_cases.inst_reference(geometry, C, k, per_head, with_vr, with_mask)
+        g = boxes_cases.inst_problem(geometry, C, k, per_head, with_vr)
+        ref = boxes_cases.inst_reference(geometry, C, k, per_head, with_vr, with_mask)
         what = "float32 chain: %s C=%d k=%d per_head=%d vr=%d mask=%d" % (geometry, C, k, per_head, with_vr, with_mask)
         assert ref["edge_share"] <= eb.EDGE_CAP, "%s: %.4f %% of the points on a cell edge" % (what,
                                                                                               100 * ref["edge_share"])
         for name, got in inst_chain_f32(g, k, with_mask).items():
             key = "%s%s" % (name, "" if with_mask or name == "out" else " (no grad_mask)")
             worst[key] = max(worst.get(key, 0.0), eb.hold(got, ref[name], "float32", "none", "%s: %s" % (what, name)))
-            if name in gpu_cases.GRAD_NAMES:
+            if name in boxes_cases.GRAD_NAMES:
                 edge[key] = max(edge.get(key, 0.0), eb.edge_dominated(ref[name]))
         go = ref["grad_offsets"]
         zero_rows += int(((ref["out"]["A"] + ref["out"]["E"]) == 0).reshape(-1, C).all(-1).sum())
@@ -263,26 +239,26 @@ def test_instance_chain_in_float32_is_within_the_bound(geometry, k):
 
 
 def test_reductions_agree_with_those_of_the_gpu_tests_expectation():
-    """reduce_grid / reduce_logits of tests/test_gpu_boxes_backward.py (restated from the kernels) on the reference's own
+    """inst_reduce_grid / inst_reduce_logits of tests/boxes_cases.py (restated from the kernels) on the reference's own
     per-point float64 gradients give the reference's three gradients."""
-    import test_gpu_boxes_backward as bw
+    import boxes_cases
     k = 6
-    g = gpu_cases.inst_problem("five_levels", 32, k, True, True)
-    gout, gmask = gpu_cases.inst_upstream(g, k)
-    kidx = gpu_cases.kernel_offsets(k)
+    g = boxes_cases.inst_problem("five_levels", 32, k, True, True)
+    gout, gmask = boxes_cases.inst_upstream(g, k)
+    kidx = boxes_cases.kernel_offsets(k)
     loc, dloc = eb.grid_reference(g["ref"], g["off"], kidx, g["vr"], 0)
     sw, lw, _, _ = eb.instance_weights_reference(g["logits"], k, True)
-    pts = eb.instance_reference(gpu_cases.every_type(g["value"]), g["shapes"], g["lsi"], loc, sw, lw, gout, gmask)
-    ref = gpu_cases.inst_reference("five_levels", 32, k, True, True, True)
-    goff, rows = bw.reduce_grid(g["ref"], g["off"], kidx, g["vr"], pts["grad_loc"]["want"])
-    glog = bw.reduce_logits(g["logits"], k, pts["grad_spatial"]["want"], pts["grad_level"]["want"])
-    for name, got in zip(gpu_cases.GRAD_NAMES, (goff, rows, glog)):
+    pts = eb.instance_reference(boxes_cases.every_type(g["value"]), g["shapes"], g["lsi"], loc, sw, lw, gout, gmask)
+    ref = boxes_cases.inst_reference("five_levels", 32, k, True, True, True)
+    goff, rows = boxes_cases.inst_reduce_grid(g["ref"], g["off"], kidx, g["vr"], pts["grad_loc"]["want"])
+    glog = boxes_cases.inst_reduce_logits(g["logits"], k, pts["grad_spatial"]["want"], pts["grad_level"]["want"])
+    for name, got in zip(boxes_cases.GRAD_NAMES, (goff, rows, glog)):
         want = ref[name]["want"]
         assert float(np.abs(got - want).max()) <= 1e-12 * max(1.0, float(np.abs(want).max())), name
 
 
 # ------------------------------------------------------------------ mutations: what the bound buys
-STORES = {"float32": 1e-4, "bf16": 1e-2, "f16": 1e-2}        # today's tolerances (test_gpu_wide_box_forward.tol_of)
+STORES = {"float32": 1e-4, "bf16": 1e-2, "f16": 1e-2}        # today's tolerances (compare_rules.tol_of)
 
 
 def passes_todays_check(got, want, tol):
@@ -309,11 +285,11 @@ def gap(mutant, ref, stores=STORES):
 
 
 def box_mutation_case(geometry, flavour=((0, 4), False, True), C=32):
-    g = gpu_cases.box_problem(geometry, C, flavour)
-    ref = gpu_cases.box_reference(geometry, C, flavour)
+    g = boxes_cases.box_problem(geometry, C, flavour)
+    ref = boxes_cases.box_reference(geometry, C, flavour)
     B, S, H, _, L, Lq, P = g["dims"]
-    args = ("box", gpu_cases.every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
-            gpu_cases.kernel_offsets(int(round(P ** 0.5))), g["vr"], g["logits"], g["angle_mode"])
+    args = ("box", boxes_cases.every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
+            boxes_cases.kernel_offsets(int(round(P ** 0.5))), g["vr"], g["logits"], g["angle_mode"])
     return g, ref, args
 
 
@@ -369,7 +345,7 @@ def test_mutation_the_last_tiles_out_of_range_slot_given_a_points_weight():
 def test_mutation_the_next_levels_box_for_the_first_point_of_a_straddling_tile():
     """odd_k: P = 9, tiles of 8: the second tile starts with point 8 of level 0 and goes on with level 1."""
     def candidates():
-        for C, flavour in itertools.product(gpu_cases.CHANNELS, gpu_cases.box_cases.FLAVOURS):
+        for C, flavour in itertools.product(boxes_cases.CHANNELS, boxes_cases.FLAVOURS):
             g, ref, args = box_mutation_case("odd_k", flavour, C)
             loc = ref["grid"][0]
             nxt, _ = eb.grid_reference(g["ref"], np.roll(g["off"], -1, 3), args[6], g["vr"], g["angle_mode"])
@@ -408,17 +384,17 @@ def test_mutation_the_softmax_maximum_over_the_first_tile_only():
     damage -- and only an exponent past float32's range (non-finite weights, which today's check refuses too) would
     show there.  The figure is printed, not asserted to be above 1."""
     geometry, C, flavour = "ragged", 32, ((0, 4), False, True)
-    g = gpu_cases.box_problem(geometry, C, flavour)
+    g = boxes_cases.box_problem(geometry, C, flavour)
     z = g["logits"].copy()
     z[..., :8] -= F(60)
-    args = ("box", gpu_cases.every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
-            gpu_cases.kernel_offsets(2), g["vr"], z, g["angle_mode"])
+    args = ("box", boxes_cases.every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
+            boxes_cases.kernel_offsets(2), g["vr"], z, g["angle_mode"])
     ref = eb.boxes_reference(*args)
     want, dw = eb.softmax_reference(z)
     fair, mutant = softmax_f32(z), softmax_f32(z, first=8)
-    print("float32 weights with the row's maximum: worst err / dw %.3f" % gpu_cases.within(fair, want, dw * want, "fair"))
+    print("float32 weights with the row's maximum: worst err / dw %.3f" % compare_rules.within(fair, want, dw * want, "fair"))
     with pytest.raises(AssertionError, match="outside the allowance"):
-        gpu_cases.within(mutant, want, dw * want, "the maximum of the first 8 logits")
+        compare_rules.within(mutant, want, dw * want, "the maximum of the first 8 logits")
     print("... with the maximum of the first 8 logits: worst err / dw %.3f"
           % float((np.abs(mutant - want) / (dw * want)).max()))
     out = eb.boxes_reference(*args, weights=[mutant])["out"]
@@ -435,14 +411,14 @@ def test_mutation_relu_gradient_omitted_in_grad_offsets():
     k = 4
 
     def candidates():
-        for geometry, C, (per_head, with_vr) in itertools.product(INST_GEOMETRIES, gpu_cases.CHANNELS,
-                                                                  gpu_cases.INST_FLAVOURS):
-            ref = gpu_cases.inst_reference(geometry, C, k, per_head, with_vr, True)["grad_offsets"]
+        for geometry, C, (per_head, with_vr) in itertools.product(INST_GEOMETRIES, boxes_cases.CHANNELS,
+                                                                  boxes_cases.INST_FLAVOURS):
+            ref = boxes_cases.inst_reference(geometry, C, k, per_head, with_vr, True)["grad_offsets"]
             whole = ref["unmasked"]
             changed = np.argwhere(whole != ref["want"])
             assert len(changed), "no collapsed box with a gradient"
             assert (ref["A"] + ref["E"])[tuple(changed.T)].max() == 0
-            if (geometry, C, per_head, with_vr) == (INST_GEOMETRIES[0], gpu_cases.CHANNELS[0], False, False):
+            if (geometry, C, per_head, with_vr) == (INST_GEOMETRIES[0], boxes_cases.CHANNELS[0], False, False):
                 yield "every row", ref, dict(want=whole)
             at = tuple(min(changed.tolist(), key=lambda a: abs(whole[tuple(a)])))
             m = ref["want"].copy()
@@ -457,8 +433,7 @@ def test_mutation_relu_gradient_omitted_in_grad_offsets():
 
 
 # ------------------------------------------------------------------ the box training step from boxes (box kind, gradients)
-BWD_NAMES = gpu_cases.GRAD_NAMES
-POINT_TOL = 1e-4             # today's rule for the three gradients (tests/test_gpu_box_boxes_backward.py: check at POINT_TOL)
+BWD_NAMES = boxes_cases.GRAD_NAMES
 
 
 def reduce_box_f32(g, kidx, gloc, gattn, attn):
@@ -509,22 +484,22 @@ def box_chain_f32(g):
     """The training step from boxes in float32 on the CPU: float32 grid and weights, the C oracle's float32 build for
     the per-point gradients, float32 reductions."""
     B, S, H, C, L, Lq, P = g["dims"]
-    kidx = gpu_cases.kernel_offsets(int(round(P ** 0.5)))
+    kidx = boxes_cases.kernel_offsets(int(round(P ** 0.5)))
     loc = c32(grid_f32(g["ref"], g["off"], kidx, g["vr"], g["angle_mode"]))
     attn = c32(softmax_f32(g["logits"]).reshape(B, Lq, H, L, P))
-    _, gloc, gattn = oc.box_attn_backward(c32(gpu_cases.every_type(g["value"])), g["shapes"], g["lsi"], loc, attn,
-                                          c32(gpu_cases.bwd_upstream(g)))
+    _, gloc, gattn = oc.box_attn_backward(c32(boxes_cases.every_type(g["value"])), g["shapes"], g["lsi"], loc, attn,
+                                          c32(boxes_cases.bwd_upstream(g)))
     return reduce_box_f32(g, kidx, np.asarray(gloc).reshape(loc.shape), np.asarray(gattn).reshape(attn.shape), attn)
 
 
-@pytest.mark.parametrize("geometry", gpu_cases.BOX_GEOMETRIES)
+@pytest.mark.parametrize("geometry", boxes_cases.BOX_GEOMETRIES)
 def test_box_backward_chain_in_float32_is_within_the_bound(geometry):
     """Every case of the GPU matrix: the reference's own arithmetic in float32 meets the bound, the inputs keep the
     cell-edge condition (with the locations' own slack), and the model has elements that must be exactly zero."""
     worst, edge, zeros, share = {}, {}, {n: 0 for n in BWD_NAMES}, 0.0
-    for C, flavour in itertools.product(gpu_cases.CHANNELS, gpu_cases.box_cases.FLAVOURS):
-        g = gpu_cases.bwd_problem(geometry, C, flavour)
-        ref = gpu_cases.bwd_reference(geometry, C, flavour)
+    for C, flavour in itertools.product(boxes_cases.CHANNELS, boxes_cases.FLAVOURS):
+        g = boxes_cases.bwd_problem(geometry, C, flavour)
+        ref = boxes_cases.bwd_reference(geometry, C, flavour)
         what = "float32 chain, box backward from boxes: %s C=%d angle=%d D=%d per_head=%d vr=%d" % (
             (geometry, C) + flavour[0] + flavour[1:])
         share = max(share, ref["edge_share"])
@@ -555,18 +530,18 @@ def test_box_gradient_model_agrees_with_float64_autograd(geometry):
     over the levels (and heads) as autograd returns them, with the sums of the planes and that many more terms."""
     from oracle import torch_fallback
     worst = 0.0
-    for flavour in gpu_cases.box_cases.FLAVOURS:
-        g = gpu_cases.bwd_problem(geometry, 16, flavour)
-        model = gpu_cases.bwd_reference(geometry, 16, flavour)
+    for flavour in boxes_cases.FLAVOURS:
+        g = boxes_cases.bwd_problem(geometry, 16, flavour)
+        model = boxes_cases.bwd_reference(geometry, 16, flavour)
         B, S, H, C, L, Lq, P = g["dims"]
         leaf = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64)).requires_grad_()
         ref, off, logits = leaf(g["ref"]), leaf(g["off"]), leaf(g["logits"])
         vr = None if g["vr"] is None else torch.from_numpy(g["vr"]).double()
-        kidx = torch.from_numpy(gpu_cases.kernel_offsets(int(round(P ** 0.5)))).double()
+        kidx = torch.from_numpy(boxes_cases.kernel_offsets(int(round(P ** 0.5)))).double()
         loc = _torch_grid(ref, off, kidx, vr, g["angle_mode"])
         attn = torch.softmax(logits, -1).view(B, Lq, H, L, P)
-        out = torch_fallback.box_attn(torch.from_numpy(gpu_cases.every_type(g["value"])), g["shapes"], loc, attn)
-        (out * torch.from_numpy(gpu_cases.bwd_upstream(g))).sum().backward()
+        out = torch_fallback.box_attn(torch.from_numpy(boxes_cases.every_type(g["value"])), g["shapes"], loc, attn)
+        (out * torch.from_numpy(boxes_cases.bwd_upstream(g))).sum().backward()
         n5 = min(5, g["ref"].shape[-1])
         axes = (3,) if g["ref"].ndim == 4 else (2, 3)
         rows = model["grad_ref_rows"]
@@ -593,17 +568,17 @@ def test_backward_building_blocks_in_float32_are_within_the_bound():
     numpy on the inputs of the GPU tests: exact float32 upstream gradients, so the bound is the reduction's roundings,
     the rotation allowance and the weights' dw alone."""
     worst = {}
-    for P, (angle_mode, per_head, with_vr) in itertools.product(gpu_cases.GRID_POINTS, gpu_cases.GRID_FLAVOURS):
-        g = gpu_cases.grid_problem(P, angle_mode, per_head, with_vr)
-        gg = gpu_cases.grid_upstream(P, angle_mode, per_head, with_vr)
+    for P, (angle_mode, per_head, with_vr) in itertools.product(boxes_cases.GRID_POINTS, boxes_cases.GRID_FLAVOURS):
+        g = boxes_cases.grid_problem(P, angle_mode, per_head, with_vr)
+        gg = boxes_cases.grid_upstream(P, angle_mode, per_head, with_vr)
         ref = eb.grid_backward_reference(g["ref"], g["off"], g["kidx"], g["vr"], angle_mode, gg)
         one = np.ones(g["off"].shape[:3] + (1,), F)
         goff, rows, _ = reduce_box_f32(g, g["kidx"], gg, one, one)
         for name, got in (("grad_offsets", goff), ("grad_ref_rows", rows)):
             what = "box_grid_backward P=%d angle=%d per_head=%d vr=%d: %s" % (P, angle_mode, per_head, with_vr, name)
             worst[name] = max(worst.get(name, 0.0), eb.hold(got, ref[name], "float32", "none", what))
-    for rows_, n in itertools.product(gpu_cases.SOFTMAX_BWD_ROWS, gpu_cases.SOFTMAX_BWD_LENGTHS):
-        a, gw = gpu_cases.softmax_bwd_problem(rows_, n)
+    for rows_, n in itertools.product(boxes_cases.SOFTMAX_BWD_ROWS, boxes_cases.SOFTMAX_BWD_LENGTHS):
+        a, gw = boxes_cases.softmax_bwd_problem(rows_, n)
         got = a * (gw - (a * gw).sum(-1, keepdims=True, dtype=F))
         ref = eb.softmax_backward_reference(a, gw)
         for store in eb.STORE:
@@ -611,8 +586,8 @@ def test_backward_building_blocks_in_float32_are_within_the_bound():
                                             eb.hold(eb.round_to(got, store), ref, store, "none",
                                                     "softmax_backward rows=%d n=%d" % (rows_, n)))
     for L, k in itertools.product((1, 5, 16), KERNEL_SIZES):
-        z = gpu_cases.cell_rows(L)
-        gs, gl = gpu_cases.cell_upstream(L, k)
+        z = boxes_cases.cell_rows(L)
+        gs, gl = boxes_cases.cell_upstream(L, k)
         for which, (s, l) in (("both", (gs, gl)), ("spatial", (gs, None)), ("level", (None, gl))):
             ref = eb.cell_logits_backward_reference(z, k, s, l)
             _, _, got = reduce_f32(dict(ref=np.zeros((1, 8, 4), F), off=np.zeros((1, 8, 1, L, 4), F), vr=None, logits=z), k,
@@ -648,9 +623,9 @@ def judge(name, mutant, ref):
 
 
 def bwd_mutants(geometry, flavour, mutation, C=32):
-    g = gpu_cases.bwd_problem(geometry, C, flavour)
-    ref = gpu_cases.bwd_reference(geometry, C, flavour)
-    a = gpu_cases.bwd_model_args(g)
+    g = boxes_cases.bwd_problem(geometry, C, flavour)
+    ref = boxes_cases.bwd_reference(geometry, C, flavour)
+    a = boxes_cases.bwd_model_args(g)
     return g, ref, eb.box_gradients(ref["points"], a[4], a[5], a[6], a[7], a[9], mutation)
 
 

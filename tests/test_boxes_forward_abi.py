@@ -5,24 +5,13 @@ from ``boxattn_fwd_route``, nothing hard-coded), and the entry points refuse wha
 pointers, with hipErrorInvalidValue before any device call.  No compute calls: there is no GPU here."""
 import ctypes
 import itertools
-import os
 import re
 
 import pytest
+from capi_cases import HEADER, INST_GEOMETRIES as GEOMETRIES, INVALID_VALUE, declarations
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
 ENTRY_POINTS = ["instattn_fwd_boxes_" + suf for suf in ("f32", "bf16", "f16")]
 WIDE = 3
-INVALID_VALUE = 1                        # hipErrorInvalidValue
-# the two small geometries of the issue: (levels, B, Lq, H)
-GEOMETRIES = [([(9, 11), (4, 5)], 2, 4, 8), ([(6, 5)], 1, 3, 2)]
-
-
-def declarations():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return {m.group(1): " ".join(m.group(2).split())
-            for m in re.finditer(r"\b((?:boxattn|instattn)_\w+)\s*\(([^;{]*?)\)\s*;", text, re.S)}
 
 
 @pytest.fixture(scope="module")

@@ -5,9 +5,7 @@ import os
 import re
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
+from capi_cases import HEADER, ROOT
 
 
 def declared_functions():

@@ -12,6 +12,8 @@ import pytest
 import torch
 
 import golden_io
+from compare_rules import PARITY_TOL as TOL
+from route_vocab import _cdt
 
 
 @pytest.fixture(scope="module")
@@ -41,7 +43,6 @@ def test_cpu_tensors_are_refused(compiled):
 
 
 # ------------------------------------------------------------------ GPU
-TOL = {torch.float64: 1e-10, torch.float32: 1e-4, torch.bfloat16: 1e-2}
 
 
 def _dev(a, dtype=None):
@@ -55,10 +56,6 @@ def _close(got, want, tol, what):
     scale = max(1.0, float(np.abs(want).max()))
     err = float(np.abs(got - want).max()) / scale
     assert err <= tol, "%s: max scaled err %.3e > %.1e" % (what, err, tol)
-
-
-def _cdt(dtype):
-    return torch.float32 if dtype == torch.bfloat16 else dtype
 
 
 @pytest.mark.gpu

@@ -17,13 +17,14 @@ import pytest
 
 import dynamic_range as dr
 import error_bounds as eb
-import test_gpu_dynamic_range as cases
+import dynamic_range
+import point_cases
+from point_cases import oracle
 from oracle import boxattn_oracle as oc
-from test_error_bounds import oracle
 
-GROUP_TYPES = [(group, dtype) for group in cases.GROUPS for dtype in ("f32", "bf16")]
+GROUP_TYPES = [(group, dtype) for group in dynamic_range.GROUPS for dtype in ("f32", "bf16")]
 # (the from-boxes inputs are numbers every storage type holds: float32 and bf16 take the same)
-ALL_GROUP_TYPES = GROUP_TYPES + [(group, "bf16") for group in cases.BOXES_GROUPS]
+ALL_GROUP_TYPES = GROUP_TYPES + [(group, "bf16") for group in dynamic_range.BOXES_GROUPS]
 STORE = {"f32": "float32", "bf16": "bf16", "f16": "f16"}
 TINY = {"float32": 2.0 ** -126, "bf16": 2.0 ** -126, "f16": 2.0 ** -14}
 HUGE = {"float32": 3.4028234663852886e38, "bf16": 3.3895313892515355e38, "f16": 65504.0}
@@ -54,23 +55,24 @@ def one_thread():
 
 # ------------------------------------------------------------------ 1. the cell-edge share
 def test_edge_share_of_every_input_is_under_the_cap():
-    inputs = [("%s %s" % (group, dtype), cases.base_input(group, dtype)) for group in cases.GROUPS for dtype in STORE]
-    inputs.append(("overflow", cases.overflow_problem()[1]))
+    inputs = [("%s %s" % (group, dtype), dynamic_range.base_input(group, dtype))
+              for group in dynamic_range.GROUPS for dtype in STORE]
+    inputs.append(("overflow", dynamic_range.overflow_problem()[1]))
     for name, inp in inputs:
         share = float(eb.on_edge(eb.f64(inp["loc"]), eb.f64(inp["shapes"])).mean())
         assert share <= eb.EDGE_CAP, "%s: %.4f %% of the points on a cell edge" % (name, 100 * share)
         assert eb.reference_of(inp)["grad_loc"]["edge_share"] <= eb.EDGE_CAP
-    for group in cases.BOXES_GROUPS:              # (with the locations' own slack: boxes_reference's count)
-        share = cases.reference_of(cases.base_input(group, "f32"))["edge_share"]
+    for group in dynamic_range.BOXES_GROUPS:              # (with the locations' own slack: boxes_reference's count)
+        share = dynamic_range.reference_of(dynamic_range.base_input(group, "f32"))["edge_share"]
         assert share <= eb.EDGE_CAP, "%s: %.4f %% of the points on a cell edge" % (group, 100 * share)
 
 
 # ------------------------------------------------------------------ 2. the range conditions, family by family
 @pytest.mark.parametrize("group,dtype", ALL_GROUP_TYPES)
 def test_exact_and_far_scalings_round_nothing_and_stay_normal(group, dtype):
-    inp, store = cases.base_input(group, dtype), STORE[dtype]
-    ref = cases.reference_of(inp)
-    for a, b in cases.EXACT + cases.FAR:
+    inp, store = dynamic_range.base_input(group, dtype), STORE[dtype]
+    ref = dynamic_range.reference_of(inp)
+    for a, b in dynamic_range.EXACT + dynamic_range.FAR:
         assert dr.is_exact(inp, a, b, store), (group, dtype, a, b)
         s = dr.scaled(inp, a, b, store)
         for k in ("value",) + dr.UPSTREAM:
@@ -86,14 +88,14 @@ def test_exact_and_far_scalings_round_nothing_and_stay_normal(group, dtype):
             assert not w.size or float((w < TINY[st] * 2.0 ** 24).mean()) <= 1e-3, (name, a, b)
 
 
-@pytest.mark.parametrize("group", cases.GROUPS + cases.BOXES_GROUPS)
+@pytest.mark.parametrize("group", dynamic_range.GROUPS + dynamic_range.BOXES_GROUPS)
 def test_f16_exponents_follow_their_rules(group):
-    inp = cases.base_input(group, "f16")
-    (ah, bh), (al, bl) = cases.f16_exponents(group)
+    inp = dynamic_range.base_input(group, "f16")
+    (ah, bh), (al, bl) = dynamic_range.f16_exponents(group)
     print("dynamic-range exponents | %s | f16 high (%d, %d) | f16 low (%d, %d)" % (group, ah, bh, al, bl))
     # high: every input finite, every f16 output at most 65504 / 2 -- and not so one exponent further
     assert dr.is_exact(inp, ah, bh, "f16")
-    s, ref = cases.f16_reference(group, ah, bh)
+    s, ref = dynamic_range.f16_reference(group, ah, bh)
     assert all(np.isfinite(s[k]).all() for k in ("value",) + dr.UPSTREAM if k in s)
     for name in dr.STORED:
         if name in ref:
@@ -101,7 +103,7 @@ def test_f16_exponents_follow_their_rules(group):
             assert top <= dr.F16_MAX / 2, (name, top)
     for a, b, names in ((ah + 1, bh, ("out", "mask_out")), (ah, bh + 1, ("grad_value",))):
         s1 = dr.scaled(inp, a, b, "f16")
-        r1 = dr.scaled_reference(cases.reference_of(inp), a, b)
+        r1 = dr.scaled_reference(dynamic_range.reference_of(inp), a, b)
         over = not all(np.isfinite(s1[k]).all() for k in ("value",) + dr.UPSTREAM if k in s1)
         over = over or any(float((np.abs(r1[n]["want"]) + dr.slack(r1[n], "f16")).max()) > dr.F16_MAX / 2
                            for n in names if n in r1)
@@ -117,7 +119,7 @@ def test_f16_exponents_follow_their_rules(group):
         assert sub >= dr.LOW_SUBNORMAL and zero <= dr.LOW_ZERO, ("upstream", bl, sub, zero)
         print("dynamic-range exponents | %s | upstream 2^%d: %.1f %% subnormal, %.1f %% zero" % (group, bl, 100 * sub, 100 * zero))
     # ... and the bound still tells: the median bound of out is a small part of the median |want|
-    s, ref = cases.f16_reference(group, al, 0)
+    s, ref = dynamic_range.f16_reference(group, al, 0)
     live = ref["out"]["want"] != 0
     share = float(np.median(eb.bound(ref["out"], "f16", "f16")[live]) / np.median(np.abs(ref["out"]["want"][live])))
     print("dynamic-range exponents | %s | out at (%d, 0): median bound / median |want| = %.4f" % (group, al, share))
@@ -125,14 +127,14 @@ def test_f16_exponents_follow_their_rules(group):
 
 
 def test_the_overflow_case_decides_nearly_every_element():
-    b, s, ref = cases.overflow_problem()
+    b, s, ref = dynamic_range.overflow_problem()
     assert all(np.isfinite(s[k]).all() for k in ("value", "grad_out")) and (s["grad_out"] >= 0).all()
     for split in ("f16", "none"):
         n_inf, n_fin, n_either, live = dr.overflow_counts(ref["grad_value"], split)
         print("dynamic-range exponents | f16 overflow | b = %d, split %s: %d inf / %d finite / %d either of %d live"
               % (b, split, n_inf, n_fin, n_either, live))
         assert n_inf >= dr.OVERFLOW_MIN and n_fin >= dr.OVERFLOW_MIN and n_either <= dr.OVERFLOW_EITHER * live
-    base = dr.overflow_input(dr.scaled(cases.encoder_input("model", "f16", 1), 0, 0, "f16"))
+    base = dr.overflow_input(dr.scaled(point_cases.encoder_input("model", "f16", 1), 0, 0, "f16"))
     less = dr.scaled_reference(eb.reference_of(base), 0, b - 1)["grad_value"]
     assert dr.overflow_counts(less, "f16")[0] < dr.OVERFLOW_MIN, "b - 1 would do as well"
     # out is a convex combination of finite values
@@ -140,7 +142,7 @@ def test_the_overflow_case_decides_nearly_every_element():
 
 
 def test_slack_is_the_bounds_r():
-    ref = eb.reference_of(cases.base_input("encoder", "f16"))["grad_value"]
+    ref = eb.reference_of(dynamic_range.base_input("encoder", "f16"))["grad_value"]
     for split in ("none", "f16", "bf16", "split3"):
         R = dr.slack(ref, split)
         want = np.where(ref["A"] + ref["E"] > 0, eb.half_ulp(np.abs(ref["want"]) + R, "f16") + R, 0.0)
@@ -151,11 +153,11 @@ def test_slack_is_the_bounds_r():
 @pytest.mark.parametrize("group,dtype", ALL_GROUP_TYPES)
 def test_the_reference_is_exactly_homogeneous(group, dtype):
     """error_bounds.box_reference, instance_reference and boxes_reference (both kinds, rotated and not)."""
-    inp, store = cases.base_input(group, dtype), STORE[dtype]
-    ref = cases.reference_of(inp)
-    for a, b in [(12, -7)] + cases.EXACT + cases.FAR:
+    inp, store = dynamic_range.base_input(group, dtype), STORE[dtype]
+    ref = dynamic_range.reference_of(inp)
+    for a, b in [(12, -7)] + dynamic_range.EXACT + dynamic_range.FAR:
         s = dr.scaled(inp, a, b, store)
-        got, want = cases.reference_of(s), dr.scaled_reference(ref, a, b)
+        got, want = dynamic_range.reference_of(s), dr.scaled_reference(ref, a, b)
         for name, planes in outputs(want).items():
             for k, v in planes.items():
                 assert np.array_equal(got[name][k], v), "%s %s (%d, %d): %s.%s" % (group, dtype, a, b, name, k)
@@ -164,15 +166,15 @@ def test_the_reference_is_exactly_homogeneous(group, dtype):
 # ------------------------------------------------------------------ 4. the float32 oracle, the arithmetic yardstick
 @pytest.mark.parametrize("group,dtype", GROUP_TYPES)
 def test_the_float32_oracle_is_homogeneous_and_inside_the_scaled_bound(group, dtype, one_thread):
-    inp, store = cases.base_input(group, dtype), STORE[dtype]
+    inp, store = dynamic_range.base_input(group, dtype), STORE[dtype]
     ref = eb.reference_of(inp)
     base = oracle(numpy_of(inp), np.float32)
-    for a, b in cases.EXACT:
+    for a, b in dynamic_range.EXACT:
         got = oracle(numpy_of(dr.scaled(inp, a, b, store)), np.float32)
         for name, x in got.items():
             want = np.asarray(base[name], dtype=np.float32) * np.float32(2.0) ** dr.factor(name, a, b)
             assert np.array_equal(np.asarray(x), want), "%s %s (%d, %d): %s" % (group, dtype, a, b, name)
-    for a, b in cases.FAR:
+    for a, b in dynamic_range.FAR:
         got = oracle(numpy_of(dr.scaled(inp, a, b, store)), np.float32)
         sref = dr.scaled_reference(ref, a, b)
         worst = {name: eb.hold(x, sref[name], "float32", "none", "%s float32 oracle (%d, %d): %s" % (group, a, b, name))
@@ -184,10 +186,10 @@ def test_the_float32_oracle_is_homogeneous_and_inside_the_scaled_bound(group, dt
 # ------------------------------------------------------------------ 5. the tests can fail
 def fault_checks():
     """name -> (inputs, store, check(got)): the f16 low, f16 overflow and far checks on the encoder input, and scale 1."""
-    (_, _), (al, bl) = cases.f16_exponents("encoder")
-    low, low_ref = cases.f16_reference("encoder", al, bl)
-    b, over, over_ref = cases.overflow_problem()
-    far32 = cases.base_input("encoder", "f32")
+    (_, _), (al, bl) = dynamic_range.f16_exponents("encoder")
+    low, low_ref = dynamic_range.f16_reference("encoder", al, bl)
+    b, over, over_ref = dynamic_range.overflow_problem()
+    far32 = dynamic_range.base_input("encoder", "f32")
 
     def bounded(ref, store, split="none"):
         def check(got):
@@ -200,7 +202,7 @@ def fault_checks():
         dr.hold_saturating(got["grad_value"], over_ref["grad_value"], "none", "grad_value")
     # scale 1: randn leaves a handful of f16 subnormals among the 26 000 stored numbers, and the bound is sharp enough
     # to see one of them flushed; the input without them is what "magnitude about 1" means
-    one = dr.scaled(cases.base_input("encoder", "f16"), 0, 0, "f16")
+    one = dr.scaled(dynamic_range.base_input("encoder", "f16"), 0, 0, "f16")
     for k in ("value", "grad_out"):
         few = (np.abs(one[k]) < dr.F16_MIN_NORMAL) & (one[k] != 0)
         assert few.sum() <= 8
@@ -208,7 +210,7 @@ def fault_checks():
     res = {"scale 1": (one, "f16", bounded(eb.reference_of(one), "f16")),
            "f16 low": (low, "f16", bounded(low_ref, "f16")),
            "f16 overflow": (over, "f16", saturating)}
-    for a, b in cases.FAR:
+    for a, b in dynamic_range.FAR:
         res["far (%d, %d)" % (a, b)] = (dr.scaled(far32, a, b, "float32"), "float32",
                                         bounded(dr.scaled_reference(eb.reference_of(far32), a, b), "float32"))
     return res
@@ -233,11 +235,11 @@ def test_each_wrong_implementation_fails_the_check_aimed_at_it_and_no_other():
 
 
 def test_the_overflow_case_from_boxes_decides_nearly_every_element():
-    b, p, gout, ref = cases.value_overflow_problem()
+    b, p, gout, ref = dynamic_range.value_overflow_problem()
     assert np.isfinite(eb.round_to(gout, "f16")).all() and np.array_equal(eb.round_to(gout, "f16"), gout) and (gout >= 0).all()
     n_inf, n_fin, n_either, live = dr.overflow_counts(ref, "none")
     print("dynamic-range exponents | f16 overflow, grad_value from boxes (%s) | b = %d: %d inf / %d finite / %d either "
-          "of %d live" % (cases.VALUE_OVERFLOW[0], b, n_inf, n_fin, n_either, live))
+          "of %d live" % (dynamic_range.VALUE_OVERFLOW[0], b, n_inf, n_fin, n_either, live))
     assert n_inf >= dr.OVERFLOW_MIN and n_fin >= dr.OVERFLOW_MIN and n_either <= dr.OVERFLOW_EITHER * live
     less = dr.scaled_reference(dict(grad_value=ref), 0, -1)["grad_value"]
     assert dr.overflow_counts(less, "none")[0] < dr.OVERFLOW_MIN, "b - 1 would do as well"

@@ -13,13 +13,11 @@ import pytest
 import torch
 
 import error_bounds as eb
-import test_gpu_error_bounds as gpu_cases
-from oracle import boxattn_oracle as oc
-from test_gpu_f16 import check as check_f16
-from test_gpu_parity import SEEDED, _seeded, close as close_parity
+import point_cases
+import route_vocab
+from compare_rules import check_f16, close_parity
+from point_cases import SEEDED, _seeded, oracle
 
-BOX_NAMES = ("out", "grad_value", "grad_loc", "grad_attn")
-INST_NAMES = ("out", "mask_out", "grad_value", "grad_loc", "grad_spatial", "grad_level")
 STORED = ("out", "mask_out", "grad_value")
 TABLE = [([(16, 16), (8, 8)], "S", "model"), ([(13, 13), (7, 7)], "S", "model"), ([(8, 8)], 192, "model"),
          ([(16, 16), (8, 8)], "S", "test"), ([(20, 30), (10, 15), (5, 8), (3, 4)], 50, "model")]
@@ -45,17 +43,6 @@ def case(name):
             ref = eb.box_reference(d["value"], d["shapes"], d["lsi"], d["loc"], d["attn"], d["grad_out"])
         _CACHE[name] = (d, ref)
     return _CACHE[name]
-
-
-def oracle(d, cast):
-    """Every output of the C oracle in float64 (cast = np.float64) or float32 arithmetic."""
-    c = lambda a: np.ascontiguousarray(a, dtype=cast)
-    if d["kind"] == "instance":
-        a = (c(d["value"]), d["shapes"], d["lsi"], c(d["loc"]), c(d["spatial_w"]), c(d["level_w"]))
-        res = list(oc.instance_attn_forward(*a)) + list(oc.instance_attn_backward(*a, c(d["grad_out"]), c(d["grad_mask"])))
-        return dict(zip(INST_NAMES, res))
-    a = (c(d["value"]), d["shapes"], d["lsi"], c(d["loc"]), c(d["attn"]))
-    return dict(zip(BOX_NAMES, [oc.box_attn_forward(*a)] + list(oc.box_attn_backward(*a, c(d["grad_out"])))))
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -153,7 +140,8 @@ def as_tensor(a, store):
 @pytest.mark.parametrize("name", MUTATED)
 def test_one_term_weights_fail_the_bound_and_pass_the_global_scale_checks(name, store):
     """Every weight a w_k kept as ONE 16-bit number (the lo term of the matrix-core kernels lost), the sums exact and
-    rounded once: outside the bound, inside test_gpu_parity.close (bf16) and test_gpu_f16.check (f16) -- the gap the
+    rounded once: outside the bound, inside compare_rules.close_parity (bf16) and compare_rules.check_f16 (f16) -- the
+    gap the
     bound closes."""
     d, ref = case(name)
     mut = eb.box_reference(d["value"], d["shapes"], d["lsi"], d["loc"], d["attn"], d["grad_out"],
@@ -194,13 +182,13 @@ def test_a_point_with_swapped_fractions_is_noticed(name, store):
 # ------------------------------------------------------------------ the CPU twin of tests/test_gpu_error_bounds.py
 def test_edge_share_of_every_gpu_input_is_under_the_cap():
     worst = 0.0
-    for name, build in gpu_cases.all_inputs():
+    for name, build in point_cases.all_inputs():
         inp = build()
         share = float(eb.on_edge(eb.f64(inp["loc"]), eb.f64(inp["shapes"])).mean())
         worst = max(worst, share)
         assert share <= eb.EDGE_CAP, "%s: %.4f %% of the points on a cell edge" % (name, 100 * share)
-    from test_gpu_boxes_backward import edge_share
-    share = edge_share(gpu_cases.boxes_input(), 14)
+    from boxes_cases import inst_edge_share as edge_share
+    share = edge_share(point_cases.boxes_input(), 14)
     assert share <= eb.EDGE_CAP, "forward from boxes: %.4f %%" % (100 * share)
     print("worst share %.4f %%" % (100 * max(worst, share)))
 
@@ -209,49 +197,52 @@ def test_every_gpu_case_expects_the_route_the_library_answers():
     """boxattn_fwd_route / boxattn_bwd_accumulate_kind / boxattn_bwd_record_kind are host code: what the GPU cases
     assert before they run can be checked here."""
     from boxer_amd import _lib
-    g = gpu_cases
     try:
         for family in ("model",):
-            for (dtype, acc_key, rec_key) in g.ENCODER_ROUTES:
+            for (dtype, acc_key, rec_key) in point_cases.ENCODER_ROUTES:
                 for dense in (2, 1):
                     for riders in (0, 1):
-                        g.set_encoder_keys(dense, riders, acc_key, rec_key)
-                        t = g.box_tensors(g.encoder_input(family, dtype, 1), g.DTYPES[dtype], "cpu")
-                        want = g.encoder_expectation(dtype, dense, riders, acc_key, rec_key)[:3]
-                        assert g.routes(t) == want, (dtype, acc_key, rec_key, dense, riders, g.routes(t), want)
-        g.set_encoder_keys(0, 0, 0, 0)
-        for dtype, dt in g.DTYPES.items():
-            acc = g.ACC_SPLIT if dtype == "f32" else g.ACC_TR
+                        route_vocab.set_encoder_keys(dense, riders, acc_key, rec_key)
+                        t = point_cases.box_tensors(point_cases.encoder_input(family, dtype, 1),
+                                                    route_vocab.DTYPES[dtype], "cpu")
+                        want = point_cases.encoder_expectation(dtype, dense, riders, acc_key, rec_key)[:3]
+                        assert route_vocab.routes(t) == want, (dtype, acc_key, rec_key, dense, riders,
+                                                               route_vocab.routes(t), want)
+        route_vocab.set_encoder_keys(0, 0, 0, 0)
+        for dtype, dt in route_vocab.DTYPES.items():
+            acc = route_vocab.ACC_SPLIT if dtype == "f32" else route_vocab.ACC_TR
             for variant in (0, 3):
                 _lib.set_variant(variant)
                 for C in ((16, 32, 64) if dtype == "bf16" else (32,)):
                     if C == 32 or dtype == "bf16":
-                        t = g.box_tensors(g.seeded6_input(C), dt, "cpu")
-                        assert g.routes(t) == (g.GATHER, acc, g.REC_POINT), (dtype, C, variant, g.routes(t))
-            for _, variant in [r for r in g.DECODER_ROUTES if r[0] == dtype]:
+                        t = point_cases.box_tensors(point_cases.seeded6_input(C), dt, "cpu")
+                        assert route_vocab.routes(t) == (route_vocab.GATHER, acc, route_vocab.REC_POINT), \
+                            (dtype, C, variant, route_vocab.routes(t))
+            for _, variant in [r for r in point_cases.DECODER_ROUTES if r[0] == dtype]:
                 _lib.set_variant(variant)
-                t = g.box_tensors(g.decoder_input("model", dtype), dt, "cpu")
-                want = (g.DECODER_FORWARD[variant], acc, g.REC_POINT)
-                assert g.routes(t) == want, (dtype, variant, g.routes(t), want)
+                t = point_cases.box_tensors(point_cases.decoder_input("model", dtype), dt, "cpu")
+                want = (point_cases.DECODER_FORWARD[variant], acc, route_vocab.REC_POINT)
+                assert route_vocab.routes(t) == want, (dtype, variant, route_vocab.routes(t), want)
             _lib.set_variant(3)
-            t = g.inst_tensors(g.shape_a_input("bf16" if dtype == "f32" else dtype), dt, "cpu")
+            t = point_cases.inst_tensors(point_cases.shape_a_input("bf16" if dtype == "f32" else dtype), dt, "cpu")
             for key in ((0,) if dtype == "f32" else (1, 2)):
                 _lib.set_option("inst_acc16", key)
-                assert g.routes(t, instance=True)[1:] == (g.ACC_TR if key == 2 else g.ACC_VALU, g.REC_POINT)
+                assert route_vocab.routes(t, instance=True)[1:] == (
+                    route_vocab.ACC_TR if key == 2 else route_vocab.ACC_VALU, route_vocab.REC_POINT)
             _lib.set_option("inst_acc16", 0)
             _lib.set_variant(0)
-            t = g.inst_tensors(g.k14_input(dtype), dt, "cpu")
-            assert g.routes(t, instance=True)[0] == g.WIDE
+            t = point_cases.inst_tensors(point_cases.k14_input(dtype), dt, "cpu")
+            assert route_vocab.routes(t, instance=True)[0] == route_vocab.WIDE
             for P in (196, 36):
-                t = g.box_tensors(g.wide_input(P), dt, "cpu")
+                t = point_cases.box_tensors(point_cases.wide_input(P), dt, "cpu")
                 _lib.set_option("wide_box", 2)
-                assert g.routes(t)[0] == g.WIDE, (dtype, P)
+                assert route_vocab.routes(t)[0] == route_vocab.WIDE, (dtype, P)
                 _lib.set_option("wide_box", 0)
-            b = g.boxes_input()
+            b = point_cases.boxes_input()
             B, S, H, C, L, Lq = b["dims"]
             assert _lib.fwd_boxes_ok(dt.itemsize, 16, b["dims"], 14) and _lib.bwd_boxes_ok(dt.itemsize, 16, b["dims"], 14)
     finally:
-        g.set_encoder_keys(0, 0, 0, 0)
+        route_vocab.set_encoder_keys(0, 0, 0, 0)
         _lib.set_option("inst_acc16", 0)
         _lib.set_option("wide_box", 0)
         _lib.set_variant(0)

@@ -10,22 +10,14 @@ import sys
 import tempfile
 
 import pytest
+from capi_cases import HEADER, ROOT, header_declarations as declarations
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
 
 F16_ENTRY_POINTS = [
     "%s_%s_f16" % (kind, op)
     for kind in ("boxattn", "instattn") for op in ("fwd", "bwd", "bwd_ws", "fwd_train")
 ] + ["boxattn_fwd_hl_f16", "boxattn_softmax_fwd_f16", "boxattn_softmax_bwd_f16",
      "boxattn_value_prep_f32_f16", "boxattn_value_prep_f16"]
-
-
-def declarations():
-    """name -> parameter list (whitespace-normalised) of every function the header declares."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return {m.group(1): " ".join(m.group(2).split())
-            for m in re.finditer(r"\b((?:boxattn|instattn)_\w+)\s*\(([^;{]*?)\)\s*;", text, re.S)}
 
 
 @pytest.fixture(scope="module")

@@ -4,26 +4,21 @@ table of the shapes that matter: box attention with few queries and a 14 x 14 gr
 against instance attention at the same shape, the benchmark's workloads, the switches.  The query is pure host
 code: no compute calls, there is no GPU here."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
+from capi_cases import C2, C2P, C5P, HEADER
+from route_vocab import FAST, GATHER, GENERIC, STAGED, WIDE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
 
-GENERIC, FAST, GATHER, WIDE, STAGED = range(5)
 # What the measurement decided for box attention at B=2, Lq=300, P=196 on the C2' levels, per element size
 # (profiles/inference_forward_step.log, DESIGN.md 4.1): True = the wave-per-pair family by default
 DEFAULT_WIDE_P196 = {2: True, 4: True}
 OPT_WIDE_BOX, OPT_DENSE = 22, 11
 WIDE_BOX_OFF, WIDE_BOX_ON = 1, 2
 
-C2P = [(100, 167), (50, 84), (25, 42), (13, 21)]
-C2 = [(100, 100), (50, 50), (25, 25), (13, 13)]
 C5 = [(468, 468)]
-C5P = [(234, 234), (117, 117)]
 # bench.py's workloads: levels, Lq (None: one query per pixel), P
 BOX_WORKLOADS = {"C2": (C2, None, 4), "C2p": (C2P, None, 4), "C3pp": (C2P, 300, 4), "C5": (C5, 1000, 4),
                  "C5p": (C5P, None, 4), "C5pp": (C5P, 300, 4)}

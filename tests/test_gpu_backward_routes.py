@@ -21,8 +21,8 @@ import ctypes
 import pytest
 import torch
 
-from test_gpu_partial_backward import (ALL, DECODER, P_OF, POINTS, REPEATS, SUFFIX, VALUE, _blib, call, profiled,
-                                       seeded_case, untouched)
+from point_cases import (ALL, PARTIAL_DECODER as DECODER, POINTS, P_OF, REPEATS, SUFFIX, VALUE, _blib,
+                         backward_with_plan as backward, call, profiled, seeded_case, untouched)
 
 pytestmark = pytest.mark.gpu
 
@@ -81,25 +81,6 @@ def train_plan(case):
     torch.cuda.synchronize()
     assert rc == 0 and built.value == 1, "the training forward builds a plan at this shape (%d, %d)" % (rc, built.value)
     return buf
-
-
-def backward(case, entry, want, outs, ws, plan):
-    """One raw call of *_bwd_ws_* (entry "ws") or *_bwd_part_* ("part"): ws (tensor view | None), plan (tensor | None),
-    no state.  -> rc"""
-    stem = "boxattn" if case.kind == "box" else "instattn"
-    args = [case.value, case.shapes, case.lsi, case.loc, *case.weights, case.grad_out]
-    if case.kind == "instance":
-        args.append(case.grad_mask)
-    args = [a.data_ptr() for a in args] + list(case.dims) + [t.data_ptr() for t in outs]
-    args += [case.sh.ctypes.data, case.ls.ctypes.data,
-             ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
-             plan.data_ptr() if plan is not None else 0, plan.numel() if plan is not None else 0, 0, 0, 0,
-             torch.cuda.current_stream().cuda_stream]
-    if entry == "part":
-        args.append(want)
-    rc = getattr(_blib().load(), "%s_bwd_%s_%s" % (stem, entry, SUFFIX[case.dtype]))(*args)
-    torch.cuda.synchronize()
-    return rc
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])

@@ -1,7 +1,7 @@
 """GPU tests (``-m gpu``) of box attention's training step from boxes and L*P logits: the one-launch box and logit
 gradients (``ops.box_attn_backward_boxes``, include/boxattn.h boxattn_bwd_boxes_*), the autograd
 Function on top of it (``BoxAttnBoxesFunction``) and the module flag ``fused_boxes_train`` in BoxAttention /
-Box3dAttention.  The problems are those of test_gpu_box_boxes_forward.py.
+Box3dAttention.  The problems are those of test_gpu_box_boxes_forward.py (boxes_cases.box_boxes_problem).
 
 Every seeded case holds the three outputs of the one call -- grad_offsets, grad_ref_rows, grad_logits, all float32 --
 against two expectations with ``|got - want| <= tol * (max(1, rms(want)) + |want|)``, tol 1e-4 (the point gradients
@@ -22,116 +22,29 @@ of the same call -- every element of the three outputs within a derived bound of
 boxes and logits, the rotated terms and the must-be-zero rows included -- lives in
 tests/test_gpu_boxes_error_bounds.py (test_box_backward_from_boxes; model: tests/error_bounds.py boxes_reference,
 CPU twin: tests/test_boxes_error_bounds.py).  The assertions here stay as they are."""
-import functools
-import math
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import boxattn_oracle as oc
-from test_boxes_error_bounds import grid_f32
-from test_gpu_box_boxes_forward import FLAVOURS, GEOMETRY, GOLDENS, golden_module, kernel_indices, problem
-from test_gpu_boxes_backward import EDGE_CAP, POINT_TOL, module_grads, offset_by_eight
-from test_gpu_parity import _g9_check, on_cell_edge
-from test_gpu_wide_box_forward import DTYPES, check, dev, rounded, tables, tol_of
+from boxes_cases import (BOX_BWD_CHANNELS as CHANNELS, EDGE_CAP, FLAVOURS, G9_NAMES, GOLDENS, GRAD_NAMES as NAMES,
+                         LEAVES, SMALL, _g9_check, box_boxes_problem as problem, box_bwd_case as case,
+                         box_golden_module as golden_module, box_reduce_grid as reduce_grid,
+                         box_reduce_logits as reduce_logits, box_upstream as upstream, device_args, eligible,
+                         function_inputs, golden_loss, module_grads, offset_by_eight, run_boxes_function,
+                         run_point_functions)
+from compare_rules import POINT_TOL, check_scaled as check, exact_zeros, rounded, tol_of
+from point_cases import on_cell_edge
+from route_vocab import DTYPES, dev
 
 pytestmark = pytest.mark.gpu
 
-SMALL = ["model", "ragged", "one_level", "odd_k", "sixteen_levels", "k4", "encoder"]
-CHANNELS = (16, 32, 64)
-
 
 # ------------------------------------------------------------------ the float64 reductions of expectation (b)
-def reduce_grid(ref, off, kidx, vr, angle_mode, gloc):
-    """Per-point grad_loc (B,Lq,H,L,P,2) -> grad_offsets (B,Lq,H,L,V), grad_ref_rows (B,Lq,H,L,5), float64:
-    grid_grad_add summed over the points of a row, then grid_grad_store."""
-    ref, off, kidx, gloc = (np.asarray(a, dtype=np.float64) for a in (ref, off, kidx, gloc))
-    lead = off.shape[:4]
-    r = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]
-    col = lambda j: np.broadcast_to(r[..., j], lead)
-    rw, rh = col(2), col(3)
-    w = rw + off[..., 2] / 8 * rw
-    h = rh + off[..., 3] / 8 * rh
-    sn, cs = np.zeros(lead), np.ones(lead)
-    if angle_mode:
-        theta = (col(4) + off[..., 4] / 16) * 2 * math.pi if angle_mode == 1 else col(4)
-        sn, cs = np.sin(theta), np.cos(theta)
-    sn, cs = sn[..., None], cs[..., None]
-    if vr is not None:
-        gloc = gloc * np.asarray(vr, dtype=np.float64)                  # d / d (unscaled grid)
-    gx, gy = gloc[..., 0], gloc[..., 1]
-    kx, ky = kidx[:, 0], kidx[:, 1]
-    lx, ly = kx * np.maximum(w, 0.0)[..., None], ky * np.maximum(h, 0.0)[..., None]
-    a_cx, a_cy = gx.sum(-1), gy.sum(-1)
-    a_w = np.where(w > 0, (kx * (gx * cs + gy * sn)).sum(-1), 0.0)      # d / d relu(w), relu'
-    a_h = np.where(h > 0, (ky * (gy * cs - gx * sn)).sum(-1), 0.0)
-    a_t = (gx * (-lx * sn - ly * cs) + gy * (lx * cs - ly * sn)).sum(-1)
-    go = [a_cx * rw / 8, a_cy * rh / 8, a_w * rw / 8, a_h * rh / 8]
-    if off.shape[-1] == 5:
-        go.append(a_t * 2 * math.pi / 16 if angle_mode == 1 else np.zeros(lead))
-    row_t = a_t * 2 * math.pi if angle_mode == 1 else a_t if angle_mode == 2 else np.zeros(lead)
-    rows = np.stack([a_cx, a_cy, a_cx * off[..., 0] / 8 + a_w * (1 + off[..., 2] / 8),
-                     a_cy * off[..., 1] / 8 + a_h * (1 + off[..., 3] / 8), row_t], -1)
-    return np.stack(go, -1), rows
-
-
-def reduce_logits(logits, gattn):
-    """Per-point weight gradients -> grad_logits (B,Lq,H,L*P), float64: a (g - sum a g), a the softmax of the row."""
-    z = np.asarray(logits, dtype=np.float64)
-    g = np.asarray(gattn, dtype=np.float64).reshape(z.shape)
-    e = np.exp(z - z.max(-1, keepdims=True))
-    a = e / e.sum(-1, keepdims=True)
-    return a * (g - (a * g).sum(-1, keepdims=True))
 
 
 # ------------------------------------------------------------------ one case: the call and its two expectations
-# The cases of the matrix whose inputs from ``problem`` break the cell-edge condition (a box of size <= 0 puts a whole
-# row of points on one line, and that line fell on an edge; 1-4 points of 384-1 280): the same construction from
-# another seed.  Keys: (geometry, C, angle_mode, ref_dim, per_head, with_vr).
-RESEED = {("model", 64, 0, 4, False, True): 1000003, ("model", 64, 1, 5, False, False): 1000003,
-          ("ragged", 16, 1, 5, False, False): 1000003, ("ragged", 64, 0, 4, True, False): 1000003,
-          ("sixteen_levels", 16, 2, 5, True, False): 1000003, ("sixteen_levels", 32, 1, 7, True, False): 1000003,
-          ("sixteen_levels", 32, 1, 7, True, True): 1000003, ("sixteen_levels", 32, 2, 5, True, True): 1000003,
-          ("sixteen_levels", 64, 2, 5, True, True): 2000006, ("k4", 32, 1, 5, True, True): 1000003,
-          ("k4", 32, 1, 7, False, False): 2000006, ("k4", 64, 0, 4, True, False): 1000003,
-          ("k4", 64, 1, 5, True, False): 1000003, ("k4", 64, 1, 7, True, True): 1000003,
-          ("encoder", 32, 0, 4, False, False): 1000003, ("encoder", 32, 1, 5, False, False): 1000003,
-          ("encoder", 32, 1, 7, True, True): 1000003, ("encoder", 64, 1, 7, True, False): 1000003}
-
-
-@functools.lru_cache(maxsize=None)
-def case(geometry, C, angle_mode, ref_dim, per_head, with_vr):
-    bump = RESEED.get((geometry, C, angle_mode, ref_dim, per_head, with_vr))
-    if bump is None:
-        return problem(geometry, C, angle_mode, ref_dim, per_head, with_vr)
-    make = np.random.default_rng
-    np.random.default_rng = lambda seed: make(seed + bump)           # (problem() seeds its generator from its arguments)
-    try:
-        return problem.__wrapped__(geometry, C, angle_mode, ref_dim, per_head, with_vr)
-    finally:
-        np.random.default_rng = make
-
-
-def edge_share(g):
-    """Share of the sample points of the problem ``g`` within 1e-4 px of a bilinear cell edge (float32 grid on the CPU)."""
-    from boxer_amd.modules import _kernel_offsets
-    P = g["dims"][6]
-    k = int(round(P ** 0.5))
-    kidx = _kernel_offsets(k, k).float().numpy()
-    grid = grid_f32(g["ref"], g["off"], kidx, g["vr"], g["angle_mode"])
-    return float(on_cell_edge(grid.astype(np.float64), g["shapes"]).mean())
-
-
-def upstream(g, dt, seed=0):
-    B, S, H, C, L, Lq, P = g["dims"]
-    return rounded(np.random.default_rng(100 + seed).standard_normal((B, Lq, H * C)), dt)
-
-
-def device_args(g, dt):
-    return dict(value=dev(g["value"], dt), shapes=dev(g["shapes"]), lsi=dev(g["lsi"]), ref=dev(g["ref"]),
-                off=dev(g["off"]), kidx=kernel_indices(g["dims"][6]), vr=None if g["vr"] is None else dev(g["vr"]),
-                logits=dev(g["logits"]), mode=g["angle_mode"])
 
 
 def boxes_call(a, gout):
@@ -168,44 +81,11 @@ def expectations(g, dt, a, gout64, what):
     return (goff, rows, glog), (want_off, want_rows, want_log), loc64
 
 
-NAMES = ("grad_offsets", "grad_ref_rows", "grad_logits")
-
-
 def hold(got, chain, oracle, what):
     for name, t, c, o in zip(NAMES, got, chain, oracle):
         assert t.dtype == torch.float32 and t.shape == c.shape, name
         check(t, c.double().cpu().numpy(), POINT_TOL, "%s %s against the chain" % (what, name))
         check(t, o, POINT_TOL, "%s %s against the oracle" % (what, name))
-
-
-def exact_zeros(g, got, loc64, what):
-    """Zeros where the model says zero: the size gradients of a box of decoded size <= 0, all of a row whose window
-    lies wholly outside the map, and the angle offset's gradient in mode 1 only."""
-    goff, rows, glog = (t.cpu().numpy() for t in got)
-    ref, off = g["ref"], g["off"]
-    r = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]
-    f = np.float32
-    w = np.broadcast_to(r[..., 2], off.shape[:4]) + off[..., 2] / f(8) * r[..., 2]
-    h = np.broadcast_to(r[..., 3], off.shape[:4]) + off[..., 3] / f(8) * r[..., 3]
-    assert (w <= 0).any() and (h <= 0).any(), what
-    assert not goff[..., 2][w <= 0].any() and not goff[..., 3][h <= 0].any(), "%s: relu' leaks" % what
-    size = np.asarray(g["shapes"], dtype=np.float64)[None, None, None, :, None, ::-1]
-    pix = loc64 * size - 0.5
-    outside = ((pix <= -1) | (pix >= size)).any(-1).all(-1)             # (B,Lq,H,L): every point of the row outside
-    assert outside.any(), what
-    assert not goff[outside].any() and not rows[outside].any(), "%s: a row outside the map has a gradient" % what
-    assert goff.shape[-1] == (5 if g["angle_mode"] == 1 else 4)
-    assert not rows[..., 4].any() if g["angle_mode"] == 0 else rows[..., 4].any(), what
-    if goff.shape[-1] == 5:
-        assert goff[..., 4].any(), what
-
-
-def eligible(geometry, C, dt):
-    from boxer_amd import ops
-    geo = GEOMETRY[geometry]
-    S = tables(geo["levels"])[2]
-    return ops.box_backward_boxes_ok(torch.empty(geo["B"], S, geo["H"], C, dtype=dt, device="cuda"),
-                                     len(geo["levels"]), geo["Lq"], geo["P"])
 
 
 @pytest.mark.parametrize("dtype", sorted(DTYPES))
@@ -326,32 +206,6 @@ def test_no_queries_and_no_pixels(dtype):
 
 
 # ------------------------------------------------------------------ the autograd Function
-LEAVES = ("value", "ref", "off", "logits")
-
-
-def function_inputs(g):
-    leaf = lambda x: dev(x).float().requires_grad_()
-    return dict(value=leaf(g["value"]), ref=leaf(g["ref"]), off=leaf(g["off"]), logits=leaf(g["logits"]),
-                shapes=dev(g["shapes"]), lsi=dev(g["lsi"]), kidx=kernel_indices(g["dims"][6]),
-                vr=None if g["vr"] is None else dev(g["vr"]), mode=g["angle_mode"])
-
-
-def run_boxes_function(x, dt):
-    from boxer_amd import BoxAttnBoxesFunction
-    value = x["value"] if dt == torch.float32 else x["value"].to(dt)
-    vr = None if x["vr"] is None else x["vr"].view(-1, x["off"].size(3), 2)
-    return BoxAttnBoxesFunction.apply(value, x["shapes"], x["lsi"], x["ref"], x["off"], x["kidx"], vr, x["logits"],
-                                      x["mode"])
-
-
-def run_point_functions(x, dt):
-    import boxer_amd as ba
-    B, Lq, H, L = x["off"].shape[:4]
-    grid = ba.BoxGridFunction.apply(x["ref"], x["off"], x["kidx"], x["vr"], x["mode"])
-    attn = ba.LogitSoftmaxFunction.apply(x["logits"]).view(B, Lq, H, L, -1)
-    fn = {torch.float32: ba.BoxAttnFunction, torch.bfloat16: ba.BoxAttnBF16Function,
-          torch.float16: ba.BoxAttnF16Function}[dt]
-    return fn.apply(x["value"], x["shapes"], x["lsi"], grid, attn, 64)
 
 
 @pytest.mark.parametrize("per_head", [False, True], ids=["shared_windows", "windows_per_head"])
@@ -447,12 +301,7 @@ def test_function_saves_no_per_point_tensor(dtype):
 
 
 # ------------------------------------------------------------------ the modules
-G9_NAMES = sorted(n for n in GOLDENS if n.startswith("G9"))
 G7_NAMES = sorted(n for n in GOLDENS if n.startswith("G7"))
-
-
-def golden_loss(g):
-    return lambda outs: (outs[0].double() * dev(g["gout0"]).double()).sum()
 
 
 @pytest.mark.parametrize("native_bf16", [False, True], ids=["fp32", "bf16"])

@@ -11,91 +11,18 @@ of test_gpu_wide_box_forward.py):
       rounded to the storage type.
 How many elements differ BITWISE from (a) is printed per case (the locations come from shared device functions; the
 softmax sums in another order, and the window-staged forward in yet another); it is reported, not asserted."""
-import functools
-import itertools
 
-import numpy as np
 import pytest
 import torch
 
-import golden_io
 from oracle import boxattn_oracle as oc
-from test_gpu_wide_box_forward import DTYPES, GATHER, STAGED, check, dev, rounded, tables, tol_of
+from boxes_cases import (BOX_GEOMETRY as GEOMETRY, FLAVOURS, GOLDENS, box_boxes_problem as problem,
+                         box_golden_module as golden_module, box_kernel_indices as kernel_indices, golden_err, hold,
+                         tables)
+from compare_rules import check_scaled as check, rounded
+from route_vocab import DTYPES, GATHER, STAGED, dev
 
 pytestmark = pytest.mark.gpu
-
-C2_LEVELS = [(100, 100), (50, 50), (25, 25), (13, 13)]
-GEOMETRY = {
-    # L P = 4 G at C 32 (16-bit storage): the model's shape; head = XCD placement
-    "model": dict(levels=[(9, 11), (4, 5), (3, 3), (2, 2)], B=2, Lq=5, H=8, P=4),
-    # L P = 12: a ragged last tile at G = 8; 42 pairs: dead waves in the last workgroup; L no power of two
-    "ragged": dict(levels=[(5, 7), (3, 4), (1, 3)], B=2, Lq=7, H=3, P=4),
-    "one_level": dict(levels=[(6, 5)], B=1, Lq=3, H=2, P=4),
-    # an odd kernel size: tiles that straddle levels
-    "odd_k": dict(levels=[(6, 5), (3, 2)], B=1, Lq=3, H=2, P=9),
-    # L P = 64 both ways
-    "sixteen_levels": dict(levels=[(1, 1), (2, 1)] * 8, B=1, Lq=3, H=2, P=4),
-    "k4": dict(levels=[(9, 11), (4, 5), (3, 3), (2, 2)], B=1, Lq=3, H=2, P=16),
-    # one query a pixel, windows of four pixels of the query's level: the three launches take the window-staged forward
-    "encoder": dict(levels=[(8, 8), (4, 4)], B=1, Lq=80, H=2, P=4),
-    # more than 8 workgroups: the XCD re-map and the magic divisions
-    "mid": dict(levels=C2_LEVELS, B=2, Lq=300, H=8, P=4),
-    "mid_h3": dict(levels=C2_LEVELS, B=2, Lq=300, H=3, P=4),
-}
-# (angle_mode, ref_dim) x per_head x with_vr
-FLAVOURS = list(itertools.product(((0, 4), (1, 5), (1, 7), (2, 5)), (False, True), (False, True)))
-
-
-def kernel_indices(P):
-    """The modules' buffer for a k x k kernel (P = k * k), divisor k."""
-    from boxer_amd.modules import _kernel_offsets
-    k = int(round(P ** 0.5))
-    assert k * k == P
-    return _kernel_offsets(k, k).float().cuda().contiguous()
-
-
-@functools.lru_cache(maxsize=None)
-def problem(geometry, C, angle_mode, ref_dim, per_head, with_vr):
-    """numpy / float32 inputs of one case (the same for every storage type)."""
-    geo = GEOMETRY[geometry]
-    shapes, lsi, S = tables(geo["levels"])
-    B, Lq, H, L, P = geo["B"], geo["Lq"], geo["H"], len(geo["levels"]), geo["P"]
-    V = 5 if angle_mode == 1 else 4
-    rng = np.random.default_rng(7919 * C + 31 * P + 1000 * sorted(GEOMETRY).index(geometry) + 8 * angle_mode
-                                + 2 * ref_dim + per_head)
-    rshape = (B, Lq, H) if per_head else (B, Lq)
-    ref = np.concatenate([rng.uniform(0.05, 0.95, rshape + (2,)), rng.uniform(0.05, 0.7, rshape + (2,)),
-                          rng.uniform(-3.0, 3.0, rshape + (ref_dim - 4,))], -1)
-    if geometry == "encoder":                      # query i = pixel i: a window of four pixels of its own level
-        rows = []
-        for hl, wl in geo["levels"]:
-            ys, xs = np.meshgrid(np.arange(hl), np.arange(wl), indexing="ij")
-            rows.append(np.stack([(xs.ravel() + 0.5) / wl, (ys.ravel() + 0.5) / hl,
-                                  np.full(hl * wl, 4.0 / wl), np.full(hl * wl, 4.0 / hl)], -1))
-        win = np.concatenate(rows, 0)[None]        # (1, S, 4)
-        ref[..., :4] = win[:, :, None, :] if per_head else win
-    flat = ref.reshape(-1, ref_dim)
-    flat[0, :4] = (2.6, 2.4, 0.2, 0.3)                       # a window wholly outside the map (valid ratios >= 0.5)
-    flat[1, :4] = (0.97, 0.02, 0.5, 0.4)                     # ... and one partly outside
-    flat[-1, :4] = (-0.7, 0.5, 0.3, 0.3)                     # wholly outside on the other side
-    if ref_dim > 4:
-        flat[2 % len(flat), 4] = 23.0                        # angles of several turns (mode 2: radians; 1: turns)
-        flat[3 % len(flat), 4] = -7.25
-    off = 3.0 * rng.standard_normal((B, Lq, H, L, V))
-    if geometry == "encoder":
-        off[..., :4] *= 0.5
-    rows = off.reshape(-1, V)
-    rows[rng.random(len(rows)) < 0.15, 2] = -12.0            # negative predicted sizes: relu puts every point on the
-    rows[rng.random(len(rows)) < 0.15, 3] = -9.5             # centre line / centre
-    rows[0, 2:4] = -8.0                                      # size exactly zero: w + (-8 / 8) w
-    if V == 5:
-        rows[1, 4] = 77.0                                    # 4.8 turns
-    logits = 3.0 * rng.standard_normal((B, Lq, H, L * P))
-    logits += 30.0 * np.where(rng.random((B, Lq, H, 1)) < 0.5, -1.0, 1.0)
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    return dict(shapes=shapes, lsi=lsi, S=S, dims=(B, S, H, C, L, Lq, P), value=rng.standard_normal((B, S, H, C)),
-                ref=f32(ref), off=f32(off), logits=f32(logits), angle_mode=angle_mode,
-                vr=f32(rng.uniform(0.5, 1.0, (B, 1, 1, L, 1, 2))) if with_vr else None)
 
 
 def three_route(geometry, C):
@@ -125,16 +52,6 @@ def run_case(g, dt, route, value=None):
     want = oc.box_attn_forward(rounded(g["value"], dt), g["shapes"], g["lsi"], grid.double().cpu().numpy(),
                                attn.double().cpu().numpy())
     return got, three, want
-
-
-def hold(got, three, want, dt, what):
-    tol = tol_of(dt)
-    assert got.dtype == dt and got.shape == three.shape
-    bits = torch.int32 if dt == torch.float32 else torch.int16
-    differ = int((got.view(bits) != three.view(bits)).sum().item())
-    print("%s: %d of %d elements differ bitwise from the three launches" % (what, differ, got.numel()))
-    check(got, three.double().cpu().numpy(), tol, "%s against the three launches" % what)
-    check(got, want, tol, "%s against the oracle" % what)
 
 
 def all_flavours(geometry, C, dtype):
@@ -239,54 +156,10 @@ def test_ops_refuse_what_has_no_kernel():
 
 
 # ------------------------------------------------------------------ the modules
-# name -> (class, constructor arguments, v_mask given, valid ratios given, (float32, bf16) tolerance on the output as
-# test_gpu_parity.py holds the golden to: max |got - want| / max(1, max |want|))
-G7 = dict(d_model=32, num_level=2, num_head=4)
-G9 = dict(d_model=256, num_level=4, num_head=8)
-GOLDENS = {
-    "G7_module_box": ("BoxAttention", dict(G7, kernel_size=2), True, True, (1e-4, 2e-2)),
-    "G7_module_box_perhead": ("BoxAttention", dict(G7, kernel_size=2), False, False, (1e-4, 2e-2)),
-    "G7_module_box3d_rot": ("Box3dAttention", dict(G7, with_rotation=True, kernel_size=2), True, True, (1e-4, 2e-2)),
-    "G7_module_box3d_fixed": ("Box3dAttention", dict(G7, with_rotation=False, kernel_size=3), False, False,
-                              (1e-4, 2e-2)),
-    "G9_module_box_dec": ("BoxAttention", dict(G9, kernel_size=2), True, True, (2e-4, 4e-2)),
-    "G9_module_box_enc": ("BoxAttention", dict(G9, kernel_size=2), True, True, (2e-4, 4e-2)),
-    "G9_module_box_enc_masked": ("BoxAttention", dict(G9, kernel_size=2), True, True, (2e-4, 4e-2)),
-    "G9_module_box3d_rot_dec": ("Box3dAttention", dict(G9, with_rotation=True, kernel_size=2), True, True,
-                                (2e-4, 4e-2)),
-    "G9_module_box3d_fixed_enc": ("Box3dAttention", dict(G9, with_rotation=False, kernel_size=2), True, True,
-                                  (2e-4, 4e-2)),
-}
-
-
-def golden_module(name, native_bf16=False):
-    import boxer_amd
-    cls, kw, with_mask, with_ratio, _ = GOLDENS[name]
-    g = golden_io.load(name)
-    m = getattr(boxer_amd, cls)(**kw).double()
-    m.load_state_dict({k[3:]: torch.from_numpy(v) for k, v in g.items() if k.startswith("sd.")}, strict=True)
-    m = m.float().cuda()
-    assert m.fused_boxes is False                    # the default: nothing changes unless it is set
-    m.native_bf16 = native_bf16
-
-    def t(key, given=True):
-        if not given or key not in g:
-            return None
-        x = dev(g[key])
-        return x.float() if x.is_floating_point() else x
-    args = (t("query"), t("value"), dev(g["shapes"]), t("v_mask", with_mask), dev(g["lsi"]), t("ratios", with_ratio),
-            t("ref_windows"))
-    return m, g, args
 
 
 def golden_out(g):
     return g["out0"] if "out0" in g else g["out"]
-
-
-def golden_err(got, want):
-    got = got.detach().double().cpu().numpy()
-    want = np.asarray(want, dtype=np.float64).reshape(got.shape)
-    return float(np.abs(got - want).max()) / max(1.0, float(np.abs(want).max()))
 
 
 class CallCounter:

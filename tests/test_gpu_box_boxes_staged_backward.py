@@ -4,7 +4,7 @@ boxattn_bwd_boxes_hl_*), the autograd Function on top of it and o
 (``BoxAttnBoxesStagedFunction``) and the module flag ``fused_boxes_train_staged`` in BoxAttention / Box3dAttention.
 Every case has one query a pixel, 32 channels a head and 2 x 2 points a level: the only shapes the entry accepts.
 
-The inputs are test_gpu_box_boxes_staged_forward.problem's -- the geometries (whole tiles, ragged tiles, H = 3, a level
+The inputs are boxes_cases.staged_problem's -- the geometries (whole tiles, ragged tiles, H = 3, a level
 smaller than a tile, a 1 x 1 level, a staged sub-window) and the two families: ``local``, served from the staged
 windows, and ``scattered``, the in-kernel global path -- four of them from another seed
 (tests/test_box_boxes_staged_backward_cases.py: the cell-edge condition of every case, proven on the CPU).
@@ -27,21 +27,16 @@ import torch
 
 import error_bounds as eb
 import isolation as iso
-from test_box_boxes_staged_backward_cases import MATRIX, case
-from test_gpu_box_boxes_backward import LEAVES, exact_zeros, function_inputs, run_boxes_function, run_point_functions
-from test_gpu_box_boxes_staged_forward import C, FAMILIES, P, encoder_module, flavours_of, operands
-from test_gpu_boxes_backward import POINT_TOL
-from test_gpu_boxes_error_bounds import GRAD_NAMES, every_type, kernel_offsets, must_be_zero, report
-from test_gpu_wide_box_forward import DTYPES, STAGED, check, dev, tol_of
+from boxes_cases import (FAMILIES, GRAD_NAMES, LEAVES, MATRIX, STAGED_C as C, STAGED_P as P, encoder_module,
+                         flavours_of, function_inputs, kernel_offsets, operands, run_boxes_function,
+                         run_point_functions, run_staged_backward as run_staged, staged_bwd_case as case,
+                         staged_upstream as upstream)
+from compare_rules import POINT_TOL, check_scaled as check, exact_zeros, must_be_zero, report_bound as report, tol_of
+from route_vocab import DTYPES, STAGED, dev
 
 pytestmark = pytest.mark.gpu
 
 SPLIT = "none"            # grad_loc / grad_attn of the window-staged point-gradient route, every storage type
-
-
-def upstream(g):
-    B, S, H, _, L, Lq, _ = g["dims"]
-    return every_type(np.random.default_rng(100).standard_normal((B, Lq, H * C)))     # (every storage type holds it)
 
 
 @functools.lru_cache(maxsize=16)
@@ -50,18 +45,6 @@ def reference(geometry, family, flavour):
     g = case(geometry, family, *flavour[0], *flavour[1:])
     return eb.boxes_reference("box", g["value"], g["shapes"], g["lsi"], g["ref"], g["off"], kernel_offsets(2), g["vr"],
                               g["logits"], g["angle_mode"], grad_out=upstream(g))
-
-
-def run_staged(g, args, gout, need_ref_grad=True):
-    from boxer_amd import ops
-    B, S, H, _, L, Lq, _ = g["dims"]
-    assert ops.box_backward_boxes_staged_ok(args[0], args[1], args[2], Lq, P), "not eligible: %s" % (g["dims"],)
-    got = ops.box_attn_backward_boxes_staged(*args, gout, need_ref_grad=need_ref_grad)
-    V = 5 if g["angle_mode"] == 1 else 4
-    assert tuple(got[0].shape) == (B, Lq, H, L, V) and tuple(got[2].shape) == (B, Lq, H, L * P)
-    assert (got[1] is None) != need_ref_grad and (got[1] is None or tuple(got[1].shape) == (B, Lq, H, L, 5))
-    assert all(t is None or t.dtype == torch.float32 for t in got)
-    return got
 
 
 def chain(g, args, gout):
@@ -456,7 +439,7 @@ def test_outputs_depend_on_nothing_their_definition_does_not_name(family, dtype)
 def test_outputs_are_isolated_on_the_edge_family(edge, dtype):
     """isolation.boxes_problem on the levels of "four_levels", one query a pixel: every level's boxes crowd into one
     patch astride ``edge``, most of every level is unreferenced, and the rows a careless kernel would fetch instead are."""
-    from test_gpu_box_boxes_staged_forward import GEOMETRY
+    from boxes_cases import STAGED_GEOMETRY as GEOMETRY
     dt = DTYPES[dtype]
     geo = GEOMETRY["four_levels"]
     g = iso.boxes_problem(geo["levels"], "S", 2, edge, kind="box", B=geo["B"], H=geo["H"], angle_mode=1, ref_dim=5,

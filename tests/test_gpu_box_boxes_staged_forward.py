@@ -3,7 +3,7 @@
 ``fused_boxes_staged`` that takes it in BoxAttention / Box3dAttention.  Every case has one query a pixel, 32 channels
 a head and 2 x 2 points a level: the only shapes the entry accepts.
 
-Two families of inputs per geometry, both with the poisoned rows of test_gpu_box_boxes_forward.problem (windows wholly and
+Two families of inputs per geometry, both with the poisoned rows of boxes_cases.box_boxes_problem (windows wholly and
 partly outside the map, negative and exactly-zero sizes, angles of several turns):
   local      query i is pixel i, its window the pixel's centre and four pixels of its level, offsets x 0.5: the points
              are served from the staged windows;
@@ -22,84 +22,16 @@ How many elements differ BITWISE from the three launches is printed, not asserte
 the softmax sums in another order)."""
 import functools
 
-import numpy as np
 import pytest
 import torch
 
 import error_bounds as eb
-from test_gpu_box_boxes_forward import C2_LEVELS, FLAVOURS, hold, kernel_indices, tables
-from test_gpu_boxes_error_bounds import every_type, kernel_offsets, report
-from test_gpu_wide_box_forward import DTYPES, STAGED, check, dev, tol_of
+from boxes_cases import (FAMILIES, STAGED_C as C, STAGED_P as P, STAGED_SPLIT as SPLIT, encoder_module, flavours_of,
+                         hold, kernel_offsets, operands, run_staged_forward as run_staged, staged_problem as problem)
+from compare_rules import check_scaled as check, report_bound as report, tol_of
+from route_vocab import DTYPES, STAGED, dev
 
 pytestmark = pytest.mark.gpu
-
-C, P = 32, 4
-GEOMETRY = {
-    "two_levels": dict(levels=[(8, 8), (4, 4)], B=1, H=2),                               # whole tiles
-    # ragged tiles on every level, a head count that is neither 8 nor a power of two
-    "four_levels": dict(levels=[(37, 23), (19, 12), (10, 6), (5, 3)], B=2, H=3),
-    "three_levels": dict(levels=[(16, 16), (8, 8), (4, 4)], B=1, H=8),
-    "one_level": dict(levels=[(9, 13)], B=2, H=1),
-    "tiny_levels": dict(levels=[(4, 5), (2, 3), (1, 1)], B=1, H=2),                      # smaller than a tile, a 1 x 1 level
-    # tile numbering and XCD order beyond a handful of workgroups (test_mid_size only)
-    "mid": dict(levels=C2_LEVELS, B=2, H=8),
-}
-FAMILIES = ["local", "scattered"]
-SPLIT = {"f32": "none", "bf16": "bf16", "f16": "f16"}
-
-
-@functools.lru_cache(maxsize=None)
-def problem(geometry, family, angle_mode, ref_dim, per_head, with_vr):
-    """numpy / float32 inputs of one case (the same for every storage type): test_gpu_box_boxes_forward.problem with one
-    query a pixel and the two families."""
-    geo = GEOMETRY[geometry]
-    shapes, lsi, S = tables(geo["levels"])
-    B, H, L, Lq = geo["B"], geo["H"], len(geo["levels"]), S
-    V = 5 if angle_mode == 1 else 4
-    rng = np.random.default_rng(104729 + 1000 * sorted(GEOMETRY).index(geometry) + 500 * FAMILIES.index(family)
-                                + 8 * angle_mode + 2 * ref_dim + per_head)
-    rshape = (B, Lq, H) if per_head else (B, Lq)
-    ref = np.concatenate([rng.uniform(0.05, 0.95, rshape + (2,)), rng.uniform(0.05, 0.7, rshape + (2,)),
-                          rng.uniform(-3.0, 3.0, rshape + (ref_dim - 4,))], -1)
-    if family == "local":                          # query i = pixel i: a window of four pixels of its own level
-        rows = []
-        for hl, wl in geo["levels"]:
-            ys, xs = np.meshgrid(np.arange(hl), np.arange(wl), indexing="ij")
-            rows.append(np.stack([(xs.ravel() + 0.5) / wl, (ys.ravel() + 0.5) / hl,
-                                  np.full(hl * wl, 4.0 / wl), np.full(hl * wl, 4.0 / hl)], -1))
-        win = np.concatenate(rows, 0)[None]        # (1, S, 4)
-        ref[..., :4] = win[:, :, None, :] if per_head else win
-    flat = ref.reshape(-1, ref_dim)
-    flat[0, :4] = (2.6, 2.4, 0.2, 0.3)                       # a window wholly outside the map (valid ratios >= 0.5)
-    flat[1, :4] = (0.97, 0.02, 0.5, 0.4)                     # ... and one partly outside
-    flat[-1, :4] = (-0.7, 0.5, 0.3, 0.3)                     # wholly outside on the other side
-    if ref_dim > 4:
-        flat[2 % len(flat), 4] = 23.0                        # angles of several turns (mode 2: radians; 1: turns)
-        flat[3 % len(flat), 4] = -7.25
-    off = 3.0 * rng.standard_normal((B, Lq, H, L, V))
-    if family == "local":
-        off[..., :4] *= 0.5
-    rows = off.reshape(-1, V)
-    rows[rng.random(len(rows)) < 0.15, 2] = -12.0            # negative predicted sizes: relu puts every point on the
-    rows[rng.random(len(rows)) < 0.15, 3] = -9.5             # centre line / centre
-    rows[0, 2:4] = -8.0                                      # size exactly zero: w + (-8 / 8) w
-    if V == 5:
-        rows[1, 4] = 77.0                                    # 4.8 turns
-    logits = 3.0 * rng.standard_normal((B, Lq, H, L * P))
-    logits += 30.0 * np.where(rng.random((B, Lq, H, 1)) < 0.5, -1.0, 1.0)
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    return dict(shapes=shapes, lsi=lsi, S=S, dims=(B, S, H, C, L, Lq, P),
-                value=every_type(rng.standard_normal((B, S, H, C))),     # (numbers every storage type holds exactly)
-                ref=f32(ref), off=f32(off), logits=f32(logits), angle_mode=angle_mode,
-                vr=f32(rng.uniform(0.5, 1.0, (B, 1, 1, L, 1, 2))) if with_vr else None)
-
-
-def flavours_of(geometry):
-    """The 16 flavours; for the largest geometry of the matrix the four (angle mode, reference values) pairs with
-    windows per head / valid ratios alternating (its float64 model is the slowest)."""
-    if geometry != "four_levels":
-        return FLAVOURS
-    return [(pair, i % 2 == 1, i % 2 == 0) for i, pair in enumerate(sorted({f[0] for f in FLAVOURS}))]
 
 
 @functools.lru_cache(maxsize=16)
@@ -109,12 +41,6 @@ def reference(geometry, family, flavour):
     g = problem(geometry, family, angle_mode, ref_dim, per_head, with_vr)
     return eb.boxes_reference("box", g["value"], g["shapes"], g["lsi"], g["ref"], g["off"], kernel_offsets(2), g["vr"],
                               g["logits"], g["angle_mode"])["out"]
-
-
-def operands(g, dt, value=None):
-    return (dev(g["value"], dt) if value is None else value, dev(g["shapes"]), dev(g["lsi"]), dev(g["ref"]),
-            dev(g["off"]), kernel_indices(P), None if g["vr"] is None else dev(g["vr"]), dev(g["logits"]),
-            g["angle_mode"])
 
 
 def three_launches(g, args):
@@ -127,15 +53,6 @@ def three_launches(g, args):
     taken = ops.forward_route(value, grid, shapes, lsi)
     assert taken == STAGED, "the three launches take route %d, wanted the window-staged one" % taken
     return ops.box_attn_forward(value, shapes, lsi, grid, attn, 64), grid
-
-
-def run_staged(g, args):
-    from boxer_amd import ops
-    B, S, H, _, L, Lq, _ = g["dims"]
-    assert ops.box_forward_boxes_staged_ok(args[0], args[1], args[2], Lq, P), "not eligible: %s" % (g["dims"],)
-    out = ops.box_attn_forward_boxes_staged(*args)
-    assert out.dtype == args[0].dtype and tuple(out.shape) == (B, Lq, H * C)
-    return out
 
 
 @pytest.mark.parametrize("dtype", sorted(DTYPES))
@@ -228,33 +145,6 @@ def test_mid_size(dtype):
 
 
 # ------------------------------------------------------------------ the modules
-LEVELS = [(8, 8), (4, 4)]
-
-
-def encoder_module(kind, native_bf16):
-    """BoxAttention / rotated Box3dAttention with 2 heads of 32 channels and random parameters, and a small encoder input
-    built as boxer_amd.layers builds it: -> (module, forward arguments)."""
-    import boxer_amd
-    from boxer_amd import layers
-    torch.manual_seed(11)
-    if kind == "box":
-        m = boxer_amd.BoxAttention(64, len(LEVELS), 2)
-    else:
-        m = boxer_amd.Box3dAttention(64, len(LEVELS), 2, with_rotation=True)
-    for p in m.parameters():
-        torch.nn.init.normal_(p, std=0.1)
-    m = m.cuda()
-    m.native_bf16 = native_bf16
-    m.fused_grid = m.fused_pointwise = True
-    shapes, lsi, S = tables(LEVELS)
-    B = 2
-    if kind == "box":
-        ref = layers.encoder_ref_windows_2d(LEVELS, B, device="cuda")
-    else:
-        ref = layers.encoder_ref_windows_3d(LEVELS, B, device="cuda")[:, :, :2].contiguous()
-    src = torch.randn(B, S, 64, device="cuda")
-    ratios = 0.5 + 0.5 * torch.rand(B, 1, 1, len(LEVELS), 1, 2, device="cuda")
-    return m, (src + 0.1 * torch.randn_like(src), src, dev(shapes), None, dev(lsi), ratios, ref)
 
 
 class StagedCalls:

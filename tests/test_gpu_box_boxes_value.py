@@ -2,13 +2,13 @@
 (``ops.box_attn_backward_boxes_value``, include/boxattn.h boxattn_bwd_boxes_value_*), the autograd
 Function ``BoxAttnBoxesValueFunction`` and the modules' ``fused_boxes_value`` flag.
 
-grad_value is held per element to ``test_box_boxes_value_cases.value_reference``: the float64 model from boxes and
+grad_value is held per element to ``boxes_cases.value_reference``: the float64 model from boxes and
 logits (tests/test_box_boxes_value_cases.py checks that yardstick without a GPU), stored in the storage type, split
 "none" -- the kernel adds a w_k g[c] in float32, whatever the storage type.  The order of the atomic adds is not fixed,
 so nothing here compares two grad_values bit for bit; the three parameter gradients of the same call are
 ``torch.equal`` to ``ops.box_attn_backward_boxes``'s, which has no atomics.
 
-The shapes are those of tests/test_gpu_boxes_error_bounds.py (imported): ragged has 42 pairs (dead waves in the last
+The shapes are those of tests/test_gpu_boxes_error_bounds.py (tests/boxes_cases.py): ragged has 42 pairs (dead waves in the last
 workgroup; L no power of two), sixteen_levels has more levels than lanes in a group (several passes, lanes without a
 level) and every query adding into the same 1 x 1 / 2 x 1 maps, one_level and odd_k the tile edges; the problems hold
 windows wholly outside the map and boxes of size <= 0.  Each case prints ``error-bound | route | type | output | worst
@@ -17,27 +17,20 @@ import pytest
 import torch
 
 import error_bounds as eb
-import test_gpu_box_boxes_backward as sibling
-import test_gpu_boxes_error_bounds as gpu_cases
-from test_box_boxes_value_cases import model_of, must_be_zero_share, value_reference
-from test_gpu_boxes_error_bounds import (BOX_GEOMETRIES, CHANNELS, DTYPES, box_args, bwd_problem, bwd_upstream, dev,
-                                         offset_by_eight, report)
+import boxes_cases
+import compare_rules
+from boxes_cases import (BOX_GEOMETRIES, CHANNELS, box_args, bwd_problem, bwd_upstream, model_of, offset_by_eight,
+                         same_parameter_gradients, value_call, value_reference)
+from compare_rules import must_be_zero_share, report_bound as report
+from route_vocab import DTYPES, dev
 
 pytestmark = pytest.mark.gpu
 
-FLAVOURS = gpu_cases.box_cases.FLAVOURS
-NAMES = gpu_cases.GRAD_NAMES
+FLAVOURS = boxes_cases.FLAVOURS
 
 
 def flavour_text(geometry, C, flavour):
     return "%s C=%d angle=%d D=%d per_head=%d vr=%d" % ((geometry, C) + flavour[0] + flavour[1:])
-
-
-def value_call(args, gout, want=3, need_ref_grad=True):
-    from boxer_amd import ops
-    res = ops.box_attn_backward_boxes_value(*args, gout, want=want, need_ref_grad=need_ref_grad)
-    torch.cuda.synchronize()
-    return res
 
 
 def points_call(args, gout):
@@ -50,11 +43,6 @@ def points_call(args, gout):
 def hold_value(got, ref, dt, value, what):
     assert got.dtype == dt and got.shape == value.shape and got.is_contiguous(), what
     return eb.hold(got, ref, dt, "none", what + ": grad_value")
-
-
-def same_parameter_gradients(got, base, what):
-    for name, x, y in zip(NAMES, got, base):
-        assert x.dtype == torch.float32 and torch.equal(x, y), "%s: %s differs from box_attn_backward_boxes" % (what, name)
 
 
 # (the topmost parametrisation varies fastest: the three types of a (geometry, C) run one after the other on the cached
@@ -123,7 +111,7 @@ def test_rows_offset_by_eight_bytes(dtype, geometry):
     flavour = ((1, 5), True, True)
     g = bwd_problem(geometry, 32, flavour)
     B, S, H, C, L, Lq, P = g["dims"]
-    args = box_args(g, dt, value=offset_by_eight(dev(gpu_cases.every_type(g["value"]), dt)))
+    args = box_args(g, dt, value=offset_by_eight(dev(boxes_cases.every_type(g["value"]), dt)))
     gout = offset_by_eight(dev(bwd_upstream(g), dt))
     assert ops.box_backward_boxes_value_ok(args[0], L, Lq, P), "not eligible at this alignment: %s %s" % (g["dims"], dt)
     what = "box backward with grad_value, rows 8 bytes off: %s C=32 [%s storage]" % (geometry, dtype)
@@ -138,7 +126,7 @@ _mid_references = {}
 
 def mid_reference(angle_mode):
     if angle_mode not in _mid_references:
-        g = sibling.problem(MID, 32, angle_mode, 5 if angle_mode else 4, False, True)
+        g = boxes_cases.box_boxes_problem(MID, 32, angle_mode, 5 if angle_mode else 4, False, True)
         _mid_references[angle_mode] = (g, model_of(g, bwd_upstream(g)))
     return _mid_references[angle_mode]
 
@@ -158,7 +146,7 @@ def test_mid_size(dtype, angle_mode):
 
 
 def raw_entry(dtype, a, dims, gout, want, grad_value, ws, ws_bytes, outs):
-    """boxattn_bwd_boxes_value_* with the device arguments ``a`` (test_gpu_box_boxes_backward.device_args)."""
+    """boxattn_bwd_boxes_value_* with the device arguments ``a`` (boxes_cases.device_args)."""
     from boxer_amd import _lib
     entry = getattr(_lib.load(), "boxattn_bwd_boxes_value_" + dtype)
     ptr = lambda t: None if t is None else t.data_ptr()
@@ -174,10 +162,10 @@ def test_no_queries_and_no_pixels(dtype):
     parameter gradients are zeros."""
     from boxer_amd import _lib
     dt = DTYPES[dtype]
-    g = sibling.case("model", 32, 1, 5, False, True)
+    g = boxes_cases.box_bwd_case("model", 32, 1, 5, False, True)
     B, S, H, C, L, Lq, P = g["dims"]
-    a = sibling.device_args(g, dt)
-    gout = dev(sibling.upstream(g, dt), dt)
+    a = boxes_cases.device_args(g, dt)
+    gout = dev(boxes_cases.box_upstream(g, dt), dt)
     outs = [torch.full((B, Lq, H, L, n), 7.0, dtype=torch.float32, device="cuda") for n in (5, 5, P)]
     ws_bytes = _lib.box_bwd_boxes_value_workspace_bytes(a["value"].element_size(), g["dims"])
     ws = torch.full((max(ws_bytes // 4, 4),), 3.0, dtype=torch.float32, device="cuda")
@@ -201,7 +189,7 @@ def test_no_queries_and_no_pixels(dtype):
 
 def test_argument_errors_come_before_any_device_call():
     from boxer_amd import ops
-    g = sibling.case("model", 32, 1, 5, False, True)
+    g = boxes_cases.box_bwd_case("model", 32, 1, 5, False, True)
     B, S, H, C, L, Lq, P = g["dims"]
     args = box_args(g, torch.float32)
     gout = dev(bwd_upstream(g), torch.float32)
@@ -257,7 +245,7 @@ def only(name):
 
 def exact_problem(g):
     """``g`` with a value every storage type holds exactly: one float64 model serves the three types."""
-    return dict(g, value=gpu_cases.every_type(g["value"]))
+    return dict(g, value=boxes_cases.every_type(g["value"]))
 
 
 def run_function(fn, x, dt):
@@ -274,28 +262,28 @@ def test_function_against_the_function_it_completes(dtype):
     weights."""
     from boxer_amd import BoxAttnBoxesFunction, BoxAttnBoxesValueFunction, _lib
     dt = DTYPES[dtype]
-    g = exact_problem(sibling.case("model", 32, 1, 5, False, True))
+    g = exact_problem(boxes_cases.box_bwd_case("model", 32, 1, 5, False, True))
     gout64 = bwd_upstream(g)
     gout = dev(gout64).float()
     ref = model_of(g, gout64)
     res = {}
     for name, fn in (("value", BoxAttnBoxesValueFunction), ("boxes", BoxAttnBoxesFunction)):
-        x = sibling.function_inputs(g)
+        x = boxes_cases.function_inputs(g)
         out = run_function(fn, x, dt)
         with Spies() as spies:
             (out.float() * gout).sum().backward()
         torch.cuda.synchronize()
-        res[name] = (out, [x[n].grad for n in sibling.LEAVES], spies.n)
+        res[name] = (out, [x[n].grad for n in boxes_cases.LEAVES], spies.n)
     (o_v, g_v, n_v), (o_b, g_b, n_b) = res["value"], res["boxes"]
     assert o_v.dtype == dt and torch.equal(o_v, o_b)
     assert n_v == only("box_attn_backward_boxes_value"), n_v
     assert n_b["box_attn_backward_boxes_value"] == 0 and n_b["box_attn_backward_boxes"] == 1, n_b
-    for name, a, b in zip(sibling.LEAVES, g_v, g_b):
+    for name, a, b in zip(boxes_cases.LEAVES, g_v, g_b):
         assert a is not None and a.dtype == torch.float32 and a.shape == b.shape, name
         if name != "value":
             assert torch.equal(a, b), "gradient of %s differs from BoxAttnBoxesFunction's" % name
     acc = _lib.bwd_accumulate_kind(2 if dt != torch.float32 else 4, 0, g["dims"])
-    from test_gpu_error_bounds import split_of
+    from route_vocab import split_of
     what = "Function, model C=32 [%s storage]" % dtype
     report("BoxAttnBoxesValueFunction: " + what, dt, "grad_value", eb.hold(g_v[0], ref, dt, "none", what))
     report("BoxAttnBoxesFunction: " + what, dt, "grad_value",
@@ -307,17 +295,17 @@ def test_function_computes_only_what_is_asked_for(dtype):
     """A frozen ``value``: want = 2 and no grad_value; frozen heads: want = 1; each time one call."""
     from boxer_amd import BoxAttnBoxesValueFunction, ops
     dt = DTYPES[dtype]
-    g = exact_problem(sibling.case("model", 32, 1, 5, False, True))
+    g = exact_problem(boxes_cases.box_bwd_case("model", 32, 1, 5, False, True))
     gout = dev(bwd_upstream(g)).float()
-    full = sibling.function_inputs(g)
+    full = boxes_cases.function_inputs(g)
     (run_function(BoxAttnBoxesValueFunction, full, dt).float() * gout).sum().backward()
     ref = model_of(g, bwd_upstream(g))
     wants = []
     orig = ops.box_attn_backward_boxes_value
     spy = lambda *a, **k: wants.append(k["want"]) or orig(*a, **k)
     for only, want in (("value", 1), ("logits", 2), ("off", 2), (None, 3)):
-        x = sibling.function_inputs(g)
-        for n in sibling.LEAVES:
+        x = boxes_cases.function_inputs(g)
+        for n in boxes_cases.LEAVES:
             x[n].requires_grad_(only is None or n == only)
         out = run_function(BoxAttnBoxesValueFunction, x, dt)
         del wants[:]
@@ -330,7 +318,7 @@ def test_function_computes_only_what_is_asked_for(dtype):
         torch.cuda.synchronize()
         assert wants == [want], (only, wants)
         assert spies.n["box_attn_backward"] == 0 and spies.n["box_grid_forward"] == 0 and spies.n["softmax_forward"] == 0
-        for n in sibling.LEAVES:
+        for n in boxes_cases.LEAVES:
             if only is not None and n != only:
                 assert x[n].grad is None, (only, n)
             elif n == "value":
@@ -343,11 +331,11 @@ def test_function_computes_only_what_is_asked_for(dtype):
 def test_function_saves_no_per_point_tensor_and_builds_none_in_the_backward(dtype):
     from boxer_amd import BoxAttnBoxesValueFunction, ops
     dt = DTYPES[dtype]
-    g = sibling.case("k4", 32, 1, 5, True, True)
-    if not sibling.eligible("k4", 32, dt):
-        g = sibling.case("odd_k", 32, 1, 5, True, True)
+    g = boxes_cases.box_bwd_case("k4", 32, 1, 5, True, True)
+    if not boxes_cases.eligible("k4", 32, dt):
+        g = boxes_cases.box_bwd_case("odd_k", 32, 1, 5, True, True)
     B, S, H, C, L, Lq, P = g["dims"]
-    x = sibling.function_inputs(g)
+    x = boxes_cases.function_inputs(g)
     out = run_function(BoxAttnBoxesValueFunction, x, dt)
     saved = [t for t in out.grad_fn.saved_tensors if t is not None]
     value_bytes = B * S * H * C * (4 if dt == torch.float32 else 2)
@@ -366,7 +354,7 @@ def test_function_saves_no_per_point_tensor_and_builds_none_in_the_backward(dtyp
     finally:
         ops.box_grid_forward, ops.softmax_forward = orig
     torch.cuda.synchronize()
-    assert all(x[n].grad is not None for n in sibling.LEAVES)
+    assert all(x[n].grad is not None for n in boxes_cases.LEAVES)
 
 
 # ------------------------------------------------------------------ the modules
@@ -375,14 +363,14 @@ def both_flags(m, value):
 
 
 @pytest.mark.parametrize("native_bf16", [False, True], ids=["fp32", "bf16"])
-@pytest.mark.parametrize("name", sibling.G9_NAMES)
+@pytest.mark.parametrize("name", boxes_cases.G9_NAMES)
 def test_module_reference_golden(name, native_bf16):
     """The G9 goldens with ``fused_boxes_train`` and ``fused_boxes_value``: fewer queries than pixels -> exactly one
     ``ops.box_attn_backward_boxes_value`` call and no other backward; as many queries as pixels (the encoder
     goldens) -> ``BoxAttnBoxesFunction`` as without the flag.  Either way the output and every gradient meet the
     reference's at the tolerances tests/test_gpu_box_boxes_backward.py holds these fixtures to.  ``fused_boxes_value``
     alone changes nothing."""
-    m, g, args = sibling.golden_module(name, native_bf16)
+    m, g, args = boxes_cases.box_golden_module(name, native_bf16)
     assert m.fused_boxes_value is False
     Lq, S = args[0].size(1), args[1].size(1)
     cross = Lq < S
@@ -391,41 +379,41 @@ def test_module_reference_golden(name, native_bf16):
     rms_only = ("ref_windows", "linear_box", "query") if native_bf16 else ()
     both_flags(m, True)
     with Spies() as spies:
-        outs, grads = sibling.module_grads(m, args, sibling.golden_loss(g), torch.bfloat16 if native_bf16 else None)
+        outs, grads = boxes_cases.module_grads(m, args, boxes_cases.golden_loss(g), torch.bfloat16 if native_bf16 else None)
     torch.cuda.synchronize()
     assert outs[1] == ()
     if cross:
         assert spies.n == only("box_attn_backward_boxes_value"), spies.n
     else:
         assert spies.n["box_attn_backward_boxes_value"] == 0 and spies.n["box_attn_backward_boxes"] == 1, spies.n
-    sibling._g9_check(name, outs[:1], grads, g, tol, "fused_boxes_value bf16=%s" % native_bf16, rms_only=rms_only)
+    boxes_cases._g9_check(name, outs[:1], grads, g, tol, "fused_boxes_value bf16=%s" % native_bf16, rms_only=rms_only)
     m.fused_boxes_train, m.fused_boxes_value = False, True
     with Spies() as spies:
-        outs, _ = sibling.module_grads(m, args, sibling.golden_loss(g), torch.bfloat16 if native_bf16 else None)
+        outs, _ = boxes_cases.module_grads(m, args, boxes_cases.golden_loss(g), torch.bfloat16 if native_bf16 else None)
     assert spies.n["box_attn_backward_boxes_value"] == 0 and isinstance(outs[1], torch.Tensor)
 
 
-@pytest.mark.parametrize("name", [n for n in sibling.G9_NAMES if not n.endswith("_dec")])
+@pytest.mark.parametrize("name", [n for n in boxes_cases.G9_NAMES if not n.endswith("_dec")])
 def test_module_with_as_many_queries_as_pixels_is_unchanged(name):
     """Lq = S: the flag changes nothing -- the output and the parameter gradients are bit for bit those without it
     (the same Function, whose grad_value sums in a fixed order at these shapes or within 1e-4 where it does not)."""
-    m, g, args = sibling.golden_module(name)
+    m, g, args = boxes_cases.box_golden_module(name)
     res = {}
     for flag in (False, True):
         both_flags(m, flag)
-        res[flag] = sibling.module_grads(m, args, sibling.golden_loss(g))
+        res[flag] = boxes_cases.module_grads(m, args, boxes_cases.golden_loss(g))
     torch.cuda.synchronize()
     (o_off, g_off), (o_on, g_on) = res[False], res[True]
     assert torch.equal(o_on[0], o_off[0])
     for k in g_on:
-        sibling.check(g_on[k], g_off[k].double().cpu().numpy(), 1e-4, "%s gradient of %s" % (name, k))
+        compare_rules.check_scaled(g_on[k], g_off[k].double().cpu().numpy(), 1e-4, "%s gradient of %s" % (name, k))
 
 
 @pytest.mark.parametrize("what", ["float64", "cpu", "no_grad", "instance"])
 def test_module_falls_through(what):
     """Flags on where the step from boxes does not run: no call of the new backward."""
     import boxer_amd
-    m, g, args = sibling.golden_module("G9_module_box_dec")
+    m, g, args = boxes_cases.box_golden_module("G9_module_box_dec")
     args = list(args)
     both_flags(m, True)
     if what == "cpu":
@@ -446,7 +434,7 @@ def test_module_falls_through(what):
             with torch.no_grad():
                 out, weights = m(*args)
         else:
-            (out, weights), grads = sibling.module_grads(m, args, lambda outs: outs[0].square().sum())
+            (out, weights), grads = boxes_cases.module_grads(m, args, lambda outs: outs[0].square().sum())
             assert all(v is not None for v in grads.values())
     torch.cuda.synchronize()
     assert spies.n["box_attn_backward_boxes_value"] == 0 and spies.n["box_attn_backward_boxes"] == 0, spies.n

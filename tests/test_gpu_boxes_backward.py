@@ -15,107 +15,27 @@ are float32 in every storage mode):
 A sample point within 1e-4 px of a bilinear cell edge has an ambiguous grad_loc and cannot be left out of a sum: for
 those points only, (b) takes the chain's per-point grad_loc.  Their share is printed and must stay <= 0.2 % of a case's
 points (a condition on the inputs, not a tolerance; tests/test_boxes_backward_cases.py checks it without a GPU)."""
-import functools
-import itertools
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import boxattn_oracle as oc
-from test_gpu_boxes_forward import GEOMETRY, KERNEL_SIZES, golden_module, kernel_indices, problem
-from test_gpu_parity import _g9_check, on_cell_edge
-from test_gpu_wide_box_forward import DTYPES, check, dev, module_problem, rounded, tol_of
+from boxes_cases import (EDGE_CAP, GRAD_NAMES as NAMES, INST_BOXES_FLAVOURS as FLAVOURS, INST_GEOMETRY as GEOMETRY,
+                         KERNEL_SIZES, LEAVES, _g9_check, inst_bwd_case as case, inst_golden_module as golden_module,
+                         inst_kernel_indices as kernel_indices, inst_reduce_grid as reduce_grid,
+                         inst_reduce_logits as reduce_logits, module_grads, module_problem, offset_by_eight)
+from compare_rules import POINT_TOL, check_scaled as check, rounded, tol_of
+from point_cases import on_cell_edge
+from route_vocab import DTYPES, dev
 
 pytestmark = pytest.mark.gpu
 
-POINT_TOL = 1e-4
-EDGE_CAP = 2e-3
-FLAVOURS = list(itertools.product((False, True), (False, True), (True, False)))     # per_head, with_vr, with_mask
-
 
 # ------------------------------------------------------------------ the float64 reductions of expectation (b)
-def grid_f32(ref, off, kidx, vr):
-    """The sampling grid (B,Lq,H,L,P,2) in float32 numpy: grid_box / grid_point of boxattn_grid.h, operation by
-    operation (angle_mode 0)."""
-    f = np.float32
-    r = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]             # (B,Lq,1|H,1,4)
-    rw, rh = r[..., 2], r[..., 3]
-    cx = r[..., 0] + off[..., 0] / f(8) * rw
-    cy = r[..., 1] + off[..., 1] / f(8) * rh
-    w = rw + off[..., 2] / f(8) * rw
-    h = rh + off[..., 3] / f(8) * rh
-    gx = cx[..., None] + kidx[:, 0] * np.maximum(w, f(0))[..., None]
-    gy = cy[..., None] + kidx[:, 1] * np.maximum(h, f(0))[..., None]
-    grid = np.stack([gx, gy], -1).astype(f)
-    return grid * vr if vr is not None else grid                                    # vr: (B,1,1,L,1,2)
-
-
-def edge_share(g, k):
-    """Share of the sample points of the problem ``g`` within 1e-4 px of a bilinear cell edge (float32 grid on the CPU)."""
-    from boxer_amd.modules import _kernel_offsets
-    kidx = _kernel_offsets(k, k).float().numpy()
-    return float(on_cell_edge(grid_f32(g["ref"], g["off"], kidx, g["vr"]).astype(np.float64), g["shapes"]).mean())
-
-
-def reduce_grid(ref, off, kidx, vr, gloc):
-    """Per-point grad_loc (B,Lq,H,L,P,2) -> grad_offsets (B,Lq,H,L,4), grad_ref_rows (B,Lq,H,L,5), float64."""
-    ref, off, kidx, gloc = (np.asarray(a, dtype=np.float64) for a in (ref, off, kidx, gloc))
-    r = ref[:, :, None, None] if ref.ndim == 3 else ref[:, :, :, None]
-    rw, rh = np.broadcast_to(r[..., 2], off.shape[:4]), np.broadcast_to(r[..., 3], off.shape[:4])
-    w = rw + off[..., 2] / 8 * rw
-    h = rh + off[..., 3] / 8 * rh
-    if vr is not None:
-        gloc = gloc * np.asarray(vr, dtype=np.float64)                  # d / d (unscaled grid)
-    gx, gy = gloc[..., 0], gloc[..., 1]
-    a_cx, a_cy = gx.sum(-1), gy.sum(-1)
-    a_w = np.where(w > 0, (kidx[:, 0] * gx).sum(-1), 0.0)               # d / d relu(w), relu'
-    a_h = np.where(h > 0, (kidx[:, 1] * gy).sum(-1), 0.0)
-    go = np.stack([a_cx * rw / 8, a_cy * rh / 8, a_w * rw / 8, a_h * rh / 8], -1)
-    rows = np.stack([a_cx, a_cy, a_cx * off[..., 0] / 8 + a_w * (1 + off[..., 2] / 8),
-                     a_cy * off[..., 1] / 8 + a_h * (1 + off[..., 3] / 8), np.zeros_like(a_cx)], -1)
-    return go, rows
-
-
-def reduce_logits(logits, k, gsw, glw):
-    """Per-point weight gradients (B,Lq,H,L,k*k) -> grad_logits (B,Lq,H,L,2,2), float64:
-    grad_z[c] = a[c] / m^2 (Gs[c] - sum_c' a[c'] Gs[c']) + t[c] (Gt[c] - sum_l' t[l'] Gt[l'])."""
-    z = np.asarray(logits, dtype=np.float64)
-    m = k // 2
-    lead = z.shape[:4]
-    cells = lambda g: np.asarray(g, dtype=np.float64).reshape(lead + (2, m, 2, m)).sum((-1, -3))
-    e = np.exp(z - z.max((-1, -2, -3), keepdims=True))
-    a = e / e.sum((-1, -2, -3), keepdims=True)
-    Gs = cells(gsw)
-    gz = a / (m * m) * (Gs - (a * Gs).sum((-1, -2, -3), keepdims=True))
-    if glw is not None:
-        e = np.exp(z - z.max(-3, keepdims=True))
-        t = e / e.sum(-3, keepdims=True)
-        Gt = cells(glw)
-        gz = gz + t * (Gt - (t * Gt).sum(-3, keepdims=True))
-    return gz
 
 
 # ------------------------------------------------------------------ one case: the call and its two expectations
-# The cases of the matrix whose inputs from ``problem`` break the cell-edge condition (a box of size <= 0 puts a whole
-# row of points on one line, and that line fell on an edge): the same construction from another seed.
-RESEED = {("five_levels", 16, 6, False, False): 1000003, ("five_levels", 64, 14, True, True): 1000003,
-          ("head_xcd", 16, 14, False, True): 2000006, ("head_xcd", 32, 4, True, True): 2000006,
-          ("sixteen_levels", 16, 4, False, True): 1000003, ("sixteen_levels", 32, 4, False, False): 1000003,
-          ("sixteen_levels", 64, 4, True, True): 1000003}
-
-
-@functools.lru_cache(maxsize=None)
-def case(geometry, C, k, per_head, with_vr):
-    bump = RESEED.get((geometry, C, k, per_head, with_vr))
-    if bump is None:
-        return problem(geometry, C, k, per_head, with_vr)
-    make = np.random.default_rng
-    np.random.default_rng = lambda seed: make(seed + bump)           # (problem() seeds its generator from its arguments)
-    try:
-        return problem.__wrapped__(geometry, C, k, per_head, with_vr)
-    finally:
-        np.random.default_rng = make
 
 
 def upstream(g, k, dt, seed=0):
@@ -179,9 +99,6 @@ def expectations(g, k, dt, a, gout64, gmask64, what):
     return (goff, rows, glog), (want_off, want_rows, want_log)
 
 
-NAMES = ("grad_offsets", "grad_ref_rows", "grad_logits")
-
-
 def hold(got, chain, oracle, what):
     for name, t, c, o in zip(NAMES, got, chain, oracle):
         assert t.dtype == torch.float32 and t.shape == c.shape, name
@@ -224,14 +141,6 @@ def test_two_runs_are_bitwise_equal(k, dtype):
     torch.cuda.synchronize()
     for name, x, y in zip(NAMES, first, again):
         assert torch.equal(x, y), "%s: two runs differ (the kernel has no atomics)" % name
-
-
-def offset_by_eight(t):
-    flat = torch.zeros(t.numel() + 4, dtype=t.dtype, device="cuda")
-    out = flat[4:].view(t.shape)
-    out.copy_(t)
-    assert out.data_ptr() % 16 == 8 and out.is_contiguous()
-    return out
 
 
 @pytest.mark.parametrize("with_mask", [True, False], ids=["mask", "no_mask"])
@@ -296,9 +205,6 @@ def run_point_functions(x, k, dt):
     fn = {torch.float32: ba.InstanceAttnFunction, torch.bfloat16: ba.InstanceAttnBF16Function,
           torch.float16: ba.InstanceAttnF16Function}[dt]
     return fn.apply(x["value"], x["shapes"], x["lsi"], grid, sw, lw, k, 64)
-
-
-LEAVES = ("value", "ref", "off", "logits")
 
 
 def loss_of(outs, gout, gmask):
@@ -400,16 +306,6 @@ def test_function_saves_no_per_point_tensor(dtype):
 
 
 # ------------------------------------------------------------------ the module
-def module_grads(m, args, loss_fn, autocast=None):
-    m.zero_grad()
-    query, value, ref = (args[0].clone().requires_grad_(), args[1].clone().requires_grad_(),
-                         args[6].clone().requires_grad_())
-    with torch.autocast("cuda", dtype=autocast or torch.float16, enabled=autocast is not None):
-        outs = m(query, value, args[2], args[3], args[4], args[5], ref)
-    loss_fn(outs).backward()
-    grads = {"query": query.grad, "value": value.grad, "ref_windows": ref.grad}
-    grads.update({"param." + n: p.grad.clone() for n, p in m.named_parameters()})
-    return outs, grads
 
 
 @pytest.mark.parametrize("native_bf16", [False, True], ids=["fp32", "bf16"])

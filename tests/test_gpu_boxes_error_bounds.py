@@ -6,257 +6,38 @@ building blocks each way (``ops.box_grid_forward`` / ``box_grid_backward``, ``op
 offsets, kernel_indices, valid ratios, logits), with nothing taken from a GPU chain.
 
 The problems are those of tests/test_gpu_box_boxes_forward.py, tests/test_gpu_box_boxes_backward.py,
-tests/test_gpu_boxes_forward.py and tests/test_gpu_boxes_backward.py (imported, not copied).  ``value`` and the upstream
-gradients are rounded to bf16 and then to f16: numbers every storage type holds exactly, so one reference serves the
-three types.  A case whose share of points within EDGE_PX + slack of a cell edge is above EDGE_CAP takes another seed
+tests/test_gpu_boxes_forward.py and tests/test_gpu_boxes_backward.py (all of them built in tests/boxes_cases.py).
+``value`` and the upstream gradients are rounded to bf16 and then to f16: numbers every storage type holds exactly, so
+one reference serves the three types.  A case whose share of points within EDGE_PX + slack of a cell edge is above
+EDGE_CAP takes another seed
 (RESEED for the instance matrix, BWD_RESEED for the box training step; tests/test_boxes_error_bounds.py checks every
 input here without a GPU).  The building blocks' backward kernels get exact float32 upstream gradients, so their bound
 is the reduction's own roundings, the rotation allowance and the weights' dw.  Each case prints ``error-bound | route |
 type | output | worst err / bound``; profiles/boxes_error_bounds.log and profiles/box_boxes_backward_error_bounds.log
 are that table from one run each."""
-import functools
-import itertools
 
 import numpy as np
 import pytest
 import torch
 
 import error_bounds as eb
-import test_gpu_box_boxes_forward as box_cases
-import test_gpu_boxes_forward as inst_cases
+import boxes_cases
+import boxes_cases as box_cases
+from boxes_cases import (BOX_GEOMETRIES, CHANNELS, GRAD_NAMES, GRID_FLAVOURS, GRID_POINTS, INST_FLAVOURS,
+                         SOFTMAX_BWD_LENGTHS, SOFTMAX_BWD_ROWS, box_args, box_problem, box_reference, bwd_problem,
+                         bwd_reference, bwd_upstream, cell_rows, cell_upstream, every_type, grid_problem, grid_upstream,
+                         inst_problem, inst_reference, inst_upstream, kernel_offsets, offset_by_eight,
+                         softmax_bwd_problem, softmax_rows)
+from compare_rules import must_be_zero, report_bound as report, within
+from route_vocab import DTYPES, dev
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
-BOX_GEOMETRIES = ["model", "ragged", "one_level", "odd_k", "sixteen_levels", "k4", "encoder"]
-CHANNELS = [16, 32, 64]
-INST_FLAVOURS = list(itertools.product((False, True), (False, True)))          # per_head, with_vr
-# (geometry, C, k, per_head, with_vr) -> what is added to the seed of test_gpu_boxes_forward.problem
-RESEED = {}
-
-
-def kernel_offsets(k):
-    """The modules' kernel_indices buffer of a k x k kernel, float32 numpy."""
-    from boxer_amd.modules import _kernel_offsets
-    return _kernel_offsets(k, k).float().numpy()
-
-
-def every_type(a):
-    """float64 numbers that float32, bf16 and f16 all hold exactly: rounded to bf16, then to f16 (which changes a bf16
-    number only below 2^-17, to a multiple of 2^-24 of at most 7 bits)."""
-    return eb.round_to(eb.round_to(a, "bf16"), "f16")
-
-
-def report(route, dtype, name, worst):
-    print("error-bound | %s | %s | %s | %.3f" % (route, eb.store_name(dtype), name, worst))
-
 
 # ------------------------------------------------------------------ inputs and references (CPU)
-def box_problem(geometry, C, flavour):
-    (angle_mode, ref_dim), per_head, with_vr = flavour
-    return box_cases.problem(geometry, C, angle_mode, ref_dim, per_head, with_vr)
-
-
-@functools.lru_cache(maxsize=16)
-def box_reference(geometry, C, flavour):
-    g = box_problem(geometry, C, flavour)
-    P = g["dims"][6]
-    return eb.boxes_reference("box", every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
-                              kernel_offsets(int(round(P ** 0.5))), g["vr"], g["logits"], g["angle_mode"])
-
-
-@functools.lru_cache(maxsize=None)
-def inst_problem(geometry, C, k, per_head, with_vr):
-    """test_gpu_boxes_backward.case (test_gpu_boxes_forward.problem, re-seeded where that file had to), re-seeded again
-    where the condition with the locations' own slack asks for it."""
-    from test_gpu_boxes_backward import case
-    bump = RESEED.get((geometry, C, k, per_head, with_vr))
-    if bump is None:
-        return case(geometry, C, k, per_head, with_vr)
-    make = np.random.default_rng
-    np.random.default_rng = lambda seed: make(seed + bump)
-    try:
-        return inst_cases.problem.__wrapped__(geometry, C, k, per_head, with_vr)
-    finally:
-        np.random.default_rng = make
-
-
-def inst_upstream(g, k):
-    B, S, H, C, L, Lq = g["dims"]
-    rng = np.random.default_rng(100)
-    return every_type(rng.standard_normal((B, Lq, H * C))), every_type(rng.standard_normal((B, Lq, k * k, H * C)))
-
-
-@functools.lru_cache(maxsize=8)
-def inst_reference(geometry, C, k, per_head, with_vr, with_mask):
-    """with_mask: {out, mask_out, the three gradients with grad_mask}; without: {out, the gradients without}."""
-    g = inst_problem(geometry, C, k, per_head, with_vr)
-    gout, gmask = inst_upstream(g, k)
-    return eb.boxes_reference("instance", every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
-                              kernel_offsets(k), g["vr"], g["logits"], 0, k, gout, gmask if with_mask else None)
-
-
-GRAD_NAMES = ("grad_offsets", "grad_ref_rows", "grad_logits")
-# (geometry, C, angle_mode, ref_dim, per_head, with_vr) -> what is added to the seed test_gpu_box_boxes_backward.case
-# uses, where the condition with the locations' own slack asks for it
-BWD_RESEED = {("k4", 32, 2, 5, False, True): 1000003}           # 2 points of 768 (0.26 %) with the slack, 1 without
-
-
-@functools.lru_cache(maxsize=None)
-def bwd_problem(geometry, C, flavour):
-    """test_gpu_box_boxes_backward.case (the forward's problem, re-seeded where that file had to), re-seeded again
-    where the share of points within EDGE_PX + slack of a cell edge is above EDGE_CAP."""
-    import test_gpu_box_boxes_backward as bwd_cases
-    (angle_mode, ref_dim), per_head, with_vr = flavour
-    key = (geometry, C, angle_mode, ref_dim, per_head, with_vr)
-    bump = BWD_RESEED.get(key)
-    if bump is None:
-        return bwd_cases.case(*key)
-    make = np.random.default_rng
-    np.random.default_rng = lambda seed: make(seed + bwd_cases.RESEED.get(key, 0) + bump)
-    try:
-        return box_cases.problem.__wrapped__(*key)
-    finally:
-        np.random.default_rng = make
-
-
-def bwd_upstream(g):
-    B, S, H, C, L, Lq, P = g["dims"]
-    return every_type(np.random.default_rng(100).standard_normal((B, Lq, H * C)))
-
-
-def bwd_model_args(g):
-    P = g["dims"][6]
-    return ("box", every_type(g["value"]), g["shapes"], g["lsi"], g["ref"], g["off"],
-            kernel_offsets(int(round(P ** 0.5))), g["vr"], g["logits"], g["angle_mode"])
-
-
-@functools.lru_cache(maxsize=16)
-def bwd_reference(geometry, C, flavour):
-    """{out, grad_offsets, grad_ref_rows, grad_logits, edge_share, points} of the training step from boxes."""
-    g = bwd_problem(geometry, C, flavour)
-    return eb.boxes_reference(*bwd_model_args(g), grad_out=bwd_upstream(g))
-
-
-@functools.lru_cache(maxsize=None)
-def grid_upstream(P, angle_mode, per_head, with_vr):
-    """float32 grad_grid (B, Lq, H, L, P, 2) for ops.box_grid_backward on its own: randn, a few rows of zeros."""
-    g = grid_problem(P, angle_mode, per_head, with_vr)
-    rng = np.random.default_rng(900 + P)
-    gg = rng.standard_normal(g["off"].shape[:4] + (P, 2))
-    gg[0, 1] = 0.0
-    return np.ascontiguousarray(gg, dtype=np.float32)
-
-
-SOFTMAX_BWD_LENGTHS = [1, 3, 4, 8, 12, 18, 32, 63, 64]
-SOFTMAX_BWD_ROWS = [1, 257]
-
-
-@functools.lru_cache(maxsize=None)
-def softmax_bwd_problem(rows, n):
-    """-> (attn: the float64 softmax of softmax_rows(n)'s kinds rounded to float32, grad_attn float32), (rows, n)."""
-    z = np.resize(softmax_rows(n), (rows, n)).astype(np.float64)
-    rng = np.random.default_rng(1000 * rows + n)
-    z = z + 0.5 * (np.arange(rows) >= 8)[:, None] * rng.standard_normal((rows, n))      # (the first 8 rows: as they are)
-    a, _ = eb.softmax_reference(z)
-    g = rng.standard_normal((rows, n)) * np.exp2(rng.integers(-6, 7, (rows, 1)))
-    return np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(g, dtype=np.float32)
-
-
-@functools.lru_cache(maxsize=None)
-def cell_upstream(L, k):
-    """float32 grad_spatial, grad_level (1, 8, 1, L, k, k) for ops.instance_weights_backward on its own."""
-    rng = np.random.default_rng(70 * L + k)
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    return f32(rng.standard_normal((1, 8, 1, L, k, k))), f32(rng.standard_normal((1, 8, 1, L, k, k)))
-
-
-GRID_POINTS = [1, 4, 9, 196]
-GRID_FLAVOURS = list(itertools.product((0, 1, 2), (False, True), (False, True)))   # angle_mode, per_head, with_vr
-
-
-@functools.lru_cache(maxsize=None)
-def grid_problem(P, angle_mode, per_head, with_vr):
-    """A few boxes for ops.box_grid_forward on its own: windows inside, partly and wholly outside the map, sizes below
-    and exactly zero, angles of 23 and -7.25 (turns in mode 1, radians in mode 2) and an offset angle of 77 / 16 turns."""
-    B, Lq, H, L = 2, 5, 3, 2
-    D, V = (7 if angle_mode else 4), (5 if angle_mode == 1 else 4)
-    rng = np.random.default_rng(500 + 10 * P + 3 * angle_mode + per_head)
-    rshape = (B, Lq, H) if per_head else (B, Lq)
-    ref = np.concatenate([rng.uniform(0.05, 0.95, rshape + (2,)), rng.uniform(0.05, 0.7, rshape + (2,)),
-                          rng.uniform(-3.0, 3.0, rshape + (D - 4,))], -1)
-    flat = ref.reshape(-1, D)
-    flat[0, :4] = (2.6, 2.4, 0.2, 0.3)
-    flat[1, :4] = (0.97, 0.02, 0.5, 0.4)
-    flat[-1, :4] = (-0.7, 0.5, 0.3, 0.3)
-    if D > 4:
-        flat[2, 4], flat[3, 4] = 23.0, -7.25
-    off = 3.0 * rng.standard_normal((B, Lq, H, L, V))
-    rows = off.reshape(-1, V)
-    rows[rng.random(len(rows)) < 0.15, 2] = -12.0
-    rows[0, 2:4] = -8.0
-    if V == 5:
-        rows[1, 4] = 77.0
-    k = int(round(P ** 0.5))
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    return dict(ref=f32(ref), off=f32(off), kidx=kernel_offsets(k), angle_mode=angle_mode,
-                vr=f32(rng.uniform(0.5, 1.0, (B, 1, 1, L, 1, 2))) if with_vr else None)
-
-
-@functools.lru_cache(maxsize=None)
-def softmax_rows(n):
-    """Rows of n logits: 3 randn; the same with a shared shift of +- 30; a spread of 60 (one logit on top, the others
-    60 and 30 below); all equal; float32."""
-    rng = np.random.default_rng(n)
-    z = 3.0 * rng.standard_normal((8, n))
-    z[2:4] += np.asarray([[30.0], [-30.0]])
-    z[4] = np.where(np.arange(n) % 2 == 0, -60.0, -30.0)
-    z[4, n // 2] = 0.0
-    z[5] = 1.25
-    z[6] = np.linspace(-60.0, 0.0, n)
-    return np.ascontiguousarray(z, dtype=np.float32)
-
-
-@functools.lru_cache(maxsize=None)
-def cell_rows(L):
-    """(1, 8, 1, L, 2, 2) logits of the same kinds for ops.instance_weights_forward."""
-    return softmax_rows(4 * L).reshape(1, 8, 1, L, 2, 2)
-
-
-def within(got, want, allowance, what):
-    """Assert |got - want| <= allowance per element; -> the worst ratio."""
-    got = eb.f64(got).reshape(want.shape)
-    err = np.abs(got - want)
-    assert np.isfinite(got).all(), what
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(err == 0, 0.0, err / allowance)
-    worst = float(r.max()) if r.size else 0.0
-    at = np.unravel_index(int(np.argmax(r)), r.shape)
-    assert worst <= 1.0, "%s: %d of %d elements outside the allowance; worst at %s: got %.9g, want %.9g, allowed %.3e" \
-        % (what, int((r > 1).sum()), r.size, at, got[at], want[at], np.broadcast_to(allowance, want.shape)[at])
-    return worst
 
 
 # ------------------------------------------------------------------ running
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return t.to(dtype) if dtype is not None else t
-
-
-def offset_by_eight(t):
-    flat = torch.zeros(t.numel() + 4, dtype=t.dtype, device="cuda")
-    out = flat[4:].view(t.shape)
-    out.copy_(t)
-    assert out.data_ptr() % 16 == 8 and out.is_contiguous()
-    return out
-
-
-def box_args(g, dt, value=None):
-    B, S, H, C, L, Lq, P = g["dims"]
-    value = dev(every_type(g["value"]), dt) if value is None else value
-    return (value, dev(g["shapes"]), dev(g["lsi"]), dev(g["ref"]), dev(g["off"]),
-            dev(kernel_offsets(int(round(P ** 0.5)))), None if g["vr"] is None else dev(g["vr"]), dev(g["logits"]),
-            g["angle_mode"])
 
 
 def run_box(g, dt, value=None):
@@ -307,9 +88,9 @@ def test_box_forward_value_offset_by_eight_bytes(geometry, dtype):
 
 
 @pytest.mark.parametrize("dtype", sorted(DTYPES))
-@pytest.mark.parametrize("k", inst_cases.KERNEL_SIZES)
+@pytest.mark.parametrize("k", boxes_cases.KERNEL_SIZES)
 @pytest.mark.parametrize("C", CHANNELS)
-@pytest.mark.parametrize("geometry", sorted(inst_cases.GEOMETRY))
+@pytest.mark.parametrize("geometry", sorted(boxes_cases.INST_GEOMETRY))
 def test_instance_forward_and_backward_from_boxes(geometry, C, k, dtype):
     """ops.instance_attn_forward_boxes with and without mask_out and ops.instance_attn_backward_boxes with and without
     grad_mask (need_ref_grad), windows shared and per head x valid ratios None and given; the gradients are float32 in
@@ -396,7 +177,7 @@ def test_softmax_forward_of_16_bit_logits_is_within_dw(n, dtype):
     softmax_forward_within_dw(n, dtype)
 
 
-@pytest.mark.parametrize("k", inst_cases.KERNEL_SIZES)
+@pytest.mark.parametrize("k", boxes_cases.KERNEL_SIZES)
 @pytest.mark.parametrize("L", [1, 5, 16])
 def test_instance_weights_forward_is_within_dw(L, k):
     from boxer_amd import ops
@@ -410,8 +191,6 @@ def test_instance_weights_forward_is_within_dw(L, k):
 
 
 # ------------------------------------------------------------------ the box training step from boxes
-def must_be_zero(ref):
-    return int(((ref["A"] + ref["E"]) == 0).sum())
 
 
 @pytest.mark.parametrize("dtype", sorted(DTYPES))
@@ -548,7 +327,7 @@ def test_softmax_backward_grad_attn_off_a_16_byte_boundary(dtype):
 
 
 @pytest.mark.parametrize("dtype", sorted(DTYPES))
-@pytest.mark.parametrize("k", inst_cases.KERNEL_SIZES)
+@pytest.mark.parametrize("k", boxes_cases.KERNEL_SIZES)
 @pytest.mark.parametrize("L", [1, 5, 16])
 def test_instance_weights_backward_is_within_the_bound(L, k, dtype):
     """ops.instance_weights_backward against the 2 x 2-logit reduction of the model, exact float32 upstream gradients,

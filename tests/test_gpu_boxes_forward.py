@@ -11,57 +11,19 @@ of test_gpu_wide_box_forward.py):
       rounded to the storage type.
 How many elements differ BITWISE from (a) is printed per case (locations and weights come from shared device
 functions, so none is expected); it is reported, not asserted."""
-import functools
 import itertools
 
-import numpy as np
 import pytest
 import torch
 
-import golden_io
 from oracle import boxattn_oracle as oc
-from test_gpu_wide_box_forward import DTYPES, WIDE, check, dev, module_problem, rounded, tables, take_family, tol_of
+from boxes_cases import (INST_BOXES_FLAVOURS as FLAVOURS, INST_GEOMETRY as GEOMETRY, KERNEL_SIZES, golden_err,
+                         inst_boxes_problem as problem, inst_golden_module as golden_module,
+                         inst_kernel_indices as kernel_indices, module_problem)
+from compare_rules import check_scaled as check, rounded, tol_of
+from route_vocab import DTYPES, WIDE, dev, take_family
 
 pytestmark = pytest.mark.gpu
-
-# five_levels: more levels than a 4-lane group (the box is decoded again for l0 > 0), 30 pairs with a last workgroup of
-# dead waves, L no power of two; head_xcd: head = XCD placement; one_level; sixteen_levels: the widest cell group
-GEOMETRY = {"five_levels": dict(levels=[(5, 7), (3, 4), (2, 2), (1, 3), (1, 1)], B=2, Lq=5, H=3),
-            "head_xcd": dict(levels=[(9, 11), (4, 5)], B=2, Lq=4, H=8),
-            "one_level": dict(levels=[(6, 5)], B=1, Lq=3, H=2),
-            "sixteen_levels": dict(levels=[(1, 1), (2, 1)] * 8, B=1, Lq=3, H=2)}
-KERNEL_SIZES = [4, 6, 14]           # one, two and four waves a pair; m odd at k = 6; a ragged last step
-FLAVOURS = list(itertools.product((False, True), (False, True), (True, False)))     # per_head, with_vr, need_mask
-
-
-def kernel_indices(k):
-    from boxer_amd.modules import _kernel_offsets
-    return _kernel_offsets(k, k).float().cuda().contiguous()
-
-
-@functools.lru_cache(maxsize=None)
-def problem(geometry, C, k, per_head, with_vr):
-    """numpy / float32 inputs of one case (the same for every storage type and both mask flavours)."""
-    geo = GEOMETRY[geometry]
-    shapes, lsi, S = tables(geo["levels"])
-    B, Lq, H, L = geo["B"], geo["Lq"], geo["H"], len(geo["levels"])
-    rng = np.random.default_rng(7919 * C + 31 * k + 2 * sorted(GEOMETRY).index(geometry) + per_head)
-    rshape = (B, Lq, H) if per_head else (B, Lq)
-    ref = np.concatenate([rng.uniform(0.05, 0.95, rshape + (2,)), rng.uniform(0.05, 0.7, rshape + (2,))], -1)
-    ref.reshape(-1, 4)[0] = (2.6, 2.4, 0.2, 0.3)             # a window wholly outside the map (valid ratios >= 0.5)
-    ref.reshape(-1, 4)[1] = (0.97, 0.02, 0.5, 0.4)           # ... and one partly outside
-    ref.reshape(-1, 4)[-1] = (-0.7, 0.5, 0.3, 0.3)           # wholly outside on the other side
-    off = 3.0 * rng.standard_normal((B, Lq, H, L, 4))
-    flat = off.reshape(-1, 4)
-    flat[rng.random(len(flat)) < 0.15, 2] = -12.0            # negative predicted sizes: relu puts every point on the
-    flat[rng.random(len(flat)) < 0.15, 3] = -9.5             # centre line / centre
-    flat[0, 2:] = -8.0                                       # size exactly zero: w + (-8 / 8) w
-    logits = 3.0 * rng.standard_normal((B, Lq, H, L, 2, 2))
-    logits += 30.0 * np.where(rng.random((B, Lq, H, 1, 1, 1)) < 0.5, -1.0, 1.0)
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    return dict(shapes=shapes, lsi=lsi, S=S, dims=(B, S, H, C, L, Lq), value=rng.standard_normal((B, S, H, C)),
-                ref=f32(ref), off=f32(off), logits=f32(logits),
-                vr=f32(rng.uniform(0.5, 1.0, (B, 1, 1, L, 1, 2))) if with_vr else None)
 
 
 def run_case(g, k, dt, need_mask, value=None):
@@ -168,23 +130,6 @@ def test_ops_refuse_what_has_no_kernel():
 
 
 # ------------------------------------------------------------------ the module
-def golden_module(native_bf16):
-    from boxer_amd import InstanceAttention
-    g = golden_io.load("G9_module_inst_k4")
-    m = InstanceAttention(256, 4, 8, 4).double()
-    m.load_state_dict({k[3:]: torch.from_numpy(v) for k, v in g.items() if k.startswith("sd.")}, strict=True)
-    m = m.float().cuda()
-    assert m.fused_boxes is False
-    m.native_bf16 = native_bf16
-    f = lambda key: dev(g[key]).float()
-    return m, g, (f("query"), f("value"), dev(g["shapes"]), dev(g["v_mask"]), dev(g["lsi"]), f("ratios"),
-                  f("ref_windows"))
-
-
-def golden_err(got, want):
-    got = got.detach().double().cpu().numpy()
-    want = np.asarray(want, dtype=np.float64).reshape(got.shape)
-    return float(np.abs(got - want).max()) / max(1.0, float(np.abs(want).max()))
 
 
 @pytest.mark.parametrize("native_bf16", [False, True], ids=["fp32", "bf16"])

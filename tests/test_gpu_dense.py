@@ -12,17 +12,12 @@ import pytest
 import torch
 
 import bench
+from point_cases import LEVELS, _lib, make_dense_case as make_case
+from route_vocab import OPT_ACC_F32, OPT_DENSE, OPT_RIDERS
 
 pytestmark = pytest.mark.gpu
 
-OPT_DENSE = 11          # boxattn_set_option key: 0 library default, 1 dense kernels off, 2 on
-OPT_RIDERS = 15         # count / scan / fill / combine inside the forward, point-gradient, accumulate launches: 0 on, 1 off
 OPT_DENSE_FWD = OPT_DENSE   # (ABI 8: one switch for the family -- forward and point gradients, both storage types)
-
-
-def _lib():
-    from boxer_amd import _lib
-    return _lib.load()
 
 
 @pytest.fixture
@@ -54,30 +49,6 @@ def binning(request):
     lib.boxattn_set_option(OPT_RIDERS, old)
 
 
-def make_case(levels, family, H=8, B=2, seed=0, dtype=torch.bfloat16):
-    """bench.make_inputs for an ad-hoc encoder shape; extra families on top of "model" / "test":
-    "mixed" = model-like with every 7th box thrown far away, "border" = locations in [-0.2, 1.2]."""
-    name = "_dense_test"
-    bench.WORKLOADS[name] = (list(levels), "S", 4, "box")
-    old_h = bench.H_HEADS
-    bench.H_HEADS = H
-    try:
-        base = "model" if family in ("model", "mixed") else "test"
-        inp = bench.make_inputs(name, dtype, "cuda", family=base, batch=B, seed=seed)
-    finally:
-        bench.H_HEADS = old_h
-        del bench.WORKLOADS[name]
-    g = torch.Generator(device="cuda").manual_seed(seed + 100)
-    loc = inp["loc"]
-    if family == "mixed":
-        far = torch.rand(loc.shape[:-2], device="cuda", generator=g) < 1.0 / 7
-        shift = torch.rand(loc.shape[:-2] + (1, 2), device="cuda", generator=g) - 0.5
-        inp["loc"] = torch.where(far[..., None, None], loc + shift, loc).contiguous()
-    elif family == "border":
-        inp["loc"] = (torch.rand(loc.shape, device="cuda", generator=g) * 1.4 - 0.2).contiguous()
-    return inp
-
-
 def run(inp, with_plan=True):
     from boxer_amd import ops
     v, sh, ls, loc, attn, go = (inp[k] for k in ("value", "shapes", "lsi", "loc", "attn", "grad_out"))
@@ -91,16 +62,6 @@ def run(inp, with_plan=True):
     return out, grads
 
 
-LEVELS = {
-    "4lv": [(20, 28), (10, 14), (5, 7), (3, 4)],
-    "4lv_odd": [(37, 23), (19, 12), (10, 6), (5, 3)],
-    "3lv": [(16, 16), (8, 8), (4, 4)],
-    "2lv": [(33, 17), (16, 9)],
-    "1lv": [(9, 13)],
-    "tiny": [(4, 5), (2, 3), (1, 1)],
-}
-
-
 @pytest.mark.parametrize("family", ["model", "test", "mixed", "border"])
 @pytest.mark.parametrize("lv", sorted(LEVELS))
 def test_dense_kernels_match_oracle(lv, family, binning, forward_kernel):
@@ -110,7 +71,6 @@ def test_dense_kernels_match_oracle(lv, family, binning, forward_kernel):
         assert worst <= tol, "%s/%s %s: worst %.3e > %.0e" % (lv, family, name, worst, tol)
 
 
-OPT_ACC_F32 = 19        # float32 accumulate: 0 bf16 matrix cores on exact three-term splits; 1 VALU; 2 float32 MFMAs
 OPT_DENSE_F32 = OPT_DENSE   # window-staged kernels: 0 on, 1 off (ABI 8: the family's one switch)
 
 

@@ -1,6 +1,7 @@
 """GPU: every route held to its bound away from magnitude 1 ("Range").  The problems, route setters and
-route assertions are those of tests/test_gpu_error_bounds.py and the from-boxes files (imported); tests/dynamic_range.py
-scales them: ``value`` by 2^a, the upstream gradients by 2^b.
+route assertions are those of tests/test_gpu_error_bounds.py and the from-boxes files (tests/point_cases.py,
+tests/boxes_cases.py, tests/route_vocab.py); tests/dynamic_range.py holds this file's own cases and scales them:
+``value`` by 2^a, the upstream gradients by 2^b.
 
   exact      float32 and bf16 storage, (20, 0), (0, 20), (20, 20), (-12, -12): the case runs at (0, 0) and again on the
              device tensors times the power of two (exact in both types); ``out``, ``mask_out`` and every location,
@@ -18,105 +19,23 @@ scales them: ``value`` by 2^a, the upstream gradients by 2^b.
 Every exponent is a property of the inputs (tests/test_dynamic_range.py computes and checks them without a GPU).  Each
 case prints ``dynamic-range | route | type | family (a, b) | output | worst err / bound`` (``exact`` for the bitwise
 claims); profiles/dynamic_range.log is that table from one run."""
-import functools
 
-import numpy as np
 import pytest
 import torch
 
 import dynamic_range as dr
 import error_bounds as eb
-import test_gpu_error_bounds as g
-from test_gpu_error_bounds import (ACC_TR, ACC_VALU, DTYPES, F32, REC_POINT, STAGED, WIDE, box_tensors,
-                                   decoder_input, encoder_expectation, encoder_input, inst_tensors, k14_input, routes,
-                                   run_box, run_instance, set_encoder_keys, shape_a_input, split_of, wide_input)
+import point_cases
+import route_vocab
+from dynamic_range import (BOXES_GROUPS, EXACT, FAR, INST_CASE, VALUE_OVERFLOW, base_input, boxes_problem,
+                           f16_exponents, f16_reference, overflow_problem, reference_of, value_overflow_problem)
+from point_cases import box_tensors, encoder_expectation, inst_tensors, run_box, run_instance
+from route_vocab import ACC_TR, ACC_VALU, DTYPES, F16, F32, REC_POINT, STAGED, WIDE, routes, set_encoder_keys, split_of
 
 pytestmark = pytest.mark.gpu
 
-F16 = torch.float16
-# the exact family's exponents as taken: tests/test_dynamic_range.py halves one the float32 oracle is not bitwise
-# homogeneous at (none had to be)
-EXACT = list(dr.EXACT)
-FAR = list(dr.FAR)
-
 
 # ------------------------------------------------------------------ inputs (CPU; the twin reads the same)
-def base_input(group, dtype):
-    if group == "encoder":
-        return encoder_input("model", dtype, 1)
-    if group == "decoder":
-        return decoder_input("model", dtype)
-    if group == "wide":
-        return wide_input(36)
-    if group == "shape_a":
-        return shape_a_input("bf16" if dtype == "f32" else dtype)
-    if group == "k14":
-        return k14_input(dtype)
-    return boxes_input(group)                  # (numbers every storage type holds: one input for the three)
-
-
-GROUPS = ("encoder", "decoder", "wide", "shape_a", "k14")
-
-
-# from boxes: the smallest geometry of each file; angle mode 0 and one rotated flavour (turns, valid ratios given)
-PLAIN, TURNS = ((0, 4), False, True), ((1, 5), False, True)
-BOXES_GROUPS = ("instance from boxes", "box from boxes, plain", "box from boxes, turns", "staged from boxes, plain",
-                "staged from boxes, turns")
-INST_CASE = ("one_level", 32, 4, False, True)               # geometry, C, k, per_head, with_vr
-BOX_GEOMETRY, STAGED_GEOMETRY = "one_level", "tiny_levels"
-
-
-def boxes_problem(group):
-    """-> (the problem of the file the group comes from, its float64 upstream gradients)."""
-    import test_gpu_box_boxes_staged_backward as staged_bwd
-    import test_gpu_boxes_error_bounds as boxes
-    flavour = TURNS if group.endswith("turns") else PLAIN
-    if group.startswith("instance"):
-        p = boxes.inst_problem(*INST_CASE)
-        return p, boxes.inst_upstream(p, INST_CASE[2])
-    if group.startswith("box"):
-        p = boxes.bwd_problem(BOX_GEOMETRY, 32, flavour)
-        return p, (boxes.bwd_upstream(p),)
-    p = staged_bwd.case(STAGED_GEOMETRY, "local", *flavour[0], *flavour[1:])
-    return p, (staged_bwd.upstream(p),)
-
-
-@functools.lru_cache(maxsize=None)
-def boxes_input(group):
-    import test_gpu_boxes_error_bounds as boxes
-    p, ups = boxes_problem(group)
-    return dict(zip(dr.UPSTREAM, ups), kind="boxes", group=group, value=boxes.every_type(p["value"]))
-
-
-def boxes_model(inp):
-    """The float64 model of a from-boxes input (the files' own: error_bounds.boxes_reference; grad_value of the box
-    step by test_box_boxes_value_cases.model_of), once per input."""
-    import test_gpu_boxes_error_bounds as boxes
-    from test_box_boxes_value_cases import model_of
-    if "_ref" not in inp:
-        p, _ = boxes_problem(inp["group"])
-        P = p["dims"][6] if len(p["dims"]) > 6 else INST_CASE[2] ** 2
-        common = (inp["value"], p["shapes"], p["lsi"], p["ref"], p["off"], boxes.kernel_offsets(int(round(P ** 0.5))),
-                  p["vr"], p["logits"])
-        if inp["group"].startswith("instance"):
-            ref = eb.boxes_reference("instance", *common, 0, INST_CASE[2], inp["grad_out"], inp["grad_mask"])
-        else:
-            ref = eb.boxes_reference("box", *common, p["angle_mode"], grad_out=inp["grad_out"])
-            if inp["group"].startswith("box"):
-                ref["grad_value"] = model_of(p, inp["grad_out"])         # (grad_value does not read ``value``)
-        inp["_ref"] = {k: v for k, v in ref.items() if k not in ("points", "grid", "weights")}
-    return inp["_ref"]
-
-
-def reference_of(inp):
-    return boxes_model(inp) if inp["kind"] == "boxes" else eb.reference_of(inp)
-
-
-@functools.lru_cache(maxsize=None)
-def f16_exponents(group):
-    """-> ((a, b) of f16 high, (a, b) of f16 low)."""
-    inp = base_input(group, "f16")
-    return dr.high_exponents(inp, reference_of), dr.low_exponents(inp)
 
 
 def f16_pairs(group):
@@ -125,21 +44,6 @@ def f16_pairs(group):
     if group == "wide":                       # (a forward alone: no upstream gradient)
         pairs = [p for p in pairs if p[2] == 0 or p[0] == "f16 high"]
     return pairs
-
-
-@functools.lru_cache(maxsize=None)
-def f16_reference(group, a, b):
-    """-> (the inputs at (a, b) rounded to f16, their reference)."""
-    return dr.reference(base_input(group, "f16"), a, b, "f16", reference_of)
-
-
-@functools.lru_cache(maxsize=None)
-def overflow_problem():
-    """-> (b, the one-pixel encoder input with |grad_out| 2^b, its reference)."""
-    inp = dr.overflow_input(dr.scaled(encoder_input("model", "f16", 1), 0, 0, "f16"))
-    b = dr.overflow_exponent(inp)
-    s, ref = dr.reference(inp, 0, b, "f16")
-    return b, s, ref
 
 
 # ------------------------------------------------------------------ running
@@ -153,7 +57,8 @@ def _fresh_state():
 
 def tensors_of(inp, dt):
     if inp["kind"] == "boxes":
-        return dict({k: g.dev(inp[k], dt) for k in ("value",) + dr.UPSTREAM if k in inp}, group=inp["group"])
+        return dict({k: route_vocab.to_device(inp[k], dt) for k in ("value",) + dr.UPSTREAM if k in inp},
+                    group=inp["group"])
     return inst_tensors(inp, dt) if inp["kind"] == "instance" else box_tensors(inp, dt)
 
 
@@ -246,7 +151,7 @@ def encoder_route(dtype, acc_key, rec_key, dense):
 
 
 @pytest.mark.parametrize("dense", [2, 1], ids=["staged", "row_gather"])
-@pytest.mark.parametrize("dtype,acc_key,rec_key", g.ENCODER_ROUTES, ids=ENCODER_IDS)
+@pytest.mark.parametrize("dtype,acc_key,rec_key", point_cases.ENCODER_ROUTES, ids=ENCODER_IDS)
 def test_encoder(dtype, acc_key, rec_key, dense):
     """(13, 13), (7, 5), one query per pixel, riders as by default."""
     route, prepare, split, splits = encoder_route(dtype, acc_key, rec_key, dense)
@@ -257,8 +162,8 @@ def test_encoder(dtype, acc_key, rec_key, dense):
 
 
 # ------------------------------------------------------------------ decoder shapes, every variant
-@pytest.mark.parametrize("dtype,variant", g.DECODER_ROUTES,
-                         ids=["%s_%s" % (dt, ("auto", "generic", "atomic", "binned")[v]) for dt, v in g.DECODER_ROUTES])
+@pytest.mark.parametrize("dtype,variant", point_cases.DECODER_ROUTES,
+                         ids=["%s_%s" % (dt, ("auto", "generic", "atomic", "binned")[v]) for dt, v in point_cases.DECODER_ROUTES])
 def test_decoder(dtype, variant):
     """Four levels, 50 queries: the generic kernels (float32), the atomic backward with the first-generation forward, the
     binned backward."""
@@ -269,13 +174,13 @@ def test_decoder(dtype, variant):
     def prepare(t):
         _lib.set_variant(variant)
         fwd, acc, rec = routes(t)
-        assert fwd == g.DECODER_FORWARD[variant] and rec == REC_POINT, (fwd, rec)
-        assert acc == (g.ACC_SPLIT if dt == F32 else ACC_TR), acc
+        assert fwd == point_cases.DECODER_FORWARD[variant] and rec == REC_POINT, (fwd, rec)
+        assert acc == (route_vocab.ACC_SPLIT if dt == F32 else ACC_TR), acc
         seen["acc"] = acc
     prepare(box_tensors(base_input("decoder", dtype), dt, "cpu"))            # (the route queries are host code)
     split = "none" if variant in (1, 2) else split_of(seen["acc"], dt)
     route = "decoder, variant %s: %s forward, grad_value split %s" % (
-        ("auto", "generic", "atomic", "binned")[variant], _lib.FWD_FAMILIES[g.DECODER_FORWARD[variant]], split)
+        ("auto", "generic", "atomic", "binned")[variant], _lib.FWD_FAMILIES[point_cases.DECODER_FORWARD[variant]], split)
     if dtype == "f16":
         f16_ends(route, "decoder", prepare, run_box, split)
     else:
@@ -285,7 +190,7 @@ def test_decoder(dtype, variant):
 # ------------------------------------------------------------------ wave per pair
 @pytest.mark.parametrize("dtype", sorted(DTYPES))
 def test_wave_per_pair_forward(dtype):
-    from test_gpu_wide_box_forward import take_family
+    from route_vocab import take_family
     route = "wave-per-pair forward, P = 36"
 
     def prepare(t):
@@ -351,7 +256,7 @@ def test_f16_grad_value_overflows_to_inf(name, variant, rec_key):
     if variant == 2:
         _lib.set_variant(2)
         fwd, acc, rec = routes(t)
-        assert fwd == g.FAST, fwd
+        assert fwd == route_vocab.FAST, fwd
         split = "none"
     else:
         set_encoder_keys(2, 0, 0, rec_key)
@@ -378,10 +283,11 @@ def test_f16_grad_value_overflows_to_inf(name, variant, rec_key):
 def run_boxes(t):
     """Every from-boxes entry point of the group on the device tensors ``t`` -> its outputs by name; each asserts that
     the route it is about is the one that runs (the library's eligibility queries, as the files it comes from do)."""
-    import test_gpu_box_boxes_staged_backward as staged_bwd
-    import test_gpu_box_boxes_staged_forward as staged_fwd
-    import test_gpu_box_boxes_value as value_route
-    import test_gpu_boxes_error_bounds as boxes
+    import boxes_cases
+    import boxes_cases
+    import boxes_cases as value_route
+    import boxes_cases
+    import route_vocab
     from boxer_amd import ops
     group = t["group"]
     p, _ = boxes_problem(group)
@@ -389,26 +295,27 @@ def run_boxes(t):
     if group.startswith("instance"):
         k = INST_CASE[2]
         B, S, H, C, L, Lq = p["dims"]
-        a = (value, boxes.dev(p["shapes"]), boxes.dev(p["lsi"]), boxes.dev(p["ref"]), boxes.dev(p["off"]),
-             boxes.dev(boxes.kernel_offsets(k)), None if p["vr"] is None else boxes.dev(p["vr"]), boxes.dev(p["logits"]), k)
+        a = (value, route_vocab.dev(p["shapes"]), route_vocab.dev(p["lsi"]), route_vocab.dev(p["ref"]),
+             route_vocab.dev(p["off"]), route_vocab.dev(boxes_cases.kernel_offsets(k)),
+             None if p["vr"] is None else route_vocab.dev(p["vr"]), route_vocab.dev(p["logits"]), k)
         assert ops.forward_boxes_ok(value, L, Lq, k) and ops.backward_boxes_ok(value, L, Lq, k)
         out, mask = ops.instance_attn_forward_boxes(*a, True)
         grads = ops.instance_attn_backward_boxes(*a, gout, t["grad_mask"], need_ref_grad=True)
-        got = dict(zip(boxes.GRAD_NAMES, grads), out=out, mask_out=mask)
+        got = dict(zip(boxes_cases.GRAD_NAMES, grads), out=out, mask_out=mask)
     elif group.startswith("box"):
         B, S, H, C, L, Lq, P = p["dims"]
-        args = boxes.box_args(p, value.dtype, value=value)
+        args = boxes_cases.box_args(p, value.dtype, value=value)
         assert ops.box_forward_boxes_ok(value, L, Lq, P) and ops.box_backward_boxes_ok(value, L, Lq, P)
         assert ops.box_backward_boxes_value_ok(value, L, Lq, P)
         out = ops.box_attn_forward_boxes(*args)
         grads = ops.box_attn_backward_boxes(*args, gout, need_ref_grad=True)
         with_value = value_route.value_call(args, gout)
         value_route.same_parameter_gradients(with_value[1:], grads, group)
-        got = dict(zip(boxes.GRAD_NAMES, grads), out=out, grad_value=with_value[0])
+        got = dict(zip(boxes_cases.GRAD_NAMES, grads), out=out, grad_value=with_value[0])
     else:
-        args = staged_fwd.operands(p, value.dtype, value=value)
-        out = staged_fwd.run_staged(p, args)
-        got = dict(zip(boxes.GRAD_NAMES, staged_bwd.run_staged(p, args, gout)), out=out)
+        args = boxes_cases.operands(p, value.dtype, value=value)
+        out = boxes_cases.run_staged_forward(p, args)
+        got = dict(zip(boxes_cases.GRAD_NAMES, boxes_cases.run_staged_backward(p, args, gout)), out=out)
     torch.cuda.synchronize()
     for name, x in got.items():
         assert x.dtype == (value.dtype if name in dr.STORED else F32), name
@@ -421,8 +328,8 @@ def test_from_boxes(group, dtype):
     """Instance attention forward and backward from boxes; box attention forward, backward and the backward with
     grad_value in its own launch; the window-staged forward and backward -- the grid and the weights are made inside the
     kernels, from operands that are not scaled."""
-    import test_gpu_box_boxes_staged_forward as staged_fwd
-    splits = {"out": staged_fwd.SPLIT[dtype] if group.startswith("staged") else "none"}
+    import boxes_cases
+    splits = {"out": boxes_cases.STAGED_SPLIT[dtype] if group.startswith("staged") else "none"}
     nothing = lambda t: None
     if dtype == "f16":
         f16_ends(group, group, nothing, run_boxes, "none", splits)
@@ -430,37 +337,16 @@ def test_from_boxes(group, dtype):
         exact_and_far(group, base_input(group, dtype), DTYPES[dtype], nothing, run_boxes, "none", splits)
 
 
-VALUE_OVERFLOW = ("encoder", 32, PLAIN)          # geometry, C, flavour of test_gpu_boxes_error_bounds.bwd_problem
-
-
-@functools.lru_cache(maxsize=None)
-def value_overflow_problem():
-    """-> (b, the problem, |upstream| 2^b, grad_value's reference): the box step from boxes with every reference window
-    shrunk onto one spot (centre 0.02 + 0.4, size 0.02: the construction of dynamic_range.overflow_input, on the windows)
-    and an upstream gradient of one sign -- the weights are a softmax, so every term of grad_value is positive and the 80
-    queries add into the same four pixels a level.  (The files' own problems never get there: their largest sums stay
-    finite at every exponent the upstream gradient itself survives.)"""
-    import test_gpu_boxes_error_bounds as boxes
-    from test_box_boxes_value_cases import model_of
-    p = dict(boxes.bwd_problem(*VALUE_OVERFLOW))
-    ref = p["ref"].copy()
-    ref[..., :4] = ref[..., :4] * np.float32(0.02) + np.asarray([0.4, 0.4, 0.0, 0.0], dtype=np.float32)
-    p["ref"] = ref
-    gout = np.abs(boxes.bwd_upstream(p))
-    base = model_of(p, gout)
-    b = dr.overflow_exponent(dict(grad_out=gout), ref=dict(grad_value=base), split="none")
-    return b, p, np.ldexp(gout, b), dr.scaled_reference(dict(grad_value=base), 0, b)["grad_value"]
-
-
 def test_f16_grad_value_from_boxes_overflows_to_inf():
     """ops.box_attn_backward_boxes_value: float32 scratch, then a cast pass to f16."""
-    import test_gpu_box_boxes_value as value_route
-    import test_gpu_boxes_error_bounds as boxes
+    import boxes_cases as value_route
+    import boxes_cases
+    import route_vocab
     from boxer_amd import ops
     b, p, gout64, ref = value_overflow_problem()
     B, S, H, C, L, Lq, P = p["dims"]
-    args = boxes.box_args(p, F16)
-    gout = boxes.dev(gout64, F16)
+    args = boxes_cases.box_args(p, F16)
+    gout = route_vocab.dev(gout64, F16)
     assert torch.isfinite(gout).all() and torch.equal(gout.double().cpu(), torch.from_numpy(gout64))
     assert ops.box_backward_boxes_value_ok(args[0], L, Lq, P)
     got = value_route.value_call(args, gout)
@@ -469,5 +355,5 @@ def test_f16_grad_value_from_boxes_overflows_to_inf():
     assert n_inf >= dr.OVERFLOW_MIN and n_fin >= dr.OVERFLOW_MIN and n_either <= dr.OVERFLOW_EITHER * live
     worst = dr.hold_saturating(got[0], ref, "none", route + ": grad_value")
     line(route, F16, "f16 overflow", 0, b, "grad_value (%d inf / %d finite / %d either)" % (n_inf, n_fin, n_either), worst)
-    for name, x in zip(boxes.GRAD_NAMES, got[1:]):
+    for name, x in zip(boxes_cases.GRAD_NAMES, got[1:]):
         assert x.dtype == F32 and torch.isfinite(x).all(), "%s: %s is not finite" % (route, name)

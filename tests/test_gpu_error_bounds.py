@@ -8,36 +8,19 @@ weight rows for ``out`` of 16-bit storage.
 The inputs are generated on the CPU, so tests/test_error_bounds.py checks the same numbers without a GPU (the cell-edge
 condition of grad_loc, the route every case expects).  Each case prints ``error-bound | route | type | output | worst
 err / bound``; profiles/error_bounds.log is that table from one run."""
-import functools
 
 import numpy as np
 import pytest
 import torch
 
 import error_bounds as eb
-from test_gpu_instance_accumulate16 import SHAPE_A, problem as inst_problem
-from test_gpu_parity import SEEDED, _seeded
+from point_cases import (DECODER_FORWARD, DECODER_ROUTES, ENCODER_ROUTES, ENCODER_SEEDS, box_tensors, boxes_input,
+                         decoder_input, encoder_expectation, encoder_input, inst_tensors, k14_input, run_box,
+                         run_instance, seeded6_input, shape_a_input, wide_input)
+from route_vocab import (ACC_SPLIT, ACC_TR, ACC_VALU, DTYPES, F32, GATHER, REC_POINT, STAGED, WIDE, routes,
+                         set_encoder_keys, split_of, to_device as dev)
 
 pytestmark = pytest.mark.gpu
-
-F32 = torch.float32
-DTYPES = {"f32": F32, "bf16": torch.bfloat16, "f16": torch.float16}
-GENERIC, FAST, GATHER, WIDE, STAGED = range(5)                # _lib.FWD_*
-ACC_VALU, ACC_TR, ACC_F32, ACC_SPLIT = range(4)               # _lib.ACC_*
-REC_POINT, REC_GROUP = range(2)                               # _lib.REC_*
-SPLIT_OF_ACC = {ACC_VALU: "none", ACC_F32: "none", ACC_SPLIT: "split3"}        # ACC_TR: the storage type's two terms
-
-ENCODER = [(13, 13), (7, 5)]
-DECODER = [(20, 30), (10, 15), (5, 8), (3, 4)]
-WIDE_LEVELS = [(11, 9), (6, 5), (3, 2)]
-ENCODER_SEEDS = (1, 2, 3)
-# (family, seed) -> the seed actually taken: a case whose share of cell-edge points is above eb.EDGE_CAP is re-seeded
-# here (tests/test_error_bounds.py checks every input below)
-RESEED = {}
-
-
-def split_of(acc, dtype):
-    return eb.store_name(dtype) if acc == ACC_TR else SPLIT_OF_ACC[acc]
 
 
 def report(route, dtype, res):
@@ -46,131 +29,12 @@ def report(route, dtype, res):
 
 
 # ------------------------------------------------------------------ inputs (CPU; moved to the device by the cases)
-@functools.lru_cache(maxsize=None)
-def encoder_input(family, dtype, seed):
-    return eb.make(ENCODER, "S", family, DTYPES[dtype], seed=RESEED.get((family, seed), seed))
-
-
-@functools.lru_cache(maxsize=None)
-def decoder_input(family, dtype):
-    return eb.make(DECODER, 50, family, DTYPES[dtype], seed=RESEED.get((family, "decoder"), 1))
-
-
-@functools.lru_cache(maxsize=None)
-def seeded6_input(C):
-    """SEEDED[6] of test_gpu_parity: value and grad_out on a 1/64 grid -- the same numbers in every storage type."""
-    shapes, B, H, _, Lq, P = SEEDED[6]
-    g = _seeded(shapes, B, H, C, Lq, P, seed=11)
-    return dict(kind="box", value=g["value"], shapes=g["shapes"], lsi=g["lsi"], loc=g["loc"], attn=g["attn"],
-                grad_out=g["grad_out"])
-
-
-@functools.lru_cache(maxsize=None)
-def wide_input(P):
-    """Few queries x many points on three levels: the wave-per-pair forward (test_gpu_wide_box_forward.seeded)."""
-    rng = np.random.default_rng(100 + P)
-    shapes = np.asarray(WIDE_LEVELS, dtype=np.int64)
-    sizes = shapes.prod(1)
-    B, Lq, H, C, L = 2, 6, 2, 32, len(WIDE_LEVELS)
-    a = rng.random((B, Lq, H, L, P))
-    a[rng.random(a.shape) < 0.1] = 0.0
-    f32 = lambda x: x.astype(np.float32).astype(np.float64)
-    return dict(kind="box", shapes=shapes, lsi=np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64),
-                value=eb.round_to(rng.standard_normal((B, int(sizes.sum()), H, C)), "bf16"),
-                loc=f32(rng.uniform(-0.2, 1.2, (B, Lq, H, L, P, 2))), attn=f32(a),
-                grad_out=np.zeros((B, Lq, H * C)))
-
-
-@functools.lru_cache(maxsize=None)
-def shape_a_input(dtype):
-    g = inst_problem(dtype=DTYPES[dtype], **SHAPE_A)
-    return dict(g, kind="instance", attn=g["spatial_w"])
-
-
-@functools.lru_cache(maxsize=None)
-def k14_input(dtype):
-    return eb.make(DECODER, 6, "model", DTYPES[dtype], kind="instance", P=196, seed=RESEED.get(("k14", 1), 1))
-
-
-@functools.lru_cache(maxsize=None)
-def boxes_input():
-    """Reference windows, box offsets and 2 x 2 logits for the forward from boxes: k = 14, six queries, four levels."""
-    rng = np.random.default_rng(RESEED.get(("boxes", 14), 14))
-    B, Lq, H, C, L = 2, 6, 2, 32, len(DECODER)
-    shapes = np.asarray(DECODER, dtype=np.int64)
-    sizes = shapes.prod(1)
-    f32 = lambda x: np.ascontiguousarray(x, dtype=np.float32)
-    ref = np.concatenate([rng.uniform(0.05, 0.95, (B, Lq, 2)), rng.uniform(0.05, 0.7, (B, Lq, 2))], -1)
-    return dict(shapes=shapes, lsi=np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64), vr=None,
-                dims=(B, int(sizes.sum()), H, C, L, Lq), value=rng.standard_normal((B, int(sizes.sum()), H, C)),
-                ref=f32(ref), off=f32(rng.standard_normal((B, Lq, H, L, 4))),
-                logits=f32(rng.standard_normal((B, Lq, H, L, 2, 2))))
 
 
 reference = eb.reference_of          # the bound's reference of an input dictionary, once per input
 
 
-# every input the cases below use, for the CPU twin: name -> a function that builds it
-def all_inputs():
-    for family in ("model", "test", "border"):
-        for dtype in DTYPES:
-            for seed in ENCODER_SEEDS:
-                yield "encoder %s %s seed %d" % (family, dtype, seed), functools.partial(encoder_input, family, dtype, seed)
-    for family in ("model", "test"):
-        for dtype in DTYPES:
-            yield "decoder %s %s" % (family, dtype), functools.partial(decoder_input, family, dtype)
-    for C in (16, 32, 64):
-        yield "SEEDED[6] C=%d" % C, functools.partial(seeded6_input, C)
-    for dtype in ("bf16", "f16"):            # (float32 takes the bf16 numbers)
-        yield "instance shape A %s" % dtype, functools.partial(shape_a_input, dtype)
-    for dtype in DTYPES:
-        yield "instance k=14 %s" % dtype, functools.partial(k14_input, dtype)
-
-
 # ------------------------------------------------------------------ running
-def dev(a, dtype=None, device="cuda"):
-    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-    t = t.to(device)
-    return t.to(dtype) if dtype is not None and t.is_floating_point() else t
-
-
-def box_tensors(inp, dtype, device="cuda"):
-    """(device "cpu": for the route queries of the CPU twin, which are host code)"""
-    d = lambda a, dt=None: dev(a, dt, device)
-    return dict(value=d(inp["value"], dtype), shapes=d(inp["shapes"]), lsi=d(inp["lsi"]), loc=d(inp["loc"], F32),
-                attn=d(inp["attn"], F32), grad_out=d(inp["grad_out"], dtype))
-
-
-def run_box(t):
-    """The reference's two calls: forward, then the full backward."""
-    from boxer_amd import ops
-    a = [t[k] for k in ("value", "shapes", "lsi", "loc", "attn")]
-    out = ops.box_attn_forward(*a, 64)
-    gv, gl, ga = ops.box_attn_backward(*a, t["grad_out"], 64)
-    torch.cuda.synchronize()
-    return dict(out=out, grad_value=gv, grad_loc=gl, grad_attn=ga)
-
-
-def run_instance(t):
-    from boxer_amd import ops
-    a = [t[k] for k in ("value", "shapes", "lsi", "loc", "attn", "level_w")]
-    out, mask = ops.instance_attn_forward(*a, 64)
-    gv, gl, gs, glw = ops.instance_attn_backward(*a, t["grad_out"], t["grad_mask"], 64)
-    torch.cuda.synchronize()
-    return dict(out=out, mask_out=mask, grad_value=gv, grad_loc=gl, grad_spatial=gs, grad_level=glw)
-
-
-def inst_tensors(inp, dtype, device="cuda"):
-    t = box_tensors(inp, dtype, device)
-    t["level_w"], t["grad_mask"] = dev(inp["level_w"], F32, device), dev(inp["grad_mask"], dtype, device)
-    return t
-
-
-def routes(t, instance=False):
-    from boxer_amd import ops
-    return (ops.forward_route(t["value"], t["loc"], t["shapes"], t["lsi"], instance=instance),
-            ops.backward_accumulate_kind(t["value"], t["loc"], instance=instance),
-            ops.backward_record_kind(t["value"], t["loc"], instance=instance))
 
 
 @pytest.fixture(autouse=True)
@@ -182,26 +46,6 @@ def _fresh_state():
 
 
 # ------------------------------------------------------------------ box attention: the encoder on odd maps
-def encoder_expectation(dtype, dense, riders, acc_key, rec_key):
-    """-> (forward family, accumulate kind, record kind, one pass?) of an encoder case under its keys."""
-    if dtype == "f32":
-        acc = {0: ACC_SPLIT, 1: ACC_VALU, 2: ACC_F32}[acc_key]
-        rec = REC_POINT
-    else:
-        acc, rec = ACC_TR, REC_GROUP if rec_key == 2 else REC_POINT
-    # the one-pass fill: riders on and a matrix-core accumulate (boxattn_host_plan.h: spec_ok)
-    return STAGED if dense == 2 else GATHER, acc, rec, riders == 0 and acc != ACC_VALU
-
-
-ENCODER_ROUTES = [("f32", acc, 0) for acc in (0, 1, 2)] + [(dt, 0, rec) for dt in ("bf16", "f16") for rec in (1, 2)]
-
-
-def set_encoder_keys(dense, riders, acc_key, rec_key):
-    from boxer_amd import _lib
-    _lib.set_option("dense", dense)
-    _lib.set_option("riders", riders)
-    _lib.set_option("acc_f32", acc_key)
-    _lib.set_option("group_records", rec_key)
 
 
 @pytest.mark.parametrize("riders", [0, 1], ids=["riders", "own_launches"])
@@ -212,7 +56,7 @@ def set_encoder_keys(dense, riders, acc_key, rec_key):
 def test_encoder_odd_maps(family, dtype, acc_key, rec_key, dense, riders):
     """(13, 13), (7, 5), one query per pixel: partial blocks on every edge.  Cold, then twice more on new inputs on the
     same state (the one-pass fill where the route has it)."""
-    from test_gpu_onepass import counters
+    from point_cases import counters
     dt = DTYPES[dtype]
     set_encoder_keys(dense, riders, acc_key, rec_key)
     fwd, acc, rec, one_pass = encoder_expectation(dtype, dense, riders, acc_key, rec_key)
@@ -257,11 +101,6 @@ def test_seeded_6_one_pixel_levels_and_chunked_items(dtype, C, variant):
     report(route, dt, eb.hold_all(run_box(t), reference(inp), dt, split_of(acc, dt), route))
 
 
-DECODER_FORWARD = {0: GATHER, 1: GENERIC, 2: FAST, 3: GATHER}        # the forward family of every kernel variant
-# (the generic variant is held in float32)
-DECODER_ROUTES = [(dt, v) for dt in sorted(DTYPES) for v in (0, 1, 2, 3) if v != 1 or dt == "f32"]
-
-
 @pytest.mark.parametrize("dtype,variant", DECODER_ROUTES,
                          ids=["%s_%s" % (dt, ("auto", "generic", "atomic", "binned")[v]) for dt, v in DECODER_ROUTES])
 @pytest.mark.parametrize("family", ["model", "test"])
@@ -286,7 +125,7 @@ def test_decoder_shape_every_variant(family, dtype, variant):
 @pytest.mark.parametrize("P", [196, 36])
 def test_wave_per_pair_forward(P, dtype):
     from boxer_amd import ops
-    from test_gpu_wide_box_forward import take_family
+    from route_vocab import take_family
     dt = DTYPES[dtype]
     inp = wide_input(P)
     t = box_tensors(inp, dt)
@@ -334,7 +173,7 @@ def test_instance_14_by_14_forward_from_boxes(dtype):
     logit gradients keep their own test, here it must run and be finite): out and mask_out held against the reference
     on the float32 grid and weights this build's chain produces (test_gpu_boxes_backward.expectations)."""
     from boxer_amd import ops
-    from test_gpu_boxes_forward import kernel_indices
+    from boxes_cases import inst_kernel_indices as kernel_indices
     dt = DTYPES[dtype]
     g, k = boxes_input(), 14
     B, S, H, C, L, Lq = g["dims"]

@@ -14,13 +14,13 @@ import torch
 import bench
 import golden_io
 from oracle import boxattn_oracle as oc
+from compare_rules import check_f16 as check, tol_of_f16 as tol_of
+from point_cases import LEVELS4, PARITY_G9 as G9, STAT_OFF
+from route_vocab import F16, VARIANTS, dev
 
 pytestmark = pytest.mark.gpu
 
-F16 = torch.float16
-VARIANTS = {"auto": 0, "generic": 1, "atomic": 2, "binned": 3}
 OPT_DENSE, OPT_RIDERS = 11, 15
-STAT_OFF = 1024          # state buffer: the one-pass counters behind the locality counters (include/boxattn.h)
 
 
 @pytest.fixture(autouse=True)
@@ -31,24 +31,6 @@ def _reset_switches():
     lib = _lib.load()
     lib.boxattn_set_option(OPT_DENSE, 0)
     lib.boxattn_set_option(OPT_RIDERS, 0)
-
-
-def tol_of(t):
-    return 1e-3 if t.dtype == F16 else 1e-4
-
-
-def check(got, want, what, ignore=None):
-    tol = tol_of(got)
-    got = got.detach().double().cpu().numpy().reshape(np.shape(want))
-    want = np.asarray(want, dtype=np.float64)
-    if ignore is not None:
-        keep = ~np.broadcast_to(ignore, want.shape)
-        got, want = got * keep, want * keep
-    assert np.isfinite(got).all(), what
-    scale = max(1.0, float(np.sqrt(np.mean(want * want)))) if want.size else 1.0
-    ratio = np.abs(got - want) / (scale + np.abs(want))
-    worst = float(ratio.max()) if want.size else 0.0
-    assert worst <= tol, "%s: worst |err| / (%.3g + |want|) = %.3e > %.1e" % (what, scale, worst, tol)
 
 
 def f16_rounded(a):
@@ -73,11 +55,6 @@ def seeded(shapes, B, H, C, Lq, P, seed):
                 grad_out=f16_rounded(rng.standard_normal((B, Lq, H * C))),
                 grad_mask=f16_rounded(rng.standard_normal((B, Lq, P, H * C))),
                 on_edge=(np.abs(pix - np.round(pix)) < 1e-4).any(-1, keepdims=True))
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return t.to(dtype) if dtype is not None else t
 
 
 def run_ops(g, kind, variant):
@@ -166,7 +143,6 @@ def test_f16_bench_workload_matches_oracle(workload):
 
 
 # ------------------------------------------------------------------ 3. encoder case: staged / riders / one pass
-LEVELS4 = [(37, 53), (19, 27), (10, 14), (5, 7)]
 
 
 def encoder_case(seed=3):
@@ -300,14 +276,6 @@ def test_f16_binned_backward_is_reproducible_and_graph_replays():
 
 
 # ------------------------------------------------------------------ 6. modules with native_f16 (G9 goldens)
-G9 = {
-    "G9_module_box_enc": ("BoxAttention", dict(kernel_size=2), 1),
-    "G9_module_box_enc_masked": ("BoxAttention", dict(kernel_size=2), 1),
-    "G9_module_box_dec": ("BoxAttention", dict(kernel_size=2), 1),
-    "G9_module_box3d_fixed_enc": ("Box3dAttention", dict(with_rotation=False, kernel_size=2), 1),
-    "G9_module_box3d_rot_dec": ("Box3dAttention", dict(with_rotation=True, kernel_size=2), 1),
-    "G9_module_inst_k4": ("InstanceAttention", dict(kernel_size=4), 2),
-}
 
 
 def g9_run(name, mode, fused_grid, fused_pointwise):

@@ -2,8 +2,8 @@
 box attention with P = 4 writes one 4-byte record per (query, level, block) and the matrix-core accumulate gathers the
 group's locations and weights by id.  Every case checks grad_value, grad_loc and grad_attn of key 24 = 2
 
-  * against the C oracle with the suite's helpers for the storage type (test_gpu_parity.close for bf16,
-    test_gpu_f16.check for f16);
+  * against the C oracle with the suite's helpers for the storage type (compare_rules.close_parity for bf16,
+    compare_rules.check_f16 for f16);
   * against the same call under key 24 = 1 (point records): grad_loc / grad_attn come from the same launch and are
     bitwise equal, grad_value is held to the suite's run-to-run bound (test_gpu_onepass.test_soak_over_changing_inputs:
     tol x max(1, max |ref|) with the storage type's oracle tolerance).
@@ -15,20 +15,11 @@ import numpy as np
 import pytest
 import torch
 
-import bench
-import error_bounds as eb
-from oracle import boxattn_oracle as oc
-from test_gpu_f16 import check as check_f16
-from test_gpu_onepass import counters
-from test_gpu_parity import close as close_parity
+from point_cases import (EACH_16BIT_DTYPE as DTYPES, RUN_TO_RUN, backward, both_routes, check_oracle, check_routes,
+                         counters, f64, make)
+from route_vocab import BF16, KEY_GROUP, KEY_POINT
 
 pytestmark = pytest.mark.gpu
-
-OPT_GROUP = 24
-KEY_POINT, KEY_GROUP = 1, 2
-BF16, F16 = torch.bfloat16, torch.float16
-RUN_TO_RUN = {BF16: 1e-2, F16: 1e-3, torch.float32: 1e-4}
-DTYPES = pytest.mark.parametrize("dtype", [BF16, F16], ids=["bf16", "f16"])
 
 
 @pytest.fixture(autouse=True)
@@ -38,116 +29,6 @@ def _reset():
     yield
     _lib.set_option("group_records", 0)
     ops.release_workspaces()
-
-
-def make(levels, lq, family="model", dtype=BF16, B=2, H=2, C=32, seed=0, kind="box"):
-    name = "_group_records_test"
-    bench.WORKLOADS[name] = (list(levels), lq, 4, kind)
-    old = bench.H_HEADS, bench.C_HEAD
-    bench.H_HEADS, bench.C_HEAD = H, C
-    try:
-        return bench.make_inputs(name, dtype, "cuda", family=family, batch=B, seed=seed)
-    finally:
-        bench.H_HEADS, bench.C_HEAD = old
-        del bench.WORKLOADS[name]
-
-
-def f64(t):
-    return t.detach().double().cpu().numpy()
-
-
-def on_edge(inp):
-    """Sample points on a bilinear cell edge: grad_loc jumps there (test_gpu_parity.on_cell_edge)."""
-    size = f64(inp["shapes"])[None, None, None, :, None, ::-1]
-    pix = f64(inp["loc"]) * size - 0.5
-    return (np.abs(pix - np.round(pix)) < 1e-4).any(-1, keepdims=True)
-
-
-def oracle(inp):
-    """grad_value, grad_loc, grad_attn of the C oracle on the stored (rounded) inputs; computed once per input set."""
-    if "_want" not in inp:
-        inp["_want"] = oc.box_attn_backward(f64(inp["value"]), inp["shapes"].cpu().numpy(), inp["lsi"].cpu().numpy(),
-                                            f64(inp["loc"]), f64(inp["attn"]), f64(inp["grad_out"]))
-        inp["_edge"] = on_edge(inp)
-        inp["_ref"] = eb.box_reference(inp["value"], inp["shapes"], inp["lsi"], inp["loc"], inp["attn"], inp["grad_out"])
-    return inp["_want"]
-
-
-def backward(inp, key):
-    from boxer_amd import _lib, ops
-    _lib.set_option("group_records", key)
-    v, sh, ls, loc, attn, go = (inp[k] for k in ("value", "shapes", "lsi", "loc", "attn", "grad_out"))
-    want_kind = _lib.REC_GROUP if key == KEY_GROUP else _lib.REC_POINT
-    assert ops.backward_record_kind(v, loc) == want_kind
-    ops.box_attn_forward(v, sh, ls, loc, attn, 64)
-    grads = ops.box_attn_backward(v, sh, ls, loc, attn, go, 64)
-    torch.cuda.synchronize()
-    return grads
-
-
-def worst(got, want):
-    want = np.asarray(want, dtype=np.float64)
-    return float(np.abs(f64(got).reshape(want.shape) - want).max()) / max(1.0, float(np.abs(want).max()))
-
-
-def check_oracle(inp, grads, what):
-    want = oracle(inp)
-    dtype = inp["value"].dtype
-    for name, t, w in zip(("grad_value", "grad_loc", "grad_attn"), grads, want):
-        ignore = inp["_edge"] if name == "grad_loc" else None
-        if dtype == F16:
-            check_f16(t, w, "%s: %s" % (what, name), ignore=ignore)
-        else:
-            close_parity(t, w, dtype if name == "grad_value" else torch.float32, "%s: %s" % (what, name), ignore=ignore)
-    hold_bound(inp, grads, what)
-
-
-def hold_bound(inp, grads, what):
-    """Every element inside the bound of tests/error_bounds.py: one rounding to the storage type, float32
-    sums, grad_value's weights in two 16-bit terms -- for both record kinds.  (The hand-placed cases put points on cell
-    edges on purpose: those are left out of grad_loc as above, their share is not capped here.)"""
-    oracle(inp)
-    dtype = inp["value"].dtype
-    if dtype not in (BF16, F16):
-        return
-    worst = []
-    for name, t in zip(("grad_value", "grad_loc", "grad_attn"), grads):
-        store, split = (dtype, eb.store_name(dtype)) if name == "grad_value" else ("float32", "none")
-        worst.append("%s %.3f" % (name, eb.hold(t, inp["_ref"][name], store, split, "%s: %s" % (what, name))))
-    print("%s: worst err / bound %s" % (what, ", ".join(worst)))
-
-
-def check_routes(inp, group, point, what):
-    """key 24 = 2 against key 24 = 1 on the same inputs."""
-    dtype = inp["value"].dtype
-    assert torch.equal(group[1], point[1]), "%s: grad_loc differs between the record kinds" % what
-    assert torch.equal(group[2], point[2]), "%s: grad_attn differs between the record kinds" % what
-    ref = point[0].float()
-    err = (group[0].float() - ref).abs().max().item()
-    bound = RUN_TO_RUN[dtype] * max(1.0, ref.abs().max().item())
-    want = oracle(inp)[0]
-    eg, ep = worst(group[0], want), worst(point[0], want)
-    print("%s: grad_value worst scaled error group %.3e / point %.3e = %.2f; group - point %.3e (bound %.1e)"
-          % (what, eg, ep, eg / max(ep, 1e-30), err, bound))
-    assert err <= bound, "%s: grad_value of the two record kinds differs by %.3e > %.1e" % (what, err, bound)
-
-
-def both_routes(sets, what):
-    """Every input set under key 24 = 2, in order, on one state; then under key 24 = 1 on a fresh one.  -> the group
-    route's (calls, redone) counters after every set."""
-    from boxer_amd import ops
-    ops.release_workspaces()
-    group, seen = [], []
-    for inp in sets:
-        group.append(backward(inp, KEY_GROUP))
-        seen.append(counters())
-    ops.release_workspaces()
-    point = [backward(inp, KEY_POINT) for inp in sets]
-    for i, inp in enumerate(sets):
-        check_oracle(inp, group[i], "%s, call %d, group records" % (what, i))
-        hold_bound(inp, point[i], "%s, call %d, point records" % (what, i))
-        check_routes(inp, group[i], point[i], "%s, call %d" % (what, i))
-    return seen
 
 
 # ------------------------------------------------------------------ encoder, odd maps: cold, then the one-pass riders

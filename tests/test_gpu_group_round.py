@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_group_records import BF16, F16, DTYPES, KEY_GROUP, RUN_TO_RUN, backward, both_routes, make
+from point_cases import EACH_16BIT_DTYPE as DTYPES, RUN_TO_RUN, backward, both_routes, make
+from route_vocab import BF16, KEY_GROUP
 
 pytestmark = pytest.mark.gpu
 

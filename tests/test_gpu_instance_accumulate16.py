@@ -13,18 +13,16 @@ import torch
 
 import error_bounds as eb
 from oracle import boxattn_oracle as oc
-from test_gpu_f16 import check as check_f16
-from test_gpu_parity import close as close_parity
+from compare_rules import check_f16, close_parity
+from point_cases import LEVELS_A, SHAPE_A, instance_problem as problem
+from route_vocab import BF16, F16, dev
 
 pytestmark = pytest.mark.gpu
 
-BF16, F16 = torch.bfloat16, torch.float16
 DTYPES = [BF16, F16]
 IDS = ["bf16", "f16"]
 OPT_INST_ACC16, OPT_BIN_CHUNK = 23, 10
 ROUTE_VALU, ROUTE_TR = 1, 2
-LEVELS_A = [(16, 24), (7, 5), (1, 3)]
-SHAPE_A = dict(levels=LEVELS_A, B=2, H=3, C=32, Lq=300, k=4)
 
 
 @pytest.fixture(autouse=True)
@@ -38,7 +36,7 @@ def _reset_switches():
 
 
 def close16(got, want, dtype, what):
-    """The suite's 16-bit comparison: bf16 by test_gpu_parity.close at the bf16 tolerance, f16 by test_gpu_f16.check
+    """The suite's 16-bit comparison: bf16 by compare_rules.close_parity at the bf16 tolerance, f16 by compare_rules.check_f16
     (parity.close has no f16 entry; that check is the f16 suite's own, at 1e-3)."""
     if dtype == BF16:
         close_parity(got, want, BF16, what)
@@ -47,35 +45,9 @@ def close16(got, want, dtype, what):
         check_f16(got, want, what)
 
 
-def rounded(a, dtype):
-    return torch.from_numpy(np.asarray(a, dtype=np.float32)).to(dtype).double().numpy()
-
-
-def problem(levels, B, H, C, Lq, k, dtype, seed=5, loc_range=(-0.2, 1.2)):
-    """numpy float64 inputs whose storage tensors are already numbers of ``dtype``."""
-    rng = np.random.default_rng(seed)
-    shapes = np.asarray(levels, dtype=np.int64)
-    sizes = shapes.prod(1)
-    lsi = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-    S, L, P = int(sizes.sum()), len(levels), k * k
-    loc = rng.uniform(*loc_range, (B, Lq, H, L, P, 2)).astype(np.float32).astype(np.float64)
-    a = rng.uniform(1e-5, 1, (B, Lq, H, L, P))
-    return dict(shapes=shapes, lsi=lsi, loc=loc, k=k, dims=(B, S, H, C, L, Lq, P),
-                value=rounded(rng.standard_normal((B, S, H, C)), dtype),
-                spatial_w=(a / a.sum((-1, -2), keepdims=True)).astype(np.float32).astype(np.float64),
-                level_w=(a / a.sum(-2, keepdims=True)).astype(np.float32).astype(np.float64),
-                grad_out=rounded(rng.standard_normal((B, Lq, H * C)), dtype),
-                grad_mask=rounded(rng.standard_normal((B, Lq, P, H * C)), dtype))
-
-
 def oracle_backward(g):
     return oc.instance_attn_backward(g["value"], g["shapes"], g["lsi"], g["loc"], g["spatial_w"], g["level_w"],
                                      g["grad_out"], g["grad_mask"])
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return t.to(dtype) if dtype is not None else t
 
 
 def tensors(g, dtype, mask_offset_bytes=0):

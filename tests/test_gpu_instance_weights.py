@@ -11,10 +11,10 @@ further ulp of the type allowed.
 """
 import pytest
 import torch
+from route_vocab import DTYPES
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 MANTISSA = {torch.bfloat16: 7, torch.float16: 10}
 
 

@@ -1,7 +1,8 @@
 """GPU: no output depends on input data its definition does not name ("Isolation"; tests/isolation.py).
 
 Every case builds an edge family on the shapes, option keys and route assertions of tests/test_gpu_error_bounds.py (and,
-from boxes, of tests/test_gpu_boxes_error_bounds.py and tests/test_gpu_box_boxes_staged_forward.py), asserts its route
+from boxes, of tests/test_gpu_boxes_error_bounds.py and tests/test_gpu_box_boxes_staged_forward.py; all of them in
+tests/point_cases.py, tests/boxes_cases.py and tests/route_vocab.py), asserts its route
 through the library's queries, runs the call clean twice (the second on the warm state: the one-pass fill where the route
 has it) and then poisoned, and compares bit for bit:
 
@@ -13,7 +14,7 @@ has it) and then poisoned, and compares bit for bit:
 
 grad_value is compared bit for bit where the route's sum is ordered (two clean runs agree; a mismatch is held against
 the route only after REPEATS more clean runs agreed, the rule of test_gpu_partial_backward.run_family, and no further
-poisoned run reproduced the clean bits: GradValue), otherwise at test_gpu_wide_box_forward.tol_of against the oracle on the
+poisoned run reproduced the clean bits: GradValue), otherwise at compare_rules.tol_of against the oracle on the
 clean inputs.  On the matrix-core accumulates a victim's non-finite upstream row may reach all pixels of the 8 x 4 blocks
 the victim touches (spread_for); the contract itself is kept for them as xfail(strict=True) cases.  Only
 data is poisoned, never a location, a box or a shape.  Each case prints ``isolation | route | type | family | edge |
@@ -26,16 +27,15 @@ import pytest
 import torch
 
 import isolation as iso
-import test_gpu_error_bounds as geb
+import point_cases
+import route_vocab
+from compare_rules import check_scaled as check, tol_of
+from isolation import BOX_FLAVOURS, DECODER, ENCODER, STAGED_GEOMETRY, STAGED_LEVELS, WIDE_LEVELS
+from point_cases import (ALL, Case, DECODER_FORWARD, DECODER_ROUTES, ENCODER_ROUTES, REPEATS, SEEDED, SHAPE_A, SUFFIX,
+                         backward_with_plan, call)
+from route_vocab import (ACC_SPLIT, ACC_TR, ACC_VALU, DTYPES, F32, GATHER, REC_GROUP, REC_POINT, STAGED, WIDE, routes,
+                         take_family, to_device as dev)
 from oracle import boxattn_oracle as oc
-from test_gpu_error_bounds import (ACC_SPLIT, ACC_TR, ACC_VALU, DECODER_FORWARD, DECODER_ROUTES, DTYPES, ENCODER_ROUTES, F32,
-                                   GATHER, REC_GROUP, REC_POINT, STAGED, WIDE, dev, routes)
-from test_gpu_instance_accumulate16 import SHAPE_A
-from test_gpu_backward_routes import backward as backward_with_plan
-from test_gpu_partial_backward import ALL, REPEATS, SUFFIX, Case, call
-from test_gpu_parity import SEEDED
-from test_gpu_wide_box_forward import check, take_family, tol_of
-from test_isolation import DECODER, ENCODER, STAGED_LEVELS, WIDE_LEVELS
 
 pytestmark = pytest.mark.gpu
 
@@ -167,7 +167,7 @@ def hold_families(route, dtype, g, run, instance=False, tensors=None, upstream=N
     "blocks" / "groups": the documented deviation of the matrix-core accumulates (spread_of).  only: the families to run
     (default all)."""
     dt = DTYPES[dtype]
-    t = (geb.inst_tensors if instance else geb.box_tensors)(g, dt) if tensors is None else tensors
+    t = (point_cases.inst_tensors if instance else point_cases.box_tensors)(g, dt) if tensors is None else tensors
     tab = Table(route, dtype, g["edge"]) if tab is None else tab
     clean, again = run(t), run(t)
     backward = "grad_value" in clean
@@ -251,11 +251,11 @@ def hold_families(route, dtype, g, run, instance=False, tensors=None, upstream=N
 def test_encoder(dtype, acc_key, rec_key, dense, riders, edge):
     """(13, 13), (7, 5), one query a pixel: every forward / accumulate / record route of the encoder, the full backward,
     the second clean call on the warm state (the one-pass fill where the route has it)."""
-    from test_gpu_onepass import counters
-    geb.set_encoder_keys(dense, riders, acc_key, rec_key)
-    fwd, acc, rec, one_pass = geb.encoder_expectation(dtype, dense, riders, acc_key, rec_key)
+    from point_cases import counters
+    route_vocab.set_encoder_keys(dense, riders, acc_key, rec_key)
+    fwd, acc, rec, one_pass = point_cases.encoder_expectation(dtype, dense, riders, acc_key, rec_key)
     g = problem(key(ENCODER), "S", 4, edge)
-    t = geb.box_tensors(g, DTYPES[dtype])
+    t = point_cases.box_tensors(g, DTYPES[dtype])
     assert routes(t) == (fwd, acc, rec), "the library answers %r" % (routes(t),)
     route = "encoder: %s forward, %s accumulate, %s records, riders %s" % (
         "staged" if dense == 2 else "row-gather", ("valu", "tr", "f32", "split")[acc], ("point", "group")[rec],
@@ -263,7 +263,7 @@ def test_encoder(dtype, acc_key, rec_key, dense, riders, edge):
     seen = []
 
     def run(tt):
-        got = geb.run_box(tt)
+        got = point_cases.run_box(tt)
         seen.append(counters())
         return got
     tab = hold_families(route, dtype, g, run, tensors=t, spread=spread_for(acc, rec))
@@ -285,12 +285,12 @@ def test_staged_levels(levels, dtype, edge):
     from boxer_amd import _lib
     _lib.set_option("dense", 2)
     g = problem(key(STAGED_LEVELS[:levels]), "S", 4, edge)
-    t = geb.box_tensors(g, DTYPES[dtype])
+    t = point_cases.box_tensors(g, DTYPES[dtype])
     fwd, acc, rec = routes(t)
     assert fwd == STAGED, fwd
     route = "staged levels, %d: staged forward, %s accumulate, %s records" % (
         levels, ("valu", "tr", "f32", "split")[acc], ("point", "group")[rec])
-    hold_families(route, dtype, g, geb.run_box, tensors=t, spread=spread_for(acc, rec)).done()
+    hold_families(route, dtype, g, point_cases.run_box, tensors=t, spread=spread_for(acc, rec)).done()
 
 
 # ------------------------------------------------------------------ box attention: decoder shapes, SEEDED[6], wave per pair
@@ -302,13 +302,14 @@ def test_decoder(dtype, variant, edge):
     binned backward without (a padded tail rules the binned route out: boxattn_host_plan.h, make_plan_blocks)."""
     from boxer_amd import _lib
     g = problem(key(DECODER), 50, 4, edge, pad=3 if variant in (1, 2) else 0)
-    t = geb.box_tensors(g, DTYPES[dtype])
+    t = point_cases.box_tensors(g, DTYPES[dtype])
     _lib.set_variant(variant)
     fwd, acc, rec = routes(t)
     assert fwd == DECODER_FORWARD[variant] and rec == REC_POINT, (fwd, rec)
     assert acc == (ACC_SPLIT if dtype == "f32" else ACC_TR), acc
     route = "decoder, variant %s: %s forward" % (("auto", "generic", "atomic", "binned")[variant], _lib.FWD_FAMILIES[fwd])
-    hold_families(route, dtype, g, geb.run_box, tensors=t, spread=None if variant in (1, 2) else spread_for(acc, rec)).done()
+    hold_families(route, dtype, g, point_cases.run_box, tensors=t,
+                  spread=None if variant in (1, 2) else spread_for(acc, rec)).done()
 
 
 @pytest.mark.parametrize("edge", EDGES)
@@ -322,12 +323,12 @@ def test_seeded_6(dtype, C, variant, edge):
     shapes, B, H, _, Lq, P = SEEDED[6]
     g = problem(key(shapes), Lq, P, edge, B=B, H=H, C=C)
     assert g["unreferenced"][:, iso.level_rows(shapes, 3)].all() and g["unreferenced"][:, iso.level_rows(shapes, 4)].all()
-    t = geb.box_tensors(g, DTYPES[dtype])
+    t = point_cases.box_tensors(g, DTYPES[dtype])
     _lib.set_variant(variant)
     fwd, acc, rec = routes(t)
     assert fwd == GATHER and rec == REC_POINT and acc == (ACC_SPLIT if dtype == "f32" else ACC_TR), (fwd, acc, rec)
     route = "SEEDED[6] C=%d, variant %d: row-gather forward, %s accumulate" % (C, variant, ("valu", "tr", "f32", "split")[acc])
-    hold_families(route, dtype, g, geb.run_box, tensors=t, spread=spread_for(acc, rec)).done()
+    hold_families(route, dtype, g, point_cases.run_box, tensors=t, spread=spread_for(acc, rec)).done()
 
 
 @pytest.mark.parametrize("edge", EDGES)
@@ -336,7 +337,7 @@ def test_seeded_6(dtype, C, variant, edge):
 def test_wave_per_pair_forward(P, dtype, edge):
     from boxer_amd import ops
     g = problem(key(WIDE_LEVELS), 6, P, edge, pad=3)
-    t = geb.box_tensors(g, DTYPES[dtype])
+    t = point_cases.box_tensors(g, DTYPES[dtype])
     take_family(t["value"], t["loc"], t["shapes"], t["lsi"], WIDE)
 
     def run(tt):
@@ -357,13 +358,13 @@ def test_instance_shape_a(dtype, opt, edge):
     from boxer_amd import _lib
     a = SHAPE_A
     g = problem(key(a["levels"]), a["Lq"], a["k"] ** 2, edge, kind="instance", B=a["B"], H=a["H"], C=a["C"])
-    t = geb.inst_tensors(g, DTYPES[dtype])
+    t = point_cases.inst_tensors(g, DTYPES[dtype])
     _lib.set_option("inst_acc16", opt)
     _lib.set_variant(3)
     fwd, acc, rec = routes(t, instance=True)
     assert acc == {0: ACC_VALU, 1: ACC_VALU, 2: ACC_TR}[opt] and rec == REC_POINT, (acc, rec)
     route = "instance shape A: %s forward, %s accumulate" % (_lib.FWD_FAMILIES[fwd], ("valu", "tr", "f32", "split")[acc])
-    hold_families(route, dtype, g, geb.run_instance, instance=True, tensors=t, spread=spread_for(acc, rec)).done()
+    hold_families(route, dtype, g, point_cases.run_instance, instance=True, tensors=t, spread=spread_for(acc, rec)).done()
 
 
 @pytest.mark.parametrize("edge", EDGES)
@@ -371,11 +372,11 @@ def test_instance_shape_a(dtype, opt, edge):
 def test_instance_14_by_14_points(dtype, edge):
     """k = 14, six queries, four levels: the wave-per-pair instance forward and the backward on its default route."""
     g = problem(key(DECODER), 6, 196, edge, kind="instance")
-    t = geb.inst_tensors(g, DTYPES[dtype])
+    t = point_cases.inst_tensors(g, DTYPES[dtype])
     fwd, acc, rec = routes(t, instance=True)
     assert fwd == WIDE and rec == REC_POINT, (fwd, rec)
     route = "instance k = 14: wide forward, %s accumulate" % ("valu", "tr", "f32", "split")[acc]
-    hold_families(route, dtype, g, geb.run_instance, instance=True, tensors=t, spread=spread_for(acc, rec)).done()
+    hold_families(route, dtype, g, point_cases.run_instance, instance=True, tensors=t, spread=spread_for(acc, rec)).done()
 
 
 # ------------------------------------------------------------------ the contract the matrix-core accumulates miss
@@ -393,13 +394,13 @@ LEAK = "a non-finite upstream row reaches all 32 pixels of the blocks its query 
 @pytest.mark.parametrize("dtype,acc_key,rec_key", MATRIX_CORE_ROUTES,
                          ids=["f32_split", "f32_mfma", "bf16_point", "bf16_group", "f16_point", "f16_group"])
 def test_upstream_contract_on_the_encoder_matrix_core_accumulates(dtype, acc_key, rec_key, edge):
-    geb.set_encoder_keys(2, 0, acc_key, rec_key)
-    fwd, acc, rec, _ = geb.encoder_expectation(dtype, 2, 0, acc_key, rec_key)
+    route_vocab.set_encoder_keys(2, 0, acc_key, rec_key)
+    fwd, acc, rec, _ = point_cases.encoder_expectation(dtype, 2, 0, acc_key, rec_key)
     g = problem(key(ENCODER), "S", 4, edge)
-    t = geb.box_tensors(g, DTYPES[dtype])
+    t = point_cases.box_tensors(g, DTYPES[dtype])
     assert routes(t) == (fwd, acc, rec) and acc != ACC_VALU
     route = "contract, encoder: %s accumulate, %s records" % (("valu", "tr", "f32", "split")[acc], ("point", "group")[rec])
-    hold_families(route, dtype, g, geb.run_box, tensors=t, only=("upstream",)).done()
+    hold_families(route, dtype, g, point_cases.run_box, tensors=t, only=("upstream",)).done()
 
 
 @pytest.mark.xfail(strict=True, raises=AssertionError, reason=LEAK)
@@ -409,11 +410,11 @@ def test_upstream_contract_on_the_instance_matrix_core_accumulate(dtype, edge):
     from boxer_amd import _lib
     a = SHAPE_A
     g = problem(key(a["levels"]), a["Lq"], a["k"] ** 2, edge, kind="instance", B=a["B"], H=a["H"], C=a["C"])
-    t = geb.inst_tensors(g, DTYPES[dtype])
+    t = point_cases.inst_tensors(g, DTYPES[dtype])
     _lib.set_option("inst_acc16", 2)
     _lib.set_variant(3)
     assert routes(t, instance=True)[1:] == (ACC_TR, REC_POINT)
-    hold_families("contract, instance shape A: tr accumulate", dtype, g, geb.run_instance, instance=True, tensors=t,
+    hold_families("contract, instance shape A: tr accumulate", dtype, g, point_cases.run_instance, instance=True, tensors=t,
                   only=("upstream",)).done()
 
 
@@ -543,7 +544,6 @@ def test_raw_entries_stay_inside_their_buffers(name, levels, Lq, P, kind, pad, d
 
 
 # ------------------------------------------------------------------ from boxes and logits
-BOX_FLAVOURS = [(0, 4), (1, 5), (1, 7), (2, 5)]                 # angle mode, values a reference window
 WINDOWS = [(False, True), (True, False)]                         # (reference windows per head, valid ratios given)
 
 
@@ -639,11 +639,8 @@ def test_instance_attention_from_boxes(k, dtype, edge):
     tab.done()
 
 
-STAGED_GEOMETRY = {"four_levels": (STAGED_LEVELS, 2, 3), "one_level": ([(9, 13)], 2, 1), "tiny_levels": ([(4, 5), (2, 3), (1, 1)], 1, 2)}
-
-
 def test_staged_geometries_are_the_staged_files():
-    from test_gpu_box_boxes_staged_forward import GEOMETRY
+    from boxes_cases import STAGED_GEOMETRY as GEOMETRY
     for name, (levels, B, H) in STAGED_GEOMETRY.items():
         assert GEOMETRY[name] == dict(levels=levels, B=B, H=H)
 
@@ -682,11 +679,11 @@ def test_box_attention_from_boxes_staged(geometry, dtype, edge):
 @pytest.mark.parametrize("dtype", sorted(DTYPES))
 @pytest.mark.parametrize("angle_mode,ref_dim", BOX_FLAVOURS, ids=["plain", "turns_5", "turns_7", "radians"])
 def test_raw_backward_from_boxes_stays_inside_its_buffers(angle_mode, ref_dim, dtype, edge):
-    """boxattn_bwd_boxes_value_* (want = 3) through tests/test_box_boxes_value_abi.call with grad_value, the three other
+    """boxattn_bwd_boxes_value_* (want = 3) through tests/capi_cases.call_value with grad_value, the three other
     gradients and the workspace (exactly boxattn_bwd_boxes_value_workspace_bytes) between 0xA5 guards, on a value
     tensor between NaN guards whose unreferenced rows hold NaN: the guards are intact, the results the clean call's."""
     from boxer_amd import _lib
-    from test_box_boxes_value_abi import call as call_value
+    from capi_cases import call_value
     dt = DTYPES[dtype]
     g = boxes_problem(key(DECODER), 50, 2, edge, "box", 2, 2, angle_mode, ref_dim, False, True, 3)
     t = boxes_tensors(g, dt)

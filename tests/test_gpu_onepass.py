@@ -14,73 +14,14 @@ the reference's forward / backward allclose tests, tests/box_attn_test.py:96-159
 """
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
 import bench
+from compare_rules import check_onepass as check
+from point_cases import LEVELS4, binning_launches, counters, make_onepass_case as make_case, step
 
 pytestmark = pytest.mark.gpu
-
-OPT_RIDERS = 15         # 0 default (one-pass fill where eligible), 1 launches of their own, 4 two-pass riders (ABI 7)
-STAT_OFF = 1024         # the one-pass counters behind the locality counters: {calls, blocks redone} (include/boxattn.h)
-
-
-def _lib():
-    from boxer_amd import _lib
-    return _lib.load()
-
-
-def make_case(levels, lq, family="model", B=2, H=8, C=32, seed=0, dtype=torch.bfloat16):
-    name = "_onepass_test"
-    bench.WORKLOADS[name] = (list(levels), lq, 4, "box")
-    old = bench.H_HEADS, bench.C_HEAD
-    bench.H_HEADS, bench.C_HEAD = H, C
-    try:
-        return bench.make_inputs(name, dtype, "cuda", family=family, batch=B, seed=seed)
-    finally:
-        bench.H_HEADS, bench.C_HEAD = old
-        del bench.WORKLOADS[name]
-
-
-def step(inp, entry="train"):
-    from boxer_amd import ops
-    v, sh, ls, loc, attn, go = (inp[k] for k in ("value", "shapes", "lsi", "loc", "attn", "grad_out"))
-    if entry == "train":
-        out, plan = ops.box_attn_forward_train(v, sh, ls, loc, attn, 64)
-        grads = ops.box_attn_backward(v, sh, ls, loc, attn, go, 64, plan=plan)
-    else:                      # the reference's two calls: nothing but the tensors goes from one to the other
-        out = ops.box_attn_forward(v, sh, ls, loc, attn, 64)
-        grads = ops.box_attn_backward(v, sh, ls, loc, attn, go, 64)
-    torch.cuda.synchronize()
-    return out, grads
-
-
-def check(inp, out, grads, what):
-    for name, worst, tol in bench.parity_report(inp, out, grads):
-        assert worst <= tol, "%s: %s worst |err| / (max(1, rms) + |want|) = %.3e > %.0e" % (what, name, worst, tol)
-
-
-def counters():
-    """{calls of the one-pass chain, blocks redone} summed over the state buffers boxer_amd.ops keeps."""
-    from boxer_amd import ops
-    tot = np.zeros(2, dtype=np.int64)
-    for st in ops._STATE.values():
-        tot += st[STAT_OFF:STAT_OFF + 16].view(torch.int64).cpu().numpy()
-    return int(tot[0]), int(tot[1])
-
-
-def binning_launches(inp, entry="train"):
-    from boxer_amd import _lib
-    _lib.profile_begin()
-    try:
-        out, grads = step(inp, entry)
-    finally:
-        slots = _lib.profile_end()
-    return out, grads, slots["bwd_binning"]["launches"]
-
-
-LEVELS4 = [(37, 53), (19, 27), (10, 14), (5, 7)]
 
 
 @pytest.mark.parametrize("dtype,C", [(torch.bfloat16, 32), (torch.float32, 32), (torch.bfloat16, 16), (torch.bfloat16, 64)],

@@ -7,7 +7,6 @@ C ABI (boxer_amd.ops -> libboxattn_hip.so), against
 Tolerances (BASELINE.json north_star): fp64 1e-10, fp32 1e-4, bf16 1e-2 -- absolute on
 O(1) data, scaled by the magnitude of the expected tensor when that exceeds 1.
 """
-import math
 
 import numpy as np
 import pytest
@@ -15,29 +14,12 @@ import torch
 
 import golden_io
 from oracle import boxattn_oracle as oc
+from boxes_cases import _g9_check
+from compare_rules import close_parity as close
+from point_cases import PARITY_G9 as G9, SEEDED, _seeded, _torch_grid
+from route_vocab import OPT_ACC_F32, VARIANTS, _cdt, dev
 
 pytestmark = pytest.mark.gpu
-
-TOL = {torch.float64: 1e-10, torch.float32: 1e-4, torch.bfloat16: 1e-2}
-VARIANTS = {"auto": 0, "generic": 1, "atomic": 2, "binned": 3}
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return t.to(dtype) if dtype is not None else t
-
-
-def close(got, want, dtype, what, ignore=None):
-    """``ignore``: boolean mask (broadcastable to ``want``) of entries excluded from the check."""
-    got = got.detach().double().cpu().numpy()
-    want = np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if ignore is not None:
-        keep = ~np.broadcast_to(ignore, want.shape)
-        got, want = got * keep, want * keep
-    scale = max(1.0, float(np.abs(want).max()) if want.size else 1.0)
-    err = float(np.abs(got - want).max()) / scale if want.size else 0.0
-    assert err <= TOL[dtype], "%s: max scaled err %.3e > %.1e" % (what, err, TOL[dtype])
 
 
 @pytest.fixture(autouse=True)
@@ -45,10 +27,6 @@ def _reset_variant():
     from boxer_amd import _lib
     yield
     _lib.set_variant(0)
-
-
-def _cdt(dtype):
-    return torch.float32 if dtype == torch.bfloat16 else dtype
 
 
 def run_box(g, dtype, variant):
@@ -139,53 +117,6 @@ def test_instance_golden_bf16(name, variant):
 
 
 # ------------------------------------------------------------------ seeded, vs the C oracle
-def _seeded(shapes, B, H, C, Lq, P, seed, lo=-0.1, hi=1.1):
-    rng = np.random.default_rng(seed)
-    shapes = np.asarray(shapes, dtype=np.int64)
-    sizes = shapes.prod(1)
-    lsi = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-    S, L = int(sizes.sum()), len(shapes)
-    value = rng.integers(-127, 128, (B, S, H, C)).astype(np.float64) / 64
-    loc = rng.uniform(lo, hi, (B, Lq, H, L, P, 2)).astype(np.float32).astype(np.float64)
-    a = rng.uniform(1e-5, 1, (B, Lq, H, L, P))
-    attn = (a / a.sum((-1, -2), keepdims=True)).astype(np.float32).astype(np.float64)
-    lvl = (a / a.sum(-2, keepdims=True)).astype(np.float32).astype(np.float64)
-    gout = rng.integers(-64, 65, (B, Lq, H * C)).astype(np.float64) / 32
-    gmask = rng.integers(-64, 65, (B, Lq, P, H * C)).astype(np.float64) / 32
-    return dict(value=value, shapes=shapes, lsi=lsi, loc=loc, attn=attn, spatial_w=attn,
-                level_w=lvl, grad_out=gout, grad_mask=gmask, on_edge=on_cell_edge(loc, shapes))
-
-
-def on_cell_edge(loc, shapes, eps=1e-4):
-    """(B,Lq,H,L,P,1) mask of points whose pixel coordinate is within eps of an integer.
-    grad_loc is discontinuous there (the bilinear cell changes), so float32 arithmetic and the
-    float64 oracle may legitimately pick different cells; such points are excluded from the
-    grad_loc comparison (their other outputs are continuous and stay checked)."""
-    size = np.asarray(shapes, dtype=np.float64)[None, None, None, :, None, ::-1]   # (W, H)
-    pix = loc * size - 0.5
-    return (np.abs(pix - np.round(pix)) < eps).any(-1, keepdims=True)
-
-
-SEEDED = [
-    # shapes, B, H, C, Lq, P
-    ([(20, 30), (10, 15), (5, 8), (3, 4)], 2, 8, 32, 333, 4),     # BoxeR encoder geometry
-    ([(20, 30), (10, 15)], 1, 8, 32, 7, 16),                      # ragged tail wave
-    ([(9, 7)], 3, 4, 16, 50, 4),                                  # G=4 path
-    ([(9, 7), (4, 3)], 2, 2, 64, 21, 9),                          # G=16 path, odd P
-    ([(9, 7), (4, 3)], 2, 3, 12, 5, 4),                           # C%4==0 but no fast variant
-    ([(6, 5)], 1, 1, 1, 3, 1),                                    # minimum everything
-    # odd map sizes (uneven destination blocks), one-pixel-wide / -high levels, enough points
-    # per block for chunked work items
-    ([(25, 25), (13, 13), (7, 5), (1, 3), (2, 1)], 1, 2, 32, 700, 4),
-    ([(13, 21), (5, 4)], 2, 2, 64, 300, 9),                       # 8 channels per lane, G=8 (bf16)
-    # few queries x many points: one wave per (query, head) pair in the instance forward;
-    # 3 and 5 levels do not fill the lane groups evenly
-    ([(11, 9), (6, 5), (3, 2)], 1, 4, 32, 6, 49),
-    ([(11, 9), (6, 5), (3, 2), (2, 2), (1, 1)], 2, 2, 32, 3, 36),
-    # ... two waves per pair (head = workgroup mod 8), an odd number of (image, query) rows: the last workgroup's second
-    # pair does not exist
-    ([(11, 9), (6, 5)], 1, 8, 32, 7, 40),
-]
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -240,7 +171,6 @@ def test_box_backward_algorithms(cfg, dtype, variant):
     close(ga, want[2], torch.float32, "grad_attn")
 
 
-OPT_ACC_F32 = 19        # boxattn_set_option: float32 accumulate -- 0 default: bf16 matrix cores on exact three-term splits,
                         # 1: VALU list walk, 2: v_mfma_f32_32x32x2_f32
 
 
@@ -647,18 +577,6 @@ def test_fused_module_paths_match_reference_goldens(fused_grid, fused_pointwise,
 
 
 # ------------------------------------------------------------------ nn.Modules at the model's head geometry (G9)
-# d = 256, 8 heads (32 channels per head), 4 levels, 2 x 2 points: the shapes the window-staged / gather / binned
-# kernels run (G7 / G8: d = 32 with 4 heads = 8 channels per head, generic kernels only).  Outputs AND gradients --
-# of query, value, reference windows and every parameter -- against what torch's autograd gives for the reference's
-# own module code in float64 (tests/golden/make_goldens.py g9), for every opt-in path, with the path that ran asserted.
-G9 = {
-    "G9_module_box_enc": ("BoxAttention", dict(kernel_size=2), 1),
-    "G9_module_box_enc_masked": ("BoxAttention", dict(kernel_size=2), 1),
-    "G9_module_box_dec": ("BoxAttention", dict(kernel_size=2), 1),
-    "G9_module_box3d_fixed_enc": ("Box3dAttention", dict(with_rotation=False, kernel_size=2), 1),
-    "G9_module_box3d_rot_dec": ("Box3dAttention", dict(with_rotation=True, kernel_size=2), 1),
-    "G9_module_inst_k4": ("InstanceAttention", dict(kernel_size=4), 2),
-}
 
 
 def _g9_run(name, dtype, fused_grid=0, fused_pointwise=False, native_bf16=False):
@@ -698,29 +616,6 @@ def _g9_run(name, dtype, fused_grid=0, fused_pointwise=False, native_bf16=False)
     return m, outs, grads, g, spies
 
 
-def _g9_check(name, outs, grads, g, tol, what, rms_only=()):
-    """Every output and gradient: max |got - want| / max(1, max |want|) <= tol; for the tensors named in `rms_only`
-    the relative root-mean-square error instead (bf16 autocast: the box offsets are bf16 numbers, a few sample
-    points per image land on the other side of a bilinear cell edge than in the float64 run, and the gradients
-    that flow through the LOCATIONS -- reference windows, box projection, query -- jump there; the reference under
-    autocast has the same sensitivity)."""
-    def errs(got, want):
-        got = got.detach().double().cpu().numpy()
-        want = np.asarray(want, dtype=np.float64).reshape(got.shape)
-        return (float(np.abs(got - want).max()) / max(1.0, float(np.abs(want).max())),
-                float(np.sqrt(((got - want) ** 2).mean()) / max(1e-30, np.sqrt((want ** 2).mean()))))
-    worst = {}
-    for i, o in enumerate(outs):
-        worst["out%d" % i] = errs(o, g["out%d" % i])[0]
-    for k, v in grads.items():
-        key = "grad_" + k if not k.startswith("param.") else "grad." + k[6:]
-        assert v is not None, "%s: no gradient reached %s" % (name, k)
-        e_max, e_rms = errs(v, g[key])
-        worst[k] = e_rms / 2 if any(r in k for r in rms_only) else e_max       # (rms criterion: 2 tol)
-    bad = {k: v for k, v in worst.items() if not v <= tol}
-    assert not bad, "%s %s: errors above %.0e: %s" % (name, what, tol, bad)
-
-
 @pytest.mark.parametrize("name", sorted(G9))
 def test_g9_modules_float64(name):
     """float64 (the generic kernels): the module glue -- projections, box decoding, softmax, masks, rotation -- and
@@ -752,23 +647,6 @@ def test_g9_modules_fast_paths(name, fused_grid, fused_pointwise, native_bf16):
 
 
 # ------------------------------------------------------------------ box -> grid (opt-in)
-def _torch_grid(ref, off, kidx, vr, angle_mode):
-    """The reference modules' _where_to_attend after the offset projection
-    (box_attention.py:63-81, 304-338)."""
-    r = ref[:, :, None, None] if ref.dim() == 3 else ref[:, :, :, None]
-    wh = r[..., 2:4]
-    boxes = r[..., :4] + off[..., :4] / 8 * torch.cat([wh, wh], dim=-1)
-    boxes = boxes.unsqueeze(-2)
-    c, size = boxes[..., :2], boxes[..., 2:]
-    local = kidx * torch.relu(size)
-    if angle_mode:
-        ang = (r[..., 4:5] + off[..., 4:5] / 16) * 2 * math.pi if angle_mode == 1 \
-            else r[..., 4:5].expand(off.shape[:4] + (1,))
-        cos, sin = torch.cos(ang), torch.sin(ang)
-        lx, ly = local[..., 0], local[..., 1]
-        local = torch.stack([lx * cos - ly * sin, lx * sin + ly * cos], dim=-1)
-    grid = c + local
-    return grid * vr if vr is not None else grid
 
 
 @pytest.mark.parametrize("angle_mode", [0, 1, 2])

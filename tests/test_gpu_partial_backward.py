@@ -3,10 +3,10 @@ for -- VALUE (grad_value) or POINTS (grad_loc + the weight gradients) -- and the
 ``ctx.needs_input_grad``.
 
 Reference gradients come from the fp64 CPU oracle (oracle/boxattn_oracle.c), compared the way the existing GPU
-tests compare the same quantity and storage type: tests/test_gpu_parity.py ``close`` (fp64 1e-10, fp32 1e-4, bf16
+tests compare the same quantity and storage type: tests/compare_rules.py ``close_parity`` (fp64 1e-10, fp32 1e-4, bf16
 1e-2, scaled by the magnitude of the expected tensor; grad_loc without the points on a bilinear cell edge),
-tests/test_gpu_f16.py ``check`` for float16 storage (1e-3 for f16 tensors, 1e-4 for float32 ones), and
-bench.parity_report for the encoder shapes tests/test_gpu_dense.py builds.
+``check_f16`` for float16 storage (1e-3 for f16 tensors, 1e-4 for float32 ones), and
+bench.parity_report (``check_onepass``) for the encoder shapes of tests/test_gpu_dense.py (point_cases.make_dense_case).
 
 grad_value sums are not ordered (float atomics; the record order inside a bin follows atomics): the bitwise claim of
 want = 3 against the existing call is made where repeated runs of the existing call agree -- two runs first, and
@@ -16,131 +16,25 @@ case gave the same bits twice and other bits the third time).
 Every case runs the full call twice, then the new entry with want = 3, 2, 1; all findings of a case are printed and
 collected before the test asserts, so one run shows everything a kernel family gets wrong.
 """
-import functools
 
 import numpy as np
 import pytest
 import torch
 
 import bench
-import test_gpu_dense as dense_tests
-import test_gpu_f16 as f16_tests
-import test_gpu_onepass as onepass_tests
-import test_gpu_parity as parity_tests
-from oracle import boxattn_oracle as oc
+import compare_rules
+import point_cases
+from point_cases import (ALL, Case, PARTIAL_DECODER as DECODER, POINTS, P_OF, REPEATS, SUFFIX, VALUE, _blib, call,
+                         profiled, seeded_case, untouched)
+from route_vocab import OPT_DENSE
 
 pytestmark = pytest.mark.gpu
 
-VALUE, POINTS, ALL = 1, 2, 3
-OPT_DENSE = 11
-HINT_FRESH_STATE = 2
-REPEATS = 6                          # further runs that settle whether a family's grad_value sum is ordered
-PATTERN = 0x5A                       # what an output nobody asked for must still hold after the call
-SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16", torch.float16: "f16"}
-
-
-def _blib():
-    from boxer_amd import _lib
-    return _lib
-
 
 # ------------------------------------------------------------------------------------------ cases
-class Case:
-    """Device tensors of one problem + what the raw entry points need."""
-
-    def __init__(self, kind, dtype, value, shapes, lsi, loc, weights, grad_out, grad_mask=None):
-        self.kind, self.dtype = kind, dtype
-        self.cdt = torch.float32 if dtype in (torch.bfloat16, torch.float16) else dtype
-        self.value, self.shapes, self.lsi, self.loc = value, shapes, lsi, loc
-        self.weights, self.grad_out, self.grad_mask = list(weights), grad_out, grad_mask
-        B, S, H, C = value.shape
-        self.dims = (B, S, H, C, shapes.size(0), loc.size(1), loc.size(4))
-        self.sh, self.ls = shapes.cpu().numpy().copy(), lsi.cpu().numpy().copy()
-        lib = _blib().load()
-        h16 = int(dtype in (torch.bfloat16, torch.float16))
-        host = (self.sh.ctypes.data, self.ls.ctypes.data)
-        self.ws_bytes = max(256, int(lib.boxattn_bwd_workspace_bytes(h16, *self.dims, *host)))
-        self.state_bytes = int(lib.boxattn_state_bytes(*self.dims, *host))
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device="cuda")
-
-    @property
-    def n_out(self):
-        return 3 if self.kind == "box" else 4
-
-    def new_state(self):
-        return torch.zeros(self.state_bytes, dtype=torch.uint8, device="cuda")
-
-    def outputs(self, pattern=False):
-        """[grad_value, grad_loc, weight gradients ...], uninitialised or filled with PATTERN bytes."""
-        outs = [torch.empty_like(self.value), torch.empty(self.loc.shape, dtype=self.cdt, device="cuda")]
-        outs += [torch.empty(w.shape, dtype=self.cdt, device="cuda") for w in self.weights]
-        if pattern:
-            for t in outs:
-                t.view(torch.uint8).fill_(PATTERN)
-        return outs
-
-
-def untouched(t):
-    return bool((t.view(torch.uint8) == PATTERN).all().item())
-
-
-def call(case, want=None, outs=None, ws="own", state=None, fresh=False, hints=0, null=()):
-    """One raw backward call: want None -> *_bwd_ws_* (float64: the plain backward), else *_bwd_part_*.
-    null: indices of outputs passed as NULL.  -> (rc, outs)"""
-    lib = _blib().load()
-    outs = case.outputs() if outs is None else outs
-    stem = "boxattn" if case.kind == "box" else "instattn"
-    f64 = case.dtype == torch.float64
-    name = "%s_bwd%s_%s" % (stem, "_part" if want is not None else ("" if f64 else "_ws"), SUFFIX[case.dtype])
-    args = [case.value, case.shapes, case.lsi, case.loc, *case.weights, case.grad_out]
-    if case.kind == "instance":
-        args.append(case.grad_mask)
-    args = [a.data_ptr() for a in args] + list(case.dims)
-    args += [0 if i in null else t.data_ptr() for i, t in enumerate(outs)]
-    if not f64:
-        wsbuf = case.ws if isinstance(ws, str) else ws
-        args += [case.sh.ctypes.data, case.ls.ctypes.data,
-                 wsbuf.data_ptr() if wsbuf is not None else 0, wsbuf.numel() if wsbuf is not None else 0, 0, 0,
-                 state.data_ptr() if state is not None else 0, state.numel() if state is not None else 0,
-                 hints | (HINT_FRESH_STATE if fresh else 0)]
-    args.append(torch.cuda.current_stream().cuda_stream)
-    if want is not None:
-        args.append(want)
-    rc = getattr(lib, name)(*args)
-    torch.cuda.synchronize()
-    return rc, outs
-
-
-def profiled(fn):
-    """-> (result of fn(), {slot: launches})"""
-    blib = _blib()
-    blib.profile_begin()
-    try:
-        res = fn()
-        torch.cuda.synchronize()
-    finally:
-        slots = blib.profile_end()
-    return res, {k: v["launches"] for k, v in slots.items()}
 
 
 # ---- seeded problems (tests/test_gpu_parity.py's generator: storage values exact in every 16-bit type)
-@functools.lru_cache(maxsize=None)
-def seeded(shapes, B, H, C, Lq, P, seed):
-    g = parity_tests._seeded([list(s) for s in shapes], B, H, C, Lq, P, seed=seed)
-    box = oc.box_attn_backward(g["value"], g["shapes"], g["lsi"], g["loc"], g["attn"], g["grad_out"])
-    inst = oc.instance_attn_backward(g["value"], g["shapes"], g["lsi"], g["loc"], g["spatial_w"], g["level_w"],
-                                     g["grad_out"], g["grad_mask"])
-    return g, {"box": list(box), "instance": list(inst)}        # computed once, shared, never written
-
-
-def seeded_case(kind, dtype, cfg, seed=31):
-    g, want = seeded(*cfg, seed)
-    dev = parity_tests.dev
-    cdt = torch.float32 if dtype in (torch.bfloat16, torch.float16) else dtype
-    weights = [dev(g["attn"], cdt)] + ([dev(g["level_w"], cdt)] if kind == "instance" else [])
-    case = Case(kind, dtype, dev(g["value"], dtype), dev(g["shapes"]), dev(g["lsi"]), dev(g["loc"], cdt), weights,
-                dev(g["grad_out"], dtype), dev(g["grad_mask"], dtype) if kind == "instance" else None)
-    return case, want[kind], g["on_edge"]
 
 
 GRAD_NAMES = {"box": ("grad_value", "grad_loc", "grad_attn"),
@@ -155,9 +49,10 @@ def oracle_errors(case, outs, want, on_edge, which):
         ignore = on_edge if name == "grad_loc" else None
         try:
             if case.dtype == torch.float16:
-                f16_tests.check(outs[i], want[i], name, ignore=ignore)
+                compare_rules.check_f16(outs[i], want[i], name, ignore=ignore)
             else:
-                parity_tests.close(outs[i], np.asarray(want[i]).reshape(outs[i].shape), outs[i].dtype, name, ignore=ignore)
+                compare_rules.close_parity(outs[i], np.asarray(want[i]).reshape(outs[i].shape), outs[i].dtype, name,
+                                           ignore=ignore)
         except AssertionError as e:
             bad.append(str(e))
     return bad
@@ -258,8 +153,6 @@ def run_family(case, errors, states=True, inexact_points=""):
 
 # ------------------------------------------------------------- 1-5: generic, fast atomic, gather / binned decoder
 GENERIC = ((((6, 4), (3, 2)), 1, 2, 2, 2), (((6, 4), (3, 2)), 1, 2, 5, 2))          # shapes, B, H, C, Lq  (+ P per kind)
-DECODER = (((12, 10), (6, 5)), 2, 8, 32, 13)
-P_OF = {"generic": {"box": 2, "instance": 4}, "decoder": {"box": 4, "instance": 16}}
 
 FAMILY_CASES = (
     [("generic", cfg, dt, v) for cfg in GENERIC for dt in (torch.float32, torch.float64) for v in (0, 1)] +
@@ -294,7 +187,7 @@ def test_partial_backward_atomic_gather_binned(kind, family, cfg, dtype, variant
 @pytest.mark.parametrize("lv", ["3lv", "4lv_odd"])
 def test_partial_backward_encoder(lv, dtype, family, staged):
     from boxer_amd import ops
-    inp = dense_tests.make_case(dense_tests.LEVELS[lv], family, dtype=dtype)
+    inp = point_cases.make_dense_case(point_cases.LEVELS[lv], family, dtype=dtype)
     _blib().load().boxattn_set_option(OPT_DENSE, 2 if staged else 1)
     case = Case("box", dtype, inp["value"], inp["shapes"], inp["lsi"], inp["loc"], [inp["attn"]], inp["grad_out"])
     out = ops.box_attn_forward(inp["value"], inp["shapes"], inp["lsi"], inp["loc"], inp["attn"], 64)
@@ -309,13 +202,13 @@ def test_partial_calls_leave_the_one_pass_state_alone():
     block redone, the oracle's tensors."""
     from boxer_amd import ops
     ops.release_workspaces()
-    inp = onepass_tests.make_case(onepass_tests.LEVELS4, 900, dtype=torch.bfloat16, C=16, seed=3)
+    inp = point_cases.make_onepass_case(point_cases.LEVELS4, 900, dtype=torch.bfloat16, C=16, seed=3)
     ns = inp["dims"]["B"] * inp["dims"]["H"]
     v, sh, ls, loc, attn, go = (inp[k] for k in ("value", "shapes", "lsi", "loc", "attn", "grad_out"))
-    onepass_tests.step(inp)
-    out, grads = onepass_tests.step(inp)
-    onepass_tests.check(inp, out, grads, "second full call")
-    before = onepass_tests.counters()
+    point_cases.step(inp)
+    out, grads = point_cases.step(inp)
+    compare_rules.check_onepass(inp, out, grads, "second full call")
+    before = point_cases.counters()
     assert before == (ns, 0), "the second full call on this shape is a one-pass call"
     snap = {k: st.clone() for k, st in ops._STATE.items()}
     for want in (VALUE, POINTS):
@@ -332,11 +225,11 @@ def test_partial_calls_leave_the_one_pass_state_alone():
     assert set(snap) == set(ops._STATE)
     for k, st in ops._STATE.items():
         assert torch.equal(st[1024:], snap[k][1024:]), "a partial call wrote the state"
-    assert onepass_tests.counters() == before
-    out, grads, launches = onepass_tests.binning_launches(inp)
-    onepass_tests.check(inp, out, grads, "full call after the partial calls")
+    assert point_cases.counters() == before
+    out, grads, launches = point_cases.binning_launches(inp)
+    compare_rules.check_onepass(inp, out, grads, "full call after the partial calls")
     assert launches == 0, "still the one-pass steady state: no count / scan / fill launch"
-    assert onepass_tests.counters() == (before[0] + ns, before[1]), "exactly one more one-pass call, nothing redone"
+    assert point_cases.counters() == (before[0] + ns, before[1]), "exactly one more one-pass call, nothing redone"
 
 
 # ------------------------------------------------------------- 7: errors

@@ -14,51 +14,11 @@ import torch
 
 import golden_io
 from oracle import boxattn_oracle as oc
+from boxes_cases import module_problem, tables
+from compare_rules import check_scaled as check, rounded, tol_of
+from route_vocab import DTYPES, GATHER, WIDE, WIDE_OFF, WIDE_ON, dev, take_family
 
 pytestmark = pytest.mark.gpu
-
-GENERIC, FAST, GATHER, WIDE, STAGED = range(5)
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
-WIDE_OFF, WIDE_ON = 1, 2
-
-
-def tol_of(dtype):
-    return 1e-4 if dtype == torch.float32 else 1e-2
-
-
-def check(got, want, tol, what):
-    got = got.detach().double().cpu().numpy().reshape(np.shape(want))
-    want = np.asarray(want, dtype=np.float64)
-    assert np.isfinite(got).all(), what
-    scale = max(1.0, float(np.sqrt(np.mean(want * want))))
-    worst = float((np.abs(got - want) / (scale + np.abs(want))).max())
-    print("%s: worst |err| / (%.3g + |want|) = %.3e (tol %.0e)" % (what, scale, worst, tol))
-    assert worst <= tol, "%s: worst |err| / (%.3g + |want|) = %.3e > %.1e" % (what, scale, worst, tol)
-
-
-def rounded(a, dtype):
-    """The float64 numbers a tensor of `dtype` holds after taking `a`."""
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dtype).double().numpy()
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return t.to(dtype) if dtype is not None else t
-
-
-def tables(levels):
-    shapes = np.asarray(levels, dtype=np.int64)
-    sizes = shapes.prod(1)
-    return shapes, np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64), int(sizes.sum())
-
-
-def take_family(value, loc, shapes, lsi, family):
-    """Assert that box attention on these tensors runs on `family`; WIDE: force key 22 on where the default is off."""
-    from boxer_amd import _lib, ops
-    if family == WIDE and ops.forward_route(value, loc, shapes, lsi) != WIDE:
-        _lib.set_option("wide_box", WIDE_ON)
-    got = ops.forward_route(value, loc, shapes, lsi)
-    assert got == family, "route %s, wanted %s" % (_lib.FWD_FAMILIES[got], _lib.FWD_FAMILIES[family])
 
 
 def box_forward(g, dtype, family=WIDE, value=None):
@@ -216,22 +176,6 @@ def test_training_forward_hands_over_a_plan(dtype):
 
 
 # ------------------------------------------------------------------ 5. the module and the compiled operator
-def module_problem():
-    from boxer_amd import InstanceAttention
-    torch.manual_seed(3)
-    g6 = golden_io.load("G6_inst_ms14")
-    shapes = dev(g6["shapes"])
-    lsi = dev(g6["lsi"])
-    S = int(g6["shapes"].prod(1).sum())
-    B, Lq, d = 2, 6, 256
-    m = InstanceAttention(d, 4, 8, 14).cuda()
-    with torch.no_grad():
-        m.linear_box_weight.normal_(0, 0.05)
-        m.linear_attn_weight.normal_(0, 0.1)
-    query = torch.randn(B, Lq, d, device="cuda")
-    value = torch.randn(B, S, d, device="cuda")
-    ref = torch.rand(B, Lq, 4, device="cuda") * 0.5 + 0.2
-    return m, (query, value, shapes, None, lsi, None, ref), (B, S, 8, 32, 4, Lq, 196), g6
 
 
 @pytest.mark.parametrize("fused_pointwise", [False, True], ids=["torch_pointwise", "fused_pointwise"])

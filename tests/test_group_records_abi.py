@@ -4,21 +4,15 @@ bumps the options epoch; the route table: group records for 16-bit box attention
 under key 24 = 2, point records for float32, instance attention, other P and key 24 = 1; the workspace of an eligible
 shape is smaller under key 24 = 2.  Pure host code: there is no GPU here."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
+from capi_cases import C2, C2P, C5P, HEADER
+from route_vocab import KEY_GROUP, KEY_POINT, OPT_GROUP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
 
 POINT, GROUP = 0, 1
-OPT_GROUP = 24
-KEY_POINT, KEY_GROUP = 1, 2
-C2 = [(100, 100), (50, 50), (25, 25), (13, 13)]
-C2P = [(100, 167), (50, 84), (25, 42), (13, 21)]
-C5P = [(234, 234), (117, 117)]
 
 
 @pytest.fixture(scope="module")

@@ -8,17 +8,9 @@ import re
 import sys
 
 import pytest
+from capi_cases import HEADER, ROOT, header_declarations as declarations
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
 NAMES = ["instattn_weights_%s_%s" % (way, suf) for way in ("fwd", "bwd") for suf in ("f32", "bf16", "f16")]
-
-
-def declarations():
-    """name -> parameter list (whitespace-normalised) of every function the header declares."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return {m.group(1): " ".join(m.group(2).split())
-            for m in re.finditer(r"\b((?:boxattn|instattn)_\w+)\s*\(([^;{]*?)\)\s*;", text, re.S)}
 
 
 @pytest.fixture(scope="module")

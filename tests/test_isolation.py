@@ -8,13 +8,10 @@ import pytest
 
 import isolation as iso
 from oracle import boxattn_oracle as oc
+from isolation import BOX_FLAVOURS, DECODER, ENCODER, STAGED_GEOMETRY, STAGED_LEVELS, WIDE_LEVELS
+from point_cases import LEVELS_A
 
-ENCODER = [(13, 13), (7, 5)]
-STAGED_LEVELS = [(37, 23), (19, 12), (10, 6), (5, 3)]
-DECODER = [(20, 30), (10, 15), (5, 8), (3, 4)]
 SEEDED_6 = [(25, 25), (13, 13), (7, 5), (1, 3), (2, 1)]
-WIDE_LEVELS = [(11, 9), (6, 5), (3, 2)]
-LEVELS_A = [(16, 24), (7, 5), (1, 3)]
 # name -> levels, queries, points: every geometry of the GPU cases
 GEOMETRIES = {
     "encoder": (ENCODER, "S", 4), "staged": (STAGED_LEVELS, "S", 4), "decoder": (DECODER, 50, 4),
@@ -24,9 +21,9 @@ GEOMETRIES = {
 
 
 def test_geometries_are_the_gpu_files():
-    import test_gpu_error_bounds as geb
-    from test_gpu_instance_accumulate16 import LEVELS_A as A
-    from test_gpu_parity import SEEDED
+    import isolation as geb
+    from point_cases import LEVELS_A as A
+    from point_cases import SEEDED
     assert (geb.ENCODER, geb.DECODER, geb.WIDE_LEVELS, A) == (ENCODER, DECODER, WIDE_LEVELS, LEVELS_A)
     assert SEEDED[6][0] == SEEDED_6 and SEEDED[6][4] == 700
 
@@ -78,11 +75,6 @@ def hold_conditions(name, levels, edge, g):
     main = iso.touched(g["shapes"], g["loc"][:1], 1, g["value"].shape[1], g["lsi"], queries=others)
     assert own.any() == any(iso.has_patch(lv, edge) for lv in levels) and not (own & main).any()
     assert not (g["opposite"] & ~g["touched"]).any()
-
-
-BOX_FLAVOURS = [(0, 4), (1, 5), (1, 7), (2, 5)]                  # angle mode, values a reference window
-STAGED_GEOMETRY = {"four_levels": (STAGED_LEVELS, 2, 3), "one_level": ([(9, 13)], 2, 1),
-                   "tiny_levels": ([(4, 5), (2, 3), (1, 1)], 1, 2)}
 
 
 @pytest.mark.parametrize("edge", iso.EDGES)

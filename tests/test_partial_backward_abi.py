@@ -10,19 +10,11 @@ import re
 import sys
 
 import pytest
+from capi_cases import HEADER, ROOT, header_declarations as declarations
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "boxattn.h")
 
 PART_ENTRY_POINTS = ["%s_bwd_part_%s" % (kind, suf) for kind in ("boxattn", "instattn")
                      for suf in ("f32", "bf16", "f16", "f64")]
-
-
-def declarations():
-    """name -> parameter list (whitespace-normalised) of every function the header declares."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return {m.group(1): " ".join(m.group(2).split())
-            for m in re.finditer(r"\b((?:boxattn|instattn)_\w+)\s*\(([^;{]*?)\)\s*;", text, re.S)}
 
 
 @pytest.fixture(scope="module")
