@@ -10,8 +10,11 @@
 // kernels here, built with the host compiler against torch's headers
 // (`python setup.py build_ext --inplace`, or __graft_entry__.build()).
 //
-// float32 / float64 as in the reference; bfloat16 `value` (with float32 locations / weights) is
-// the storage mode this library adds.
+// float32 / float64 as in the reference; bfloat16 and float16 `value` (with float32 locations /
+// weights) are the storage modes this library adds.  Each family of C entry points is called from
+// ONE place: with_storage picks the struct of `value`'s storage type (element types, entry points),
+// and the two sequences box and instance attention share -- forward, backward_ws -- take the
+// call itself as a lambda.
 #include <torch/extension.h>
 
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -24,7 +27,9 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "boxattn.h"
@@ -32,8 +37,14 @@
 namespace e2edet {
 namespace {
 
-struct Dims {
+// One call: the tensors the shared sequences need (w1: instance attention's level weights, NULL for box attention),
+// the dimensions, the device pointers of the two level tables and the stream.
+struct Call {
+    const at::Tensor &value, &shapes, &lsi, &loc, &w0;
+    const at::Tensor *w1;
     int B, S, H, C, L, Lq, P;
+    const int64_t *sh, *ls;
+    void *stream;
 };
 
 void check_input(const at::Tensor &t, const char *name)
@@ -42,54 +53,50 @@ void check_input(const at::Tensor &t, const char *name)
     TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
-void check_chunks(int64_t batch, int im2col_step)
+bool is_h16(const at::Tensor &value)       // 16-bit storage
 {
-    const int64_t step = std::min<int64_t>(batch, im2col_step);
-    if (batch > 0)
-        TORCH_CHECK(step > 0 && batch % step == 0, "batch(", batch, ") must divide im2col_step(",
-                    step, ")");
+    return value.scalar_type() == at::kBFloat16 || value.scalar_type() == at::kHalf;
 }
 
 // The reference's CHECK_INPUT block plus the shape relations its kernels silently assume.
-Dims prepare(const at::Tensor &value, const at::Tensor &shapes, const at::Tensor &lsi,
-             const at::Tensor &loc, std::initializer_list<const at::Tensor *> weights,
-             int im2col_step)
+Call prepare(const at::Tensor &value, const at::Tensor &shapes, const at::Tensor &lsi, const at::Tensor &loc,
+             const at::Tensor &w0, const at::Tensor *w1, int im2col_step)
 {
     check_input(value, "value");
     check_input(shapes, "spatial_shapes");
     check_input(lsi, "level_start_index");
     check_input(loc, "sampling_loc");
-    for (const at::Tensor *w : weights) check_input(*w, "attn_weight");
+    for (const at::Tensor *w : {&w0, w1})
+        if (w) check_input(*w, "attn_weight");
     const auto vt = value.scalar_type();
-    const bool h16 = vt == at::kBFloat16 || vt == at::kHalf;     // 16-bit storage
+    const bool h16 = is_h16(value);
     TORCH_CHECK(vt == at::kFloat || vt == at::kDouble || h16,
                 "box_attn: unsupported dtype (float32, float64, bfloat16, float16)");
     TORCH_CHECK(shapes.scalar_type() == at::kLong && lsi.scalar_type() == at::kLong,
                 "spatial_shapes / level_start_index must be int64");
     TORCH_CHECK(value.dim() == 4 && loc.dim() == 6 && loc.size(5) == 2,
                 "expected value (B,S,H,C) and sampling_loc (B,Lq,H,L,P,2)");
-    Dims d;
-    d.B = (int)value.size(0); d.S = (int)value.size(1); d.H = (int)value.size(2);
-    d.C = (int)value.size(3); d.L = (int)shapes.size(0);
-    d.Lq = (int)loc.size(1); d.P = (int)loc.size(4);
-    TORCH_CHECK(loc.size(0) == d.B && loc.size(2) == d.H && loc.size(3) == d.L &&
-                    lsi.numel() == d.L,
+    Call c = {value, shapes, lsi, loc, w0, w1};
+    c.B = (int)value.size(0); c.S = (int)value.size(1); c.H = (int)value.size(2);
+    c.C = (int)value.size(3); c.L = (int)shapes.size(0);
+    c.Lq = (int)loc.size(1); c.P = (int)loc.size(4);
+    TORCH_CHECK(loc.size(0) == c.B && loc.size(2) == c.H && loc.size(3) == c.L && lsi.numel() == c.L,
                 "sampling_loc / spatial_shapes do not match value");
     const auto wt = h16 ? at::kFloat : vt;     // 16-bit storage: fp32 geometry
     TORCH_CHECK(loc.scalar_type() == wt, "sampling_loc must be ",
                 h16 ? "float32 for bfloat16 / float16 value" : "of value's dtype");
-    const int64_t n_w = (int64_t)d.B * d.Lq * d.H * d.L * d.P;
-    for (const at::Tensor *w : weights) {
+    const int64_t n_w = (int64_t)c.B * c.Lq * c.H * c.L * c.P;
+    for (const at::Tensor *w : {&w0, w1}) {
+        if (!w) continue;
         TORCH_CHECK(w->numel() == n_w, "attention weights must have B*Lq*H*L*P elements");
         TORCH_CHECK(w->scalar_type() == wt, "attention weights must have sampling_loc's dtype");
     }
-    check_chunks(d.B, im2col_step);
-    return d;
-}
-
-int is_h16(const at::Tensor &value)
-{
-    return value.scalar_type() == at::kBFloat16 || value.scalar_type() == at::kHalf;
+    const int64_t step = std::min<int64_t>(c.B, im2col_step);
+    if (c.B > 0)
+        TORCH_CHECK(step > 0 && c.B % step == 0, "batch(", c.B, ") must divide im2col_step(", step, ")");
+    c.sh = shapes.data_ptr<int64_t>();
+    c.ls = lsi.data_ptr<int64_t>();
+    return c;
 }
 
 void check_rc(int rc, const char *what)
@@ -149,7 +156,7 @@ std::shared_ptr<const std::vector<int64_t>> host_table(const at::Tensor &t)
 }
 struct HostTables {
     std::shared_ptr<const std::vector<int64_t>> shapes, lsi;
-    HostTables(const at::Tensor &s, const at::Tensor &l) : shapes(host_table(s)), lsi(host_table(l)) {}
+    explicit HostTables(const Call &c) : shapes(host_table(c.shapes)), lsi(host_table(c.lsi)) {}
     const int64_t *sh() const { return shapes->data(); }
     const int64_t *ls() const { return lsi->data(); }
 };
@@ -171,28 +178,28 @@ bool capturing()
 }
 
 // the backward's scratch of this stream (contents only live inside one call; calls on a stream never overlap)
-at::Tensor workspace(const at::Tensor &value, const Dims &d, const HostTables &h, void *stream)
+at::Tensor workspace(const Call &c, const HostTables &h)
 {
     const size_t bytes = std::max<size_t>(
-        boxattn_bwd_workspace_bytes(is_h16(value), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
-                                    h.sh(), h.ls()), 256);
-    const StreamKey key(value.get_device(), stream);
+        boxattn_bwd_workspace_bytes(is_h16(c.value), c.B, c.S, c.H, c.C, c.L, c.Lq, c.P, h.sh(), h.ls()), 256);
+    const StreamKey key(c.value.get_device(), c.stream);
     const bool keep = !capturing();
     std::lock_guard<std::mutex> g(g_mu);
     const auto it = g_workspace.find(key);
     if (it != g_workspace.end() && (size_t)it->second.numel() >= bytes) return it->second;
-    at::Tensor ws = at::empty({(int64_t)bytes}, value.options().dtype(at::kByte));
+    at::Tensor ws = at::empty({(int64_t)bytes}, c.value.options().dtype(at::kByte));
     if (keep) g_workspace[key] = ws;
     return ws;
 }
 // the library's state buffer of this (stream, geometry): zeroed once; every call leaves its tickets zero and the
-// record ranges of the next backward's one-pass fill
-at::Tensor state(const at::Tensor &value, const Dims &d, const HostTables &h, void *stream, int *hints)
+// record ranges of the next backward's one-pass fill.  Adds the fresh-state bit to *hints -- the only hint this
+// module ever gives.
+at::Tensor state(const Call &c, const HostTables &h, int *hints)
 {
-    const size_t bytes = boxattn_state_bytes(d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, h.sh(), h.ls());
+    const size_t bytes = boxattn_state_bytes(c.B, c.S, c.H, c.C, c.L, c.Lq, c.P, h.sh(), h.ls());
     uint64_t geo = 1469598103934665603ull;
-    for (int i = 0; i < 2 * d.L; ++i) geo = (geo ^ (uint64_t)h.sh()[i]) * 1099511628211ull;
-    const StateKey key(value.get_device(), stream, d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, (int)value.scalar_type(), geo);
+    for (int i = 0; i < 2 * c.L; ++i) geo = (geo ^ (uint64_t)h.sh()[i]) * 1099511628211ull;
+    const StateKey key(c.value.get_device(), c.stream, c.B, c.S, c.H, c.C, c.L, c.Lq, c.P, (int)c.value.scalar_type(), geo);
     const bool keep = !capturing();
     std::lock_guard<std::mutex> g(g_mu);
     const auto it = g_state.find(key);
@@ -201,7 +208,7 @@ at::Tensor state(const at::Tensor &value, const Dims &d, const HostTables &h, vo
         it->second.fresh = false;
         return it->second.buf;
     }
-    at::Tensor st = at::zeros({(int64_t)bytes}, value.options().dtype(at::kByte));
+    at::Tensor st = at::zeros({(int64_t)bytes}, c.value.options().dtype(at::kByte));
     *hints |= BOXATTN_HINT_FRESH_STATE;
     if (keep) {
         if (g_state.size() >= kStateCap) g_state.clear();
@@ -221,14 +228,13 @@ struct Parked {
 std::deque<Parked> g_parked;
 constexpr size_t kParkCap = 32;
 
-PlanKey plan_key(const at::Tensor &value, void *stream, const Dims &d, const at::Tensor &loc, const at::Tensor &w0,
-                 const at::Tensor *w1)
+PlanKey plan_key(const Call &c)
 {
     // (the storage type is part of the key: at 16 / 64 channels per head a bfloat16 plan bins contiguous query ranges,
     // a float32 one interleaved ones)
-    return PlanKey(value.get_device(), stream, d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, boxattn_options_epoch(),
-                   (int)value.scalar_type(), loc.data_ptr(), version_of(loc), w0.data_ptr(), version_of(w0), w1 ? w1->data_ptr() : nullptr,
-                   w1 ? version_of(*w1) : 0u);
+    return PlanKey(c.value.get_device(), c.stream, c.B, c.S, c.H, c.C, c.L, c.Lq, c.P, boxattn_options_epoch(),
+                   (int)c.value.scalar_type(), c.loc.data_ptr(), version_of(c.loc), c.w0.data_ptr(), version_of(c.w0),
+                   c.w1 ? c.w1->data_ptr() : nullptr, c.w1 ? version_of(*c.w1) : 0u);
 }
 void park(PlanKey key, at::Tensor plan, std::vector<at::Tensor> keep)
 {
@@ -250,25 +256,87 @@ at::Tensor take_parked(const PlanKey &key)
         }
     return at::Tensor();
 }
-bool wants_plan(std::initializer_list<const at::Tensor *> ts)
+
+// ---- the storage type of `value`: e() / g() type the pointers of value-typed tensors (value, outputs, upstream
+// gradients, grad_value) and of geometry-typed ones (locations, weights, their gradients); then that type's entry
+// points.  float64 has the plain entries only -- no host tables, workspace, plan or state.
+template <class E, class G> struct Storage {
+    static constexpr bool plain_only = std::is_same<E, double>::value;
+    static E *e(const at::Tensor &t) { return static_cast<E *>(t.data_ptr()); }
+    static G *g(const at::Tensor &t) { return static_cast<G *>(t.data_ptr()); }
+};
+struct F64 : Storage<double, double> {
+    static constexpr auto box_fwd = boxattn_fwd_f64, box_bwd = boxattn_bwd_f64;
+    static constexpr auto inst_fwd = instattn_fwd_f64, inst_bwd = instattn_bwd_f64;
+};
+struct F32 : Storage<float, float> {
+    static constexpr auto box_fwd_hl = boxattn_fwd_hl_f32, box_fwd_train = boxattn_fwd_train_f32;
+    static constexpr auto inst_fwd = instattn_fwd_f32, inst_fwd_train = instattn_fwd_train_f32;
+    static constexpr auto box_bwd_ws = boxattn_bwd_ws_f32, inst_bwd_ws = instattn_bwd_ws_f32;
+};
+struct BF16 : Storage<uint16_t, float> {
+    static constexpr auto box_fwd_hl = boxattn_fwd_hl_bf16, box_fwd_train = boxattn_fwd_train_bf16;
+    static constexpr auto inst_fwd = instattn_fwd_bf16, inst_fwd_train = instattn_fwd_train_bf16;
+    static constexpr auto box_bwd_ws = boxattn_bwd_ws_bf16, inst_bwd_ws = instattn_bwd_ws_bf16;
+};
+struct F16 : Storage<uint16_t, float> {
+    static constexpr auto box_fwd_hl = boxattn_fwd_hl_f16, box_fwd_train = boxattn_fwd_train_f16;
+    static constexpr auto inst_fwd = instattn_fwd_f16, inst_fwd_train = instattn_fwd_train_f16;
+    static constexpr auto box_bwd_ws = boxattn_bwd_ws_f16, inst_bwd_ws = instattn_bwd_ws_f16;
+};
+// call(one of the four structs above): the one place that looks at value's dtype (prepare admits no fifth)
+template <class F> int with_storage(const at::Tensor &value, F call)
 {
-    for (const at::Tensor *t : ts)
-        if (t->requires_grad()) return true;
-    return false;
-}
-at::Tensor plan_buffer(const at::Tensor &value, const Dims &d, const HostTables &h)
-{
-    const size_t bytes = boxattn_plan_bytes(is_h16(value), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
-                                            h.sh(), h.ls());
-    return bytes ? at::empty({(int64_t)bytes}, value.options().dtype(at::kByte)) : at::Tensor();
+    switch (value.scalar_type()) {
+    case at::kDouble: return call(F64());
+    case at::kFloat: return call(F32());
+    case at::kHalf: return call(F16());
+    default: return call(BF16());
+    }
 }
 
-const uint16_t *bf(const at::Tensor &t) { return (const uint16_t *)t.data_ptr(); }
-uint16_t *bf(at::Tensor &t) { return (uint16_t *)t.data_ptr(); }
-// the entry point of the 16-bit storage type of `value` (the bf16 and f16 twins share a signature)
-template <class F> F h16_entry(const at::Tensor &value, F bf16, F f16)
+// the arguments that *_fwd_train_* and *_bwd_ws_* take between the outputs and the stream, under the header's names
+struct Extra {
+    const int64_t *shapes_host, *lsi_host;
+    void *workspace; size_t workspace_bytes;           // (backward)
+    void *plan; size_t plan_bytes;
+    void *state; size_t state_bytes;
+    int hints, plan_built;                             // (plan_built: forward)
+};
+
+// The forward of both flavours but for float64.  If an input requires a gradient and the library plans for these
+// dimensions: `train`, a *_fwd_train_* call with the plan buffer and the state buffer, whose plan is parked if one was
+// built.  Else `plain`.  h: the caller's host tables, or NULL: fetched here, and only for the training forward.
+template <class Train, class Plain> int forward(const Call &c, const HostTables *h, Train train, Plain plain)
 {
-    return value.scalar_type() == at::kHalf ? f16 : bf16;
+    if (!c.value.requires_grad() && !c.loc.requires_grad() && !c.w0.requires_grad() && !(c.w1 && c.w1->requires_grad()))
+        return plain();
+    std::optional<HostTables> fetched;
+    if (!h) h = &fetched.emplace(c);
+    const size_t bytes = boxattn_plan_bytes(is_h16(c.value), c.B, c.S, c.H, c.C, c.L, c.Lq, c.P, h->sh(), h->ls());
+    if (!bytes) return plain();
+    at::Tensor plan = at::empty({(int64_t)bytes}, c.value.options().dtype(at::kByte));
+    Extra x = {h->sh(), h->ls(), nullptr, 0, plan.data_ptr(), bytes};
+    const at::Tensor state_buf = state(c, *h, &x.hints);
+    x.state = state_buf.data_ptr(); x.state_bytes = (size_t)state_buf.numel();
+    const int rc = train(x);          // a backward will follow: the forward's launch prepares its plan
+    if (rc == 0 && x.plan_built)
+        park(plan_key(c), plan, c.w1 ? std::vector<at::Tensor>{c.loc, c.w0, *c.w1} : std::vector<at::Tensor>{c.loc, c.w0});
+    return rc;
+}
+
+// The backward of both flavours but for float64: `ws`, a *_bwd_ws_* call with the stream's workspace, the geometry's
+// state buffer and the plan the forward parked, if it parked one.
+template <class Ws> int backward_ws(const Call &c, Ws ws)
+{
+    const HostTables h(c);
+    const at::Tensor scratch = workspace(c, h);
+    Extra x = {h.sh(), h.ls(), scratch.data_ptr(), (size_t)scratch.numel()};
+    const at::Tensor state_buf = state(c, h, &x.hints);
+    x.state = state_buf.data_ptr(); x.state_bytes = (size_t)state_buf.numel();
+    const at::Tensor plan = take_parked(plan_key(c));
+    if (plan.defined()) { x.plan = plan.data_ptr(); x.plan_bytes = (size_t)plan.numel(); }
+    return ws(x);
 }
 
 }  // namespace
@@ -278,227 +346,128 @@ at::Tensor box_attn_forward(const at::Tensor &value, const at::Tensor &spatial_s
                             const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
                             const at::Tensor &attn_weight, const int im2col_step)
 {
-    const Dims d = prepare(value, spatial_shapes, level_start_index, sampling_loc, {&attn_weight},
-                           im2col_step);
+    Call c = prepare(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, nullptr, im2col_step);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
-    at::Tensor out = at::empty({d.B, d.Lq, (int64_t)d.H * d.C}, value.options());
-    const int64_t *sh = spatial_shapes.data_ptr<int64_t>(), *ls = level_start_index.data_ptr<int64_t>();
-    void *st = current_stream(value);
-    int rc;
-    if (value.scalar_type() == at::kDouble) {
-        rc = boxattn_fwd_f64(value.data_ptr<double>(), sh, ls, sampling_loc.data_ptr<double>(),
-                             attn_weight.data_ptr<double>(), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
-                             out.data_ptr<double>(), st);
-    } else {
-        const HostTables h(spatial_shapes, level_start_index);
-        at::Tensor plan;
-        if (wants_plan({&value, &sampling_loc, &attn_weight})) plan = plan_buffer(value, d, h);
-        if (plan.defined()) {          // a backward will follow: the forward's launch prepares its plan
-            int hints = 0;
-            at::Tensor state_buf = state(value, d, h, st, &hints);
-            int built = 0;
-            if (value.scalar_type() == at::kFloat)
-                rc = boxattn_fwd_train_f32(value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
-                                           attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
-                                           out.data_ptr<float>(), h.sh(), h.ls(), plan.data_ptr(), (size_t)plan.numel(),
-                                           state_buf.data_ptr(), (size_t)state_buf.numel(), hints, &built, st);
-            else
-                rc = h16_entry(value, boxattn_fwd_train_bf16, boxattn_fwd_train_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
-                                            attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, bf(out),
-                                            h.sh(), h.ls(), plan.data_ptr(), (size_t)plan.numel(), state_buf.data_ptr(),
-                                            (size_t)state_buf.numel(), hints, &built, st);
-            if (rc == 0 && built)
-                park(plan_key(value, st, d, sampling_loc, attn_weight, nullptr), plan, {sampling_loc, attn_weight});
-        } else if (value.scalar_type() == at::kFloat)
-            rc = boxattn_fwd_hl_f32(value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
-                                    attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq,
-                                    d.P, out.data_ptr<float>(), h.sh(), h.ls(), st);
-        else
-            rc = h16_entry(value, boxattn_fwd_hl_bf16, boxattn_fwd_hl_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
-                                     attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq,
-                                     d.P, bf(out), h.sh(), h.ls(), st);
-    }
-    check_rc(rc, "boxattn_fwd");
+    at::Tensor out = at::empty({c.B, c.Lq, (int64_t)c.H * c.C}, value.options());
+    c.stream = current_stream(value);
+    check_rc(with_storage(value, [&](auto t) {
+        if constexpr (decltype(t)::plain_only) {
+            return t.box_fwd(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(attn_weight), c.B, c.S, c.H, c.C, c.L, c.Lq,
+                             c.P, t.e(out), c.stream);
+        } else {
+            const HostTables h(c);         // on every call: the _hl entry takes them too
+            return forward(c, &h, [&](Extra &x) {
+                return t.box_fwd_train(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(attn_weight), c.B, c.S, c.H, c.C,
+                                       c.L, c.Lq, c.P, t.e(out), x.shapes_host, x.lsi_host, x.plan, x.plan_bytes, x.state,
+                                       x.state_bytes, x.hints, &x.plan_built, c.stream);
+            }, [&]() {
+                return t.box_fwd_hl(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(attn_weight), c.B, c.S, c.H, c.C,
+                                    c.L, c.Lq, c.P, t.e(out), h.sh(), h.ls(), c.stream);
+            });
+        }
+    }), "boxattn_fwd");
     return out;
 }
 
 // box_attn.h:56-83 -> {grad_value, grad_sampling_loc, grad_attn_weight}
 std::vector<at::Tensor> box_attn_backward(const at::Tensor &value, const at::Tensor &spatial_shapes,
-                                          const at::Tensor &level_start_index,
-                                          const at::Tensor &sampling_loc,
-                                          const at::Tensor &attn_weight,
-                                          const at::Tensor &grad_output, const int im2col_step)
+                                          const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
+                                          const at::Tensor &attn_weight, const at::Tensor &grad_output,
+                                          const int im2col_step)
 {
-    const Dims d = prepare(value, spatial_shapes, level_start_index, sampling_loc, {&attn_weight},
-                           im2col_step);
+    Call c = prepare(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, nullptr, im2col_step);
     check_input(grad_output, "grad_output");
-    TORCH_CHECK(grad_output.scalar_type() == value.scalar_type(),
-                "grad_output must have the dtype of value");
-    TORCH_CHECK(grad_output.numel() == (int64_t)d.B * d.Lq * d.H * d.C,
-                "grad_output must have B*Lq*H*C elements");
+    TORCH_CHECK(grad_output.scalar_type() == value.scalar_type(), "grad_output must have the dtype of value");
+    TORCH_CHECK(grad_output.numel() == (int64_t)c.B * c.Lq * c.H * c.C, "grad_output must have B*Lq*H*C elements");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
     // the library defines every output element: no zero-fill
     at::Tensor grad_value = at::empty_like(value);
     at::Tensor grad_loc = at::empty_like(sampling_loc);
     at::Tensor grad_attn = at::empty_like(attn_weight);
-    const int64_t *sh = spatial_shapes.data_ptr<int64_t>(), *ls = level_start_index.data_ptr<int64_t>();
-    void *st = current_stream(value);
-    int rc;
-    if (value.scalar_type() == at::kDouble) {
-        rc = boxattn_bwd_f64(value.data_ptr<double>(), sh, ls, sampling_loc.data_ptr<double>(),
-                             attn_weight.data_ptr<double>(), grad_output.data_ptr<double>(), d.B, d.S,
-                             d.H, d.C, d.L, d.Lq, d.P, grad_value.data_ptr<double>(),
-                             grad_loc.data_ptr<double>(), grad_attn.data_ptr<double>(), st);
-    } else {
-        const HostTables h(spatial_shapes, level_start_index);
-        at::Tensor ws = workspace(value, d, h, st);
-        int hints = 0;
-            at::Tensor state_buf = state(value, d, h, st, &hints);
-        const at::Tensor plan = take_parked(plan_key(value, st, d, sampling_loc, attn_weight, nullptr));
-        const void *pp = plan.defined() ? plan.data_ptr() : nullptr;
-        const size_t pn = plan.defined() ? (size_t)plan.numel() : 0;
-        if (value.scalar_type() == at::kFloat)
-            rc = boxattn_bwd_ws_f32(value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
-                                    attn_weight.data_ptr<float>(), grad_output.data_ptr<float>(),
-                                    d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, grad_value.data_ptr<float>(),
-                                    grad_loc.data_ptr<float>(), grad_attn.data_ptr<float>(), h.sh(),
-                                    h.ls(), ws.data_ptr(), (size_t)ws.numel(), pp, pn, state_buf.data_ptr(),
-                                    (size_t)state_buf.numel(), hints, st);
-        else
-            rc = h16_entry(value, boxattn_bwd_ws_bf16, boxattn_bwd_ws_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
-                                     attn_weight.data_ptr<float>(), bf(grad_output), d.B, d.S, d.H,
-                                     d.C, d.L, d.Lq, d.P, bf(grad_value), grad_loc.data_ptr<float>(),
-                                     grad_attn.data_ptr<float>(), h.sh(), h.ls(), ws.data_ptr(),
-                                     (size_t)ws.numel(), pp, pn, state_buf.data_ptr(), (size_t)state_buf.numel(), hints, st);
-    }
-    check_rc(rc, "boxattn_bwd");
+    c.stream = current_stream(value);
+    check_rc(with_storage(value, [&](auto t) {
+        if constexpr (decltype(t)::plain_only) {
+            return t.box_bwd(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(attn_weight), t.e(grad_output), c.B, c.S,
+                             c.H, c.C, c.L, c.Lq, c.P, t.e(grad_value), t.g(grad_loc), t.g(grad_attn), c.stream);
+        } else {
+            return backward_ws(c, [&](const Extra &x) {
+                return t.box_bwd_ws(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(attn_weight), t.e(grad_output), c.B,
+                                    c.S, c.H, c.C, c.L, c.Lq, c.P, t.e(grad_value), t.g(grad_loc), t.g(grad_attn),
+                                    x.shapes_host, x.lsi_host, x.workspace, x.workspace_bytes, x.plan, x.plan_bytes,
+                                    x.state, x.state_bytes, x.hints, c.stream);
+            });
+        }
+    }), "boxattn_bwd");
     return {grad_value, grad_loc, grad_attn};
 }
 
 // instance_attn.h:32-59 -> {output (B,Lq,H*C), mask_output (B,Lq,P,H*C)}
-std::vector<at::Tensor> instance_attn_forward(const at::Tensor &value,
-                                              const at::Tensor &spatial_shapes,
-                                              const at::Tensor &level_start_index,
-                                              const at::Tensor &sampling_loc,
+std::vector<at::Tensor> instance_attn_forward(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                                              const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
                                               const at::Tensor &spatial_attn_weight,
-                                              const at::Tensor &level_attn_weight,
-                                              const int im2col_step)
+                                              const at::Tensor &level_attn_weight, const int im2col_step)
 {
-    const Dims d = prepare(value, spatial_shapes, level_start_index, sampling_loc,
-                           {&spatial_attn_weight, &level_attn_weight}, im2col_step);
+    Call c = prepare(value, spatial_shapes, level_start_index, sampling_loc, spatial_attn_weight, &level_attn_weight,
+                     im2col_step);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
-    at::Tensor out = at::empty({d.B, d.Lq, (int64_t)d.H * d.C}, value.options());
-    at::Tensor mask = at::empty({d.B, d.Lq, d.P, (int64_t)d.H * d.C}, value.options());
-    const int64_t *sh = spatial_shapes.data_ptr<int64_t>(), *ls = level_start_index.data_ptr<int64_t>();
-    void *st = current_stream(value);
-    int rc;
-    at::Tensor plan;
-    if (value.scalar_type() != at::kDouble &&
-        wants_plan({&value, &sampling_loc, &spatial_attn_weight, &level_attn_weight})) {
-        const HostTables h(spatial_shapes, level_start_index);
-        plan = plan_buffer(value, d, h);
-        if (plan.defined()) {
-            int hints = 0;
-            at::Tensor state_buf = state(value, d, h, st, &hints);
-            int built = 0;
-            if (value.scalar_type() == at::kFloat)
-                rc = instattn_fwd_train_f32(value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
-                                            spatial_attn_weight.data_ptr<float>(), level_attn_weight.data_ptr<float>(),
-                                            d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, out.data_ptr<float>(),
-                                            mask.data_ptr<float>(), h.sh(), h.ls(), plan.data_ptr(), (size_t)plan.numel(),
-                                            state_buf.data_ptr(), (size_t)state_buf.numel(), hints, &built, st);
-            else
-                rc = h16_entry(value, instattn_fwd_train_bf16, instattn_fwd_train_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
-                                             spatial_attn_weight.data_ptr<float>(), level_attn_weight.data_ptr<float>(),
-                                             d.B, d.S, d.H, d.C, d.L, d.Lq, d.P, bf(out), bf(mask), h.sh(), h.ls(),
-                                             plan.data_ptr(), (size_t)plan.numel(), state_buf.data_ptr(),
-                                             (size_t)state_buf.numel(), hints, &built, st);
-            if (rc == 0 && built)
-                park(plan_key(value, st, d, sampling_loc, spatial_attn_weight, &level_attn_weight), plan,
-                     {sampling_loc, spatial_attn_weight, level_attn_weight});
-            check_rc(rc, "instattn_fwd");
-            return {out, mask};
+    at::Tensor out = at::empty({c.B, c.Lq, (int64_t)c.H * c.C}, value.options());
+    at::Tensor mask = at::empty({c.B, c.Lq, c.P, (int64_t)c.H * c.C}, value.options());
+    c.stream = current_stream(value);
+    check_rc(with_storage(value, [&](auto t) {
+        const auto plain = [&]() {         // (all four types; it takes no host tables)
+            return t.inst_fwd(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(spatial_attn_weight),
+                              t.g(level_attn_weight), c.B, c.S, c.H, c.C, c.L, c.Lq, c.P, t.e(out), t.e(mask), c.stream);
+        };
+        if constexpr (decltype(t)::plain_only) {
+            return plain();
+        } else {
+            return forward(c, nullptr, [&](Extra &x) {
+                return t.inst_fwd_train(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(spatial_attn_weight),
+                                        t.g(level_attn_weight), c.B, c.S, c.H, c.C, c.L, c.Lq, c.P, t.e(out), t.e(mask),
+                                        x.shapes_host, x.lsi_host, x.plan, x.plan_bytes, x.state, x.state_bytes, x.hints,
+                                        &x.plan_built, c.stream);
+            }, plain);
         }
-    }
-    if (value.scalar_type() == at::kDouble)
-        rc = instattn_fwd_f64(value.data_ptr<double>(), sh, ls, sampling_loc.data_ptr<double>(),
-                              spatial_attn_weight.data_ptr<double>(),
-                              level_attn_weight.data_ptr<double>(), d.B, d.S, d.H, d.C, d.L, d.Lq,
-                              d.P, out.data_ptr<double>(), mask.data_ptr<double>(), st);
-    else if (value.scalar_type() == at::kFloat)
-        rc = instattn_fwd_f32(value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
-                              spatial_attn_weight.data_ptr<float>(),
-                              level_attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
-                              out.data_ptr<float>(), mask.data_ptr<float>(), st);
-    else
-        rc = h16_entry(value, instattn_fwd_bf16, instattn_fwd_f16)(bf(value), sh, ls, sampling_loc.data_ptr<float>(),
-                               spatial_attn_weight.data_ptr<float>(),
-                               level_attn_weight.data_ptr<float>(), d.B, d.S, d.H, d.C, d.L, d.Lq,
-                               d.P, bf(out), bf(mask), st);
-    check_rc(rc, "instattn_fwd");
+    }), "instattn_fwd");
     return {out, mask};
 }
 
-// instance_attn.h:61-92 -> {grad_value, grad_sampling_loc, grad_spatial_attn_weight,
-//                           grad_level_attn_weight}
+// instance_attn.h:61-92 -> {grad_value, grad_sampling_loc, grad_spatial_attn_weight, grad_level_attn_weight}
 std::vector<at::Tensor> instance_attn_backward(
     const at::Tensor &value, const at::Tensor &spatial_shapes, const at::Tensor &level_start_index,
-    const at::Tensor &sampling_loc, const at::Tensor &spatial_attn_weight,
-    const at::Tensor &level_attn_weight, const at::Tensor &grad_output,
-    const at::Tensor &grad_mask_output, const int im2col_step)
+    const at::Tensor &sampling_loc, const at::Tensor &spatial_attn_weight, const at::Tensor &level_attn_weight,
+    const at::Tensor &grad_output, const at::Tensor &grad_mask_output, const int im2col_step)
 {
-    const Dims d = prepare(value, spatial_shapes, level_start_index, sampling_loc,
-                           {&spatial_attn_weight, &level_attn_weight}, im2col_step);
+    Call c = prepare(value, spatial_shapes, level_start_index, sampling_loc, spatial_attn_weight, &level_attn_weight,
+                     im2col_step);
     check_input(grad_output, "grad_output");
     check_input(grad_mask_output, "grad_mask_output");
-    TORCH_CHECK(grad_output.scalar_type() == value.scalar_type() &&
-                    grad_mask_output.scalar_type() == value.scalar_type(),
+    TORCH_CHECK(grad_output.scalar_type() == value.scalar_type() && grad_mask_output.scalar_type() == value.scalar_type(),
                 "grad_output / grad_mask_output must have the dtype of value");
-    TORCH_CHECK(grad_output.numel() == (int64_t)d.B * d.Lq * d.H * d.C &&
-                    grad_mask_output.numel() == (int64_t)d.B * d.Lq * d.P * d.H * d.C,
+    TORCH_CHECK(grad_output.numel() == (int64_t)c.B * c.Lq * c.H * c.C &&
+                    grad_mask_output.numel() == (int64_t)c.B * c.Lq * c.P * c.H * c.C,
                 "grad_output / grad_mask_output have the wrong number of elements");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
     at::Tensor grad_value = at::empty_like(value);
     at::Tensor grad_loc = at::empty_like(sampling_loc);
     at::Tensor grad_sw = at::empty_like(spatial_attn_weight);
     at::Tensor grad_lw = at::empty_like(level_attn_weight);
-    const int64_t *sh = spatial_shapes.data_ptr<int64_t>(), *ls = level_start_index.data_ptr<int64_t>();
-    void *st = current_stream(value);
-    int rc;
-    if (value.scalar_type() == at::kDouble) {
-        rc = instattn_bwd_f64(value.data_ptr<double>(), sh, ls, sampling_loc.data_ptr<double>(),
-                              spatial_attn_weight.data_ptr<double>(),
-                              level_attn_weight.data_ptr<double>(), grad_output.data_ptr<double>(),
-                              grad_mask_output.data_ptr<double>(), d.B, d.S, d.H, d.C, d.L, d.Lq,
-                              d.P, grad_value.data_ptr<double>(), grad_loc.data_ptr<double>(),
-                              grad_sw.data_ptr<double>(), grad_lw.data_ptr<double>(), st);
-    } else {
-        const HostTables h(spatial_shapes, level_start_index);
-        at::Tensor ws = workspace(value, d, h, st);
-        int hints = 0;
-            at::Tensor state_buf = state(value, d, h, st, &hints);
-        const at::Tensor plan =
-            take_parked(plan_key(value, st, d, sampling_loc, spatial_attn_weight, &level_attn_weight));
-        const void *pp = plan.defined() ? plan.data_ptr() : nullptr;
-        const size_t pn = plan.defined() ? (size_t)plan.numel() : 0;
-        if (value.scalar_type() == at::kFloat)
-            rc = instattn_bwd_ws_f32(
-                value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
-                spatial_attn_weight.data_ptr<float>(), level_attn_weight.data_ptr<float>(),
-                grad_output.data_ptr<float>(), grad_mask_output.data_ptr<float>(), d.B, d.S, d.H,
-                d.C, d.L, d.Lq, d.P, grad_value.data_ptr<float>(), grad_loc.data_ptr<float>(),
-                grad_sw.data_ptr<float>(), grad_lw.data_ptr<float>(), h.sh(), h.ls(), ws.data_ptr(),
-                (size_t)ws.numel(), pp, pn, state_buf.data_ptr(), (size_t)state_buf.numel(), hints, st);
-        else
-            rc = h16_entry(value, instattn_bwd_ws_bf16, instattn_bwd_ws_f16)(
-                bf(value), sh, ls, sampling_loc.data_ptr<float>(),
-                spatial_attn_weight.data_ptr<float>(), level_attn_weight.data_ptr<float>(),
-                bf(grad_output), bf(grad_mask_output), d.B, d.S, d.H, d.C, d.L, d.Lq, d.P,
-                bf(grad_value), grad_loc.data_ptr<float>(), grad_sw.data_ptr<float>(),
-                grad_lw.data_ptr<float>(), h.sh(), h.ls(), ws.data_ptr(), (size_t)ws.numel(), pp, pn,
-                state_buf.data_ptr(), (size_t)state_buf.numel(), hints, st);
-    }
-    check_rc(rc, "instattn_bwd");
+    c.stream = current_stream(value);
+    check_rc(with_storage(value, [&](auto t) {
+        if constexpr (decltype(t)::plain_only) {
+            return t.inst_bwd(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(spatial_attn_weight), t.g(level_attn_weight),
+                              t.e(grad_output), t.e(grad_mask_output), c.B, c.S, c.H, c.C, c.L, c.Lq, c.P,
+                              t.e(grad_value), t.g(grad_loc), t.g(grad_sw), t.g(grad_lw), c.stream);
+        } else {
+            return backward_ws(c, [&](const Extra &x) {
+                return t.inst_bwd_ws(t.e(value), c.sh, c.ls, t.g(sampling_loc), t.g(spatial_attn_weight),
+                                     t.g(level_attn_weight), t.e(grad_output), t.e(grad_mask_output), c.B, c.S, c.H, c.C,
+                                     c.L, c.Lq, c.P, t.e(grad_value), t.g(grad_loc), t.g(grad_sw), t.g(grad_lw),
+                                     x.shapes_host, x.lsi_host, x.workspace, x.workspace_bytes, x.plan, x.plan_bytes,
+                                     x.state, x.state_bytes, x.hints, c.stream);
+            });
+        }
+    }), "instattn_bwd");
     return {grad_value, grad_loc, grad_sw, grad_lw};
 }
 

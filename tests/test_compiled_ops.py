@@ -105,20 +105,63 @@ def test_instance_functions_match_goldens(compiled, name, dtype):
 
 
 @pytest.mark.gpu
-def test_same_results_as_the_ctypes_binding(compiled):
-    """Both bindings marshal into the same library: identical forward, grad_loc and grad_attn
-    bits; grad_value to float32 summation order."""
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("kind", ["box", "instance"])
+def test_same_results_as_the_ctypes_binding(compiled, kind, dtype):
+    """Both bindings marshal into the same library, from the same device tensors.  float32 and the 16-bit types:
+    identical forward, location- and weight-gradient bits; grad_value to the order of its sums (float32: rtol 1e-5,
+    atol 1e-6; 16-bit: 1e-3 of the largest element, the bound of test_gpu_f16's compiled-module test).  float64:
+    every tensor to the parity tolerance -- its backward adds with atomics, no bits are claimed.
+    The forward runs twice: with nothing requiring a gradient (the plain / host-table entries) and with the inputs
+    requiring one (the training entries; the backward then meets whatever plan they parked), so that every entry
+    point the module calls is compared in every storage type that has it."""
     from boxer_amd import ops
-    g = golden_io.load("G6_box_ml")
-    value, loc, attn = (_dev(g[k], torch.float32) for k in ("value", "loc", "attn"))
-    shapes, lsi, gout = _dev(g["shapes"]), _dev(g["lsi"]), _dev(g["grad_out"], torch.float32)
-    a = compiled.box_attn_forward(value, shapes, lsi, loc, attn, 64)
-    b = ops.box_attn_forward(value, shapes, lsi, loc, attn, 64)
-    assert torch.equal(a, b)
-    ga = compiled.box_attn_backward(value, shapes, lsi, loc, attn, gout, 64)
-    gb = ops.box_attn_backward(value, shapes, lsi, loc, attn, gout, 64)
-    assert torch.equal(ga[1], gb[1]) and torch.equal(ga[2], gb[2])
-    assert torch.allclose(ga[0], gb[0], rtol=1e-5, atol=1e-6)
+    from compare_rules import close_parity
+    g = golden_io.load("G6_box_ml" if kind == "box" else "G6_inst_ms4")
+    cdt = torch.float64 if dtype == torch.float64 else torch.float32       # locations, weights and their gradients
+    weights = ("attn",) if kind == "box" else ("spatial_w", "level_w")
+    value, loc = _dev(g["value"], dtype), _dev(g["loc"], cdt)
+    ws = [_dev(g[k], cdt) for k in weights]
+    shapes, lsi = _dev(g["shapes"]), _dev(g["lsi"])
+    grads = [_dev(g["grad_out"], dtype)]
+    if kind == "instance":
+        gm = g["grad_mask"]
+        grads.append(_dev(gm.reshape(gm.shape[0], gm.shape[1], -1, gm.shape[-1]), dtype))
+    fwd, bwd = "%s_attn_forward" % kind, "%s_attn_backward" % kind
+
+    def same(a, b, what):
+        assert a.dtype == b.dtype and a.shape == b.shape, what
+        if dtype == torch.float64:
+            close_parity(a, b.detach().cpu().numpy(), torch.float64, what)
+        else:
+            assert torch.equal(a, b), what
+
+    def forwards(what):
+        a = getattr(compiled, fwd)(value, shapes, lsi, loc, *ws, 64)
+        b = getattr(ops, fwd)(value, shapes, lsi, loc, *ws, 64)
+        a, b = ([a], [b]) if kind == "box" else (a, b)
+        assert len(a) == len(b) == len(grads)
+        for i, (x, y) in enumerate(zip(a, b)):
+            same(x, y, "%s output %d" % (what, i))
+
+    forwards("inference forward")
+    for t in [value, loc] + ws:
+        t.requires_grad_()
+    forwards("training forward")
+    ga = getattr(compiled, bwd)(value, shapes, lsi, loc, *ws, *grads, 64)
+    gb = getattr(ops, bwd)(value, shapes, lsi, loc, *ws, *grads, 64)
+    assert len(ga) == len(gb) == 2 + len(ws)
+    for i in range(1, len(ga)):
+        same(ga[i], gb[i], "gradient %d" % i)
+    if dtype == torch.float64:
+        same(ga[0], gb[0], "grad_value")
+    elif dtype == torch.float32:
+        assert ga[0].dtype == gb[0].dtype == dtype
+        assert torch.allclose(ga[0], gb[0], rtol=1e-5, atol=1e-6)
+    else:
+        assert ga[0].dtype == gb[0].dtype == dtype
+        gv_a, gv_b = ga[0].float(), gb[0].float()
+        assert float((gv_a - gv_b).abs().max()) <= 1e-3 * max(1.0, float(gv_b.abs().max()))
 
 
 @pytest.mark.gpu
@@ -130,6 +173,22 @@ def test_error_behaviour(compiled):
         compiled.box_attn_forward(value.transpose(2, 3), shapes, lsi, loc, attn, 64)
     with pytest.raises(RuntimeError, match="CUDA tensor"):
         compiled.box_attn_forward(value.cpu(), shapes, lsi, loc, attn, 64)
+    # the backward's own refusals, all before any launch
+    gout = _dev(g["grad_out"], torch.float32)
+    with pytest.raises(RuntimeError, match="must have the dtype of value"):
+        compiled.box_attn_backward(value, shapes, lsi, loc, attn, gout.double(), 64)
+    with pytest.raises(RuntimeError, match=r"B\*Lq\*H\*C elements"):
+        compiled.box_attn_backward(value, shapes, lsi, loc, attn, gout.flatten()[:-1].contiguous(), 64)
+    gi = golden_io.load("G6_inst_ms4")
+    ivalue, iloc, sw, lw = (_dev(gi[k], torch.float32) for k in ("value", "loc", "spatial_w", "level_w"))
+    ishapes, ilsi, igout = _dev(gi["shapes"]), _dev(gi["lsi"]), _dev(gi["grad_out"], torch.float32)
+    gm = gi["grad_mask"]
+    gmask = _dev(gm.reshape(gm.shape[0], gm.shape[1], -1, gm.shape[-1]), torch.float32)
+    with pytest.raises(RuntimeError, match="wrong number of elements"):
+        compiled.instance_attn_backward(ivalue, ishapes, ilsi, iloc, sw, lw, igout, gmask[:, :, :-1].contiguous(), 64)
+    assert not gmask.transpose(1, 2).is_contiguous()
+    with pytest.raises(RuntimeError, match="grad_mask_output must be contiguous"):
+        compiled.instance_attn_backward(ivalue, ishapes, ilsi, iloc, sw, lw, igout, gmask.transpose(1, 2), 64)
     b = value.size(0)
     if b % 2 == 1:
         value, loc, attn = (torch.cat([t, t]) for t in (value, loc, attn))
