@@ -279,7 +279,12 @@ def _locality(key):
     # everything else simply never sees a non-zero miss count)
     loc = _LOCALITY.get(key)
     if loc is None:
-        loc = _bounded(_LOCALITY)[key] = _Locality()
+        loc = _Locality()
+        # (a shape first met while the stream captures a graph: its entry would describe the capture alone -- a replay
+        # runs no host code -- under a stream handle that is another stream's once this one is gone; like the state
+        # buffer created with it, it serves this call and is not kept)
+        if not torch.cuda.is_current_stream_capturing():
+            _bounded(_LOCALITY)[key] = loc
     return loc
 
 

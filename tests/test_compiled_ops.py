@@ -331,3 +331,69 @@ def test_runs_on_the_current_stream(compiled):
         out = compiled.box_attn_forward(scratch, shapes, lsi, loc, attn, 64)
     side.synchronize()
     assert torch.equal(out, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["same_stream", "new_stream"])
+@pytest.mark.parametrize("kind,dtype", [("box", torch.bfloat16), ("box", torch.float32), ("instance", torch.bfloat16)],
+                         ids=["box_bf16", "box_f32", "instance_bf16"])
+def test_step_replayed_from_a_hip_graph_on_new_inputs(compiled, kind, dtype, mode, monkeypatch):
+    """Forward + backward through the module's four functions (the reference's own Functions,
+    bench.reference_style_functions) captured in a HIP graph -- warmed up on the capture stream, and captured on a stream
+    that has run nothing, where the module's ``capturing()`` keeps state, workspace and plan out of its tables -- and
+    replayed on a second input set and on the first again.  Each replay is held to the rule of the eager tests of the
+    route (tests/test_gpu_graph_replay.py: compare_rules.check_onepass for the encoder box step, error_bounds.hold_all
+    for instance attention with the binned backward required and its accumulate on the matrix cores); the bitwise
+    reproducible outputs equal the ctypes binding's, called eagerly on the same inputs after the replay."""
+    import bench
+    import error_bounds as eb
+    import graph_cases as gc
+    import point_cases
+    from boxer_amd import _lib, ops
+    from compare_rules import check_onepass
+    from route_vocab import ACC_TR, REC_POINT, routes, split_of
+    monkeypatch.setattr(ops._Locality, "enabled", False)       # (the module gives no locality hint: the same kernels)
+    ops.release_workspaces()
+    compiled.release_buffers()
+    ref_box, ref_inst = bench.reference_style_functions(compiled)
+    if kind == "box":
+        inputs = gc.onepass_sets("S", dtype)[:2]
+        sets, leaves = inputs, ("value", "loc", "attn")
+    else:
+        _lib.set_option("inst_acc16", 2)
+        _lib.set_variant(3)
+        inputs = gc.instance_sets(point_cases.SHAPE_A, "bf16", (5, 6))
+        sets, leaves = [point_cases.inst_tensors(inp, dtype) for inp in inputs], ("value", "loc", "attn", "level_w")
+        fwd, acc, rec = routes(sets[0], instance=True)
+        assert acc == ACC_TR and rec == REC_POINT, (acc, rec)
+    static = gc.clone(sets[0], leaves=leaves)
+
+    def step():
+        a = [static[k] for k in ("value", "shapes", "lsi", "loc", "attn")]
+        if kind == "box":
+            outs, ups = [ref_box.apply(*a, 64)], [static["grad_out"]]
+        else:
+            outs, ups = list(ref_inst.apply(*a, static["level_w"], 64)), [static["grad_out"], static["grad_mask"]]
+        grads = torch.autograd.grad(outs, [static[n] for n in leaves], ups)
+        return [o.detach() for o in outs], list(grads)
+
+    def check(i, kept, what):
+        outs, grads = kept
+        if kind == "box":
+            check_onepass(sets[i], outs[0], grads, what)
+            e_out, e_grads = point_cases.step(sets[i], entry="reference")
+            pairs = [("out", outs[0], e_out), ("grad_loc", grads[1], e_grads[1]), ("grad_attn", grads[2], e_grads[2])]
+        else:
+            eb.hold_all(dict(zip(point_cases.INST_NAMES, outs + grads)), eb.reference_of(inputs[i]), dtype,
+                        split_of(ACC_TR, dtype), what)
+            e = point_cases.run_instance(sets[i])
+            pairs = [(n, t, e[n]) for n, t in zip(point_cases.INST_NAMES, outs + grads) if n != "grad_value"]
+        for name, a, b in pairs:
+            assert a.dtype == b.dtype and torch.equal(a, b), "%s: %s differs from the ctypes binding's" % (what, name)
+        assert compiled.parked_plans() == 0, what
+
+    try:
+        gc.replay_on(mode, step, static, sets, (0, 1, 0), check)
+    finally:
+        compiled.release_buffers()
+        ops.release_workspaces()

@@ -173,8 +173,12 @@ def test_soak_over_changing_inputs(dtype, monkeypatch):
 
 
 def test_one_pass_step_in_a_hip_graph():
-    """A captured step replays the one-pass fill against the live state buffer (its ranges are re-planned by every
-    replay); results as eager."""
+    """A step captured the way bench.graph_step captures it -- warmed up on one stream, captured on another that has run
+    nothing.  The state key holds the stream handle, so the state buffer of the captured step is created INSIDE the
+    capture (a ``torch.zeros`` node of the graph, not kept in ops._STATE) and handed over as fresh: the library notes it
+    as cold, and what every replay runs is the cold two-pass step on a buffer the graph has just zeroed -- not the
+    one-pass fill.  Results as the oracle's.  (The one-pass fill inside a graph, on a stream that was warmed up, and
+    replays on new locations: tests/test_gpu_graph_replay.py.)"""
     from boxer_amd import ops
     ops.release_workspaces()
     inp = make_case(LEVELS4, "S", dtype=torch.bfloat16, seed=9)
